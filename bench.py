@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the ballooning hot path on MI355X (contract: task statement, section 4).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).  --full adds
+everything else the bench measures, after the headline: the dominant kernel's event-timed `kernel_ms` and `roofline`, the
+CPU baseline and the parity check against the C oracle, the extra legs (stress, Sturm sweep, configs[2..4], long grids, ...)
+and, for N > 1, the sharded legs.  --dump-outputs DIR writes what the timed path returned in its last step (rank 0) as
+DIR/<name>.npy (float64): the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ...` the ranks come from the
 environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*); run directly (`python bench.py --gpus N`) the parent spawns the
@@ -17,7 +23,7 @@ BASELINE.json configs[2] (64 surfaces x 32 alpha x 16 theta0, N_zeta = 1024) wit
 the ranks (geometry -> scan -> argmax on each rank's own surfaces, ONE all-gather of the per-surface rows), checked
 bitwise against the table rank 0 computes alone.
 
-Prints ONE JSON line on rank 0 (metric/unit from BASELINE.json) with `roofline` (dominant kernel
+Prints ONE JSON line on rank 0 (metric/unit from BASELINE.json); with --full it also carries `roofline` (dominant kernel
 k_gamma_scan, HIP-event timed) and `cpu_baseline` (C oracle on the host cores, bounded sample);
 the extra `stress` object is config 5 (raw (g,c,f) systems) where the batch is large enough for a
 roofline figure to mean something.
@@ -253,8 +259,9 @@ def compact_line(out, limit=LINE_LIMIT):
     if len(cfg.get("workload", "")) > 340:
         cfg["workload"] = cfg["workload"][:337] + "..."
     o["config"] = _sig(cfg)
-    o["solves_per_s_kernel"] = _sig(out.get("solves_per_s_kernel"))
-    o["roofline"] = _sig(compact_roofline(out.get("roofline"), head=True))
+    if "roofline" in out:                 # (a plain run, without --full, carries neither)
+        o["solves_per_s_kernel"] = _sig(out.get("solves_per_s_kernel"))
+        o["roofline"] = _sig(compact_roofline(out.get("roofline"), head=True))
     for k in ("cpu_baseline", "cpu_reference_cost"):
         if k in out:
             o[k] = _sig({a: b for a, b in out[k].items() if a != "sample" or k == "cpu_baseline"})
@@ -348,6 +355,20 @@ def emit(out):
         print("bench.py: could not write %s (%s)" % (DETAIL_FILE, e), file=sys.stderr)
     print("bench.py detail: " + full, file=sys.stderr, flush=True)
     print(compact_line(out), flush=True)
+
+
+def dump_outputs(dirname, plan, pack):
+    """--dump-outputs: what a caller of the step receives from its last launch, as DIR/<name>.npy in float64 (a few KB):
+    the growth rates and eigenvalues of every (line, theta0) solve, each surface's largest growth rate and the flat
+    (alpha, theta0) index of its first occurrence (`pack`: the buffer the step gathers), and the status half of every solve's
+    info word (0 = converged)"""
+    os.makedirs(dirname, exist_ok=True)
+    info = plan.info.cpu().numpy()
+    pk = pack.cpu().numpy()
+    arrays = {"gam": plan.gam.cpu().numpy(), "lam": plan.lam.cpu().numpy(),
+              "surface_best_val": pk[:, 0], "surface_best_idx": pk[:, 1], "status": (info >> 16).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
@@ -1221,6 +1242,11 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-stress", action="store_true", help="skip the config-5 stress leg")
     ap.add_argument("--stress-systems", type=int, default=262144)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else: kernel_ms / roofline, CPU baseline and oracle parity, "
+                         "the extra legs, the sharded legs for N > 1 (--no-cpu / --no-stress trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned in its last step as DIR/<name>.npy (float64, rank 0)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -1368,25 +1394,30 @@ def main():
         torch.cuda.synchronize()
         n_spin += 64
     fence()
-    dt, kern_ms_live = timed_steps(args.steps, True)
-    # `kernel_ms`: an UNTIMED pass of 25 brackets, each around 8 back-to-back launches of the step's one kernel, divided
-    # by 8.  A bracket around a single launch over-reads rocprofv3's kernel-trace average by ~3 us (the event records
-    # are stream work themselves: `event_bracket_ms` is an empty bracket), which is how the figure of a short run could
-    # exceed ms_per_step; spread over 8 launches that is < 0.5 us, and the launch gap it adds instead is part of every
-    # step as well.  The sparse single-launch brackets inside the timed region are reported as `kernel_ms_live_raw`.
-    n_un, per = 25, 8
-    un = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_un)]
-    emp = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_un)]
-    for (a, b), (c, d) in zip(un, emp):
-        a.record()
-        for _ in range(per):
-            plan.scan_argmax()
-        b.record()
-        c.record(); d.record()
-    torch.cuda.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in un])) / per
-    head_kernel, head_waves = ctx.last_launch()          # the step's one kernel: ibs::k_gamma_scan<double, 8>, 1,024 waves
-    empty_ms = float(np.median([c.elapsed_time(d) for c, d in emp]))
+    # (the sparse event brackets of the dominant kernel inside the timed region feed `roofline`: --full only)
+    dt, kern_ms_live = timed_steps(args.steps, args.full)
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's results, before anything else launches (the headline mode gathers from slot 0)
+        dump_outputs(args.dump_outputs, plan, plan.pack)
+    if args.full:
+        # `kernel_ms`: an UNTIMED pass of 25 brackets, each around 8 back-to-back launches of the step's one kernel, divided
+        # by 8.  A bracket around a single launch over-reads rocprofv3's kernel-trace average by ~3 us (the event records
+        # are stream work themselves: `event_bracket_ms` is an empty bracket), which is how the figure of a short run could
+        # exceed ms_per_step; spread over 8 launches that is < 0.5 us, and the launch gap it adds instead is part of every
+        # step as well.  The sparse single-launch brackets inside the timed region are reported as `kernel_ms_live_raw`.
+        n_un, per = 25, 8
+        un = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_un)]
+        emp = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_un)]
+        for (a, b), (c, d) in zip(un, emp):
+            a.record()
+            for _ in range(per):
+                plan.scan_argmax()
+            b.record()
+            c.record(); d.record()
+        torch.cuda.synchronize()
+        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in un])) / per
+        head_kernel, head_waves = ctx.last_launch()          # the step's one kernel: ibs::k_gamma_scan<double, 8>, 1,024 waves
+        empty_ms = float(np.median([c.elapsed_time(d) for c, d in emp]))
     gather_ok = roundtrip_ok() if use_dist else None
     seen = ranks_seen(False) if use_dist else 1
     info = plan.info.cpu().numpy()
@@ -1395,9 +1426,6 @@ def main():
 
     out = None
     if rank == 0:
-        bytes_per_solve = (7 * NPTS * 8 + 8) / N_THETA0 + 8            # SURVEY 8d: geometry-fed path
-        alg_bytes = n_solves * bytes_per_solve
-        rp_ms, rp_file = rocprof_kernel_ms(head_kernel.replace("ibs::", ""))
         out = {
             "metric": "field-line eigenvalue solves/sec (N_zeta=512)",
             "value": n_ranks * n_solves * args.steps / dt,
@@ -1406,9 +1434,6 @@ def main():
             "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic (NCSX_op-derived field-line geometry, perturbed per line)",
-            # the same workload priced on the kernel alone (n_ranks x solves per launch / kernel_ms): what a run of any
-            # length converges to; `value` of a 20-step run carries the two fences of a 0.6 ms timed region
-            "solves_per_s_kernel": n_ranks * n_solves / (kern_ms * 1e-3),
             "config": {"workload": "configs[1] D3D-shape: 16 surfaces x 8 alpha x 8 theta0 = 1024 solves/step/GPU, "
                                    "N_zeta=512 (513 points), geometry-fed scan with fused per-surface argmax (one launch)"
                                    + (" + all-gather (%s, %d ranks, in the step's stream) of the per-surface maxima" % (
@@ -1417,20 +1442,27 @@ def main():
                        "nonconverged": nbad, "ranks_in_collective": seen, "allgather_roundtrip_ok": gather_ok,
                        "untimed_spinup_steps": args.warmup + n_spin,
                        "headline_gather": "torch_in_stream" if use_dist else None},
-            # `bound` = what binds this launch (FP64 VALU issue: 1,024 waves on 1,024 SIMDs); achieved / peak /
-            # frac (= hbm_frac) are the HBM figures on algorithmic bytes the task defines; `valu_issue` prices the launch
-            # against the binding bound.  Counters: the PMC entry of EXACTLY this kernel at this launch size.
-            "roofline": hbm_roofline(
-                alg_bytes, kern_ms, "valu_issue", head_kernel, head_waves,
-                kernel_role="scan + fused per-surface argmax, one launch", kernel_ms=kern_ms,
-                kernel_ms_how="untimed pass after the timed region: 25 HIP-event brackets around 8 back-to-back launches "
-                              "each, / 8 (includes the launch gap; rocprofv3's kernel-trace average of the same kernel: "
-                              "kernel_ms_rocprof)",
-                kernel_ms_rocprof=rp_ms, kernel_ms_rocprof_source=("profiles/" + rp_file) if rp_file else None,
-                event_bracket_ms=empty_ms, kernel_ms_live_raw=kern_ms_live,
-                note="FP64-VALU-issue bound, not HBM bound (DESIGN.md 4); every step re-scans the same 3.7 MB of geometry, "
-                     "which stays in L2 / Infinity Cache: the HBM figures are nominal for this leg"),
         }
+    if rank == 0 and args.full:
+        bytes_per_solve = (7 * NPTS * 8 + 8) / N_THETA0 + 8            # SURVEY 8d: geometry-fed path
+        alg_bytes = n_solves * bytes_per_solve
+        rp_ms, rp_file = rocprof_kernel_ms(head_kernel.replace("ibs::", ""))
+        # the same workload priced on the kernel alone (n_ranks x solves per launch / kernel_ms): what a run of any
+        # length converges to; `value` of a 20-step run carries the two fences of a 0.6 ms timed region
+        out["solves_per_s_kernel"] = n_ranks * n_solves / (kern_ms * 1e-3)
+        # `bound` = what binds this launch (FP64 VALU issue: 1,024 waves on 1,024 SIMDs); achieved / peak /
+        # frac (= hbm_frac) are the HBM figures on algorithmic bytes the task defines; `valu_issue` prices the launch
+        # against the binding bound.  Counters: the PMC entry of EXACTLY this kernel at this launch size.
+        out["roofline"] = hbm_roofline(
+            alg_bytes, kern_ms, "valu_issue", head_kernel, head_waves,
+            kernel_role="scan + fused per-surface argmax, one launch", kernel_ms=kern_ms,
+            kernel_ms_how="untimed pass after the timed region: 25 HIP-event brackets around 8 back-to-back launches "
+                          "each, / 8 (includes the launch gap; rocprofv3's kernel-trace average of the same kernel: "
+                          "kernel_ms_rocprof)",
+            kernel_ms_rocprof=rp_ms, kernel_ms_rocprof_source=("profiles/" + rp_file) if rp_file else None,
+            event_bracket_ms=empty_ms, kernel_ms_live_raw=kern_ms_live,
+            note="FP64-VALU-issue bound, not HBM bound (DESIGN.md 4); every step re-scans the same 3.7 MB of geometry, "
+                 "which stays in L2 / Infinity Cache: the HBM figures are nominal for this leg")
 
     # ---- N > 1: everything after the headline runs under a watchdog -- `out` already holds the headline, and a phase that
     # overruns (a rank that left a leg early while the others wait in its collective, a communicator that never comes up)
@@ -1438,7 +1470,7 @@ def main():
     dog = Watchdog(rank, lambda: out)
     if use_dist and os.environ.get("IBS_BENCH_DIE_RANK") == str(rank) and os.environ.get("IBS_BENCH_DIE_AFTER") == "headline":
         os._exit(17)           # test hook (tests/test_gpu_round5.py): a rank that dies while the others enter a collective
-    if use_dist:
+    if use_dist and args.full:
         for key, leg, label in (("ncsx_c2_sharded", lambda: c2_sharded_leg(ctx, device, rank, world, dist, fence, native=False),
                                  "configs[2] sharded, torch.distributed gather"),
                                 ("ncsx_c2_sharded_refined", lambda: c2_refined_leg(ctx, device, rank, world, dist, fence),
@@ -1494,13 +1526,14 @@ def main():
                     out["ms_per_step"] = valid[best]["ms_per_step"]
                     out["config"]["headline_gather"] = best
             mode[0] = "native"
-            dog.arm("configs[2] sharded with the library's gather", 180)
-            try:
-                c2n = c2_sharded_leg(ctx, device, rank, world, dist, fence, native=True)
-            except Exception as e:
-                c2n = dict(error="%s: %s" % (type(e).__name__, e)) if rank == 0 else None
-            if out is not None and c2n is not None:
-                out["ncsx_c2_sharded_native"] = c2n
+            if args.full:
+                dog.arm("configs[2] sharded with the library's gather", 180)
+                try:
+                    c2n = c2_sharded_leg(ctx, device, rank, world, dist, fence, native=True)
+                except Exception as e:
+                    c2n = dict(error="%s: %s" % (type(e).__name__, e)) if rank == 0 else None
+                if out is not None and c2n is not None:
+                    out["ncsx_c2_sharded_native"] = c2n
             dog.arm("ncclCommDestroy", 60)
             ctx.comm_destroy()
         mode[0] = "torch"
@@ -1508,7 +1541,7 @@ def main():
 
     rc = 0
     if rank == 0:
-        if world == 1 and not use_dist and not args.no_cpu:
+        if args.full and world == 1 and not use_dist and not args.no_cpu:
             cb, gam_cpu = cpu_baseline(h, base, dP, theta0)
             out["cpu_baseline"] = cb
             out["max_abs_dgam_vs_oracle"] = float(np.abs(plan.gam.cpu().numpy() - gam_cpu).max())
@@ -1517,7 +1550,7 @@ def main():
             if not out["parity_ok"]:
                 rc = 3
             out["cpu_reference_cost"] = cpu_reference_cost(h, base, dP, theta0)
-        if world == 1 and not use_dist and not args.no_stress:
+        if args.full and world == 1 and not use_dist and not args.no_stress:
             out["stress"] = stress(ctx, device, args.stress_systems, "smooth")
             out["stress_rough"] = stress(ctx, device, max(args.stress_systems // 4, 1024), "rough")
             out["sturm_sweep"] = sturm_sweep(ctx, device, args.stress_systems)

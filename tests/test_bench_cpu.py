@@ -159,6 +159,20 @@ def test_the_stdout_line_fits_the_drivers_capture():
     assert json.loads(fl)["dropped_for_length"] == ["future_leg"] and "c5_matrix" in json.loads(fl)
 
 
+def test_the_line_of_a_plain_run_holds_the_headline_only():
+    """a run without --full records the headline keys and `config` only: its line carries them unchanged and no empty
+    `roofline` / `solves_per_s_kernel` placeholders"""
+    import json
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r06a_bench_detail.json")))
+    head = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data")
+    plain = dict({k: full[k] for k in head}, config=full["config"])
+    o = json.loads(bench.compact_line(plain))
+    assert {k: o[k] for k in head} == {k: full[k] for k in head}
+    assert set(o) == set(head) | {"config", "detail"}
+
+
 def test_emit_writes_detail_file_and_one_stdout_line(tmp_path, monkeypatch, capsys):
     import json
     import bench

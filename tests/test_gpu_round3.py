@@ -48,6 +48,37 @@ def test_bench_workload_against_oracle(ctx):
         assert np.abs(pk[:, 0] - tab_c.max(axis=1)).max() < 1e-8
 
 
+def test_plain_bench_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one JSON line with the headline keys and
+    steps = K, none of the --full legs, and DIR/*.npy holding what the last timed step returned -- every growth rate against the
+    C oracle to 1e-8, every per-surface argmax exact, no solve flagged."""
+    import json
+    import subprocess
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import c_oracle as co
+    dump = tmp_path / "out"
+    env = dict(os.environ, IBS_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--dump-outputs", str(dump)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    o = json.loads(lines[0])
+    assert o["unit"] == "solves/s" and o["higher_is_better"] is True and o["dtype"] == "f64" and o["steps"] == 20
+    assert o["value"] > 0 and abs(o["ms_per_step"] - 1024 * 1e3 / o["value"]) < 1e-9 * o["ms_per_step"]
+    assert not {"roofline", "cpu_baseline", "stress", "c5_matrix"} & set(o), sorted(o)
+    got = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert set(got) == {"gam", "lam", "surface_best_val", "surface_best_idx", "status"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    h, _, _, _, base, dP, theta0 = bench.build_workload(0, "cpu")
+    gam_c, _, _ = co.gamma_scan(h, *[base[:, k, :] for k in range(7)], dP, theta0)
+    assert got["gam"].shape == gam_c.shape and np.abs(got["gam"] - gam_c).max() < 1e-8
+    tab_c = gam_c.reshape(bench.N_SURF, -1)
+    assert np.array_equal(got["surface_best_idx"].astype(np.int64), tab_c.argmax(axis=1))
+    assert np.abs(got["surface_best_val"] - tab_c.max(axis=1)).max() < 1e-8 and not got["status"].any()
+
+
 def test_config4_refined_maxima_and_gradient(ctx):
     """BASELINE configs[3] with the quantity the reference differentiates: 73 equilibria x 5 surfaces, coarse 24 x 15 scan ->
     argmax -> L-BFGS-B on the device for all 365 starts in ONE ibs_refine_f64 call -> final solve (ball_scan.py:305-339), then

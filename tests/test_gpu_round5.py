@@ -129,7 +129,7 @@ def test_two_ranks_share_the_gpu_through_bench(tmp_path):
     the headline's per-step gather and the three sharded legs run on two ranks and check themselves against one rank, the
     ONE stdout line parses, is under 6,000 bytes and says so."""
     detail = tmp_path / "detail.json"
-    p, dt = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-stress"], {"IBS_BENCH_DETAIL": str(detail)}, 900)
+    p, dt = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-stress", "--full"], {"IBS_BENCH_DETAIL": str(detail)}, 900)
     assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -150,7 +150,7 @@ def test_a_dying_rank_ends_the_run_nonzero():
     """rank 1 kills itself (IBS_BENCH_DIE_RANK / _AFTER: a test hook in bench.py) inside the first sharded leg, while rank 0
     waits in that leg's collective: the parent notices the dead child, stops the other rank and leaves non-zero -- well
     inside the watchdog period (300 s), not after a hang."""
-    p, dt = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-stress"],
+    p, dt = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-stress", "--full"],
                    {"IBS_BENCH_DIE_RANK": "1", "IBS_BENCH_DIE_AFTER": "headline"}, 600)
     assert p.returncode != 0, p.stdout[-1000:]
     assert dt < 300, dt
