@@ -71,6 +71,7 @@ struct ibs_options {
   int reclose = 1;        // FP64 raw systems: 1 = a solve whose closing bracket fails its consistency checks is re-closed in division form, 2 = only marked, 0 = off
   int refine_tangent = -1; // refinement: alpha-tangent of a point staged in LDS (1) or read from global memory in the sums (0); -1 = by batch size
   double chain_w1 = 0.25, chain_w2 = 1.0;   // relative widths of the chain's warm starts
+  long nearest_chunk_systems = 0;  // ibs_gamma_scan_nearest_f64: systems per chunk (rounded down to whole lines, at least one); 0 = by workspace budget
 };
 
 struct ibs_ctx {
@@ -666,6 +667,7 @@ int ibs_set_option(ibs_ctx* c, const char* name, double value) {
   else if (n == "refine_tangent") c->opt.refine_tangent = reset ? c->opt_created.refine_tangent : (int)value;
   else if (n == "chain_w1") c->opt.chain_w1 = reset ? c->opt_created.chain_w1 : value;
   else if (n == "chain_w2") c->opt.chain_w2 = reset ? c->opt_created.chain_w2 : value;
+  else if (n == "nearest_chunk_systems") c->opt.nearest_chunk_systems = reset ? c->opt_created.nearest_chunk_systems : (long)value;
   else if (n == "all" && reset) c->opt = c->opt_created;
   else return fail(IBS_ERR_ARG, "unknown option '%s'", name);
   return 0;
@@ -849,6 +851,160 @@ int ibs_solve_gcf_f32(ibs_ctx* ctx, int64_t n_sys, int32_t N, float h, const flo
                       const float* f, int64_t ld, float* lam, float* gam, float* X, float* dX,
                       int32_t* info, int32_t mem) {
   return solve_gcf_impl<float>(ctx, n_sys, N, h, g, c, f, ld, lam, gam, X, dX, info, mem, ibs::launch_table().gcf_f32);
+}
+
+// ---- the eigenpair nearest sigma (ibs_nearest.hip; utils.py:1597)
+// device pointers: the persistent grid of long_waves() with its workspace in ctx->long_ws (nearest_ws_doubles(N) per wave)
+static int nearest_device(ibs_ctx* ctx, long n_sys, int32_t N, double h, const double* g, const double* gh, const double* c,
+                          const double* f, long ld, const double* sigma, double* lam, int32_t* idx, double* gam, double* X,
+                          double* dX, int32_t* info) {
+  const int nw = long_waves(ctx, n_sys);
+  const size_t ws = (size_t)nw * ibs::nearest_ws_doubles(N);
+  if (int r = ensure_long_ws(ctx, ws * sizeof(double))) return r;
+  ibs::NearestArgs a{};
+  a.n_sys = n_sys; a.N = N; a.h = h; a.g = g; a.c = c; a.f = f; a.gh = gh; a.ld = ld; a.sigma = sigma;
+  a.lam = lam; a.idx = idx; a.gam = gam; a.X = X; a.dX = dX; a.info = info;
+  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+  HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
+  return 0;
+}
+
+int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
+                              const double* c, const double* f, int64_t ld, const double* sigma, double* lam,
+                              int32_t* idx, double* gam, double* X, double* dX, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_sys < 0 || !g || !c || !f || !sigma || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_sys=%lld ld=%lld N=%d)", (long long)n_sys, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_sys == 0) return 0;
+  ON_DEVICE(ctx);
+  if (mem != IBS_MEM_HOST) return nearest_device(ctx, (long)n_sys, N, h, g, gh, c, f, (long)ld, sigma, lam, idx, gam, X, dX, info);
+  const size_t in_elems = (size_t)n_sys * ld, out_elems = (size_t)n_sys * N;
+  const size_t need = (gh ? 4 : 3) * pad256(in_elems * 8) + 3 * pad256(n_sys * 8) + 2 * pad256(n_sys * 4) +
+                      (X ? pad256(out_elems * 8) : 0) + (dX ? pad256(out_elems * 8) : 0) + 4096;
+  if (int r = ensure_ws(ctx, need)) return r;
+  Arena ar(ctx);
+  HostStage hs(ctx, need);
+  double* dg = ar.take<double>(in_elems); double* dc = ar.take<double>(in_elems); double* df = ar.take<double>(in_elems);
+  double* dgh = gh ? ar.take<double>(in_elems) : nullptr;
+  double* dsig = ar.take<double>(n_sys);
+  HIPCHK(hs.up(g, in_elems * 8, dg));
+  HIPCHK(hs.up(c, in_elems * 8, dc));
+  HIPCHK(hs.up(f, in_elems * 8, df));
+  if (gh) HIPCHK(hs.up(gh, in_elems * 8, dgh));
+  HIPCHK(hs.up(sigma, (size_t)n_sys * 8, dsig));
+  HIPCHK(hs.flush_in());
+  double* dlam = lam ? ar.take<double>(n_sys) : nullptr; double* dgam = gam ? ar.take<double>(n_sys) : nullptr;
+  int* didx = idx ? ar.take<int>(n_sys) : nullptr;
+  double* dX_ = X ? ar.take<double>(out_elems) : nullptr; double* ddX = dX ? ar.take<double>(out_elems) : nullptr;
+  int* d_info = ar.take<int>(n_sys); int* d_nbad = ar.take<int>(1);
+  if (int r = nearest_device(ctx, (long)n_sys, N, h, dg, dgh, dc, df, (long)ld, dsig, dlam, didx, dgam, dX_, ddX, d_info)) return r;
+  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, d_info, d_nbad);
+  if (lam) HIPCHK(hs.down(lam, dlam, n_sys * 8));
+  if (idx) HIPCHK(hs.down(idx, didx, n_sys * 4));
+  if (gam) HIPCHK(hs.down(gam, dgam, n_sys * 8));
+  if (X) HIPCHK(hs.down(X, dX_, out_elems * 8));
+  if (dX) HIPCHK(hs.down(dX, ddX, out_elems * 8));
+  if (info) HIPCHK(hs.down(info, d_info, n_sys * 4));
+  int nbad = 0;
+  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
+  HIPCHK(hs.flush_out());
+  return nbad;
+}
+
+// Coarse scan with the nearest eigenpair: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
+// arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and solved by k_solve_gcf_nearest; chunks are
+// bounded by kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".
+static constexpr size_t kNearestScanBytes = size_t(1) << 30;
+static int scan_nearest_device(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const geo7[7],
+                               int64_t ld, const double* dPdrho, const double* theta0, const double* sigma, double* gam,
+                               double* lam, int32_t* idx, int32_t* info) {
+  auto bytes_of = [&](long L) {
+    const long S = L * n_theta0;
+    return ((size_t)3 * S * N + (size_t)long_waves(ctx, S) * ibs::nearest_ws_doubles(N)) * sizeof(double);
+  };
+  long L = n_lines;
+  if (ctx->opt.nearest_chunk_systems > 0) L = ctx->opt.nearest_chunk_systems / n_theta0;
+  else while (L > 1 && bytes_of(L) > kNearestScanBytes) L = (L + 1) / 2;
+  if (L < 1) L = 1;
+  if (L > n_lines) L = n_lines;
+  const size_t need = bytes_of(L);
+  if (ensure_long_ws(ctx, need) != 0) {
+    (void)hipGetLastError();
+    return fail(IBS_ERR_HIP, "gamma_scan_nearest: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
+                "which could not be allocated", L, n_theta0, N, need);
+  }
+  const long S_max = L * n_theta0;
+  const int nw = long_waves(ctx, S_max);
+  double* w = static_cast<double*>(ctx->long_ws);
+  double* work = w; w += (size_t)nw * ibs::nearest_ws_doubles(N);
+  double* G = w; w += (size_t)S_max * N; double* C = w; w += (size_t)S_max * N; double* F = w;
+  for (long l0 = 0; l0 < n_lines; l0 += L) {
+    const int Lc = (int)(n_lines - l0 < L ? n_lines - l0 : L);
+    const long s0 = l0 * n_theta0, S = (long)Lc * n_theta0;
+    ibs::ScanArgs<double> sa{};
+    sa.n_lines = Lc; sa.n_theta0 = n_theta0; sa.N = N; sa.h = h; sa.ld = ld; sa.t0_stride = 0;
+    sa.bmag = geo7[0] + l0 * ld; sa.gradpar = geo7[1] + l0 * ld; sa.cvdrift = geo7[2] + l0 * ld; sa.cvdrift0 = geo7[3] + l0 * ld;
+    sa.gds2 = geo7[4] + l0 * ld; sa.gds21 = geo7[5] + l0 * ld; sa.gds22 = geo7[6] + l0 * ld;
+    sa.dPdrho = dPdrho + l0; sa.theta0 = theta0;
+    HIPCHK(ibs::launch_assemble_long(sa, G, C, F, nullptr, nullptr, nullptr, ctx->stream));
+    ibs::NearestArgs a{};
+    a.n_sys = S; a.N = N; a.h = h; a.g = G; a.c = C; a.f = F; a.gh = nullptr; a.ld = N; a.sigma = sigma + s0;
+    a.lam = lam ? lam + s0 : nullptr; a.idx = idx ? idx + s0 : nullptr; a.gam = gam ? gam + s0 : nullptr; a.X = nullptr; a.dX = nullptr;
+    a.info = info ? info + s0 : nullptr;
+    a.work = work; a.work_doubles = (size_t)nw * ibs::nearest_ws_doubles(N); a.n_waves = nw;
+    HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
+  }
+  return 0;
+}
+
+int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
+                               const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
+                               const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                               const double* dPdrho, const double* theta0, const double* sigma, double* gam, double* lam,
+                               int32_t* idx, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_lines < 0 || n_theta0 < 0 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho ||
+      !theta0 || !sigma || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  if (mem != IBS_MEM_HOST)
+    return scan_nearest_device(ctx, n_lines, n_theta0, N, h, src, ld, dPdrho, theta0, sigma, gam, lam, idx, info);
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
+  const size_t need = 7 * pad256(in_elems * 8) + pad256(n_lines * 8) + pad256(n_theta0 * 8) + 3 * pad256(n_sys * 8) +
+                      2 * pad256(n_sys * 4) + 4096;
+  if (int r = ensure_ws(ctx, need)) return r;
+  Arena ar(ctx);
+  HostStage hs(ctx, need);
+  const double* dev[7];
+  for (int k = 0; k < 7; ++k) {
+    double* d = ar.take<double>(in_elems);
+    HIPCHK(hs.up(src[k], in_elems * 8, d));
+    dev[k] = d;
+  }
+  double* ddP = ar.take<double>(n_lines); double* dt0 = ar.take<double>(n_theta0); double* dsig = ar.take<double>(n_sys);
+  HIPCHK(hs.up(dPdrho, (size_t)n_lines * 8, ddP));
+  HIPCHK(hs.up(theta0, (size_t)n_theta0 * 8, dt0));
+  HIPCHK(hs.up(sigma, n_sys * 8, dsig));
+  HIPCHK(hs.flush_in());
+  double* dgam = gam ? ar.take<double>(n_sys) : nullptr; double* dlam = lam ? ar.take<double>(n_sys) : nullptr;
+  int* didx = idx ? ar.take<int>(n_sys) : nullptr;
+  int* d_info = ar.take<int>(n_sys); int* d_nbad = ar.take<int>(1);
+  if (int r = scan_nearest_device(ctx, n_lines, n_theta0, N, h, dev, ld, ddP, dt0, dsig, dgam, dlam, didx, d_info)) return r;
+  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, d_info, d_nbad);
+  if (gam) HIPCHK(hs.down(gam, dgam, n_sys * 8));
+  if (lam) HIPCHK(hs.down(lam, dlam, n_sys * 8));
+  if (idx) HIPCHK(hs.down(idx, didx, n_sys * 4));
+  if (info) HIPCHK(hs.down(info, d_info, n_sys * 4));
+  int nbad = 0;
+  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
+  HIPCHK(hs.flush_out());
+  return nbad;
 }
 
 // Geometry-fed scan on a grid beyond 2050 points: the (g, c, f) rows of every (line, theta0) system -- and their theta0 tangents when

@@ -57,6 +57,16 @@ struct LongGcfArgs {
   double* work; int n_waves;                // n_waves * 3 * N doubles of workspace; the grid is min(n_sys, n_waves) waves
 };
 hipError_t launch_gcf_long(const LongGcfArgs& a, hipStream_t st);
+// the eigenpair nearest sigma[sys] (ibs_nearest.hip), FP64, any N in [66, kMaxLongN]: one wave per system, persistent grid of
+// min(n_sys, n_waves) waves, each with nearest_ws_doubles(N) doubles of workspace at work + wave * nearest_ws_doubles(N)
+constexpr size_t nearest_ws_doubles(int N) { return 3 * (size_t)N; }
+struct NearestArgs {
+  long n_sys; int N; double h;
+  const double *g, *c, *f, *gh; long ld; const double* sigma;     // gh: null = mean of neighbouring g
+  double* lam; int* idx; double* gam; double* X; double* dX; int* info;
+  double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
+};
+hipError_t launch_gcf_nearest(const NearestArgs& a, hipStream_t st);
 hipError_t launch_sturm_long(const SturmArgs<double>& a, hipStream_t st);
 hipError_t launch_sturm_div(const SturmArgs<double>& a, hipStream_t st);     // lanes as systems, division form, any N
 template <typename T> struct ScanArgs;

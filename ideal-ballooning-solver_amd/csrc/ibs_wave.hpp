@@ -409,6 +409,28 @@ __device__ __forceinline__ bool multisect(CountF&& count, T lo, T hi, T normA, T
   lam = T(0.5) * (lo + hi);
   return ok;
 }
+// The same multisection for the k-th largest eigenvalue (k >= 1; k = 1 is lam_max): keeps the interval between the highest shift
+// with at least k eigenvalues above it and the next shift.  A bracket that does not hold it is moved and widened as above.
+template <typename T, class CountF>
+__device__ __forceinline__ bool multisect_k(CountF&& count, int k, T lo, T hi, T normA, T stop_eps, int lane, T& lam, int& passes) {
+  const T epsA = Eps<T>::v * normA;
+  bool ok = false;
+  passes = 0;
+  while (passes < 24) {
+    ++passes;
+    const T w = hi - lo;
+    const T sig = lane == kWave - 1 ? hi : xfma(T(lane) * T(1.0 / 63.0), w, lo);
+    const int cnt = count(sig);
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(cnt >= k);
+    if (!(m & 1ull)) { hi = lo; lo = lo - T(64) * w; continue; }          // lam_k < lo
+    const int top = 63 - __builtin_clzll(m);                              // the highest shift with k eigenvalues above it
+    if (top == kWave - 1) { lo = hi; hi = hi + T(64) * w; continue; }     // lam_k >= hi
+    lo = readlane_t(sig, top); hi = readlane_t(sig, top + 1);
+    if (!(hi - lo > stop_eps * epsA)) { ok = true; break; }
+  }
+  lam = T(0.5) * (lo + hi);
+  return ok;
+}
 // ... on the rows of `src` in memory, to 2 eps ||A||
 template <typename T, class Src>
 __device__ __forceinline__ bool multisect_division(const Src& src, int N, T h, T lo, T hi, T normA, int lane, T& lam, int& passes) {

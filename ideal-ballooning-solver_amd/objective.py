@@ -64,7 +64,8 @@ def chunk_cuts(n, n_chunks, growth=1.0):
 
 class AdjointStep:
     """The ballooning work of ONE optimizer iteration for all equilibria of the step at once: the base equilibrium and one
-    per boundary DOF (BASELINE configs[3]: 73 x 5 surfaces x 24 alpha x 15 theta0, N = 969).
+    per boundary DOF (BASELINE configs[3]: 73 x 5 surfaces x 24 alpha x 15 theta0, N = 969).  Like the scan driver it works on
+    lam_max's eigenpair throughout (the nearest-sigma mode, operators.py eigenpair="nearest", is the drop-ins' alone).
 
     Upstream this is ball_submit.py:64-95 (one `srun ball_scan.py iter dof ngroups` per DOF-perturbed equilibrium, each
     running vmec_splines -> coarse scan -> argmax -> L-BFGS-B -> final solve, ball_scan.py:190-347) followed by

@@ -10,6 +10,12 @@ have returned another eigenpair (or lam_max itself, if it happens to be the near
 hiding it: the solve carries the informational status bit 4 (include/ibs.h), `gamma_ball_full(..., info=d)` fills
 d["above_sigma0"], and a NearestSigmaWarning is issued.  All eigen-work runs on the GPU through libibs_hip.so; the only host
 arithmetic is the elementwise coefficient formulas returned to the caller as (g, c, f).
+
+Two modes, chosen by `eigenpair`:
+  "max"      (the default) lam_max's eigenpair -- the physical one: the largest growth rate of the line, what the scan driver
+             (scan.py) and AdjointStep use throughout;
+  "nearest"  the eigenpair nearest sigma0 -- the FAITHFUL one: what utils.py:1597 returns on every input, lam_max >= sigma0
+             included (include/ibs.h: ibs_solve_gcf_nearest_f64).  No NearestSigmaWarning: there is nothing to report.
 """
 import warnings
 
@@ -52,14 +58,21 @@ def _report_sigma(r, sigma0, info):
                       "nearest sigma0 here, this library the largest eigenvalue's" % (lam, sigma0), NearestSigmaWarning, stacklevel=3)
 
 
-def gamma_ball_full(dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, vguess=None, sigma0=0.42, ctx=None, info=None):
+def gamma_ball_full(dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, vguess=None, sigma0=0.42, ctx=None, info=None, eigenpair="max"):
     """reference: utils.py:1550-1624.  Returns (gam, X, dX, g, c, f) with the same meaning.
     Uniform grids go through the fused geometry-fed kernel; a non-uniform theta_PEST is regridded exactly
     as upstream (np.interp of g, c, f onto the uniform grid, g interpolated at the uniform half points,
     utils.py:1567-1576 -- elementwise host glue) and solved by the raw (g, gh, c, f) kernel.
-    The returned eigenpair is lam_max's; upstream's is the one nearest sigma0 -- the same whenever lam_max < sigma0.  Otherwise
-    (module docstring) a NearestSigmaWarning is issued; info (optional dict) receives lam (the matrix eigenvalue), above_sigma0,
-    status, sweeps."""
+    eigenpair="max": the returned eigenpair is lam_max's; upstream's is the one nearest sigma0 -- the same whenever
+    lam_max < sigma0.  Otherwise (module docstring) a NearestSigmaWarning is issued; info (optional dict) receives lam (the matrix
+    eigenvalue), above_sigma0, status, sweeps.
+    eigenpair="nearest": the eigenpair nearest sigma0, as upstream, from the host-side (g, c, f) (regridded as above on a non-uniform
+    grid) by ibs_solve_gcf_nearest_f64; info receives lam, idx (eigenvalues above lam: 0 = lam_max), status (bit 5: the two
+    eigenvalues about sigma0 are equally near, the larger is returned), sweeps (multisection passes)."""
+    if eigenpair == "nearest":
+        return _gamma_ball_nearest(ctx or default_context(), dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, sigma0, info)
+    if eigenpair != "max":
+        raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
     ctx = ctx or default_context()
     ctx.set_option("sigma0", float(sigma0))
     try:
@@ -97,12 +110,39 @@ def _gamma_ball_full(ctx, dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, sigma0,
     return float(r["gam"][0]), r["X"][0], r["dX"][0], g_u, c_u, f_u
 
 
+def _gamma_ball_nearest(ctx, dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, sigma0, info):
+    theta = np.asarray(theta_PEST, dtype=np.float64)
+    B = np.asarray(B, dtype=np.float64)
+    gradpar = np.asarray(gradpar, dtype=np.float64)
+    cvdrift = np.asarray(cvdrift, dtype=np.float64)
+    gds2 = np.asarray(gds2, dtype=np.float64)
+    N = len(B)
+    gp = np.abs(gradpar)
+    g = gp * gds2 / B                         # utils.py:1560
+    c = -1 * dPdrho * cvdrift * 1 / (gp * B)  # utils.py:1561
+    f = gds2 / B ** 2 * 1 / (gp * B)          # utils.py:1562
+    if is_uniform(theta):
+        h, gh = uniform_spacing(theta), None
+    else:
+        tu = np.linspace(theta[0], theta[-1], N)                       # utils.py:1565
+        g, c, f = np.interp(tu, theta, g), np.interp(tu, theta, c), np.interp(tu, theta, f)      # utils.py:1567-1571
+        th_half = (tu[:-1] + tu[1:]) / 2                                # utils.py:1574
+        h = np.diff(th_half)[2]                                         # utils.py:1575
+        gh = np.zeros((1, N))
+        gh[0, :-1] = np.interp(th_half, theta, gp * gds2 / B)           # utils.py:1576
+    r = ctx.solve_gcf_nearest(h, g[None], c[None], f[None], float(sigma0), gh=gh, want_X=True, want_info=True)
+    if info is not None:
+        word = int(r["info"][0])
+        info.update(lam=float(r["lam"][0]), idx=int(r["idx"][0]), status=word >> 16, sweeps=word & 0xffff)
+    return float(r["gam"][0]), r["X"][0], r["dX"][0], g, c, f
+
+
 def dPdrho_of(cvdrift, gbdrift, bmag):
     """ball_scan.py:262 / utils.py:1657"""
     return -1.0 * 0.5 * np.mean((cvdrift - gbdrift) * bmag ** 2)
 
 
-def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004):
+def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004, eigenpair="max"):
     """Factory for a drop-in `obj_w_grad(x0, vs, rho_val, theta, vguess00, sigma00=0.42)` (utils.py:1632).
 
     `fieldlines(vs, rho_val, alphas, theta)` supplies the geometry exactly as the reference gets it from
@@ -110,7 +150,16 @@ def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004):
     (3, 8, N) in scan.GEO_ORDER.  With the reference available:
         fl = lambda vs, s, al, th: np.stack([[getattr(utils.vmec_fieldlines(vs, s, al, theta1d=th), k)[0][i]
                                              for k in GEO_ORDER] for i in range(3)])
-    Returns (-gam, array([-dgam/dalpha, -dgam/dtheta0])) like utils.py:1728 (scipy jac=True convention)."""
+    Returns (-gam, array([-dgam/dalpha, -dgam/dtheta0])) like utils.py:1728 (scipy jac=True convention).
+    eigenpair="max": lam_max's eigenpair, one fused ibs_obj_w_grad_f64 call (sigma00 unused).  eigenpair="nearest": the eigenpair
+    nearest sigma00, as upstream on every input: the centre line is solved by ibs_solve_gcf_nearest_f64, the alpha tangents (right
+    minus left line, each with its own dPdrho, over del_alpha: utils.py:1683-1718) and theta0 tangents (utils.py:1669-1673) are built
+    on the host and both derivatives taken by ibs_hf_grad_f64 (utils.py:1676-1680, 1721-1725)."""
+    if eigenpair == "nearest":
+        return _make_obj_w_grad_nearest(fieldlines, ctx, del_alpha)
+    if eigenpair != "max":
+        raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
+
     def obj_w_grad(x0, vs, rho_val, theta, vguess00=None, sigma00=0.42):
         c = ctx or default_context()
         alpha_val, theta0_val = float(x0[0]), float(x0[1])
@@ -118,6 +167,40 @@ def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004):
         geo = np.asarray(fieldlines(vs, rho_val, al, theta), dtype=np.float64)
         val, jac = c.obj_w_grad(uniform_spacing(theta), geo[None], np.array([theta0_val]), del_alpha)
         return float(val[0]), np.asarray(jac[0], dtype=np.float64)
+    return obj_w_grad
+
+
+def _make_obj_w_grad_nearest(fieldlines, ctx, del_alpha):
+    def gcf_of(line, theta0):
+        bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, gbdrift = line
+        dP = dPdrho_of(cvdrift, gbdrift, bmag)                        # utils.py:1657 (each line its own)
+        cv = cvdrift + theta0 * cvdrift0                               # utils.py:1659
+        gd = gds2 + 2 * theta0 * gds21 + theta0 ** 2 * gds22           # utils.py:1660
+        gp = np.abs(gradpar)
+        return dP, gp * gd / bmag, -1 * dP * cv * 1 / (gp * bmag), gd / bmag ** 2 * 1 / (gp * bmag)   # utils.py:1560-1562
+
+    def obj_w_grad(x0, vs, rho_val, theta, vguess00=None, sigma00=0.42):
+        c = ctx or default_context()
+        alpha_val, theta0_val = float(x0[0]), float(x0[1])
+        al = np.array([alpha_val - 0.5 * del_alpha, alpha_val, alpha_val + 0.5 * del_alpha])
+        geo = np.asarray(fieldlines(vs, rho_val, al, theta), dtype=np.float64)
+        h = uniform_spacing(theta)
+        dP, g, cc, f = gcf_of(geo[1], theta0_val)
+        r = c.solve_gcf_nearest(h, g[None], cc[None], f[None], float(sigma00), want_X=True)
+        gam = float(r["gam"][0])
+        bmag, gradpar, _, cvdrift0, _, gds21, gds22, _ = geo[1]
+        gp = np.abs(gradpar)
+        dgd = 2 * gds21 + 2 * theta0_val * gds22
+        g_t = gp * dgd / bmag                                          # utils.py:1669
+        c_t = -1 * dP * cvdrift0 * 1 / (gp * bmag)                     # utils.py:1670
+        f_t = dgd / bmag ** 2 * 1 / (gp * bmag)                        # utils.py:1671-1673
+        _, g_r, c_r, f_r = gcf_of(geo[2], theta0_val)                  # utils.py:1683-1693, 1707-1709
+        _, g_l, c_l, f_l = gcf_of(geo[0], theta0_val)                  # utils.py:1695-1705, 1711-1713
+        g_a, c_a, f_a = (g_r - g_l) / del_alpha, (c_r - c_l) / del_alpha, (f_r - f_l) / del_alpha    # utils.py:1716-1718
+        two = lambda a: np.ascontiguousarray(np.broadcast_to(a, (2, len(a))))
+        jac = c.hf_grad(two(r["X"][0]), two(r["dX"][0]), two(f), np.stack([g_a, g_t]), np.stack([c_a, c_t]),
+                        np.stack([f_a, f_t]), np.array([gam, gam]))
+        return -1 * gam, np.array([-1 * float(jac[0]), -1 * float(jac[1])])                         # utils.py:1728
     return obj_w_grad
 
 

@@ -74,7 +74,9 @@ def gather_surfaces(local, n_surf, rank, world, dist=None, device=None, ctx=None
 
 
 class BallooningScan:
-    """Coarse (alpha, theta0) scan -> argmax -> L-BFGS-B refinement -> final solve, per surface."""
+    """Coarse (alpha, theta0) scan -> argmax -> L-BFGS-B refinement -> final solve, per surface.
+    Every stage returns lam_max's eigenpair (the physical growth rate); the nearest-sigma mode of the drop-ins
+    (operators.py: eigenpair="nearest") is not used here."""
 
     def __init__(self, ctx, fieldlines, theta, rho_arr, nalpha=24, ntheta0=15, del_alpha=0.004,
                  rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None):

@@ -204,6 +204,67 @@ class Context:
             out.update(info=info)
         return out
 
+    def _sigma_rows(self, ar, sigma, shape, ref):
+        """sigma as a float64 array of `shape` in the memory kind of the call (a scalar is broadcast)"""
+        if ref is not None:
+            import torch
+            t = torch.as_tensor(sigma, dtype=torch.float64, device=ref.device)
+            return ar.inp(t.expand(shape).contiguous() if t.dim() == 0 else t.reshape(shape))
+        a = np.asarray(sigma.detach().cpu().numpy() if _is_torch(sigma) else sigma, dtype=np.float64)
+        return ar.inp(np.broadcast_to(a, shape) if a.ndim == 0 else a.reshape(shape))
+
+    def solve_gcf_nearest(self, h, g, c, f, sigma, gh=None, want_X=False, want_info=False):
+        """the eigenpair NEAREST sigma (ibs_solve_gcf_nearest_f64: what utils.py:1597's eigs(A, 1, sigma=sigma0) returns).
+        g, c, f (and gh, optional half-grid g as in solve_gcf): (n_sys, N); sigma: a scalar or (n_sys,).
+        Returns dict(lam, idx, gam[, X, dX][, info], nbad): idx = the number of eigenvalues above lam (0 = lam_max, -1 = invalid
+        data); info status bit 5 = the two eigenvalues about sigma are equally near within 4 N eps ||A|| (the larger is returned)."""
+        ar = _Args()
+        n_sys, N = g.shape
+        pg, pc, pf = ar.inp(g), ar.inp(c), ar.inp(f)
+        pgh = ar.inp(gh) if gh is not None else C.c_void_p(None)
+        ref = g if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        psig = self._sigma_rows(ar, sigma, (n_sys,), ref)
+        lam, plam = ar.out((n_sys,), ref)
+        idx, pidx = ar.out((n_sys,), ref, dtype=np.int32)
+        gam, pgam = ar.out((n_sys,), ref)
+        X, pX = ar.out((n_sys, N), ref, want=want_X)
+        dX, pdX = ar.out((n_sys, N), ref, want=want_X)
+        info, pinfo = ar.out((n_sys,), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_solve_gcf_nearest_f64(self._h, n_sys, N, float(h), pg, pgh, pc, pf, N, psig, plam, pidx, pgam,
+                                                       pX, pdX, pinfo, ar.mem), "ibs_solve_gcf_nearest_f64")
+        out = dict(lam=lam, idx=idx, gam=gam, nbad=rc)
+        if want_X:
+            out.update(X=X, dX=dX)
+        if want_info:
+            out.update(info=info)
+        return out
+
+    def gamma_scan_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma, want_info=False):
+        """the coarse scan of ball_scan.py:248-273 with the eigenpair nearest sigma, as upstream (sigma = 1.0 there: ball_scan.py:230);
+        ibs_gamma_scan_nearest_f64.  Geometry arrays (n_lines, N); dPdrho (n_lines,); theta0 (n_theta0,); sigma a scalar or
+        (n_lines, n_theta0).  Returns dict(gam, lam, idx[, info], nbad) shaped (n_lines, n_theta0)."""
+        ar = _Args()
+        n_lines, N = bmag.shape
+        n_t0 = int(theta0.shape[0])
+        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
+        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
+        ref = bmag if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        psig = self._sigma_rows(ar, sigma, (n_lines, n_t0), ref)
+        gam, pgam = ar.out((n_lines, n_t0), ref)
+        lam, plam = ar.out((n_lines, n_t0), ref)
+        idx, pidx = ar.out((n_lines, n_t0), ref, dtype=np.int32)
+        info, pinfo = ar.out((n_lines, n_t0), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_gamma_scan_nearest_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, psig, pgam, plam,
+                                                        pidx, pinfo, ar.mem), "ibs_gamma_scan_nearest_f64")
+        out = dict(gam=gam, lam=lam, idx=idx, nbad=rc)
+        if want_info:
+            out.update(info=info)
+        return out
+
     # ---- geometry x theta0 scan ---------------------------------------------------------------
     def gamma_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0,
                    want_X=False, want_dtheta0=False, want_info=False, lam_guess=None, guess_width=None):

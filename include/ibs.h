@@ -33,7 +33,13 @@
  *            e_r + e_{r+1}) / f_r of utils.py:1584-1592's rows;
  *     bit 4, only with option "sigma0" set and both lam and info requested: lam_max >= sigma0.  The reference's ARPACK call returns
  *            the eigenpair NEAREST sigma0 (utils.py:1597); this library always returns lam_max's.  They are the same eigenpair
- *            whenever lam_max < sigma0 -- and only then: this bit marks the one case in which upstream may have returned another).
+ *            whenever lam_max < sigma0 -- and only then: this bit marks the one case in which upstream may have returned another);
+ *     bit 5, nearest-sigma entry points (ibs_solve_gcf_nearest_f64, ibs_gamma_scan_nearest_f64): "nearest not determined" -- the
+ *            eigenvalues on either side of sigma lie at distances that differ by less than 4 N eps ||A||; the larger one is returned
+ *            (these entry points never set bit 3, whose re-close diagnostic occupies bits 5 and up on the lam_max entry points).
+ *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
+ *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
+ *     for every sigma, lam_max's among them; they never set bit 4.
  */
 #ifndef IBS_H
 #define IBS_H
@@ -157,6 +163,24 @@ int ibs_solve_gcfh_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const d
 int ibs_solve_gcf_f32(ibs_ctx* ctx, int64_t n_sys, int32_t N, float h, const float* g, const float* c,
                       const float* f, int64_t ld, float* lam, float* gam, float* X, float* dX,
                       int32_t* info, int32_t mem);
+
+/* The eigenpair NEAREST sigma[sys] (utils.py:1597: eigs(A, 1, sigma=sigma0)); gh may be NULL (mean of neighbouring g).
+ * Arrays as in ibs_solve_gcf_f64 / ibs_solve_gcfh_f64; sigma[n_sys]; idx[n_sys] (conventions above; optional).  FP64, any odd N in
+ * [66, 65537], one wavefront per system in division form (csrc/ibs_nearest.hip): |lam - lam_nearest| <= 4 N eps ||A||.  info: bits 0-15
+ * = multisection passes in total (two to three multisections per system), status bits 1 (also: sigma not finite) and 5.
+ * X is scaled so that its entry of largest magnitude is +1 (an interior eigenfunction changes sign; lam_max's does not). */
+int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
+                              const double* c, const double* f, int64_t ld, const double* sigma, double* lam,
+                              int32_t* idx, double* gam, double* X, double* dX, int32_t* info, int32_t mem);
+/* the coarse scan of ball_scan.py:248-273 with upstream's shift: sigma[n_lines][n_theta0] (1.0 there, ball_scan.py:230 / 269).
+ * Arrays as in ibs_gamma_scan_f64; outputs [n_lines][n_theta0], all optional.  The (g, c, f) rows of whole lines are assembled in a
+ * workspace of about 1 GiB at most and solved by the kernel of ibs_solve_gcf_nearest_f64, chunk after chunk (option
+ * "nearest_chunk_systems" sets the chunk instead); a chunk of one line that cannot be allocated fails with the bytes it needs. */
+int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
+                               const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
+                               const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                               const double* dPdrho, const double* theta0, const double* sigma, double* gam, double* lam,
+                               int32_t* idx, int32_t* info, int32_t mem);
 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
