@@ -165,6 +165,17 @@ struct Arena {  // carve device buffers out of the context workspace
   }
 };
 size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
+// Device buffers of one host-pointer call, sized by the very sequence of take() calls that carves them: a first pass without a
+// buffer only counts (Carve{nullptr}), the second carves ctx->ws.
+struct Carve {
+  char* base; size_t off = 0;
+  template <typename T> T* take(size_t n) {
+    off = pad256(off);
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += n * sizeof(T);
+    return p;
+  }
+};
 
 int ensure_long_ws(ibs_ctx* c, size_t bytes) {
   if (bytes <= c->long_ws_bytes) return 0;
@@ -1001,6 +1012,123 @@ int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
   if (lam) HIPCHK(hs.down(lam, dlam, n_sys * 8));
   if (idx) HIPCHK(hs.down(idx, didx, n_sys * 4));
   if (info) HIPCHK(hs.down(info, d_info, n_sys * 4));
+  int nbad = 0;
+  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
+  HIPCHK(hs.flush_out());
+  return nbad;
+}
+
+// ---- geometry-fed points with the eigenpair nearest sigma[p] (ibs_nearest_grad.hip): the refinement's objective + gradient and
+// the final solve of ball_scan.py:305-339 in upstream's mode, one wave per point on the persistent grid of long_waves()
+// device pointers: the per-wave workspace (ibs::nearest_points_ws) in ctx->long_ws
+static int points_nearest_device(ibs_ctx* ctx, ibs::NearestPointsArgs a, bool grad) {
+  const int nw = long_waves(ctx, a.n_pts);
+  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::nearest_points_ws(a.N, grad).total * sizeof(double))) return r;
+  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+  HIPCHK(grad ? ibs::launch_obj_w_grad_nearest(a, ctx->stream) : ibs::launch_points_nearest(a, ctx->stream));
+  return 0;
+}
+
+int ibs_obj_w_grad_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
+                               const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
+                               double* lam, int32_t* idx, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_pts < 0 || !geo || !theta0 || !sigma || !val || !jac || ld < N || !(del_alpha > 0))
+    return fail(IBS_ERR_ARG, "bad arguments (n_pts=%d ld=%lld N=%d del_alpha=%g)", n_pts, (long long)ld, N, del_alpha);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_pts == 0) return 0;
+  ON_DEVICE(ctx);
+  ibs::NearestPointsArgs a{};
+  a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld; a.del_alpha = del_alpha;
+  if (mem != IBS_MEM_HOST) {
+    a.geo = geo; a.theta0 = theta0; a.sigma = sigma; a.val = val; a.jac = jac; a.lam = lam; a.idx = idx; a.info = info;
+    return points_nearest_device(ctx, a, true);
+  }
+  const size_t n = (size_t)n_pts, geo_elems = n * 3 * 8 * (size_t)ld;
+  double *dgeo, *dt0, *dsig, *dval, *djac, *dlam;
+  int *didx, *d_info, *d_nbad;
+  auto carve = [&](Carve& cv) {          // inputs first, then the outputs: each side one contiguous span of HostStage
+    dgeo = cv.take<double>(geo_elems); dt0 = cv.take<double>(n); dsig = cv.take<double>(n);
+    dval = cv.take<double>(n); djac = cv.take<double>(2 * n); dlam = lam ? cv.take<double>(n) : nullptr;
+    didx = idx ? cv.take<int>(n) : nullptr; d_info = cv.take<int>(n); d_nbad = cv.take<int>(1);
+  };
+  Carve sz{nullptr};
+  carve(sz);
+  if (int r = ensure_ws(ctx, sz.off)) return r;
+  Carve cv{static_cast<char*>(ctx->ws)};
+  carve(cv);
+  HostStage hs(ctx, sz.off);
+  HIPCHK(hs.up(geo, geo_elems * 8, dgeo));
+  HIPCHK(hs.up(theta0, n * 8, dt0));
+  HIPCHK(hs.up(sigma, n * 8, dsig));
+  HIPCHK(hs.flush_in());
+  a.geo = dgeo; a.theta0 = dt0; a.sigma = dsig; a.val = dval; a.jac = djac; a.lam = dlam; a.idx = didx; a.info = d_info;
+  if (int r = points_nearest_device(ctx, a, true)) return r;
+  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long)n, d_info, d_nbad);
+  HIPCHK(hs.down(val, dval, n * 8));
+  HIPCHK(hs.down(jac, djac, n * 16));
+  if (lam) HIPCHK(hs.down(lam, dlam, n * 8));
+  if (idx) HIPCHK(hs.down(idx, didx, n * 4));
+  if (info) HIPCHK(hs.down(info, d_info, n * 4));
+  int nbad = 0;
+  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
+  HIPCHK(hs.flush_out());
+  return nbad;
+}
+
+int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
+                                 const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
+                                 const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, const double* sigma,
+                                 double* gam, double* lam, int32_t* idx, double* X, double* dX, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_pts < 0 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho || !theta0 || !sigma ||
+      !gam || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_pts=%d ld=%lld N=%d)", n_pts, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_pts == 0) return 0;
+  ON_DEVICE(ctx);
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  ibs::NearestPointsArgs a{};
+  a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld;
+  if (mem != IBS_MEM_HOST) {
+    for (int k = 0; k < 7; ++k) a.geo7[k] = src[k];
+    a.dPdrho = dPdrho; a.theta0 = theta0; a.sigma = sigma; a.gam = gam; a.lam = lam; a.idx = idx; a.X = X; a.dX = dX; a.info = info;
+    return points_nearest_device(ctx, a, false);
+  }
+  const size_t n = (size_t)n_pts, in_elems = n * (size_t)ld, out_elems = n * (size_t)N;
+  double* dev[7];
+  double *ddP, *dt0, *dsig, *dgam, *dlam, *dX_, *ddX;
+  int *didx, *d_info, *d_nbad;
+  auto carve = [&](Carve& cv) {          // inputs first, then the outputs: each side one contiguous span of HostStage
+    for (int k = 0; k < 7; ++k) dev[k] = cv.take<double>(in_elems);
+    ddP = cv.take<double>(n); dt0 = cv.take<double>(n); dsig = cv.take<double>(n);
+    dgam = cv.take<double>(n); dlam = lam ? cv.take<double>(n) : nullptr; didx = idx ? cv.take<int>(n) : nullptr;
+    dX_ = X ? cv.take<double>(out_elems) : nullptr; ddX = dX ? cv.take<double>(out_elems) : nullptr;
+    d_info = cv.take<int>(n); d_nbad = cv.take<int>(1);
+  };
+  Carve sz{nullptr};
+  carve(sz);
+  if (int r = ensure_ws(ctx, sz.off)) return r;
+  Carve cv{static_cast<char*>(ctx->ws)};
+  carve(cv);
+  HostStage hs(ctx, sz.off);
+  for (int k = 0; k < 7; ++k) HIPCHK(hs.up(src[k], in_elems * 8, dev[k]));
+  HIPCHK(hs.up(dPdrho, n * 8, ddP));
+  HIPCHK(hs.up(theta0, n * 8, dt0));
+  HIPCHK(hs.up(sigma, n * 8, dsig));
+  HIPCHK(hs.flush_in());
+  for (int k = 0; k < 7; ++k) a.geo7[k] = dev[k];
+  a.dPdrho = ddP; a.theta0 = dt0; a.sigma = dsig; a.gam = dgam; a.lam = dlam; a.idx = didx; a.X = dX_; a.dX = ddX; a.info = d_info;
+  if (int r = points_nearest_device(ctx, a, false)) return r;
+  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long)n, d_info, d_nbad);
+  HIPCHK(hs.down(gam, dgam, n * 8));
+  if (lam) HIPCHK(hs.down(lam, dlam, n * 8));
+  if (idx) HIPCHK(hs.down(idx, didx, n * 4));
+  if (X) HIPCHK(hs.down(X, dX_, out_elems * 8));
+  if (dX) HIPCHK(hs.down(dX, ddX, out_elems * 8));
+  if (info) HIPCHK(hs.down(info, d_info, n * 4));
   int nbad = 0;
   HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
   HIPCHK(hs.flush_out());

@@ -67,6 +67,28 @@ struct NearestArgs {
   double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
 };
 hipError_t launch_gcf_nearest(const NearestArgs& a, hipStream_t st);
+// geometry-fed points with the eigenpair nearest sigma[p] (ibs_nearest_grad.hip): one wave per point on the persistent grid of
+// min(n_pts, n_waves) waves.  Per-wave workspace, in this order (NearestPointsWs: the kernel carves it, the host sizes it):
+// the solver's nearest_ws_doubles(N), the centre line's g, c, f rows, and with GRAD the eigenfunction X and dX.
+struct NearestPointsWs {
+  size_t work, g, c, f, X, dX, total;
+};
+constexpr NearestPointsWs nearest_points_ws(int N, bool grad) {
+  const size_t n = (size_t)N, w = nearest_ws_doubles(N);
+  return NearestPointsWs{0, w, w + n, w + 2 * n, grad ? w + 3 * n : 0, grad ? w + 4 * n : 0, w + (grad ? 5 : 3) * n};
+}
+struct NearestPointsArgs {
+  int n_pts, N; double h; long ld;
+  // GRAD: geo [n_pts][3][8][ld] (lines alpha - d/2, alpha, alpha + d/2 x bmag gradpar cvdrift cvdrift0 gds2 gds21 gds22 gbdrift);
+  // else geo7[k] [n_pts][ld] (the seven arrays of ibs_gamma_points_f64) and dPdrho [n_pts]
+  const double* geo; const double* geo7[7]; const double* dPdrho;
+  const double* theta0; const double* sigma; double del_alpha;      // theta0, sigma: [n_pts]
+  double *val, *jac;                                                  // GRAD: [n_pts], [n_pts][2] (required)
+  double* gam; double* lam; int* idx; double* X; double* dX; int* info;     // optional, except gam without GRAD
+  double* work; size_t work_doubles; long n_waves;                    // the launch refuses less than min(n_pts, n_waves) waves' worth
+};
+hipError_t launch_obj_w_grad_nearest(const NearestPointsArgs& a, hipStream_t st);
+hipError_t launch_points_nearest(const NearestPointsArgs& a, hipStream_t st);
 hipError_t launch_sturm_long(const SturmArgs<double>& a, hipStream_t st);
 hipError_t launch_sturm_div(const SturmArgs<double>& a, hipStream_t st);     // lanes as systems, division form, any N
 template <typename T> struct ScanArgs;

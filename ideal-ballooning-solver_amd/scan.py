@@ -73,19 +73,37 @@ def gather_surfaces(local, n_surf, rank, world, dist=None, device=None, ctx=None
     return gather_rows_tensor(t, n_surf, rank, world, dist, ctx).cpu().numpy()
 
 
+EIGENPAIRS = ("max", "nearest")
+# upstream's shifts (eigenpair="nearest"): the coarse scan (ball_scan.py:230, 269) and the final solve (ball_scan.py:337, the
+# default of gamma_ball_full); the refinement's is 1.3 |gam| + 0.05 of the surface's coarse maximum (ball_scan.py:289, 295)
+SIGMA_COARSE = 1.0
+SIGMA_FINAL = 0.42
+
+
+def check_eigenpair(eigenpair):
+    if eigenpair not in EIGENPAIRS:
+        raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
+    return eigenpair
+
+
 class BallooningScan:
     """Coarse (alpha, theta0) scan -> argmax -> L-BFGS-B refinement -> final solve, per surface.
-    Every stage returns lam_max's eigenpair (the physical growth rate); the nearest-sigma mode of the drop-ins
-    (operators.py: eigenpair="nearest") is not used here."""
+    eigenpair="max" (the default): every stage returns lam_max's eigenpair (the physical growth rate).  eigenpair="nearest":
+    every stage returns the eigenpair nearest upstream's shift, as ball_scan.py's eigs(A, 1, sigma=sigma0) does (utils.py:1597):
+    sigma = 1.0 in the coarse scan, 1.3 |gam| + 0.05 of the surface's coarse maximum in the refinement, 0.42 in the final solve.
+    The two agree wherever lam_max lies below the shifts; on strongly driven surfaces they differ."""
 
     def __init__(self, ctx, fieldlines, theta, rho_arr, nalpha=24, ntheta0=15, del_alpha=0.004,
-                 rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None):
+                 rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None, eigenpair="max"):
         """fieldlines: host geometry callable (see module docstring), or None together with
         tables=SurfaceTables (row F1): then the geometry is produced on `device` by the HIP geometry kernel and consumed
         there -- coarse scan, per-surface maximum, start points, refinement and final solve all stay in HBM and ONE small
         copy returns the rows.  surf_index[k] = index of surface k (of rho_arr) in `tables`; default: the surface of
         tables.s nearest to rho_arr[k].  Table sets that hold several equilibria (SurfaceTables.from_wouts: s repeats
-        per equilibrium) need the explicit index."""
+        per equilibrium) need the explicit index.
+        eigenpair: "max" or "nearest" (see the class docstring); anything else raises ValueError."""
+        self.eigenpair = check_eigenpair(eigenpair)
+        self.nearest = eigenpair == "nearest"
         self.ctx = ctx
         self.tables = tables
         self.device = device
@@ -130,9 +148,14 @@ class BallooningScan:
             r = self.ctx.fieldline_geometry(self.tables, surf, np.tile(self.alpha_scan, len(self.own)), self.theta,
                                             device=self.device)
             t0 = torch.from_numpy(self.theta0_scan).to(self.device)
-            out = self.ctx.gamma_scan(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, want_info=True)
-            # device-pointer calls are asynchronous and return no count of flagged systems: read the info words
-            nbad = int(((out["info"] >> 16) != 0).sum().item())
+            geo7 = [r["geo"][k] for k in range(7)]
+            if self.nearest:
+                out = self.ctx.gamma_scan_nearest(self.h, *geo7, r["dPdrho"], t0, SIGMA_COARSE, want_info=True)
+                nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())      # (bit 5, a tie, is informational)
+            else:
+                out = self.ctx.gamma_scan(self.h, *geo7, r["dPdrho"], t0, want_info=True)
+                # device-pointer calls are asynchronous and return no count of flagged systems: read the info words
+                nbad = int(((out["info"] >> 16) != 0).sum().item())
             if nbad:
                 raise IbsError("%d of %d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)"
                                % (nbad, out["info"].numel()))
@@ -142,35 +165,50 @@ class BallooningScan:
             return np.zeros((0, len(self.alpha_scan), len(self.theta0_scan)))
         geo = np.concatenate(geos, axis=0)                                 # (n_own*nalpha, 8, N)
         dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
-        r = self.ctx.gamma_scan(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan)
+        geo7 = [np.ascontiguousarray(geo[:, k]) for k in range(7)]
+        if self.nearest:
+            r = self.ctx.gamma_scan_nearest(self.h, *geo7, dP, self.theta0_scan, SIGMA_COARSE)
+        else:
+            r = self.ctx.gamma_scan(self.h, *geo7, dP, self.theta0_scan)
         if r.get("nbad", 0):
             raise IbsError("%d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)" % r["nbad"])
         return np.asarray(r["gam"]).reshape(len(self.own), len(self.alpha_scan), len(self.theta0_scan))
 
-    # -- A6: objective with gradient at one point of one surface (utils.py:1632-1728)
-    def obj_w_grad(self, x, s):
+    # -- A6: objective with gradient at one point of one surface (utils.py:1632-1728); sigma0: the shift of eigenpair="nearest"
+    def obj_w_grad(self, x, s, sigma0=None):
         a, t0 = float(x[0]), float(x[1])
         d = self.del_alpha
         geo = np.asarray(self.fieldlines(s, np.array([a - 0.5 * d, a, a + 0.5 * d])))
-        val, jac = self.ctx.obj_w_grad(self.h, geo[None], np.array([t0]), d)
+        if self.nearest:
+            val, jac = self.ctx.obj_w_grad_nearest(self.h, geo[None], np.array([t0]), float(sigma0), d)
+            if not (np.isfinite(val[0]) and np.all(np.isfinite(jac[0]))):
+                raise IbsError("the objective's solve at (alpha, theta0) = (%g, %g) was flagged (invalid data or iteration cap)" % (a, t0))
+        else:
+            val, jac = self.ctx.obj_w_grad(self.h, geo[None], np.array([t0]), d)
         return float(val[0]), np.asarray(jac[0], dtype=np.float64)
 
-    # -- A7: refinement + final solve (ball_scan.py:305-339)
-    def refine(self, s, a0, t0):
+    # -- A7: refinement + final solve (ball_scan.py:305-339); sigma0: the refinement's shift of eigenpair="nearest" (pick_start)
+    def refine(self, s, a0, t0, sigma0=None):
         from scipy.optimize import minimize
-        res = minimize(self.obj_w_grad, x0=(a0, t0), args=(s,), jac=True,
+        res = minimize(self.obj_w_grad, x0=(a0, t0), args=(s, sigma0) if self.nearest else (s,), jac=True,
                        bounds=((0.0, np.pi), (0.0, 0.5 * np.pi)),
                        options={"ftol": 5.0e-11, "gtol": 2.0e-08, "maxiter": 30})
         a, t = float(res.x[0]), float(res.x[1])
         geo = np.asarray(self.fieldlines(s, np.array([a])))[0]
         dP = -0.5 * np.mean((geo[2] - geo[7]) * geo[0] ** 2)
+        if self.nearest:
+            r = self.ctx.gamma_points_nearest(self.h, *[geo[k][None] for k in range(7)], np.array([dP]), np.array([t]), SIGMA_FINAL)
+            if r.get("nbad", 0):
+                raise IbsError("the final solve at (alpha, theta0) = (%g, %g) was flagged (invalid data or iteration cap)" % (a, t))
+            return t, a, float(np.asarray(r["gam"])[0]), res
         r = self.ctx.gamma_scan(self.h, *[geo[k][None] for k in range(7)], np.array([dP]), np.array([t]))
         return t, a, float(np.asarray(r["gam"])[0, 0]), res
 
     # -- F2: all owned surfaces refined in lockstep; every evaluation of every surface is ONE batched launch
-    def batched_obj_w_grad(self, surf_idx, X):
+    def batched_obj_w_grad(self, surf_idx, X, sigma=None):
         """objective and gradient at X[k] = (alpha, theta0) of surface surf_idx[k] for all k at once
-        (device geometry for the 3 n lines, then the fused obj_w_grad kernel).  Returns (val (n,), jac (n, 2))."""
+        (device geometry for the 3 n lines, then the fused obj_w_grad kernel; eigenpair="nearest": the eigenpair nearest
+        sigma[k], ibs_obj_w_grad_nearest_f64).  Returns (val (n,), jac (n, 2))."""
         n = len(surf_idx)
         d = self.del_alpha
         al = np.stack([X[:, 0] - 0.5 * d, X[:, 0], X[:, 0] + 0.5 * d], axis=1).reshape(-1)
@@ -179,15 +217,19 @@ class BallooningScan:
         geo = r["geo"].view(8, n, 3, N).permute(1, 2, 0, 3).contiguous()
         import torch
         t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
-        val, jac = self.ctx.obj_w_grad(self.h, geo, t0, d)
+        if self.nearest:
+            sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device)
+            val, jac = self.ctx.obj_w_grad_nearest(self.h, geo, t0, sg, d)
+        else:
+            val, jac = self.ctx.obj_w_grad(self.h, geo, t0, d)
         return val.cpu().numpy(), jac.cpu().numpy()
 
-    def refine_batched(self, starts, maxiter=30, ftol=5.0e-11, gtol=2.0e-8):
+    def refine_batched(self, starts, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, sigma0=None):
         """the per-surface L-BFGS-B of ball_scan.py:307-314 (same bounds, tolerances and iteration cap) for every owned
         surface at once, driven from the host: one optimizer state per surface (csrc/ibs_lbfgsb2.hpp through the C ABI
         ibs_lbfgsb2_*), and every round ONE batched geometry + objective launch for the surfaces still running.
         The host-driven form of refine_device(), which it is tested against.
-        starts: (n, 2).  Returns (x_opt (n, 2), f_opt (n,) = -gam, rounds)."""
+        starts: (n, 2); sigma0 (n,): the shifts of eigenpair="nearest".  Returns (x_opt (n, 2), f_opt (n,) = -gam, rounds)."""
         import ctypes as C
         from . import _lib
         lib = _lib.lib()
@@ -203,7 +245,13 @@ class BallooningScan:
         rounds = 0
         while active.any():
             idx = np.nonzero(active)[0]
-            f, g = self.batched_obj_w_grad(surf[idx], x[idx])
+            if not self.nearest:
+                f, g = self.batched_obj_w_grad(surf[idx], x[idx])
+            else:
+                f, g = self.batched_obj_w_grad(surf[idx], x[idx], np.asarray(sigma0)[idx])
+                if not (np.all(np.isfinite(f)) and np.all(np.isfinite(g))):
+                    raise IbsError("%d objective solves of the refinement were flagged (invalid data or iteration cap)"
+                                   % int(np.sum(~(np.isfinite(f) & np.isfinite(g).all(axis=1)))))
             rounds += 1
             for q, k in enumerate(idx):
                 gk = np.ascontiguousarray(g[q], dtype=np.float64)
@@ -235,7 +283,10 @@ class BallooningScan:
         xo = np.asarray(xo, dtype=np.float64).reshape(-1, 2)
         r = self.ctx.fieldline_geometry(self.tables, self._own_surf(), np.ascontiguousarray(xo[:, 0]), self.theta, device=self.device)
         t0 = torch.from_numpy(np.ascontiguousarray(xo[:, 1])).to(self.device)
-        out = self.ctx.gamma_points(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0)
+        if self.nearest:
+            out = self.ctx.gamma_points_nearest(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, SIGMA_FINAL)
+        else:
+            out = self.ctx.gamma_points(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0)
         return out["gam"].cpu().numpy()
 
     # -- the whole per-surface worker of ball_scan.py:248-339 for the owned surfaces, resident in HBM
@@ -259,6 +310,10 @@ class BallooningScan:
         (ibs_gamma_scan_argmax_f64) -> start points on the device (ibs_scan_starts_f64) -> L-BFGS-B per surface on the device
         (ibs_refine_f64 on device pointers) -> final geometry + solve, one line per point (ibs_gamma_points_f64).  Nothing
         returns to the host in between.
+        eigenpair="nearest": the coarse scan with the eigenpair nearest 1.0 (ibs_gamma_scan_nearest_f64) -> per-surface first
+        maximum (ibs_surface_argmax_pack_f64) -> start points and each surface's shift 1.3 |max| + 0.05 (ibs_scan_starts_f64) ->
+        the host-driven L-BFGS-B (refine_batched: one geometry + ibs_obj_w_grad_nearest_f64 launch per round) -> final geometry +
+        ibs_gamma_points_nearest_f64 at 0.42.  A solve counts as failed on status bits 0-1 only (bit 5, a tie, is informational).
         chunks: optional list of (c0, c1) ranges of owned surfaces: the coarse part (geometry, scan, starts) runs chunk by chunk,
         and fill(c0, c1) -- if given -- is called on the host before a chunk's launches (AdjointStep: the tables of the next
         equilibria are computed and uploaded while the GPU works on the previous ones).
@@ -280,6 +335,7 @@ class BallooningScan:
         chunks = chunks or [(0, n)]
         start = torch.empty((n, 2), dtype=torch.float64, device=dev)
         gmax = torch.empty((n,), dtype=torch.float64, device=dev)
+        sig0 = torch.empty((n,), dtype=torch.float64, device=dev) if self.nearest else None
         bad = res["n_bad"][0] * 0
         t_fill = 0.0
         for c0, c1 in chunks:
@@ -288,16 +344,37 @@ class BallooningScan:
             mark("g0")
             geo = ctx.fieldline_geometry(self.tables, res["surf"][c0 * na:c1 * na], res["al"][c0 * na:c1 * na], res["th"], device=dev)
             mark("g1")
-            sc = ctx.gamma_scan_argmax(self.h, [geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], c1 - c0)
-            st = ctx.scan_starts(res["alpha"], res["t0"], sc["pack"], res["n_bad"])
+            if self.nearest:
+                sc = ctx.gamma_scan_nearest(self.h, *[geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], SIGMA_COARSE,
+                                            want_info=True)
+                sc["pack"] = ctx.surface_argmax_pack(sc["gam"].view(c1 - c0, -1))
+                st, sg = ctx.scan_starts(res["alpha"], res["t0"], sc["pack"], res["n_bad"], want_sigma0=True)
+                sig0[c0:c1] = sg
+                flagged = ((sc["info"] >> 16) & 3) != 0
+            else:
+                sc = ctx.gamma_scan_argmax(self.h, [geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], c1 - c0)
+                st = ctx.scan_starts(res["alpha"], res["t0"], sc["pack"], res["n_bad"])
+                flagged = (sc["info"] >> 16) != 0
             mark("s1")
             if len(chunks) == 1:
                 start, gmax = st, sc["pack"][:, 0]
             else:
                 start[c0:c1] = st; gmax[c0:c1] = sc["pack"][:, 0]
-            bad = bad + ((sc["info"] >> 16) != 0).sum()
+            bad = bad + flagged.sum()
         mark("r0")
-        if refine:
+        if refine and self.nearest:
+            # ibs_refine_f64 has no nearest-sigma form: the host-driven state machines, one geometry + ibs_obj_w_grad_nearest_f64
+            # launch per round at each surface's shift
+            xh, fh, rounds = self.refine_batched(start.cpu().numpy(), sigma0=sig0.cpu().numpy())
+            xo = torch.from_numpy(xh).to(dev)
+            mark("r1")
+            xa, xt = xo[:, 0].contiguous(), xo[:, 1].contiguous()
+            gf = ctx.fieldline_geometry(self.tables, res["pt_surf"], xa, res["th"], device=dev)
+            fin = ctx.gamma_points_nearest(self.h, *[gf["geo"][k] for k in range(7)], gf["dPdrho"], xt, SIGMA_FINAL, want_info=True)
+            rows = torch.stack([xt, xa, fin["gam"]], dim=1)
+            bad = bad + (((fin["info"] >> 16) & 3) != 0).sum()
+            self.last_refine = dict(n_evals=None, rounds=rounds)
+        elif refine:
             if len(self.theta) > 2050:
                 # ibs_refine_f64 holds the register-resident evaluation kernel (N <= 2050): beyond, the same L-BFGS-B state machines
                 # run on the host (ibs_lbfgsb2_*) and every round is ONE batched geometry + ibs_obj_w_grad_f64 launch for the
@@ -344,7 +421,7 @@ class BallooningScan:
         for k, tab in zip(self.own, tabs):
             a0, t0, sigma0, ij = pick_start(tab, self.alpha_scan, self.theta0_scan)
             if refine:
-                t, a, gam, _ = self.refine(self.rho_arr[k], a0, t0)
+                t, a, gam, _ = self.refine(self.rho_arr[k], a0, t0, sigma0 if self.nearest else None)
             else:
                 t, a, gam = t0, a0, float(np.max(tab))
             rows.append((t, a, gam))

@@ -351,18 +351,20 @@ class Context:
             out.update(info=info)
         return out
 
-    def scan_starts(self, alpha_scan, theta0_scan, pack, n_bad):
+    def scan_starts(self, alpha_scan, theta0_scan, pack, n_bad, want_sigma0=False):
         """start points (n_surf, 2) = (alpha, theta0) of the refinement from the per-surface maxima `pack`, on the device
         (ibs_scan_starts_f64; ball_scan.py:279-295).  All arguments device tensors; n_bad: int32 tensor of one element that
-        accumulates the number of surfaces whose maximum is not finite."""
+        accumulates the number of surfaces whose maximum is not finite.  want_sigma0: returns (start, sigma0 (n_surf,)) with
+        the refinement's shift of every surface, 1.3 |max| + 0.05 (0.05 for an all-zero table: ball_scan.py:282, 289)."""
         import torch
         n_surf = pack.shape[0]
         start = torch.empty((n_surf, 2), dtype=torch.float64, device=pack.device)
+        sigma0 = torch.empty((n_surf,), dtype=torch.float64, device=pack.device) if want_sigma0 else None
         self._stream_from_torch(pack)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())
         check(self._lib.ibs_scan_starts_f64(self._h, n_surf, alpha_scan.shape[0], theta0_scan.shape[0], p(alpha_scan),
-                                            p(theta0_scan), p(pack), p(start), C.c_void_p(None), p(n_bad)), "ibs_scan_starts_f64")
-        return start
+                                            p(theta0_scan), p(pack), p(start), p(sigma0), p(n_bad)), "ibs_scan_starts_f64")
+        return (start, sigma0) if want_sigma0 else start
 
     def obj_w_grad(self, h, geo, theta0, del_alpha=0.004, want_info=False):
         """geo: (n_pts, 3, 8, N) -- lines (alpha-d/2, alpha, alpha+d/2) x (bmag, gradpar, cvdrift, cvdrift0,
@@ -382,6 +384,56 @@ class Context:
         check(self._lib.ibs_obj_w_grad_f64(self._h, n_pts, N, float(h), pg, N, pt, float(del_alpha), pval, pjac,
                                            pinfo, ar.mem), "ibs_obj_w_grad_f64")
         return (val, jac, info) if want_info else (val, jac)
+
+    def obj_w_grad_nearest(self, h, geo, theta0, sigma, del_alpha=0.004, want_info=False):
+        """obj_w_grad with the eigenpair NEAREST sigma (ibs_obj_w_grad_nearest_f64: utils.py:1632-1728 as the refinement of
+        ball_scan.py:305-314 runs it, sigma = 1.3 |gam| + 0.05).  geo (n_pts, 3, 8, N), theta0 (n_pts,), sigma a scalar or (n_pts,).
+        Returns (val, jac) or, with want_info, (val, jac, dict(lam, idx, info)); a failed solve gives NaN val and jac."""
+        ar = _Args()
+        n_pts, three, eight, N = geo.shape
+        if three != 3 or eight != 8:
+            raise IbsError("geo must be (n_pts, 3, 8, N)")
+        pg, pt = ar.inp(geo), ar.inp(theta0)
+        ref = geo if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        psig = self._sigma_rows(ar, sigma, (n_pts,), ref)
+        val, pval = ar.out((n_pts,), ref)
+        jac, pjac = ar.out((n_pts, 2), ref)
+        lam, plam = ar.out((n_pts,), ref, want=want_info)
+        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        check(self._lib.ibs_obj_w_grad_nearest_f64(self._h, n_pts, N, float(h), pg, N, pt, psig, float(del_alpha), pval, pjac,
+                                                   plam, pidx, pinfo, ar.mem), "ibs_obj_w_grad_nearest_f64")
+        return (val, jac, dict(lam=lam, idx=idx, info=info)) if want_info else (val, jac)
+
+    def gamma_points_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma,
+                             want_X=False, want_info=False):
+        """gamma_points with the eigenpair NEAREST sigma (ibs_gamma_points_nearest_f64: the final solve of ball_scan.py:322-339,
+        sigma = 0.42 there).  Geometry arrays (n_pts, N); dPdrho, theta0 (n_pts,); sigma a scalar or (n_pts,).
+        Returns dict(gam, lam, idx[, X, dX][, info], nbad)."""
+        ar = _Args()
+        n_pts, N = bmag.shape
+        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
+        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
+        ref = bmag if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        psig = self._sigma_rows(ar, sigma, (n_pts,), ref)
+        gam, pgam = ar.out((n_pts,), ref)
+        lam, plam = ar.out((n_pts,), ref)
+        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32)
+        X, pX = ar.out((n_pts, N), ref, want=want_X)
+        dX, pdX = ar.out((n_pts, N), ref, want=want_X)
+        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_gamma_points_nearest_f64(self._h, n_pts, N, float(h), *ptrs, N, pdP, pt0, psig, pgam, plam, pidx,
+                                                          pX, pdX, pinfo, ar.mem), "ibs_gamma_points_nearest_f64")
+        out = dict(gam=gam, lam=lam, idx=idx, nbad=rc)
+        if want_X:
+            out.update(X=X, dX=dX)
+        if want_info:
+            out.update(info=info)
+        return out
 
     def fieldline_geometry(self, tables, line_surf, line_alpha, theta, device=None, use_rows=True):
         """geometry of the field lines (tables.s[line_surf[i]], line_alpha[i]) on the grid theta (row F1).
@@ -571,6 +623,20 @@ class Context:
         check(self._lib.ibs_sturm_count_f64(self._h, n_sys, N, float(h), pg, pc, pf, N, ps, pcnt, ar.mem),
               "ibs_sturm_count_f64")
         return cnt
+
+    def surface_argmax_pack(self, gam):
+        """gam: device tensor (n_surf, n_per_surf) -> pack (n_surf, 2) = (max, first row-major index) on the device
+        (ibs_surface_argmax_pack_f64; ball_scan.py:283-288), the input of scan_starts."""
+        import torch
+        n_surf, n_per = gam.shape
+        if not (_is_torch(gam) and gam.is_cuda):
+            raise IbsError("surface_argmax_pack takes a device tensor")
+        gam = gam.to(torch.float64).contiguous()
+        self._stream_from_torch(gam)
+        pack = torch.empty((n_surf, 2), dtype=torch.float64, device=gam.device)
+        check(self._lib.ibs_surface_argmax_pack_f64(self._h, n_surf, n_per, C.c_void_p(gam.data_ptr()), C.c_void_p(pack.data_ptr())),
+              "ibs_surface_argmax_pack_f64")
+        return pack
 
     def surface_argmax(self, gam):
         """gam: (n_surf, n_per_surf) -> (idx int32 (n_surf,), val (n_surf,)); first index on ties (ball_scan.py:283-288)."""

@@ -34,8 +34,8 @@
  *     bit 4, only with option "sigma0" set and both lam and info requested: lam_max >= sigma0.  The reference's ARPACK call returns
  *            the eigenpair NEAREST sigma0 (utils.py:1597); this library always returns lam_max's.  They are the same eigenpair
  *            whenever lam_max < sigma0 -- and only then: this bit marks the one case in which upstream may have returned another);
- *     bit 5, nearest-sigma entry points (ibs_solve_gcf_nearest_f64, ibs_gamma_scan_nearest_f64): "nearest not determined" -- the
- *            eigenvalues on either side of sigma lie at distances that differ by less than 4 N eps ||A||; the larger one is returned
+ *     bit 5, nearest-sigma entry points (ibs_*_nearest_f64): "nearest not determined" -- the eigenvalues on either side of
+ *            sigma lie at distances that differ by less than 4 N eps ||A||; the larger one is returned
  *            (these entry points never set bit 3, whose re-close diagnostic occupies bits 5 and up on the lam_max entry points).
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
  *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
@@ -181,6 +181,22 @@ int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
                                const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                                const double* dPdrho, const double* theta0, const double* sigma, double* gam, double* lam,
                                int32_t* idx, int32_t* info, int32_t mem);
+/* ibs_obj_w_grad_f64 with the eigenpair nearest sigma[n_pts] (utils.py:1632-1728 as the refinement of ball_scan.py:305-314 runs it,
+ * sigma = 1.3 |gam| + 0.05 of the surface's coarse maximum): geo, theta0, del_alpha, val and jac as in ibs_obj_w_grad_f64; lam,
+ * idx and info [n_pts] optional (conventions above: status bits 1 (also: sigma not finite) and 5, idx).  FP64, any odd N in
+ * [66, 65537]: one wavefront per point forms dPdrho of the three lines, the centre line's rows, its nearest eigenpair (as
+ * ibs_solve_gcf_nearest_f64) and both Hellmann-Feynman derivatives in one kernel (csrc/ibs_nearest_grad.hip).  A point whose solve
+ * fails (status bits 0-1) gets val = jac = NaN. */
+int ibs_obj_w_grad_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
+                               const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
+                               double* lam, int32_t* idx, int32_t* info, int32_t mem);
+/* ibs_gamma_points_f64 with the eigenpair nearest sigma[n_pts] (the final solve of ball_scan.py:322-339: sigma = 0.42 there, the
+ * default of gamma_ball_full): one (line, theta0) per point, arrays as in ibs_gamma_points_f64; gam [n_pts] required; lam, idx, info
+ * [n_pts] and X, dX [n_pts][N] optional.  The same kernel as ibs_obj_w_grad_nearest_f64 without its gradient pass. */
+int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
+                                 const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
+                                 const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, const double* sigma,
+                                 double* gam, double* lam, int32_t* idx, double* X, double* dX, int32_t* info, int32_t mem);
 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
