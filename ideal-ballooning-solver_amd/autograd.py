@@ -1,0 +1,81 @@
+"""Differentiable growth rates: torch.autograd Functions over the HIP solver, whose backward is the exact vector-Jacobian product
+of the library (Context.solve_gcf_vjp, ibs_solve_gcf_vjp_f64) -- the derivative of the very gam the forward returns (the FD4 /
+Simpson quotient of utils.py:1601-1621), not the Hellmann-Feynman formulas of utils.py:1666-1725.
+
+    from ibs_amd import autograd as iag
+    gam = iag.growth_rate(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0)
+    gam.sum().backward()            # gradients in every geometry array, dPdrho and theta0
+
+Float64 CUDA tensors throughout; uniform grids, odd N in [66, 65537] (the limits of the kernels).  A backward whose VJP flags a system
+(status bits 0-1 of ibs_solve_gcf_vjp_f64) issues a VjpStatusWarning.  `import ibs_amd` does not import
+this module, nor torch."""
+import warnings
+
+import torch
+
+from .solver import VjpStatusWarning, default_context, vjp_status_message
+
+_MODES = ("max", "nearest")
+
+
+def _check_mode(eigenpair, sigma):
+    if eigenpair not in _MODES:
+        raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
+    if eigenpair == "nearest" and sigma is None:
+        raise ValueError("eigenpair='nearest' needs sigma")
+
+
+class _SolveGcf(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, h, g, c, f, eigenpair, sigma, ictx):
+        if eigenpair == "max":
+            r = ictx.solve_gcf(h, g, c, f, want_X=True)
+        else:
+            r = ictx.solve_gcf_nearest(h, g, c, f, sigma, want_X=True)
+        fctx.save_for_backward(g, c, f, r["lam"], r["X"])
+        fctx.h, fctx.ictx = h, ictx
+        return r["gam"], r["lam"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gam_bar, lam_bar):
+        g, c, f, lam, X = fctx.saved_tensors
+        r = fctx.ictx.solve_gcf_vjp(fctx.h, g, c, f, lam, X, gam_bar=gam_bar.contiguous(), lam_bar=lam_bar.contiguous(),
+                                    want_info=True)
+        st = (r["info"] >> 16) & 3
+        n_pivot, n_bad = torch.stack([(st & 1).ne(0).sum(), (st & 2).ne(0).sum()]).tolist()     # (one host synchronisation)
+        if n_pivot or n_bad:
+            warnings.warn(vjp_status_message(n_pivot, n_bad), VjpStatusWarning, stacklevel=2)
+        return None, r["g_bar"], r["c_bar"], r["f_bar"], None, None, None
+
+
+def solve_gcf(h, g, c, f, eigenpair="max", sigma=None, ctx=None):
+    """(gam, lam), each (n_sys,), of the raw systems g, c, f (n_sys, N): lam_max's eigenpair (Context.solve_gcf) or, with
+    eigenpair="nearest", the one nearest sigma (a scalar or (n_sys,): Context.solve_gcf_nearest).  Differentiable in g, c and f;
+    the eigenpair is locally constant in sigma (no gradient)."""
+    _check_mode(eigenpair, sigma)
+    return _SolveGcf.apply(float(h), g, c, f, eigenpair, sigma, ctx or default_context(g.device.index or 0))
+
+
+def growth_rate(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, eigenpair="max", sigma=None, ctx=None):
+    """gam (n_lines, n_theta0) of the lines (geometry arrays (n_lines, N), dPdrho (n_lines,)) at theta0 ((n_theta0,), shared by all
+    lines as in Context.gamma_scan, or (n_lines, n_theta0)): the theta0 fold of ball_scan.py:267-268 and the coefficients of
+    utils.py:1560-1562 as torch expressions on the device, then solve_gcf.  Differentiable in every tensor argument.
+    eigenpair="nearest": the eigenpair nearest sigma (a scalar or (n_lines, n_theta0))."""
+    _check_mode(eigenpair, sigma)
+    n_lines, N = bmag.shape
+    t0 = theta0 if theta0.dim() == 2 else theta0.expand(n_lines, theta0.shape[0])
+    n_t0 = t0.shape[1]
+    t = t0[:, :, None]
+    cv = cvdrift[:, None, :] + t * cvdrift0[:, None, :]                                   # ball_scan.py:267
+    gd = gds2[:, None, :] + 2 * t * gds21[:, None, :] + t ** 2 * gds22[:, None, :]      # ball_scan.py:268
+    gp = torch.abs(gradpar)[:, None, :]
+    B = bmag[:, None, :]
+    g = gp * gd / B                                                                     # utils.py:1560
+    c = -1 * dPdrho[:, None, None] * cv * 1 / (gp * B)                                  # utils.py:1561
+    f = gd / B ** 2 * 1 / (gp * B)                                                      # utils.py:1562
+    if eigenpair == "nearest":
+        sigma = torch.as_tensor(sigma, dtype=torch.float64, device=bmag.device)
+        sigma = sigma.expand(n_lines, n_t0).reshape(-1) if sigma.dim() == 0 else sigma.reshape(-1)
+    gam, _ = solve_gcf(h, g.reshape(-1, N), c.reshape(-1, N), f.reshape(-1, N), eigenpair, sigma, ctx)
+    return gam.reshape(n_lines, n_t0)

@@ -924,6 +924,68 @@ int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, 
   return nbad;
 }
 
+// ---- exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip)
+// device pointers: the persistent grid of long_waves() with its workspace in ctx->long_ws (vjp_ws_doubles(N) per wave)
+static int vjp_device(ibs_ctx* ctx, long n_sys, int32_t N, double h, const double* g, const double* c, const double* f, long ld,
+                      const double* lam, const double* X, const double* gam_bar, const double* lam_bar, double* g_bar, double* c_bar,
+                      double* f_bar, int32_t* info) {
+  const int nw = long_waves(ctx, n_sys);
+  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::vjp_ws_doubles(N) * sizeof(double))) return r;
+  ibs::VjpArgs a{};
+  a.n_sys = n_sys; a.N = N; a.h = h; a.g = g; a.c = c; a.f = f; a.ld = ld; a.lam = lam; a.X = X; a.gam_bar = gam_bar; a.lam_bar = lam_bar;
+  a.g_bar = g_bar; a.c_bar = c_bar; a.f_bar = f_bar; a.info = info;
+  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+  HIPCHK(ibs::launch_gcf_vjp(a, ctx->stream));
+  return 0;
+}
+
+int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c, const double* f,
+                          int64_t ld, const double* lam, const double* X, const double* gam_bar, const double* lam_bar, double* g_bar,
+                          double* c_bar, double* f_bar, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_sys < 0 || !g || !c || !f || !lam || !X || !g_bar || !c_bar || !f_bar || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_sys=%lld ld=%lld N=%d)", (long long)n_sys, (long long)ld, N);
+  if (!gam_bar && !lam_bar) return fail(IBS_ERR_ARG, "gam_bar and lam_bar are both null");
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_sys == 0) return 0;
+  ON_DEVICE(ctx);
+  if (mem != IBS_MEM_HOST)
+    return vjp_device(ctx, (long)n_sys, N, h, g, c, f, (long)ld, lam, X, gam_bar, lam_bar, g_bar, c_bar, f_bar, info);
+  const size_t rows = (size_t)n_sys * ld;
+  Carve need{nullptr};
+  auto carve = [&](Carve& cv, double** in, double** vec, double** out, int** di) {
+    for (int k = 0; k < 4; ++k) in[k] = cv.take<double>(rows);
+    vec[0] = cv.take<double>(n_sys); vec[1] = gam_bar ? cv.take<double>(n_sys) : nullptr; vec[2] = lam_bar ? cv.take<double>(n_sys) : nullptr;
+    for (int k = 0; k < 3; ++k) out[k] = cv.take<double>(rows);
+    di[0] = cv.take<int>(n_sys); di[1] = cv.take<int>(1);
+  };
+  double* din[4]; double* dvec[3]; double* dout[3]; int* dint[2];
+  carve(need, din, dvec, dout, dint);
+  if (int r = ensure_ws(ctx, need.off + 256)) return r;
+  Carve cv{static_cast<char*>(ctx->ws)};
+  carve(cv, din, dvec, dout, dint);
+  HostStage hs(ctx, cv.off);
+  const double* hin[4] = {g, c, f, X};
+  for (int k = 0; k < 4; ++k) HIPCHK(hs.up(hin[k], rows * 8, din[k]));
+  HIPCHK(hs.up(lam, (size_t)n_sys * 8, dvec[0]));
+  if (gam_bar) HIPCHK(hs.up(gam_bar, (size_t)n_sys * 8, dvec[1]));
+  if (lam_bar) HIPCHK(hs.up(lam_bar, (size_t)n_sys * 8, dvec[2]));
+  HIPCHK(hs.flush_in());
+  if (ld > N) for (int k = 0; k < 3; ++k) HIPCHK(hipMemsetAsync(dout[k], 0, rows * 8, ctx->stream));     // (padding columns: zero)
+  if (int r = vjp_device(ctx, (long)n_sys, N, h, din[0], din[1], din[2], (long)ld, dvec[0], din[3], dvec[1], dvec[2], dout[0], dout[1],
+                         dout[2], dint[0]))
+    return r;
+  HIPCHK(hipMemsetAsync(dint[1], 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, dint[0], dint[1]);
+  double* hout[3] = {g_bar, c_bar, f_bar};
+  for (int k = 0; k < 3; ++k) HIPCHK(hs.down(hout[k], dout[k], rows * 8));
+  if (info) HIPCHK(hs.down(info, dint[0], (size_t)n_sys * 4));
+  int nbad = 0;
+  HIPCHK(hs.down(&nbad, dint[1], sizeof(int)));
+  HIPCHK(hs.flush_out());
+  return nbad;
+}
+
 // Coarse scan with the nearest eigenpair: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
 // arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and solved by k_solve_gcf_nearest; chunks are
 // bounded by kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".

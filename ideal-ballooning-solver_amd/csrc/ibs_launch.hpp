@@ -67,6 +67,17 @@ struct NearestArgs {
   double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
 };
 hipError_t launch_gcf_nearest(const NearestArgs& a, hipStream_t st);
+// exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip), FP64, any N in [66, kMaxLongN]: one wave per
+// system, persistent grid of min(n_sys, n_waves) waves, each with vjp_ws_doubles(N) doubles of workspace at work + wave * vjp_ws_doubles(N)
+constexpr size_t vjp_ws_doubles(int N) { return 3 * (size_t)N; }
+struct VjpArgs {
+  long n_sys; int N; double h;
+  const double *g, *c, *f; long ld;                              // every row array (inputs, X and the outputs) has rows ld apart
+  const double *lam, *X, *gam_bar, *lam_bar;                      // gam_bar / lam_bar: null = 0
+  double *g_bar, *c_bar, *f_bar; int* info;                       // info optional
+  double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
+};
+hipError_t launch_gcf_vjp(const VjpArgs& a, hipStream_t st);
 // geometry-fed points with the eigenpair nearest sigma[p] (ibs_nearest_grad.hip): one wave per point on the persistent grid of
 // min(n_pts, n_waves) waves.  Per-wave workspace, in this order (NearestPointsWs: the kernel carves it, the host sizes it):
 // the solver's nearest_ws_doubles(N), the centre line's g, c, f rows, and with GRAD the eigenfunction X and dX.

@@ -21,7 +21,7 @@ import warnings
 
 import numpy as np
 
-from .solver import default_context
+from .solver import VjpStatusWarning, default_context, vjp_status_message
 from ._lib import IbsError
 
 
@@ -142,7 +142,7 @@ def dPdrho_of(cvdrift, gbdrift, bmag):
     return -1.0 * 0.5 * np.mean((cvdrift - gbdrift) * bmag ** 2)
 
 
-def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004, eigenpair="max"):
+def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004, eigenpair="max", jac="reference"):
     """Factory for a drop-in `obj_w_grad(x0, vs, rho_val, theta, vguess00, sigma00=0.42)` (utils.py:1632).
 
     `fieldlines(vs, rho_val, alphas, theta)` supplies the geometry exactly as the reference gets it from
@@ -154,7 +154,17 @@ def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004, eigenpair="max"):
     eigenpair="max": lam_max's eigenpair, one fused ibs_obj_w_grad_f64 call (sigma00 unused).  eigenpair="nearest": the eigenpair
     nearest sigma00, as upstream on every input: the centre line is solved by ibs_solve_gcf_nearest_f64, the alpha tangents (right
     minus left line, each with its own dPdrho, over del_alpha: utils.py:1683-1718) and theta0 tangents (utils.py:1669-1673) are built
-    on the host and both derivatives taken by ibs_hf_grad_f64 (utils.py:1676-1680, 1721-1725)."""
+    on the host and both derivatives taken by ibs_hf_grad_f64 (utils.py:1676-1680, 1721-1725).
+    jac="reference" (the default): the Hellmann-Feynman formulas above, as upstream -- they put gam in place of lam and are not the
+    derivative of the gam returned (0.1-5 % off on field-line data).  jac="exact": the same val; jac is the exact derivative of that
+    gam (ibs_solve_gcf_vjp_f64) along the rows' tangents -- in theta0 the exact one (utils.py:1669-1673), in alpha (right minus left
+    line, each with its own dPdrho, over del_alpha: utils.py:1683-1718), which is the only approximation left.  Either eigenpair."""
+    if jac == "exact":
+        if eigenpair not in ("max", "nearest"):
+            raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
+        return _make_obj_w_grad_exact(fieldlines, ctx, del_alpha, eigenpair)
+    if jac != "reference":
+        raise ValueError("jac must be 'reference' or 'exact', not %r" % (jac,))
     if eigenpair == "nearest":
         return _make_obj_w_grad_nearest(fieldlines, ctx, del_alpha)
     if eigenpair != "max":
@@ -170,14 +180,53 @@ def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004, eigenpair="max"):
     return obj_w_grad
 
 
+def _line_gcf(line, theta0):
+    """(dPdrho, g, c, f) of one field line (8, N) at theta0"""
+    bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, gbdrift = line
+    dP = dPdrho_of(cvdrift, gbdrift, bmag)                        # utils.py:1657 (each line its own)
+    cv = cvdrift + theta0 * cvdrift0                               # utils.py:1659
+    gd = gds2 + 2 * theta0 * gds21 + theta0 ** 2 * gds22           # utils.py:1660
+    gp = np.abs(gradpar)
+    return dP, gp * gd / bmag, -1 * dP * cv * 1 / (gp * bmag), gd / bmag ** 2 * 1 / (gp * bmag)   # utils.py:1560-1562
+
+
+def _theta0_tangent(line, theta0, dP):
+    """d(g, c, f)/dtheta0 of one field line (8, N) at theta0 (utils.py:1669-1673)"""
+    bmag, gradpar, _, cvdrift0, _, gds21, gds22, _ = line
+    gp = np.abs(gradpar)
+    dgd = 2 * gds21 + 2 * theta0 * gds22
+    return gp * dgd / bmag, -1 * dP * cvdrift0 * 1 / (gp * bmag), dgd / bmag ** 2 * 1 / (gp * bmag)
+
+
+def _make_obj_w_grad_exact(fieldlines, ctx, del_alpha, eigenpair):
+    def obj_w_grad(x0, vs, rho_val, theta, vguess00=None, sigma00=0.42):
+        c = ctx or default_context()
+        alpha_val, theta0_val = float(x0[0]), float(x0[1])
+        al = np.array([alpha_val - 0.5 * del_alpha, alpha_val, alpha_val + 0.5 * del_alpha])
+        geo = np.asarray(fieldlines(vs, rho_val, al, theta), dtype=np.float64)
+        h = uniform_spacing(theta)
+        dP, g, cc, f = _line_gcf(geo[1], theta0_val)
+        if eigenpair == "nearest":
+            r = c.solve_gcf_nearest(h, g[None], cc[None], f[None], float(sigma00), want_X=True)
+        else:
+            r = c.solve_gcf(h, g[None], cc[None], f[None], want_X=True)
+        gam = float(r["gam"][0])
+        v = c.solve_gcf_vjp(h, g[None], cc[None], f[None], r["lam"], r["X"], gam_bar=1.0, want_info=True)
+        if v["nbad"]:
+            st = int(v["info"][0]) >> 16
+            warnings.warn(vjp_status_message(st & 1, (st >> 1) & 1), VjpStatusWarning, stacklevel=2)
+        gb, cb, fb = v["g_bar"][0], v["c_bar"][0], v["f_bar"][0]
+        g_t, c_t, f_t = _theta0_tangent(geo[1], theta0_val, dP)
+        jac_t = gb @ g_t + cb @ c_t + fb @ f_t
+        _, g_r, c_r, f_r = _line_gcf(geo[2], theta0_val)
+        _, g_l, c_l, f_l = _line_gcf(geo[0], theta0_val)
+        jac_a = (gb @ (g_r - g_l) + cb @ (c_r - c_l) + fb @ (f_r - f_l)) / del_alpha
+        return -1 * gam, np.array([-1 * float(jac_a), -1 * float(jac_t)])
+    return obj_w_grad
+
+
 def _make_obj_w_grad_nearest(fieldlines, ctx, del_alpha):
-    def gcf_of(line, theta0):
-        bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, gbdrift = line
-        dP = dPdrho_of(cvdrift, gbdrift, bmag)                        # utils.py:1657 (each line its own)
-        cv = cvdrift + theta0 * cvdrift0                               # utils.py:1659
-        gd = gds2 + 2 * theta0 * gds21 + theta0 ** 2 * gds22           # utils.py:1660
-        gp = np.abs(gradpar)
-        return dP, gp * gd / bmag, -1 * dP * cv * 1 / (gp * bmag), gd / bmag ** 2 * 1 / (gp * bmag)   # utils.py:1560-1562
+    gcf_of = _line_gcf
 
     def obj_w_grad(x0, vs, rho_val, theta, vguess00=None, sigma00=0.42):
         c = ctx or default_context()
@@ -188,12 +237,7 @@ def _make_obj_w_grad_nearest(fieldlines, ctx, del_alpha):
         dP, g, cc, f = gcf_of(geo[1], theta0_val)
         r = c.solve_gcf_nearest(h, g[None], cc[None], f[None], float(sigma00), want_X=True)
         gam = float(r["gam"][0])
-        bmag, gradpar, _, cvdrift0, _, gds21, gds22, _ = geo[1]
-        gp = np.abs(gradpar)
-        dgd = 2 * gds21 + 2 * theta0_val * gds22
-        g_t = gp * dgd / bmag                                          # utils.py:1669
-        c_t = -1 * dP * cvdrift0 * 1 / (gp * bmag)                     # utils.py:1670
-        f_t = dgd / bmag ** 2 * 1 / (gp * bmag)                        # utils.py:1671-1673
+        g_t, c_t, f_t = _theta0_tangent(geo[1], theta0_val, dP)        # utils.py:1669-1673
         _, g_r, c_r, f_r = gcf_of(geo[2], theta0_val)                  # utils.py:1683-1693, 1707-1709
         _, g_l, c_l, f_l = gcf_of(geo[0], theta0_val)                  # utils.py:1695-1705, 1711-1713
         g_a, c_a, f_a = (g_r - g_l) / del_alpha, (c_r - c_l) / del_alpha, (f_r - f_l) / del_alpha    # utils.py:1716-1718

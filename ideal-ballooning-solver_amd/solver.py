@@ -13,6 +13,16 @@ from . import _lib
 from ._lib import MEM_DEVICE, MEM_HOST, IbsError, check
 
 
+class VjpStatusWarning(UserWarning):
+    """solve_gcf_vjp flagged systems: status bit 1 (the pair is not an eigenpair of its rows, or invalid data: NaN rows) or status bit 0
+    (a pivot of the adjoint solve fell below pivmin and was replaced: the rows may be inaccurate)"""
+
+
+def vjp_status_message(n_pivot, n_bad):
+    return ("solve_gcf_vjp: %d system(s) with a replaced pivot in the adjoint solve (status bit 0: rows may be inaccurate), %d not an "
+            "eigenpair of their rows or with invalid data (status bit 1: NaN rows)" % (n_pivot, n_bad))
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -237,6 +247,32 @@ class Context:
         out = dict(lam=lam, idx=idx, gam=gam, nbad=rc)
         if want_X:
             out.update(X=X, dX=dX)
+        if want_info:
+            out.update(info=info)
+        return out
+
+    def solve_gcf_vjp(self, h, g, c, f, lam, X, gam_bar=None, lam_bar=None, want_info=False):
+        """exact vector-Jacobian product of gam and lam in the rows (ibs_solve_gcf_vjp_f64): g, c, f, X (n_sys, N), lam (n_sys,), the
+        eigenpair any simple one of the rows (solve_gcf's or solve_gcf_nearest's); gam_bar, lam_bar (n_sys,) or scalars, either may be
+        None (= 0), not both.  Returns dict(g_bar, c_bar, f_bar[, info], nbad) with rows (n_sys, N); a system whose (lam, X) is not
+        an eigenpair of its rows (or whose data are invalid) gets status bit 1 and NaN rows."""
+        if gam_bar is None and lam_bar is None:
+            raise IbsError("solve_gcf_vjp: gam_bar and lam_bar are both None")
+        ar = _Args()
+        n_sys, N = g.shape
+        pg, pc, pf, pX, plam = ar.inp(g), ar.inp(c), ar.inp(f), ar.inp(X), ar.inp(lam)
+        ref = g if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        pgb = self._sigma_rows(ar, gam_bar, (n_sys,), ref) if gam_bar is not None else C.c_void_p(None)
+        plb = self._sigma_rows(ar, lam_bar, (n_sys,), ref) if lam_bar is not None else C.c_void_p(None)
+        gb, pgb_out = ar.out((n_sys, N), ref)
+        cb, pcb_out = ar.out((n_sys, N), ref)
+        fb, pfb_out = ar.out((n_sys, N), ref)
+        info, pinfo = ar.out((n_sys,), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_solve_gcf_vjp_f64(self._h, n_sys, N, float(h), pg, pc, pf, N, plam, pX, pgb, plb, pgb_out, pcb_out,
+                                                   pfb_out, pinfo, ar.mem), "ibs_solve_gcf_vjp_f64")
+        out = dict(g_bar=gb, c_bar=cb, f_bar=fb, nbad=rc)
         if want_info:
             out.update(info=info)
         return out

@@ -172,6 +172,25 @@ int ibs_solve_gcf_f32(ibs_ctx* ctx, int64_t n_sys, int32_t N, float h, const flo
 int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
                               const double* c, const double* f, int64_t ld, const double* sigma, double* lam,
                               int32_t* idx, double* gam, double* X, double* dX, int32_t* info, int32_t mem);
+/* Exact vector-Jacobian product of gam (the FD4 / Simpson quotient of utils.py:1601-1621) and of lam with respect to the rows
+ * (g, c, f) of raw systems on a uniform grid, the half-grid g the mean of neighbouring g (the systems of ibs_solve_gcf_f64).  Nothing
+ * upstream corresponds: its only derivatives are the Hellmann-Feynman formulas of obj_w_grad (utils.py:1666-1725), which put gam in
+ * place of lam and are not the derivative of the gam they come with.
+ *   g, c, f, X [n_sys][ld] (X: the eigenvector of lam, any scale and sign; X[0] and X[N-1] are taken as 0); lam[n_sys];
+ *   gam_bar[n_sys], lam_bar[n_sys]: the cotangents (either may be NULL = 0, not both);
+ *   g_bar, c_bar, f_bar [n_sys][ld] (out): gam_bar d gam / d row + lam_bar d lam / d row, entries 0 .. N-1 of each row (a host call
+ *   returns the padding entries N .. ld-1 as 0); info[n_sys] optional.
+ * (lam, X) may be ANY simple eigenpair: lam_max's (ibs_solve_gcf_f64, ibs_gamma_points_f64) or the nearest-sigma one
+ * (ibs_solve_gcf_nearest_f64, ibs_gamma_points_nearest_f64).  The singular adjoint system (S - lam F) z = d gam / d X is solved by a
+ * twisted split at the row of largest |X| with z orthogonal to F X afterwards (csrc/ibs_vjp.hip).  Status: bit 1 = the pair is not an
+ * eigenpair of these rows (residual max_r |((S - lam F) X)_r| / f_r above 1024 N eps (||A|| + |lam|) max |X|), invalid data (as in
+ * ibs_solve_gcf_f64) or a non-finite lam, X or cotangent: that system's rows are NaN; bit 0 = a pivot of the adjoint solve fell below
+ * pivmin and was replaced (the rows may be inaccurate; never on lam_max's pair, whose pivots are bounded away from 0).  FP64, any odd N
+ * in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED, as every entry point); one wavefront per system; no floating-point atomics:
+ * the rows are bitwise repeatable and independent of the batch. */
+int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c, const double* f,
+                          int64_t ld, const double* lam, const double* X, const double* gam_bar, const double* lam_bar, double* g_bar,
+                          double* c_bar, double* f_bar, int32_t* info, int32_t mem);
 /* the coarse scan of ball_scan.py:248-273 with upstream's shift: sigma[n_lines][n_theta0] (1.0 there, ball_scan.py:230 / 269).
  * Arrays as in ibs_gamma_scan_f64; outputs [n_lines][n_theta0], all optional.  The (g, c, f) rows of whole lines are assembled in a
  * workspace of about 1 GiB at most and solved by the kernel of ibs_solve_gcf_nearest_f64, chunk after chunk (option
@@ -201,6 +220,8 @@ int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
  * and utils.py:1556-1624; with dgam_dtheta0 also utils.py:1666-1680 (Hellmann-Feynman d/dtheta0).
+ *   dgam_dtheta0 keeps the reference's formula (gam in place of lam, Simpson sums): it is NOT the derivative of the gam returned;
+ *   the exact one is the rows' theta0 tangents contracted with ibs_solve_gcf_vjp_f64's rows (ibs_amd.autograd.growth_rate).
  *   geometry arrays [n_lines][ld] (first N of each row used): bmag, gradpar (gradpar_theta_pest),
  *   cvdrift, cvdrift0, gds2, gds21, gds22;  dPdrho[n_lines] (ball_scan.py:262);  theta0[n_theta0].
  *   outputs are [n_lines][n_theta0] (X, dX: [n_lines][n_theta0][N]). */
