@@ -154,19 +154,9 @@ struct DeviceGuard {
   DeviceGuard dev_guard_((ctx_)->device);                                                                   \
   if (dev_guard_.err != hipSuccess) return fail(IBS_ERR_HIP, "hipSetDevice(%d) -> %s", (ctx_)->device, hipGetErrorString(dev_guard_.err))
 
-struct Arena {  // carve device buffers out of the context workspace
-  ibs_ctx* c; size_t off = 0;
-  explicit Arena(ibs_ctx* c_) : c(c_) {}
-  template <typename T> T* take(size_t n) {
-    off = (off + 255) & ~size_t(255);
-    T* p = reinterpret_cast<T*>(static_cast<char*>(c->ws) + off);
-    off += n * sizeof(T);
-    return p;
-  }
-};
 size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-// Device buffers of one host-pointer call, sized by the very sequence of take() calls that carves them: a first pass without a
-// buffer only counts (Carve{nullptr}), the second carves ctx->ws.
+// Device buffers carved out of one workspace, sized by the very sequence of take() calls that carves them: a first pass without a
+// buffer only counts (Carve{nullptr}), the second carves.
 struct Carve {
   char* base; size_t off = 0;
   template <typename T> T* take(size_t n) {
@@ -182,6 +172,15 @@ int ensure_long_ws(ibs_ctx* c, size_t bytes) {
   if (c->long_ws) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->long_ws)); c->long_ws = nullptr; c->long_ws_bytes = 0; }
   HIPCHK(hipMalloc(&c->long_ws, bytes));
   c->long_ws_bytes = bytes;
+  return 0;
+}
+// ctx->long_ws sized by the carve sequence that uses it (a function of a Carve&), then carved
+template <typename F> int carve_long(ibs_ctx* c, F&& carve) {
+  Carve sz{nullptr};
+  carve(sz);
+  if (int r = ensure_long_ws(c, sz.off)) return r;
+  Carve cv{static_cast<char*>(c->long_ws)};
+  carve(cv);
   return 0;
 }
 int ensure_fix(ibs_ctx* c, long n_sys) {
@@ -204,16 +203,16 @@ int ensure_ws(ibs_ctx* c, size_t bytes) {
 
 // Small host-pointer calls (the drop-in gamma_ball_full: one system, ~70 KB in, ~16 KB out) spent most of their 0.17-0.22 ms
 // in a dozen pageable hipMemcpyAsync of a few KB each (every one staged and waited for by the runtime).  HostStage mirrors the
-// device arena in page-locked host memory: up() copies a source into the mirror at its device offset, flush_in() moves the
+// device workspace (ctx->ws) in page-locked host memory: up() copies a source into the mirror at its device offset, flush_in() moves the
 // whole input span with ONE copy; down() records an output, flush_out() brings the output span back with ONE copy, waits for
-// the stream and hands the pieces to the caller's buffers.  Calls whose arena exceeds kMaxBytes take the direct copies.
+// the stream and hands the pieces to the caller's buffers.  Calls whose spans exceed kMaxBytes take the direct copies.
 struct HostStage {
   static constexpr size_t kMaxBytes = 4u << 20;
   ibs_ctx* c; bool on = false;
   size_t in_lo = ~size_t(0), in_hi = 0, out_lo = ~size_t(0), out_hi = 0;
   struct Piece { void* dst; size_t off, bytes; };
   std::vector<Piece> outs;
-  bool in_flight = false;      // flush_in() ran and flush_out() has not: the pinned mirror / arena are still being read by the stream
+  bool in_flight = false;      // flush_in() ran and flush_out() has not: the pinned mirror / workspace are still being read by the stream
   // (an early error return between the two must not leave that copy running while the next call refills the mirror)
   ~HostStage() { if (in_flight) (void)hipStreamSynchronize(c->stream); }
   HostStage(const HostStage&) = delete;
@@ -242,13 +241,11 @@ struct HostStage {
     in_flight = true;
     return hipMemcpyAsync(static_cast<char*>(c->ws) + in_lo, static_cast<char*>(c->hs) + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, c->stream);
   }
-  hipError_t down(void* dst, const void* dev, size_t bytes) {
-    if (!on) return hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+  void down(void* dst, const void* dev, size_t bytes) {      // (only recorded: flush_out() moves it)
     const size_t o = off_of(dev);
     outs.push_back(Piece{dst, o, bytes});
     if (o < out_lo) out_lo = o;
     if (o + bytes > out_hi) out_hi = o + bytes;
-    return hipSuccess;
   }
   // ends with the stream synchronised and every recorded output in the caller's memory
   hipError_t flush_out() {
@@ -256,10 +253,15 @@ struct HostStage {
       hipError_t e = hipMemcpyAsync(static_cast<char*>(c->hs) + out_lo, static_cast<char*>(c->ws) + out_lo, out_hi - out_lo, hipMemcpyDeviceToHost, c->stream);
       if (e != hipSuccess) return e;
     }
+    if (!on)
+      for (const Piece& p : outs) {
+        hipError_t e = hipMemcpyAsync(p.dst, static_cast<char*>(c->ws) + p.off, p.bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) return e;
+      }
     hipError_t e = hipStreamSynchronize(c->stream);
     in_flight = false;
     if (e != hipSuccess) return e;
-    for (const Piece& p : outs) std::memcpy(p.dst, static_cast<char*>(c->hs) + p.off, p.bytes);
+    if (on) for (const Piece& p : outs) std::memcpy(p.dst, static_cast<char*>(c->hs) + p.off, p.bytes);
     return hipSuccess;
   }
 };
@@ -306,6 +308,81 @@ __global__ void k_count_status(long n, const int* info, int* out) {
   int bad = (i < n) && (((info[i] >> 16) & 3) != 0);      // (status bit 2 is informational: an FP32 result re-solved in FP64)
   unsigned long long m = __ballot(bad);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(out, __popcll(m));
+}
+
+// The host-pointer protocol of every entry point that takes `mem`.  The entry point declares its device buffers ONCE, in a function
+// of a Stage& (in / out / scratch / status), and staged() runs that declaration twice: against no workspace to size ctx->ws, then
+// against ctx->ws to carve it.  Host pointers: the inputs lie in one span of ctx->ws (moved up with one copy: HostStage), the outputs
+// in the span behind it (moved back with one copy), scratch behind both.  Device pointers: in / out / status return the caller's
+// pointers and only scratch is carved.
+class Stage {
+ public:
+  const bool host;
+  // input of n elements (a null source stays null)
+  template <typename T> const T* in(const T* src, size_t n) {
+    if (!host || !src) return src;
+    T* d = in_.take<T>(n);
+    if (hs_ && err_ == hipSuccess) err_ = hs_->up(src, n * sizeof(T), d);
+    return d;
+  }
+  // output of n elements, copied back to dst; a null dst is carved too when `always` (the device code needs the buffer either way)
+  template <typename T> T* out(T* dst, size_t n, bool always = false) {
+    if (!host || !(dst || always)) return dst;
+    T* d = out_.take<T>(n);
+    if (hs_ && dst) hs_->down(dst, d, n * sizeof(T));
+    return d;
+  }
+  // workspace of the device code alone, in either mode
+  template <typename T> T* scratch(size_t n, bool when = true) { return when ? scr_.take<T>(n) : nullptr; }
+  // status words: host pointers always get a device buffer, whose count of bad words is what staged() returns
+  int* status(int32_t* info, size_t n) {
+    if (!host) return info;
+    status_ = out(info, n, true);
+    nbad_ = out_.take<int>(1);
+    n_status_ = n;
+    return status_;
+  }
+
+ private:
+  template <typename D, typename L> friend int staged(ibs_ctx*, int32_t, D&&, L&&);
+  Stage(bool host_, char* ws, size_t in_bytes, size_t io_bytes, HostStage* hs)
+      : host(host_), in_{ws}, out_{ws ? ws + in_bytes : nullptr}, scr_{ws ? ws + io_bytes : nullptr}, hs_(hs) {}
+  Carve in_, out_, scr_;
+  HostStage* hs_;
+  hipError_t err_ = hipSuccess;
+  int *status_ = nullptr, *nbad_ = nullptr;
+  size_t n_status_ = 0;
+};
+
+// decl(Stage&) declares the buffers and fills the launch arguments, launch() launches (IBS error code or 0), in either mode.
+// Returns: host pointers, the count of status words with bit 0 or 1 set (0 without status()); device pointers, 0.
+template <typename Decl, typename Launch>
+int staged(ibs_ctx* ctx, int32_t mem, Decl&& decl, Launch&& launch) {
+  const bool host = mem == IBS_MEM_HOST;
+  Stage sz(host, nullptr, 0, 0, nullptr);
+  decl(sz);
+  const size_t in_bytes = pad256(sz.in_.off), io_bytes = in_bytes + pad256(sz.out_.off), bytes = io_bytes + sz.scr_.off;
+  if (bytes) if (int r = ensure_ws(ctx, bytes)) return r;
+  char* ws = static_cast<char*>(ctx->ws);
+  if (!host) {
+    Stage s(false, ws, 0, 0, nullptr);
+    decl(s);
+    return launch();
+  }
+  HostStage hs(ctx, io_bytes);
+  Stage s(true, ws, in_bytes, io_bytes, &hs);
+  decl(s);
+  if (s.err_ != hipSuccess) return fail(IBS_ERR_HIP, "host -> device copy -> %s", hipGetErrorString(s.err_));
+  HIPCHK(hs.flush_in());
+  if (int r = launch()) return r;
+  int nbad = 0;
+  if (s.nbad_) {
+    HIPCHK(hipMemsetAsync(s.nbad_, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_count_status, dim3((unsigned)((s.n_status_ + 255) / 256)), dim3(256), 0, ctx->stream, (long)s.n_status_, s.status_, s.nbad_);
+    hs.down(&nbad, s.nbad_, sizeof(int));
+  }
+  HIPCHK(hs.flush_out());
+  return nbad;
 }
 
 // Nearest-sigma report (option "sigma0"): the reference takes the eigenpair NEAREST sigma0 (eigs(..., sigma=sigma0), utils.py:1597;
@@ -518,46 +595,19 @@ int solve_gcf_impl(ibs_ctx* ctx, int64_t n_sys, int32_t N, T h, const T* g, cons
   ibs::GcfArgs<T> a{};
   a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.wpb = wpb;
   a.flags = ctx->opt.reclose == 1 ? 1 : (ctx->opt.reclose == 2 ? 2 : 0);
-  int* d_info = nullptr;
-  int* d_nbad = nullptr;
-  if (mem == IBS_MEM_HOST) {
-    const size_t in_elems = (size_t)n_sys * ld, out_elems = (size_t)n_sys * N;
-    size_t need = 4 * pad256(in_elems * sizeof(T)) + 2 * pad256(n_sys * sizeof(T)) + 2 * pad256(out_elems * sizeof(T)) +
-                  pad256(n_sys * sizeof(int)) + 4096;
-    if (int r = ensure_ws(ctx, need)) return r;
-    Arena ar(ctx);
-    HostStage hs(ctx, need);
-    T* dg = ar.take<T>(in_elems); T* dc = ar.take<T>(in_elems); T* df = ar.take<T>(in_elems);
-    T* dgh = gh ? ar.take<T>(in_elems) : nullptr;
-    T* dlam = ar.take<T>(n_sys); T* dgam = ar.take<T>(n_sys);
-    T* dX_ = X ? ar.take<T>(out_elems) : nullptr; T* ddX = dX ? ar.take<T>(out_elems) : nullptr;
-    d_info = ar.take<int>(n_sys); d_nbad = ar.take<int>(1);
-    HIPCHK(hs.up(g, in_elems * sizeof(T), dg));
-    HIPCHK(hs.up(c, in_elems * sizeof(T), dc));
-    HIPCHK(hs.up(f, in_elems * sizeof(T), df));
-    if (gh) HIPCHK(hs.up(gh, in_elems * sizeof(T), dgh));
-    HIPCHK(hs.flush_in());
-    // (gam not asked for: the kernels then take their eigenvalue-only exits, as they do for device-pointer calls)
-    a.g = dg; a.c = dc; a.f = df; a.lam = dlam; a.gam = gam ? dgam : nullptr; a.X = dX_; a.dX = ddX; a.info = d_info;
-    if (gh) a.gh = dgh;
+  const size_t in_elems = (size_t)n_sys * ld, out_elems = (size_t)n_sys * N;
+  // (host pointers: lam and info are always carved; gam not asked for stays null -- the kernels then take their eigenvalue-only
+  //  exits, as they do for device-pointer calls)
+  auto decl = [&](Stage& s) {
+    a.g = s.in(g, in_elems); a.c = s.in(c, in_elems); a.f = s.in(f, in_elems); a.gh = s.in(gh, in_elems);
+    a.lam = s.out(lam, n_sys, true); a.gam = s.out(gam, n_sys); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
     if (int r = launch_it(a)) return r;
     flag_sigma<T>(ctx, (long)n_sys, a.lam, a.info);
-    HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, d_info, d_nbad);
-    if (lam) HIPCHK(hs.down(lam, dlam, n_sys * sizeof(T)));
-    if (gam) HIPCHK(hs.down(gam, dgam, n_sys * sizeof(T)));
-    if (X) HIPCHK(hs.down(X, dX_, out_elems * sizeof(T)));
-    if (dX) HIPCHK(hs.down(dX, ddX, out_elems * sizeof(T)));
-    if (info) HIPCHK(hs.down(info, d_info, n_sys * sizeof(int)));
-    int nbad = 0;
-    HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
-    HIPCHK(hs.flush_out());
-    return nbad;
-  }
-  a.g = g; a.c = c; a.f = f; a.lam = lam; a.gam = gam; a.X = X; a.dX = dX; a.info = info; a.gh = gh;
-  if (int r = launch_it(a)) return r;
-  flag_sigma<T>(ctx, (long)n_sys, a.lam, a.info);
-  return 0;
+    return 0;
+  });
 }
 
 
@@ -865,16 +915,11 @@ int ibs_solve_gcf_f32(ibs_ctx* ctx, int64_t n_sys, int32_t N, float h, const flo
 }
 
 // ---- the eigenpair nearest sigma (ibs_nearest.hip; utils.py:1597)
-// device pointers: the persistent grid of long_waves() with its workspace in ctx->long_ws (nearest_ws_doubles(N) per wave)
-static int nearest_device(ibs_ctx* ctx, long n_sys, int32_t N, double h, const double* g, const double* gh, const double* c,
-                          const double* f, long ld, const double* sigma, double* lam, int32_t* idx, double* gam, double* X,
-                          double* dX, int32_t* info) {
-  const int nw = long_waves(ctx, n_sys);
-  const size_t ws = (size_t)nw * ibs::nearest_ws_doubles(N);
+// the persistent grid of long_waves() with its workspace in ctx->long_ws (nearest_ws_doubles(N) per wave)
+static int nearest_device(ibs_ctx* ctx, ibs::NearestArgs a) {
+  const int nw = long_waves(ctx, a.n_sys);
+  const size_t ws = (size_t)nw * ibs::nearest_ws_doubles(a.N);
   if (int r = ensure_long_ws(ctx, ws * sizeof(double))) return r;
-  ibs::NearestArgs a{};
-  a.n_sys = n_sys; a.N = N; a.h = h; a.g = g; a.c = c; a.f = f; a.gh = gh; a.ld = ld; a.sigma = sigma;
-  a.lam = lam; a.idx = idx; a.gam = gam; a.X = X; a.dX = dX; a.info = info;
   a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
   HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
   return 0;
@@ -889,51 +934,22 @@ int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, 
   if (int r = check_grid(N, h, true)) return r;
   if (n_sys == 0) return 0;
   ON_DEVICE(ctx);
-  if (mem != IBS_MEM_HOST) return nearest_device(ctx, (long)n_sys, N, h, g, gh, c, f, (long)ld, sigma, lam, idx, gam, X, dX, info);
   const size_t in_elems = (size_t)n_sys * ld, out_elems = (size_t)n_sys * N;
-  const size_t need = (gh ? 4 : 3) * pad256(in_elems * 8) + 3 * pad256(n_sys * 8) + 2 * pad256(n_sys * 4) +
-                      (X ? pad256(out_elems * 8) : 0) + (dX ? pad256(out_elems * 8) : 0) + 4096;
-  if (int r = ensure_ws(ctx, need)) return r;
-  Arena ar(ctx);
-  HostStage hs(ctx, need);
-  double* dg = ar.take<double>(in_elems); double* dc = ar.take<double>(in_elems); double* df = ar.take<double>(in_elems);
-  double* dgh = gh ? ar.take<double>(in_elems) : nullptr;
-  double* dsig = ar.take<double>(n_sys);
-  HIPCHK(hs.up(g, in_elems * 8, dg));
-  HIPCHK(hs.up(c, in_elems * 8, dc));
-  HIPCHK(hs.up(f, in_elems * 8, df));
-  if (gh) HIPCHK(hs.up(gh, in_elems * 8, dgh));
-  HIPCHK(hs.up(sigma, (size_t)n_sys * 8, dsig));
-  HIPCHK(hs.flush_in());
-  double* dlam = lam ? ar.take<double>(n_sys) : nullptr; double* dgam = gam ? ar.take<double>(n_sys) : nullptr;
-  int* didx = idx ? ar.take<int>(n_sys) : nullptr;
-  double* dX_ = X ? ar.take<double>(out_elems) : nullptr; double* ddX = dX ? ar.take<double>(out_elems) : nullptr;
-  int* d_info = ar.take<int>(n_sys); int* d_nbad = ar.take<int>(1);
-  if (int r = nearest_device(ctx, (long)n_sys, N, h, dg, dgh, dc, df, (long)ld, dsig, dlam, didx, dgam, dX_, ddX, d_info)) return r;
-  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, d_info, d_nbad);
-  if (lam) HIPCHK(hs.down(lam, dlam, n_sys * 8));
-  if (idx) HIPCHK(hs.down(idx, didx, n_sys * 4));
-  if (gam) HIPCHK(hs.down(gam, dgam, n_sys * 8));
-  if (X) HIPCHK(hs.down(X, dX_, out_elems * 8));
-  if (dX) HIPCHK(hs.down(dX, ddX, out_elems * 8));
-  if (info) HIPCHK(hs.down(info, d_info, n_sys * 4));
-  int nbad = 0;
-  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
-  HIPCHK(hs.flush_out());
-  return nbad;
+  ibs::NearestArgs a{};
+  a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld;
+  auto decl = [&](Stage& s) {
+    a.g = s.in(g, in_elems); a.c = s.in(c, in_elems); a.f = s.in(f, in_elems); a.gh = s.in(gh, in_elems); a.sigma = s.in(sigma, n_sys);
+    a.lam = s.out(lam, n_sys); a.gam = s.out(gam, n_sys); a.idx = s.out(idx, n_sys); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&] { return nearest_device(ctx, a); });
 }
 
 // ---- exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip)
-// device pointers: the persistent grid of long_waves() with its workspace in ctx->long_ws (vjp_ws_doubles(N) per wave)
-static int vjp_device(ibs_ctx* ctx, long n_sys, int32_t N, double h, const double* g, const double* c, const double* f, long ld,
-                      const double* lam, const double* X, const double* gam_bar, const double* lam_bar, double* g_bar, double* c_bar,
-                      double* f_bar, int32_t* info) {
-  const int nw = long_waves(ctx, n_sys);
-  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::vjp_ws_doubles(N) * sizeof(double))) return r;
-  ibs::VjpArgs a{};
-  a.n_sys = n_sys; a.N = N; a.h = h; a.g = g; a.c = c; a.f = f; a.ld = ld; a.lam = lam; a.X = X; a.gam_bar = gam_bar; a.lam_bar = lam_bar;
-  a.g_bar = g_bar; a.c_bar = c_bar; a.f_bar = f_bar; a.info = info;
+// the persistent grid of long_waves() with its workspace in ctx->long_ws (vjp_ws_doubles(N) per wave)
+static int vjp_device(ibs_ctx* ctx, ibs::VjpArgs a) {
+  const int nw = long_waves(ctx, a.n_sys);
+  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::vjp_ws_doubles(a.N) * sizeof(double))) return r;
   a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
   HIPCHK(ibs::launch_gcf_vjp(a, ctx->stream));
   return 0;
@@ -949,41 +965,20 @@ int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, cons
   if (int r = check_grid(N, h, true)) return r;
   if (n_sys == 0) return 0;
   ON_DEVICE(ctx);
-  if (mem != IBS_MEM_HOST)
-    return vjp_device(ctx, (long)n_sys, N, h, g, c, f, (long)ld, lam, X, gam_bar, lam_bar, g_bar, c_bar, f_bar, info);
   const size_t rows = (size_t)n_sys * ld;
-  Carve need{nullptr};
-  auto carve = [&](Carve& cv, double** in, double** vec, double** out, int** di) {
-    for (int k = 0; k < 4; ++k) in[k] = cv.take<double>(rows);
-    vec[0] = cv.take<double>(n_sys); vec[1] = gam_bar ? cv.take<double>(n_sys) : nullptr; vec[2] = lam_bar ? cv.take<double>(n_sys) : nullptr;
-    for (int k = 0; k < 3; ++k) out[k] = cv.take<double>(rows);
-    di[0] = cv.take<int>(n_sys); di[1] = cv.take<int>(1);
+  ibs::VjpArgs a{};
+  a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld;
+  auto decl = [&](Stage& s) {
+    a.g = s.in(g, rows); a.c = s.in(c, rows); a.f = s.in(f, rows); a.X = s.in(X, rows);
+    a.lam = s.in(lam, n_sys); a.gam_bar = s.in(gam_bar, n_sys); a.lam_bar = s.in(lam_bar, n_sys);
+    a.g_bar = s.out(g_bar, rows); a.c_bar = s.out(c_bar, rows); a.f_bar = s.out(f_bar, rows);
+    a.info = s.status(info, n_sys);
   };
-  double* din[4]; double* dvec[3]; double* dout[3]; int* dint[2];
-  carve(need, din, dvec, dout, dint);
-  if (int r = ensure_ws(ctx, need.off + 256)) return r;
-  Carve cv{static_cast<char*>(ctx->ws)};
-  carve(cv, din, dvec, dout, dint);
-  HostStage hs(ctx, cv.off);
-  const double* hin[4] = {g, c, f, X};
-  for (int k = 0; k < 4; ++k) HIPCHK(hs.up(hin[k], rows * 8, din[k]));
-  HIPCHK(hs.up(lam, (size_t)n_sys * 8, dvec[0]));
-  if (gam_bar) HIPCHK(hs.up(gam_bar, (size_t)n_sys * 8, dvec[1]));
-  if (lam_bar) HIPCHK(hs.up(lam_bar, (size_t)n_sys * 8, dvec[2]));
-  HIPCHK(hs.flush_in());
-  if (ld > N) for (int k = 0; k < 3; ++k) HIPCHK(hipMemsetAsync(dout[k], 0, rows * 8, ctx->stream));     // (padding columns: zero)
-  if (int r = vjp_device(ctx, (long)n_sys, N, h, din[0], din[1], din[2], (long)ld, dvec[0], din[3], dvec[1], dvec[2], dout[0], dout[1],
-                         dout[2], dint[0]))
-    return r;
-  HIPCHK(hipMemsetAsync(dint[1], 0, sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, dint[0], dint[1]);
-  double* hout[3] = {g_bar, c_bar, f_bar};
-  for (int k = 0; k < 3; ++k) HIPCHK(hs.down(hout[k], dout[k], rows * 8));
-  if (info) HIPCHK(hs.down(info, dint[0], (size_t)n_sys * 4));
-  int nbad = 0;
-  HIPCHK(hs.down(&nbad, dint[1], sizeof(int)));
-  HIPCHK(hs.flush_out());
-  return nbad;
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (mem == IBS_MEM_HOST && ld > N)                  // (host pointers: the padding columns come back as zero)
+      for (double* o : {a.g_bar, a.c_bar, a.f_bar}) HIPCHK(hipMemsetAsync(o, 0, rows * sizeof(double), ctx->stream));
+    return vjp_device(ctx, a);
+  });
 }
 
 // Coarse scan with the nearest eigenpair: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
@@ -993,26 +988,28 @@ static constexpr size_t kNearestScanBytes = size_t(1) << 30;
 static int scan_nearest_device(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const geo7[7],
                                int64_t ld, const double* dPdrho, const double* theta0, const double* sigma, double* gam,
                                double* lam, int32_t* idx, int32_t* info) {
-  auto bytes_of = [&](long L) {
+  int nw = 0;
+  double *work, *G, *C, *F;
+  auto carve = [&](Carve& cv, long L) {          // ctx->long_ws of a chunk of L lines
     const long S = L * n_theta0;
-    return ((size_t)3 * S * N + (size_t)long_waves(ctx, S) * ibs::nearest_ws_doubles(N)) * sizeof(double);
+    nw = long_waves(ctx, S);
+    work = cv.take<double>((size_t)nw * ibs::nearest_ws_doubles(N));
+    G = cv.take<double>((size_t)S * N); C = cv.take<double>((size_t)S * N); F = cv.take<double>((size_t)S * N);
   };
+  auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
   long L = n_lines;
   if (ctx->opt.nearest_chunk_systems > 0) L = ctx->opt.nearest_chunk_systems / n_theta0;
   else while (L > 1 && bytes_of(L) > kNearestScanBytes) L = (L + 1) / 2;
   if (L < 1) L = 1;
   if (L > n_lines) L = n_lines;
-  const size_t need = bytes_of(L);
-  if (ensure_long_ws(ctx, need) != 0) {
+  const size_t bytes = bytes_of(L);
+  if (ensure_long_ws(ctx, bytes) != 0) {
     (void)hipGetLastError();
     return fail(IBS_ERR_HIP, "gamma_scan_nearest: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
-                "which could not be allocated", L, n_theta0, N, need);
+                "which could not be allocated", L, n_theta0, N, bytes);
   }
-  const long S_max = L * n_theta0;
-  const int nw = long_waves(ctx, S_max);
-  double* w = static_cast<double*>(ctx->long_ws);
-  double* work = w; w += (size_t)nw * ibs::nearest_ws_doubles(N);
-  double* G = w; w += (size_t)S_max * N; double* C = w; w += (size_t)S_max * N; double* F = w;
+  Carve cv{static_cast<char*>(ctx->long_ws)};
+  carve(cv, L);
   for (long l0 = 0; l0 < n_lines; l0 += L) {
     const int Lc = (int)(n_lines - l0 < L ? n_lines - l0 : L);
     const long s0 = l0 * n_theta0, S = (long)Lc * n_theta0;
@@ -1045,44 +1042,22 @@ int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
   const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  if (mem != IBS_MEM_HOST)
-    return scan_nearest_device(ctx, n_lines, n_theta0, N, h, src, ld, dPdrho, theta0, sigma, gam, lam, idx, info);
   const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
-  const size_t need = 7 * pad256(in_elems * 8) + pad256(n_lines * 8) + pad256(n_theta0 * 8) + 3 * pad256(n_sys * 8) +
-                      2 * pad256(n_sys * 4) + 4096;
-  if (int r = ensure_ws(ctx, need)) return r;
-  Arena ar(ctx);
-  HostStage hs(ctx, need);
-  const double* dev[7];
-  for (int k = 0; k < 7; ++k) {
-    double* d = ar.take<double>(in_elems);
-    HIPCHK(hs.up(src[k], in_elems * 8, d));
-    dev[k] = d;
-  }
-  double* ddP = ar.take<double>(n_lines); double* dt0 = ar.take<double>(n_theta0); double* dsig = ar.take<double>(n_sys);
-  HIPCHK(hs.up(dPdrho, (size_t)n_lines * 8, ddP));
-  HIPCHK(hs.up(theta0, (size_t)n_theta0 * 8, dt0));
-  HIPCHK(hs.up(sigma, n_sys * 8, dsig));
-  HIPCHK(hs.flush_in());
-  double* dgam = gam ? ar.take<double>(n_sys) : nullptr; double* dlam = lam ? ar.take<double>(n_sys) : nullptr;
-  int* didx = idx ? ar.take<int>(n_sys) : nullptr;
-  int* d_info = ar.take<int>(n_sys); int* d_nbad = ar.take<int>(1);
-  if (int r = scan_nearest_device(ctx, n_lines, n_theta0, N, h, dev, ld, ddP, dt0, dsig, dgam, dlam, didx, d_info)) return r;
-  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, d_info, d_nbad);
-  if (gam) HIPCHK(hs.down(gam, dgam, n_sys * 8));
-  if (lam) HIPCHK(hs.down(lam, dlam, n_sys * 8));
-  if (idx) HIPCHK(hs.down(idx, didx, n_sys * 4));
-  if (info) HIPCHK(hs.down(info, d_info, n_sys * 4));
-  int nbad = 0;
-  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
-  HIPCHK(hs.flush_out());
-  return nbad;
+  const double *geo7[7], *dP, *t0, *sig;
+  double *dgam, *dlam;
+  int *didx, *dinfo;
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) geo7[k] = s.in(src[k], in_elems);
+    dP = s.in(dPdrho, n_lines); t0 = s.in(theta0, n_theta0); sig = s.in(sigma, n_sys);
+    dgam = s.out(gam, n_sys); dlam = s.out(lam, n_sys); didx = s.out(idx, n_sys); dinfo = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl,
+                [&] { return scan_nearest_device(ctx, n_lines, n_theta0, N, h, geo7, ld, dP, t0, sig, dgam, dlam, didx, dinfo); });
 }
 
 // ---- geometry-fed points with the eigenpair nearest sigma[p] (ibs_nearest_grad.hip): the refinement's objective + gradient and
 // the final solve of ball_scan.py:305-339 in upstream's mode, one wave per point on the persistent grid of long_waves()
-// device pointers: the per-wave workspace (ibs::nearest_points_ws) in ctx->long_ws
+// the per-wave workspace (ibs::nearest_points_ws) in ctx->long_ws
 static int points_nearest_device(ibs_ctx* ctx, ibs::NearestPointsArgs a, bool grad) {
   const int nw = long_waves(ctx, a.n_pts);
   if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::nearest_points_ws(a.N, grad).total * sizeof(double))) return r;
@@ -1100,43 +1075,14 @@ int ibs_obj_w_grad_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h,
   if (int r = check_grid(N, h, true)) return r;
   if (n_pts == 0) return 0;
   ON_DEVICE(ctx);
+  const size_t n = (size_t)n_pts, geo_elems = n * 3 * 8 * (size_t)ld;
   ibs::NearestPointsArgs a{};
   a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld; a.del_alpha = del_alpha;
-  if (mem != IBS_MEM_HOST) {
-    a.geo = geo; a.theta0 = theta0; a.sigma = sigma; a.val = val; a.jac = jac; a.lam = lam; a.idx = idx; a.info = info;
-    return points_nearest_device(ctx, a, true);
-  }
-  const size_t n = (size_t)n_pts, geo_elems = n * 3 * 8 * (size_t)ld;
-  double *dgeo, *dt0, *dsig, *dval, *djac, *dlam;
-  int *didx, *d_info, *d_nbad;
-  auto carve = [&](Carve& cv) {          // inputs first, then the outputs: each side one contiguous span of HostStage
-    dgeo = cv.take<double>(geo_elems); dt0 = cv.take<double>(n); dsig = cv.take<double>(n);
-    dval = cv.take<double>(n); djac = cv.take<double>(2 * n); dlam = lam ? cv.take<double>(n) : nullptr;
-    didx = idx ? cv.take<int>(n) : nullptr; d_info = cv.take<int>(n); d_nbad = cv.take<int>(1);
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, geo_elems); a.theta0 = s.in(theta0, n); a.sigma = s.in(sigma, n);
+    a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.lam = s.out(lam, n); a.idx = s.out(idx, n); a.info = s.status(info, n);
   };
-  Carve sz{nullptr};
-  carve(sz);
-  if (int r = ensure_ws(ctx, sz.off)) return r;
-  Carve cv{static_cast<char*>(ctx->ws)};
-  carve(cv);
-  HostStage hs(ctx, sz.off);
-  HIPCHK(hs.up(geo, geo_elems * 8, dgeo));
-  HIPCHK(hs.up(theta0, n * 8, dt0));
-  HIPCHK(hs.up(sigma, n * 8, dsig));
-  HIPCHK(hs.flush_in());
-  a.geo = dgeo; a.theta0 = dt0; a.sigma = dsig; a.val = dval; a.jac = djac; a.lam = dlam; a.idx = didx; a.info = d_info;
-  if (int r = points_nearest_device(ctx, a, true)) return r;
-  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long)n, d_info, d_nbad);
-  HIPCHK(hs.down(val, dval, n * 8));
-  HIPCHK(hs.down(jac, djac, n * 16));
-  if (lam) HIPCHK(hs.down(lam, dlam, n * 8));
-  if (idx) HIPCHK(hs.down(idx, didx, n * 4));
-  if (info) HIPCHK(hs.down(info, d_info, n * 4));
-  int nbad = 0;
-  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
-  HIPCHK(hs.flush_out());
-  return nbad;
+  return staged(ctx, mem, decl, [&] { return points_nearest_device(ctx, a, true); });
 }
 
 int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
@@ -1151,88 +1097,49 @@ int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double 
   if (n_pts == 0) return 0;
   ON_DEVICE(ctx);
   const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  const size_t n = (size_t)n_pts, in_elems = n * (size_t)ld, out_elems = n * (size_t)N;
   ibs::NearestPointsArgs a{};
   a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld;
-  if (mem != IBS_MEM_HOST) {
-    for (int k = 0; k < 7; ++k) a.geo7[k] = src[k];
-    a.dPdrho = dPdrho; a.theta0 = theta0; a.sigma = sigma; a.gam = gam; a.lam = lam; a.idx = idx; a.X = X; a.dX = dX; a.info = info;
-    return points_nearest_device(ctx, a, false);
-  }
-  const size_t n = (size_t)n_pts, in_elems = n * (size_t)ld, out_elems = n * (size_t)N;
-  double* dev[7];
-  double *ddP, *dt0, *dsig, *dgam, *dlam, *dX_, *ddX;
-  int *didx, *d_info, *d_nbad;
-  auto carve = [&](Carve& cv) {          // inputs first, then the outputs: each side one contiguous span of HostStage
-    for (int k = 0; k < 7; ++k) dev[k] = cv.take<double>(in_elems);
-    ddP = cv.take<double>(n); dt0 = cv.take<double>(n); dsig = cv.take<double>(n);
-    dgam = cv.take<double>(n); dlam = lam ? cv.take<double>(n) : nullptr; didx = idx ? cv.take<int>(n) : nullptr;
-    dX_ = X ? cv.take<double>(out_elems) : nullptr; ddX = dX ? cv.take<double>(out_elems) : nullptr;
-    d_info = cv.take<int>(n); d_nbad = cv.take<int>(1);
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
+    a.dPdrho = s.in(dPdrho, n); a.theta0 = s.in(theta0, n); a.sigma = s.in(sigma, n);
+    a.gam = s.out(gam, n); a.lam = s.out(lam, n); a.idx = s.out(idx, n); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
+    a.info = s.status(info, n);
   };
-  Carve sz{nullptr};
-  carve(sz);
-  if (int r = ensure_ws(ctx, sz.off)) return r;
-  Carve cv{static_cast<char*>(ctx->ws)};
-  carve(cv);
-  HostStage hs(ctx, sz.off);
-  for (int k = 0; k < 7; ++k) HIPCHK(hs.up(src[k], in_elems * 8, dev[k]));
-  HIPCHK(hs.up(dPdrho, n * 8, ddP));
-  HIPCHK(hs.up(theta0, n * 8, dt0));
-  HIPCHK(hs.up(sigma, n * 8, dsig));
-  HIPCHK(hs.flush_in());
-  for (int k = 0; k < 7; ++k) a.geo7[k] = dev[k];
-  a.dPdrho = ddP; a.theta0 = dt0; a.sigma = dsig; a.gam = dgam; a.lam = dlam; a.idx = didx; a.X = dX_; a.dX = ddX; a.info = d_info;
-  if (int r = points_nearest_device(ctx, a, false)) return r;
-  HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long)n, d_info, d_nbad);
-  HIPCHK(hs.down(gam, dgam, n * 8));
-  if (lam) HIPCHK(hs.down(lam, dlam, n * 8));
-  if (idx) HIPCHK(hs.down(idx, didx, n * 4));
-  if (X) HIPCHK(hs.down(X, dX_, out_elems * 8));
-  if (dX) HIPCHK(hs.down(dX, ddX, out_elems * 8));
-  if (info) HIPCHK(hs.down(info, d_info, n * 4));
-  int nbad = 0;
-  HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
-  HIPCHK(hs.flush_out());
-  return nbad;
+  return staged(ctx, mem, decl, [&] { return points_nearest_device(ctx, a, false); });
 }
 
 // Geometry-fed scan on a grid beyond 2050 points: the (g, c, f) rows of every (line, theta0) system -- and their theta0 tangents when
 // dgam/dtheta0 is wanted -- are written out (k_assemble_gcf_long: the arithmetic the scan kernels do while staging), solved by the
 // generic long-grid kernel, and the Hellmann-Feynman sums (utils.py:1676-1680) taken by k_hf_grad.  Warm-start guesses are not
-// used (they only ever steer).  The context travels in a thread-local: the launch table's signature has no room for it.
-static thread_local ibs_ctx* g_long_ctx = nullptr;
-static hipError_t launch_scan_long(const ibs::ScanArgs<double>& a, hipStream_t st) {
-  ibs_ctx* ctx = g_long_ctx;
-  const size_t n_sys = (size_t)a.n_lines * a.n_theta0, N = (size_t)a.N;
+// used (they only ever steer).
+static int launch_scan_long(ibs_ctx* ctx, const ibs::ScanArgs<double>& a) {
+  const size_t n_sys = (size_t)a.n_lines * a.n_theta0, N = (size_t)a.N, rows = n_sys * N;
   const bool hf = a.dth0 != nullptr;
   const int nw = long_waves(ctx, (long)n_sys);
-  const size_t rows = n_sys * N;
-  size_t need = (size_t)nw * 3 * N + (hf ? 6 : 3) * rows + 256;
-  if (hf) need += (a.X ? 0 : rows) + (a.dX ? 0 : rows) + (a.gam ? 0 : n_sys);
-  if (ensure_long_ws(ctx, need * sizeof(double)) != 0) return hipErrorOutOfMemory;
-  double* w = static_cast<double*>(ctx->long_ws);
-  double* work = w; w += (size_t)nw * 3 * N;
-  double* g = w; w += rows; double* c = w; w += rows; double* f = w; w += rows;
-  double *gt = nullptr, *ct = nullptr, *ft = nullptr, *Xw = a.X, *dXw = a.dX, *gamw = a.gam;
-  if (hf) {
-    gt = w; w += rows; ct = w; w += rows; ft = w; w += rows;
-    if (!Xw) { Xw = w; w += rows; }
-    if (!dXw) { dXw = w; w += rows; }
-    if (!gamw) { gamw = w; w += n_sys; }
-  }
-  hipError_t e = ibs::launch_assemble_long(a, g, c, f, gt, ct, ft, st);
-  if (e != hipSuccess) return e;
+  double *work, *g, *c, *f, *gt = nullptr, *ct = nullptr, *ft = nullptr, *Xw = a.X, *dXw = a.dX, *gamw = a.gam;
+  auto carve = [&](Carve& cv) {
+    work = cv.take<double>((size_t)nw * 3 * N);
+    g = cv.take<double>(rows); c = cv.take<double>(rows); f = cv.take<double>(rows);
+    if (hf) {
+      gt = cv.take<double>(rows); ct = cv.take<double>(rows); ft = cv.take<double>(rows);
+      if (!a.X) Xw = cv.take<double>(rows);
+      if (!a.dX) dXw = cv.take<double>(rows);
+      if (!a.gam) gamw = cv.take<double>(n_sys);
+    }
+  };
+  if (int r = carve_long(ctx, carve)) return r;
+  HIPCHK(ibs::launch_assemble_long(a, g, c, f, gt, ct, ft, ctx->stream));
   ibs::LongGcfArgs la{};
   la.n_sys = (long)n_sys; la.N = a.N; la.h = a.h; la.g = g; la.c = c; la.f = f; la.gh = nullptr; la.f32 = 0; la.ld = (long)N;
   la.lam = a.lam; la.gam = gamw; la.X = Xw; la.dX = dXw; la.info = a.info; la.work = work; la.n_waves = nw;
-  e = ibs::launch_gcf_long(la, st);
-  if (e != hipSuccess) return e;
+  HIPCHK(ibs::launch_gcf_long(la, ctx->stream));
   if (hf) {
-    hipLaunchKernelGGL(k_hf_grad, dim3((unsigned)((n_sys + 3) / 4)), dim3(256), 0, st, (long)n_sys, a.N, (long)N, Xw, dXw, f, gt, ct, ft, gamw, a.dth0);
-    e = hipGetLastError();
+    hipLaunchKernelGGL(k_hf_grad, dim3((unsigned)((n_sys + 3) / 4)), dim3(256), 0, ctx->stream, (long)n_sys, a.N, (long)N, Xw, dXw, f, gt, ct,
+                       ft, gamw, a.dth0);
+    HIPCHK(hipGetLastError());
   }
-  return e;
+  return 0;
 }
 
 static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
@@ -1253,15 +1160,14 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
   if (n_lines == 0 || n_theta0 == 0) return 0;
   const bool lng = is_long(N);                 // grids beyond 2050 points: launch_scan_long
   int M = lng ? 1 : rows_per_lane(N);
-  auto fn = ibs::launch_table().scan_f64[M];
+  auto fn = ibs::launch_table().scan_f64[M];     // (on long grids only a check that the build is complete)
   if (!fn) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", M, N);
   ON_DEVICE(ctx);
   ibs::ScanArgs<double> a{};
   a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = ld; a.wpb = 1;
   a.t0_stride = t0_per_line ? 1 : 0;
   int G = 1;
-  if (lng) { fn = &launch_scan_long; g_long_ctx = ctx; }
-  else {
+  if (!lng) {
   const size_t per_arr = (size_t)ibs::lds_pitch(N) * sizeof(double);
   if (8 * per_arr > (size_t)ctx->lds_per_block) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
   int cap = ibs::scan_max_threads(M) / 64;
@@ -1365,81 +1271,49 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
     }
   }
   }   // (!lng)
-  const size_t n_sys = (size_t)n_lines * n_theta0;
-  if (mem == IBS_MEM_HOST) {
-    const size_t in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
-    const size_t n_t0_vals = t0_per_line ? (size_t)n_lines : (size_t)n_theta0;
-    size_t need = 7 * pad256(in_elems * 8) + pad256(n_lines * 8) + pad256(n_t0_vals * 8) + 4 * pad256(n_sys * 8) +
-                  2 * pad256(out_elems * 8) + pad256(n_sys * 4) + 8192;
-    if (int r = ensure_ws(ctx, need)) return r;
-    Arena ar(ctx);
-    HostStage hs(ctx, need);
-    const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-    double* dev[7];
-    for (int k = 0; k < 7; ++k) {
-      dev[k] = ar.take<double>(in_elems);
-      HIPCHK(hs.up(src[k], in_elems * 8, dev[k]));
-    }
-    double* ddP = ar.take<double>(n_lines); double* dt0 = ar.take<double>(n_t0_vals);
-    HIPCHK(hs.up(dPdrho, (size_t)n_lines * 8, ddP));
-    HIPCHK(hs.up(theta0, n_t0_vals * 8, dt0));
-    double* dguess = lam_guess ? ar.take<double>(n_sys) : nullptr;
-    if (lam_guess) HIPCHK(hs.up(lam_guess, n_sys * 8, dguess));
-    HIPCHK(hs.flush_in());
-    double* dgam = ar.take<double>(n_sys); double* dlam = ar.take<double>(n_sys); double* dd = ar.take<double>(n_sys);
-    double* dX_ = X ? ar.take<double>(out_elems) : nullptr; double* ddX = dX ? ar.take<double>(out_elems) : nullptr;
-    int* d_info = ar.take<int>(n_sys); int* d_nbad = ar.take<int>(1);
-    a.bmag = dev[0]; a.gradpar = dev[1]; a.cvdrift = dev[2]; a.cvdrift0 = dev[3]; a.gds2 = dev[4]; a.gds21 = dev[5]; a.gds22 = dev[6];
-    a.dPdrho = ddP; a.theta0 = dt0; a.gam = dgam; a.lam = dlam; a.X = dX_; a.dX = ddX; a.dth0 = dth0 ? dd : nullptr; a.info = d_info;
-    if (lam_guess) { a.lam_guess = dguess; a.guess_width = guess_width; }
-    HIPCHK(fn(a, ctx->stream));
-    flag_sigma<double>(ctx, (long)n_sys, a.lam, a.info);
-    HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_sys + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_sys, d_info, d_nbad);
-    if (gam) HIPCHK(hs.down(gam, dgam, n_sys * 8));
-    if (lam) HIPCHK(hs.down(lam, dlam, n_sys * 8));
-    if (dth0) HIPCHK(hs.down(dth0, dd, n_sys * 8));
-    if (X) HIPCHK(hs.down(X, dX_, out_elems * 8));
-    if (dX) HIPCHK(hs.down(dX, ddX, out_elems * 8));
-    if (info) HIPCHK(hs.down(info, d_info, n_sys * 4));
-    int nbad = 0;
-    HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
-    HIPCHK(hs.flush_out());
-    return nbad;
-  }
-  a.bmag = bmag; a.gradpar = gradpar; a.cvdrift = cvdrift; a.cvdrift0 = cvdrift0; a.gds2 = gds2; a.gds21 = gds21; a.gds22 = gds22;
-  a.dPdrho = dPdrho; a.theta0 = theta0; a.gam = gam; a.lam = lam; a.X = X; a.dX = dX; a.dth0 = dth0; a.info = info;
-  a.lam_guess = lam_guess; a.guess_width = guess_width;
-  if (pack && fn == ibs::launch_table().scan_f64[M] && G == 1) {
-    // one launch: the block that completes a surface reduces it (k_gamma_scan's epilogue)
-    ibs_ctx::SurfCounters* sc = nullptr;
-    for (auto& e : ctx->surf_counters) if (e.stream == ctx->stream) { sc = &e; break; }
-    if (!sc) { ctx->surf_counters.push_back(ibs_ctx::SurfCounters{ctx->stream, nullptr, 0}); sc = &ctx->surf_counters.back(); }
-    if (sc->n < n_surf) {
-      if (sc->buf) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipFree(sc->buf)); sc->buf = nullptr; sc->n = 0; }
-      const int cap_n = n_surf > 1024 ? n_surf : 1024;
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&sc->buf), (size_t)cap_n * sizeof(int)));
-      HIPCHK(hipMemsetAsync(sc->buf, 0, (size_t)cap_n * sizeof(int), ctx->stream));
-      sc->n = cap_n;
-    }
-    a.lines_per_surf = n_lines / n_surf; a.surf_counter = sc->buf; a.pack = pack;
-    {
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
+  const size_t n_t0_vals = t0_per_line ? (size_t)n_lines : (size_t)n_theta0;
+  a.guess_width = guess_width;
+  // (host pointers: gam, lam and info are always carved)
+  auto decl = [&](Stage& s) {
+    a.bmag = s.in(bmag, in_elems); a.gradpar = s.in(gradpar, in_elems); a.cvdrift = s.in(cvdrift, in_elems);
+    a.cvdrift0 = s.in(cvdrift0, in_elems); a.gds2 = s.in(gds2, in_elems); a.gds21 = s.in(gds21, in_elems); a.gds22 = s.in(gds22, in_elems);
+    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_t0_vals); a.lam_guess = s.in(lam_guess, n_sys);
+    a.gam = s.out(gam, n_sys, true); a.lam = s.out(lam, n_sys, true); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
+    a.dth0 = s.out(dth0, n_sys); a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    const bool fused = !lng && pack && fn == ibs::launch_table().scan_f64[M] && G == 1;
+    if (fused) {
+      // one launch: the block that completes a surface reduces it (k_gamma_scan's epilogue)
+      ibs_ctx::SurfCounters* sc = nullptr;
+      for (auto& e : ctx->surf_counters) if (e.stream == ctx->stream) { sc = &e; break; }
+      if (!sc) { ctx->surf_counters.push_back(ibs_ctx::SurfCounters{ctx->stream, nullptr, 0}); sc = &ctx->surf_counters.back(); }
+      if (sc->n < n_surf) {
+        if (sc->buf) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipFree(sc->buf)); sc->buf = nullptr; sc->n = 0; }
+        const int cap_n = n_surf > 1024 ? n_surf : 1024;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&sc->buf), (size_t)cap_n * sizeof(int)));
+        HIPCHK(hipMemsetAsync(sc->buf, 0, (size_t)cap_n * sizeof(int), ctx->stream));
+        sc->n = cap_n;
+      }
+      a.lines_per_surf = n_lines / n_surf; a.surf_counter = sc->buf; a.pack = pack;
       const long nblocks = (long)((n_theta0 + a.wpb - 1) / a.wpb) * n_lines;
       a.pack_mode = (nblocks <= ctx->n_cu && ctx->opt.pack_mode != 2) ? 1 : 2;
       if (ctx->opt.pack_mode == 1) a.pack_mode = 1;
     }
-    HIPCHK(fn(a, ctx->stream));
+    if (lng) {
+      if (int r = launch_scan_long(ctx, a)) return r;
+    } else {
+      HIPCHK(fn(a, ctx->stream));
+    }
     flag_sigma<double>(ctx, (long)n_sys, a.lam, a.info);
+    if (pack && !fused) {                          // chained / sub-wave / long-grid scans: the reduction is a second launch
+      const int n_per = (n_lines / n_surf) * n_theta0;
+      hipLaunchKernelGGL(k_surface_argmax, dim3(n_surf), dim3(argmax_threads(n_per)), 0, ctx->stream, n_per, gam, (int*)nullptr, (double*)nullptr, pack);
+      HIPCHK(hipGetLastError());
+    }
     return 0;
-  }
-  HIPCHK(fn(a, ctx->stream));
-  flag_sigma<double>(ctx, (long)n_sys, a.lam, a.info);
-  if (pack) {                                    // chained / sub-wave scan kernels: the reduction is a second launch
-    const int n_per = (n_lines / n_surf) * n_theta0;
-    hipLaunchKernelGGL(k_surface_argmax, dim3(n_surf), dim3(argmax_threads(n_per)), 0, ctx->stream, n_per, gam, (int*)nullptr, (double*)nullptr, pack);
-    HIPCHK(hipGetLastError());
-  }
-  return 0;
+  });
 }
 
 int ibs_gamma_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
@@ -1521,30 +1395,28 @@ __global__ void k_grad_long_out(int n_pts, const double* __restrict__ gam, const
   if (da_o) da_o[p] = ja[p];
   if (dt_o) dt_o[p] = jt[p];
 }
-static hipError_t launch_grad_long(const ibs::GradArgs<double>& a, hipStream_t st) {
-  ibs_ctx* ctx = g_long_ctx;
+static int launch_grad_long(ibs_ctx* ctx, const ibs::GradArgs<double>& a) {
   const size_t n = (size_t)a.n_pts, N = (size_t)a.N, rows = n * N;
   const int nw = long_waves(ctx, (long)n);
-  const size_t need = (size_t)nw * 3 * N + 6 * 3 * rows + 11 * rows + 6 * n + 3 * n + 512;
-  if (ensure_long_ws(ctx, need * sizeof(double)) != 0) return hipErrorOutOfMemory;
-  double* w = static_cast<double*>(ctx->long_ws);
-  auto take = [&](size_t k) { double* q = w; w += k; return q; };
-  double* work = take((size_t)nw * 3 * N);
-  double *G = take(3 * rows), *C = take(3 * rows), *F = take(3 * rows), *GT = take(3 * rows), *CT = take(3 * rows), *FT = take(3 * rows);
-  double *gC = take(rows), *cC = take(rows), *fC = take(rows), *gtC = take(rows), *ctC = take(rows), *ftC = take(rows);
-  double *gaC = take(rows), *caC = take(rows), *faC = take(rows), *Xw = take(rows), *dXw = take(rows);
-  double *dP3 = take(3 * n), *th3 = take(3 * n), *gamw = take(n), *lamw = take(n), *ja = take(n), *jt = take(n);
+  double *work, *G, *C, *F, *GT, *CT, *FT, *gC, *cC, *fC, *gtC, *ctC, *ftC, *gaC, *caC, *faC, *Xw, *dXw, *dP3, *th3, *gamw, *lamw, *ja, *jt;
+  auto carve = [&](Carve& cv) {
+    work = cv.take<double>((size_t)nw * 3 * N);
+    for (double** p : {&G, &C, &F, &GT, &CT, &FT}) *p = cv.take<double>(3 * rows);
+    for (double** p : {&gC, &cC, &fC, &gtC, &ctC, &ftC, &gaC, &caC, &faC, &Xw, &dXw}) *p = cv.take<double>(rows);
+    dP3 = cv.take<double>(3 * n); th3 = cv.take<double>(3 * n);
+    for (double** p : {&gamw, &lamw, &ja, &jt}) *p = cv.take<double>(n);
+  };
+  if (int r = carve_long(ctx, carve)) return r;
+  const hipStream_t st = ctx->stream;
   const long lds = a.ld;                                                  // geo: [n_pts][3][8][ld]
-  hipError_t e = ibs::launch_line_dPdrho((int)(3 * n), a.N, 8 * lds, (size_t)lds, a.geo, dP3, st);
-  if (e != hipSuccess) return e;
+  HIPCHK(ibs::launch_line_dPdrho((int)(3 * n), a.N, 8 * lds, (size_t)lds, a.geo, dP3, st));
   hipLaunchKernelGGL(k_grad_long_t0, dim3((unsigned)((3 * n + 255) / 256)), dim3(256), 0, st, a.n_pts, a.theta0, th3);
   ibs::ScanArgs<double> sa{};
   sa.n_lines = (int)(3 * n); sa.n_theta0 = 1; sa.N = a.N; sa.h = a.h; sa.ld = 8 * lds;
   sa.bmag = a.geo; sa.gradpar = a.geo + lds; sa.cvdrift = a.geo + 2 * lds; sa.cvdrift0 = a.geo + 3 * lds;
   sa.gds2 = a.geo + 4 * lds; sa.gds21 = a.geo + 5 * lds; sa.gds22 = a.geo + 6 * lds;
   sa.dPdrho = dP3; sa.theta0 = th3; sa.t0_stride = 1;
-  e = ibs::launch_assemble_long(sa, G, C, F, GT, CT, FT, st);
-  if (e != hipSuccess) return e;
+  HIPCHK(ibs::launch_assemble_long(sa, G, C, F, GT, CT, FT, st));
   int bx = (a.N + 255) / 256;
   if (bx > 16) bx = 16;
   hipLaunchKernelGGL(k_grad_long_pack, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, st, a.n_pts, a.N, 1.0 / a.del_alpha, G, C, F, GT, CT, FT,
@@ -1552,13 +1424,13 @@ static hipError_t launch_grad_long(const ibs::GradArgs<double>& a, hipStream_t s
   ibs::LongGcfArgs la{};
   la.n_sys = (long)n; la.N = a.N; la.h = a.h; la.g = gC; la.c = cC; la.f = fC; la.gh = nullptr; la.f32 = 0; la.ld = (long)N;
   la.lam = lamw; la.gam = gamw; la.X = Xw; la.dX = dXw; la.info = a.info; la.work = work; la.n_waves = nw;
-  e = ibs::launch_gcf_long(la, st);
-  if (e != hipSuccess) return e;
+  HIPCHK(ibs::launch_gcf_long(la, st));
   const unsigned hb = (unsigned)((n + 3) / 4);
   hipLaunchKernelGGL(k_hf_grad, dim3(hb), dim3(256), 0, st, (long)n, a.N, (long)N, Xw, dXw, fC, gtC, ctC, ftC, gamw, jt);
   hipLaunchKernelGGL(k_hf_grad, dim3(hb), dim3(256), 0, st, (long)n, a.N, (long)N, Xw, dXw, fC, gaC, caC, faC, gamw, ja);
   hipLaunchKernelGGL(k_grad_long_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.n_pts, gamw, ja, jt, a.val, a.jac, a.gam, a.dalpha, a.dth0);
-  return hipGetLastError();
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 int ibs_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
@@ -1570,9 +1442,8 @@ int ibs_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const d
   if (n_pts == 0) return 0;
   const bool lng = is_long(N);                 // grids beyond 2050 points: launch_grad_long
   const int M = lng ? 1 : rows_per_lane(N);
-  auto fn = lng ? &launch_grad_long : ibs::launch_table().grad_f64[M];
-  if (!fn) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", M, N);
-  if (lng) g_long_ctx = ctx;
+  const auto fn = ibs::launch_table().grad_f64[M];
+  if (!lng && !fn) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", M, N);
   ON_DEVICE(ctx);
   const size_t per_wave = (size_t)8 * ibs::lds_pitch(lng ? 66 : N) * sizeof(double);
   int wpb = (int)((size_t)ctx->lds_per_block / per_wave);
@@ -1585,38 +1456,19 @@ int ibs_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const d
   }
   ibs::GradArgs<double> a{};
   a.n_pts = n_pts; a.N = N; a.h = h; a.ld = ld; a.del_alpha = del_alpha; a.wpb = wpb;
-  const size_t geo_elems = (size_t)n_pts * 3 * 8 * ld;
-  const bool host = (mem == IBS_MEM_HOST);
-  size_t need = 3 * pad256((size_t)n_pts * 8) + pad256((size_t)n_pts * 4) + 4096;
-  if (host) need += pad256(geo_elems * 8) + pad256((size_t)n_pts * 8) * 2 + pad256((size_t)n_pts * 16) + pad256((size_t)n_pts * 4) + 4096;
-  if (int r = ensure_ws(ctx, need)) return r;
-  Arena ar(ctx);
-  a.gam = ar.take<double>(n_pts); a.dalpha = ar.take<double>(n_pts); a.dth0 = ar.take<double>(n_pts);
-  int* d_info = ar.take<int>(n_pts);
-  if (host) {
-    double* dgeo = ar.take<double>(geo_elems); double* dt0 = ar.take<double>(n_pts);
-    double* dval = ar.take<double>(n_pts); double* djac = ar.take<double>((size_t)2 * n_pts);
-    int* d_info_h = ar.take<int>(n_pts);            // (behind the inputs: the outputs come back as one contiguous span)
-    int* d_nbad = ar.take<int>(1);
-    HostStage hs(ctx, need);
-    HIPCHK(hs.up(geo, geo_elems * 8, dgeo));
-    HIPCHK(hs.up(theta0, (size_t)n_pts * 8, dt0));
-    HIPCHK(hs.flush_in());
-    a.geo = dgeo; a.theta0 = dt0; a.val = dval; a.jac = djac; a.info = d_info_h;
+  const size_t n = (size_t)n_pts, geo_elems = n * 3 * 8 * ld;
+  auto decl = [&](Stage& s) {
+    a.gam = s.scratch<double>(n); a.dalpha = s.scratch<double>(n); a.dth0 = s.scratch<double>(n);
+    a.geo = s.in(geo, geo_elems); a.theta0 = s.in(theta0, n);
+    a.val = s.out(val, n); a.jac = s.out(jac, 2 * n);
+    a.info = s.status(info, n);
+    if (!s.host && !info) a.info = s.scratch<int>(n);        // (the kernels always write status words)
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (lng) return launch_grad_long(ctx, a);
     HIPCHK(fn(a, ctx->stream));
-    HIPCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_count_status, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, ctx->stream, (long)n_pts, d_info_h, d_nbad);
-    HIPCHK(hs.down(val, dval, (size_t)n_pts * 8));
-    HIPCHK(hs.down(jac, djac, (size_t)n_pts * 16));
-    if (info) HIPCHK(hs.down(info, d_info_h, (size_t)n_pts * 4));
-    int nbad = 0;
-    HIPCHK(hs.down(&nbad, d_nbad, sizeof(int)));
-    HIPCHK(hs.flush_out());
-    return nbad;
-  }
-  a.geo = geo; a.theta0 = theta0; a.val = val; a.jac = jac; a.info = info ? info : d_info;
-  HIPCHK(fn(a, ctx->stream));
-  return 0;
+    return 0;
+  });
 }
 
 // The mode rows a caller hands to the geometry entry points ({first mode, count} per row): 1 = every row lies inside the mode
@@ -1708,52 +1560,27 @@ int ibs_fieldline_geometry_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int3
   if (rows) { a.nrows_mn = nrows_mn; a.nrows_nyq = nrows_nyq; a.dn_mn = dn_mn; a.dn_nyq = dn_nyq; }
   a.form = ibs::geo_pick_usable(a, n_lines, N, ctx->n_cu);
   const size_t img_bytes = geo_img_bytes(a, a.form.lpp);
-  if (mem == IBS_MEM_HOST) {
+  const bool host = mem == IBS_MEM_HOST;
+  if (host)
     for (int i = 0; i < n_lines; ++i)
       if (line_surf[i] < 0 || line_surf[i] >= n_surf) return fail(IBS_ERR_ARG, "line_surf[%d]=%d out of range", i, line_surf[i]);
-    const size_t n_mn = (size_t)n_surf * 6 * mnmax, n_nyq = (size_t)n_surf * 7 * mnmax_nyq, n_geo = (size_t)8 * n_lines * ld;
-    size_t need = pad256(n_mn * 8) + pad256(n_nyq * 8) + 2 * pad256((size_t)mnmax * 8) + 2 * pad256((size_t)mnmax_nyq * 8) +
-                  pad256((size_t)n_surf * 48) + pad256((size_t)n_lines * 4) + 2 * pad256((size_t)n_lines * 8) +
-                  pad256((size_t)N * 8) + pad256(n_geo * 8) + pad256((size_t)nrows_mn * 8) + pad256((size_t)nrows_nyq * 8) + img_bytes + 8192;
-    if (int r = ensure_ws(ctx, need)) return r;
-    Arena ar(ctx);
-    auto up = [&](const void* src, size_t bytes, void* dst) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream); };
-    double* d_xm = ar.take<double>(mnmax); double* d_xn = ar.take<double>(mnmax);
-    double* d_xmq = ar.take<double>(mnmax_nyq); double* d_xnq = ar.take<double>(mnmax_nyq);
-    double* d_mn = ar.take<double>(n_mn); double* d_nyq = ar.take<double>(n_nyq); double* d_sc = ar.take<double>((size_t)n_surf * 6);
-    int* d_ls = ar.take<int>(n_lines); double* d_la = ar.take<double>(n_lines); double* d_th = ar.take<double>(N);
-    double* d_geo = ar.take<double>(n_geo); double* d_dP = ar.take<double>(n_lines);
-    HIPCHK(up(xm, (size_t)mnmax * 8, d_xm)); HIPCHK(up(xn, (size_t)mnmax * 8, d_xn));
-    HIPCHK(up(xm_nyq, (size_t)mnmax_nyq * 8, d_xmq)); HIPCHK(up(xn_nyq, (size_t)mnmax_nyq * 8, d_xnq));
-    HIPCHK(up(tab_mn, n_mn * 8, d_mn)); HIPCHK(up(tab_nyq, n_nyq * 8, d_nyq)); HIPCHK(up(scal, (size_t)n_surf * 48, d_sc));
-    HIPCHK(up(line_surf, (size_t)n_lines * 4, d_ls)); HIPCHK(up(line_alpha, (size_t)n_lines * 8, d_la)); HIPCHK(up(theta, (size_t)N * 8, d_th));
-    a.xm = d_xm; a.xn = d_xn; a.xm_nyq = d_xmq; a.xn_nyq = d_xnq; a.tab_mn = d_mn; a.tab_nyq = d_nyq; a.scal = d_sc;
-    a.line_surf = d_ls; a.line_alpha = d_la; a.theta = d_th; a.geo = d_geo; a.dPdrho = d_dP;
-    if (rows) {
-      int* d_r1 = ar.take<int>((size_t)2 * nrows_mn); int* d_r2 = ar.take<int>((size_t)2 * nrows_nyq);
-      HIPCHK(up(rows_mn, (size_t)nrows_mn * 8, d_r1)); HIPCHK(up(rows_nyq, (size_t)nrows_nyq * 8, d_r2));
-      a.rows_mn = d_r1; a.rows_nyq = d_r2;
-    }
-    if (img_bytes) a.img[ibs::geo_lpp_index(a.form.lpp)] = ar.take<double>(img_bytes / sizeof(double));
+  // a device-pointer call whose lines touch few of the surfaces (a large table set worked through piece by piece) builds their
+  // images only
+  const bool mark = !host && img_bytes && n_surf >= 32 && (long)n_lines < 8L * n_surf;
+  const size_t n_mn = (size_t)n_surf * 6 * mnmax, n_nyq = (size_t)n_surf * 7 * mnmax_nyq, n_geo = (size_t)8 * n_lines * ld;
+  auto decl = [&](Stage& s) {
+    a.xm = s.in(xm, mnmax); a.xn = s.in(xn, mnmax); a.xm_nyq = s.in(xm_nyq, mnmax_nyq); a.xn_nyq = s.in(xn_nyq, mnmax_nyq);
+    a.tab_mn = s.in(tab_mn, n_mn); a.tab_nyq = s.in(tab_nyq, n_nyq); a.scal = s.in(scal, (size_t)n_surf * 6);
+    a.line_surf = s.in(line_surf, n_lines); a.line_alpha = s.in(line_alpha, n_lines); a.theta = s.in(theta, N);
+    if (rows) { a.rows_mn = s.in(rows_mn, (size_t)2 * nrows_mn); a.rows_nyq = s.in(rows_nyq, (size_t)2 * nrows_nyq); }
+    a.geo = s.out(geo, n_geo); a.dPdrho = s.out(dPdrho, n_lines, true);
+    if (img_bytes) a.img[ibs::geo_lpp_index(a.form.lpp)] = s.scratch<double>(img_bytes / sizeof(double));
+    a.surf_used = s.scratch<int>(n_surf, mark);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
     HIPCHK(ibs::launch_geometry(a, ctx->stream, ctx->n_cu));
-    HIPCHK(hipMemcpyAsync(geo, d_geo, n_geo * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (dPdrho) HIPCHK(hipMemcpyAsync(dPdrho, d_dP, (size_t)n_lines * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
-  }
-  a.xm = xm; a.xn = xn; a.xm_nyq = xm_nyq; a.xn_nyq = xn_nyq; a.tab_mn = tab_mn; a.tab_nyq = tab_nyq; a.scal = scal;
-  a.line_surf = line_surf; a.line_alpha = line_alpha; a.theta = theta; a.geo = geo; a.dPdrho = dPdrho;
-  if (rows) { a.rows_mn = rows_mn; a.rows_nyq = rows_nyq; }
-  if (img_bytes) {
-    // a call whose lines touch few of the surfaces (a large table set worked through piece by piece) builds their images only
-    const bool mark = n_surf >= 32 && (long)n_lines < 8L * n_surf;
-    if (int r = ensure_ws(ctx, img_bytes + pad256((size_t)n_surf * sizeof(int)) + 4096)) return r;
-    Arena ar(ctx);
-    a.img[ibs::geo_lpp_index(a.form.lpp)] = ar.take<double>(img_bytes / sizeof(double));
-    if (mark) a.surf_used = ar.take<int>(n_surf);
-  }
-  HIPCHK(ibs::launch_geometry(a, ctx->stream, ctx->n_cu));
-  return 0;
+  });
 }
 
 int ibs_hf_grad_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, const double* X, const double* dX, const double* f,
@@ -1765,29 +1592,20 @@ int ibs_hf_grad_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, const double* X, con
   if (N < 3 || !(N & 1)) return fail(IBS_ERR_UNSUPPORTED, "N=%d: the Simpson rule of the reference needs N odd", N);
   if (n_sys == 0) return 0;
   ON_DEVICE(ctx);
-  const dim3 grid((unsigned)((n_sys + 3) / 4));
-  if (mem == IBS_MEM_HOST) {
-    const size_t ne = (size_t)n_sys * ld;
-    if (int r = ensure_ws(ctx, 6 * pad256(ne * 8) + 2 * pad256(n_sys * 8) + 4096)) return r;
-    Arena ar(ctx);
-    const double* src[6] = {X, dX, f, g_p, c_p, f_p};
-    double* dev[6];
-    for (int k = 0; k < 6; ++k) {
-      dev[k] = ar.take<double>(ne);
-      HIPCHK(hipMemcpyAsync(dev[k], src[k], ne * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    double* dgam = ar.take<double>(n_sys); double* djac = ar.take<double>(n_sys);
-    HIPCHK(hipMemcpyAsync(dgam, gam, (size_t)n_sys * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_hf_grad, grid, dim3(256), 0, ctx->stream, (long)n_sys, N, (long)ld, dev[0], dev[1], dev[2], dev[3],
-                       dev[4], dev[5], dgam, djac);
+  const size_t ne = (size_t)n_sys * ld;
+  const double* d[7];
+  double* djac;
+  auto decl = [&](Stage& s) {
+    const double* src[7] = {X, dX, f, g_p, c_p, f_p, gam};
+    for (int k = 0; k < 7; ++k) d[k] = s.in(src[k], k < 6 ? ne : (size_t)n_sys);
+    djac = s.out(jac, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    hipLaunchKernelGGL(k_hf_grad, dim3((unsigned)((n_sys + 3) / 4)), dim3(256), 0, ctx->stream, (long)n_sys, N, (long)ld, d[0], d[1], d[2],
+                       d[3], d[4], d[5], d[6], djac);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(jac, djac, (size_t)n_sys * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
-  }
-  hipLaunchKernelGGL(k_hf_grad, grid, dim3(256), 0, ctx->stream, (long)n_sys, N, (long)ld, X, dX, f, g_p, c_p, f_p, gam, jac);
-  HIPCHK(hipGetLastError());
-  return 0;
+  });
 }
 
 int ibs_sturm_count_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c,
@@ -1823,26 +1641,15 @@ int ibs_sturm_count_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const 
   if (wpb < 1) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, per_wave);
   ibs::SturmArgs<double> a{};
   a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.wpb = wpb;
-  if (mem == IBS_MEM_HOST) {
-    const size_t in_elems = (size_t)n_sys * ld;
-    size_t need = 3 * pad256(in_elems * 8) + pad256(n_sys * 8) + pad256(n_sys * 4) + 4096;
-    if (int r = ensure_ws(ctx, need)) return r;
-    Arena ar(ctx);
-    double* dg = ar.take<double>(in_elems); double* dc = ar.take<double>(in_elems); double* df = ar.take<double>(in_elems);
-    double* ds = ar.take<double>(n_sys); int* dcount = ar.take<int>(n_sys);
-    HIPCHK(hipMemcpyAsync(dg, g, in_elems * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(dc, c, in_elems * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(df, f, in_elems * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ds, shift, n_sys * 8, hipMemcpyHostToDevice, ctx->stream));
-    a.g = dg; a.c = dc; a.f = df; a.shift = ds; a.count = dcount;
+  const size_t in_elems = (size_t)n_sys * ld;
+  auto decl = [&](Stage& s) {
+    a.g = s.in(g, in_elems); a.c = s.in(c, in_elems); a.f = s.in(f, in_elems); a.shift = s.in(shift, n_sys);
+    a.count = s.out(count, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
     HIPCHK(fn(a, ctx->stream));
-    HIPCHK(hipMemcpyAsync(count, dcount, n_sys * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
-  }
-  a.g = g; a.c = c; a.f = f; a.shift = shift; a.count = count;
-  HIPCHK(fn(a, ctx->stream));
-  return 0;
+  });
 }
 
 int ibs_surface_argmax_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per, const double* gam, int32_t* idx,
@@ -1851,22 +1658,15 @@ int ibs_surface_argmax_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per, const do
   if (n_surf < 0 || n_per <= 0 || !gam || !idx || !val) return fail(IBS_ERR_ARG, "bad arguments");
   if (n_surf == 0) return 0;
   ON_DEVICE(ctx);
-  if (mem == IBS_MEM_HOST) {
-    const size_t ne = (size_t)n_surf * n_per;
-    if (int r = ensure_ws(ctx, pad256(ne * 8) + pad256(n_surf * 8) + pad256(n_surf * 4) + 4096)) return r;
-    Arena ar(ctx);
-    double* dg = ar.take<double>(ne); double* dv = ar.take<double>(n_surf); int* di = ar.take<int>(n_surf);
-    HIPCHK(hipMemcpyAsync(dg, gam, ne * 8, hipMemcpyHostToDevice, ctx->stream));
+  const double* dg;
+  int* di;
+  double* dv;
+  auto decl = [&](Stage& s) { dg = s.in(gam, (size_t)n_surf * n_per); di = s.out(idx, n_surf); dv = s.out(val, n_surf); };
+  return staged(ctx, mem, decl, [&]() -> int {
     hipLaunchKernelGGL(k_surface_argmax, dim3(n_surf), dim3(argmax_threads(n_per)), 0, ctx->stream, n_per, dg, di, dv, (double*)nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(idx, di, (size_t)n_surf * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(val, dv, (size_t)n_surf * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
-  }
-  hipLaunchKernelGGL(k_surface_argmax, dim3(n_surf), dim3(argmax_threads(n_per)), 0, ctx->stream, n_per, gam, idx, val, (double*)nullptr);
-  HIPCHK(hipGetLastError());
-  return 0;
+  });
 }
 
 int ibs_surface_argmax_pack_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per, const double* gam, double* pack) {
@@ -1946,109 +1746,85 @@ int ibs_refine_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_ny
     if (fit < 0) return fit;
     if (fit == 1) { ga.nrows_mn = nrows_mn; ga.nrows_nyq = nrows_nyq; ga.dn_mn = dn_mn; ga.dn_nyq = dn_nyq; }
   }
-  size_t need = pad256(n_geo * 8) + pad256((size_t)n_lines * 4) + pad256((size_t)n_lines * 8) + 10 * pad256((size_t)n_pts * 16) +
-                pad256((size_t)n_pts * sizeof(RefineState)) + pad256((size_t)N * 8) + 8192;
   // the lanes-per-point forms the rounds can take as the batch shrinks (geo_pick_form is monotone in the batch size)
   const int lpp_first = ibs::geo_pick_usable(ga, n_lines, N, ctx->n_cu).lpp;
   const int lpp_last = ibs::geo_pick_usable(ga, 3, N, ctx->n_cu).lpp;
-  for (int lpp = lpp_first; lpp <= lpp_last; lpp *= 2) need += geo_img_bytes(ga, lpp) + 256;
-  if (host) need += pad256(n_mn * 8) + pad256(n_nyq * 8) + 2 * pad256((size_t)mnmax * 8) + 2 * pad256((size_t)mnmax_nyq * 8) +
-                    pad256((size_t)n_surf * 48) + pad256((size_t)nrows_mn * 8) + pad256((size_t)nrows_nyq * 8) + 4096;
-  if (int r = ensure_ws(ctx, need)) return r;
-  Arena ar(ctx);
-  hipStream_t st = ctx->stream;
-  auto up = [&](const void* src, size_t bytes, void* dst) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, st); };
-  if (host) {
-    double* d_xm = ar.take<double>(mnmax); double* d_xn = ar.take<double>(mnmax);
-    double* d_xmq = ar.take<double>(mnmax_nyq); double* d_xnq = ar.take<double>(mnmax_nyq);
-    double* d_mn = ar.take<double>(n_mn); double* d_nyq = ar.take<double>(n_nyq); double* d_sc = ar.take<double>((size_t)n_surf * 6);
-    HIPCHK(up(xm, (size_t)mnmax * 8, d_xm)); HIPCHK(up(xn, (size_t)mnmax * 8, d_xn));
-    HIPCHK(up(xm_nyq, (size_t)mnmax_nyq * 8, d_xmq)); HIPCHK(up(xn_nyq, (size_t)mnmax_nyq * 8, d_xnq));
-    HIPCHK(up(tab_mn, n_mn * 8, d_mn)); HIPCHK(up(tab_nyq, n_nyq * 8, d_nyq)); HIPCHK(up(scal, (size_t)n_surf * 48, d_sc));
-    ga.xm = d_xm; ga.xn = d_xn; ga.xm_nyq = d_xmq; ga.xn_nyq = d_xnq; ga.tab_mn = d_mn; ga.tab_nyq = d_nyq; ga.scal = d_sc;
-    if (ga.nrows_mn) {
-      int* d_r1 = ar.take<int>((size_t)2 * nrows_mn); int* d_r2 = ar.take<int>((size_t)2 * nrows_nyq);
-      HIPCHK(up(rows_mn, (size_t)nrows_mn * 8, d_r1)); HIPCHK(up(rows_nyq, (size_t)nrows_nyq * 8, d_r2));
-      ga.rows_mn = d_r1; ga.rows_nyq = d_r2;
-    }
-  } else {
-    ga.xm = xm; ga.xn = xn; ga.xm_nyq = xm_nyq; ga.xn_nyq = xn_nyq; ga.tab_mn = tab_mn; ga.tab_nyq = tab_nyq; ga.scal = scal;
-    if (ga.nrows_mn) { ga.rows_mn = rows_mn; ga.rows_nyq = rows_nyq; }
-  }
-  const double* d_th = theta; const int* d_ps = pt_surf; const double* d_start = start;   // (device pointers are used in place)
-  if (host) {
-    double* t_ = ar.take<double>(N); int* p_ = ar.take<int>(n_pts); double* s_ = ar.take<double>((size_t)2 * n_pts);
-    HIPCHK(up(theta, (size_t)N * 8, t_)); HIPCHK(up(pt_surf, (size_t)n_pts * 4, p_)); HIPCHK(up(start, (size_t)n_pts * 16, s_));
-    d_th = t_; d_ps = p_; d_start = s_;
-  }
-  double* d_geo = ar.take<double>(n_geo);
-  int* d_ls = ar.take<int>(n_lines); double* d_la = ar.take<double>(n_lines); double* d_t0 = ar.take<double>(n_pts); int* d_idx = ar.take<int>(n_pts);
-  RefineState* d_st = ar.take<RefineState>(n_pts);
-  double* d_gam = ar.take<double>(n_pts); double* d_da = ar.take<double>(n_pts); double* d_dt = ar.take<double>(n_pts);
-  int* d_info = ar.take<int>(n_pts);
-  RefineCtrl* d_ctrl = ar.take<RefineCtrl>(1);
-  double* d_xo = x_opt; double* d_fo = f_opt; int* d_ne = n_evals;                          // (device pointers: written in place)
-  if (host) { d_xo = ar.take<double>((size_t)2 * n_pts); d_fo = ar.take<double>(n_pts); d_ne = ar.take<int>(n_pts); }
-  for (int lpp = lpp_first; lpp <= lpp_last; lpp *= 2)
-    if (geo_img_bytes(ga, lpp)) ga.img[ibs::geo_lpp_index(lpp)] = ar.take<double>(geo_img_bytes(ga, lpp) / sizeof(double));
-  ga.theta = d_th; ga.geo = d_geo; ga.dPdrho = nullptr;
-  ga.line_surf = d_ls; ga.line_alpha = d_la;
-  ga.n_lines_dev = &d_ctrl->n_lines;
-  ga.plane = (size_t)n_lines * ld;                                        // fixed: the batch shrinks, the planes stay
-
-  RefineParams prm{};
-  prm.lo[0] = 0.0; prm.lo[1] = 0.0; prm.hi[0] = 3.141592653589793; prm.hi[1] = 1.5707963267948966;   // ball_scan.py:311
-  prm.del_alpha = del_alpha; prm.ftol = ftol; prm.gtol = gtol; prm.maxiter = maxiter; prm.n_surf = n_surf;
   ibs::RefineEvalArgs<double> ea{};
-  ea.N = N; ea.geo = d_geo; ea.ld = ld; ea.plane = ga.plane;
-  ea.st = d_st; ea.prm = prm; ea.ctrl = d_ctrl; ea.idx = d_idx; ea.pt_surf = d_ps;
-  ea.line_surf = d_ls; ea.line_alpha = d_la; ea.th0 = d_t0;
-  ea.gam = d_gam; ea.dalpha = d_da; ea.dth0 = d_dt; ea.info = d_info;
-  ea.hist = ctx->refine_hist; ea.hist_len = max_rounds + 2; ea.lds_tangent = lds_tangent;
-
-  const dim3 grd((unsigned)((n_pts + 127) / 128)), blk(128);
-  const dim3 gri((unsigned)((n_pts > N ? n_pts : N) + 127) / 128);
-  hipLaunchKernelGGL(k_refine_init, gri, blk, 0, st, n_pts, d_ps, d_start, d_st, prm, d_idx, d_ls, d_la, d_t0, d_ctrl, N, d_th,
-                     ctx->refine_hist + ctx->refine_hist_len + 4);
-  HIPCHK(hipGetLastError());
-  // Rounds are enqueued kLook ahead of the last one whose count the device has posted: the grid sizes and the geometry
-  // form of round r are functions of the count after round r - 1 - kLook -- of the trajectory, not of host timing, so the
-  // arithmetic (summation order of the geometry kernel's forms) is reproducible -- and the GPU never waits for the host.
-  // Rounds enqueued after the last point has finished find an empty batch and return at once.
-  constexpr int kLook = 1;
+  const double *d_th, *d_start;
+  RefineState* d_st;
+  RefineCtrl* d_ctrl;
+  double *d_xo, *d_fo;
+  int* d_ne;
+  auto decl = [&](Stage& s) {
+    ga.xm = s.in(xm, mnmax); ga.xn = s.in(xn, mnmax); ga.xm_nyq = s.in(xm_nyq, mnmax_nyq); ga.xn_nyq = s.in(xn_nyq, mnmax_nyq);
+    ga.tab_mn = s.in(tab_mn, n_mn); ga.tab_nyq = s.in(tab_nyq, n_nyq); ga.scal = s.in(scal, (size_t)n_surf * 6);
+    if (ga.nrows_mn) { ga.rows_mn = s.in(rows_mn, (size_t)2 * nrows_mn); ga.rows_nyq = s.in(rows_nyq, (size_t)2 * nrows_nyq); }
+    d_th = s.in(theta, N); ea.pt_surf = s.in(pt_surf, n_pts); d_start = s.in(start, (size_t)2 * n_pts);
+    // (host pointers: n_evals is written on the device whether it is asked for or not)
+    d_xo = s.out(x_opt, (size_t)2 * n_pts); d_fo = s.out(f_opt, n_pts); d_ne = s.out(n_evals, n_pts, true);
+    ga.geo = s.scratch<double>(n_geo); ea.line_surf = s.scratch<int>(n_lines); ea.line_alpha = s.scratch<double>(n_lines);
+    ea.th0 = s.scratch<double>(n_pts); ea.idx = s.scratch<int>(n_pts); d_st = s.scratch<RefineState>(n_pts);
+    ea.gam = s.scratch<double>(n_pts); ea.dalpha = s.scratch<double>(n_pts); ea.dth0 = s.scratch<double>(n_pts);
+    ea.info = s.scratch<int>(n_pts); d_ctrl = s.scratch<RefineCtrl>(1);
+    for (int lpp = lpp_first; lpp <= lpp_last; lpp *= 2)
+      if (geo_img_bytes(ga, lpp)) ga.img[ibs::geo_lpp_index(lpp)] = s.scratch<double>(geo_img_bytes(ga, lpp) / sizeof(double));
+  };
+  const hipStream_t st = ctx->stream;
   int enq = 0, rounds = -1;
-  while (enq < max_rounds) {
-    const int need_r = enq > kLook ? enq - kLook : 0;
-    int spins = 0;
-    const auto t_start = std::chrono::steady_clock::now();       // (the limit is per awaited round, not per call)
-    while (hist[need_r] == 0) {
-      if (++spins > 2000) {
-        std::this_thread::yield();
-        if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(120)) {
-          (void)hipStreamSynchronize(st);
-          return fail(IBS_ERR_HIP, "refinement round %d did not report within 120 s", need_r);
+  auto launch = [&]() -> int {
+    ga.theta = d_th; ga.dPdrho = nullptr;
+    ga.n_lines_dev = &d_ctrl->n_lines;
+    ga.plane = (size_t)n_lines * ld;                                        // fixed: the batch shrinks, the planes stay
+
+    RefineParams prm{};
+    prm.lo[0] = 0.0; prm.lo[1] = 0.0; prm.hi[0] = 3.141592653589793; prm.hi[1] = 1.5707963267948966;   // ball_scan.py:311
+    prm.del_alpha = del_alpha; prm.ftol = ftol; prm.gtol = gtol; prm.maxiter = maxiter; prm.n_surf = n_surf;
+    ea.N = N; ea.geo = ga.geo; ea.ld = ld; ea.plane = ga.plane;
+    ea.st = d_st; ea.prm = prm; ea.ctrl = d_ctrl;
+    ga.line_surf = ea.line_surf; ga.line_alpha = ea.line_alpha;
+    ea.hist = ctx->refine_hist; ea.hist_len = max_rounds + 2; ea.lds_tangent = lds_tangent;
+
+    const dim3 grd((unsigned)((n_pts + 127) / 128)), blk(128);
+    const dim3 gri((unsigned)((n_pts > N ? n_pts : N) + 127) / 128);
+    hipLaunchKernelGGL(k_refine_init, gri, blk, 0, st, n_pts, ea.pt_surf, d_start, d_st, prm, ea.idx, ea.line_surf, ea.line_alpha, ea.th0,
+                       d_ctrl, N, d_th, ctx->refine_hist + ctx->refine_hist_len + 4);
+    HIPCHK(hipGetLastError());
+    // Rounds are enqueued kLook ahead of the last one whose count the device has posted: the grid sizes and the geometry
+    // form of round r are functions of the count after round r - 1 - kLook -- of the trajectory, not of host timing, so the
+    // arithmetic (summation order of the geometry kernel's forms) is reproducible -- and the GPU never waits for the host.
+    // Rounds enqueued after the last point has finished find an empty batch and return at once.
+    constexpr int kLook = 1;
+    while (enq < max_rounds) {
+      const int need_r = enq > kLook ? enq - kLook : 0;
+      int spins = 0;
+      const auto t_start = std::chrono::steady_clock::now();       // (the limit is per awaited round, not per call)
+      while (hist[need_r] == 0) {
+        if (++spins > 2000) {
+          std::this_thread::yield();
+          if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(120)) {
+            (void)hipStreamSynchronize(st);
+            return fail(IBS_ERR_HIP, "refinement round %d did not report within 120 s", need_r);
+          }
         }
       }
+      const int nc = hist[need_r] - 1;
+      if (nc <= 0) { rounds = need_r; break; }
+      ga.n_lines = 3 * nc;
+      ga.form = ibs::geo_pick_usable(ga, ga.n_lines, N, ctx->n_cu);
+      HIPCHK(ibs::launch_geometry(ga, st, ctx->n_cu));
+      ea.n_c_max = nc;
+      HIPCHK(eval(ea, st));
+      ++enq;
     }
-    const int nc = hist[need_r] - 1;
-    if (nc <= 0) { rounds = need_r; break; }
-    ga.n_lines = 3 * nc;
-    ga.form = ibs::geo_pick_usable(ga, ga.n_lines, N, ctx->n_cu);
-    HIPCHK(ibs::launch_geometry(ga, st, ctx->n_cu));
-    ea.n_c_max = nc;
-    HIPCHK(eval(ea, st));
-    ++enq;
-  }
-  hipLaunchKernelGGL(k_refine_out, grd, blk, 0, st, n_pts, d_st, d_xo, d_fo, d_ne, h_stats);
-  HIPCHK(hipGetLastError());
-  ctx->refine_pending = true;
-  if (host) {
-    HIPCHK(up(d_xo, (size_t)n_pts * 16, x_opt)); HIPCHK(up(d_fo, (size_t)n_pts * 8, f_opt));
-    if (n_evals) HIPCHK(up(d_ne, (size_t)n_pts * 4, n_evals));
-  }
+    hipLaunchKernelGGL(k_refine_out, grd, blk, 0, st, n_pts, d_st, d_xo, d_fo, d_ne, h_stats);
+    HIPCHK(hipGetLastError());
+    ctx->refine_pending = !host;         // (host pointers: staged() waits for the stream)
+    return 0;
+  };
+  if (int r = staged(ctx, mem, decl, launch)) return r;
   // device pointers: the results are complete once the stream reaches this point (the rounds themselves are known to be
   // over -- their counts were read above -- unless the loop ended on the round limit)
-  if (host || rounds < 0) { HIPCHK(hipStreamSynchronize(st)); ctx->refine_pending = false; }
+  if (rounds < 0 && ctx->refine_pending) { HIPCHK(hipStreamSynchronize(st)); ctx->refine_pending = false; }
   if (*h_status != 0) {
     HIPCHK(hipStreamSynchronize(st)); ctx->refine_pending = false;
     return *h_status == 1 ? fail(IBS_ERR_UNSUPPORTED, "theta grid is not uniform") : fail(IBS_ERR_ARG, "h must be > 0");
