@@ -1,0 +1,154 @@
+"""Grid lengths on lane, chunk and path edges, and two families of raw systems whose mode sits where the caller puts it: the inputs of
+tests/test_gpu_edge_lengths.py, pinned with the oracle alone in tests/test_edge_cases_cpu.py.  Test infrastructure only.
+
+Rows per lane of the register kernels: M = ceil((N - 2) / 64), N <= 2050.  Beyond that the long path (csrc/ibs_long.hpp) passes the
+n = N - 2 rows through LDS in chunks of 768 (counts) and 384 (pivots, eigenvector, adjoint solve, nearest sigma): the last chunk
+holds n mod 768 / n mod 384 rows, the inner loops are unrolled by 8, and the coarse-grid start of long_lam_max needs
+(N - 1) % 16 == 0."""
+import numpy as np
+
+EPS = 2.220446049250313e-16
+LONG_CHUNK, VEC_CHUNK = 768, 384                    # kLongChunk, kVecChunk of csrc/ibs_long.hpp
+
+EDGE_N_SHORT = [
+    67, 69,      # smallest odd lengths: the M = 2 branch, 65 / 67 rows = one full register row plus one / three
+    99,          # N - 2 = 97: the first length the 32-lane form takes (pick_lanes: 32 * 3 + 1 rows)
+    129, 131,    # last length of M = 2, first of M = 3 (the M >= 3 code)
+    195,         # M = 4
+    257, 259,    # N - 2 = 255 / 257: last length the 16-lane form takes (16 * 16 rows), first without it; M = 4 / 5
+    323,         # M = 6
+    387,         # M = 7, one row in the last register row
+    451,         # M = 8
+    577,         # M = 9
+    641, 643,    # N - 2 = 639 / 641: last length the 32-lane form takes (32 * 20 rows), first without it; M = 10 / 11
+    705,         # M = 11
+    707,         # M = 12, one row in the last register row
+    833,         # M = 13
+    835,         # M = 14, one row in the last register row
+    961,         # M = 15
+    963,         # M = 16, one row in the last register row
+    1089,        # M = 17
+    1091,        # M = 18, one row in the last register row
+    1217,        # M = 19
+    1219,        # M = 20, one row in the last register row
+    1283,        # M = 21, one row in the last register row
+    1347,        # M = 22, one row in the last register row
+    1473,        # M = 23
+    1475,        # M = 24, one row in the last register row (first length of the row-streamed raw solve)
+    1539,        # M = 25, one row in the last register row
+    1603,        # M = 26, one row in the last register row
+    1729,        # M = 27
+    1731,        # M = 28, one row in the last register row
+    1795,        # M = 29, one row in the last register row
+    1859,        # M = 30, one row in the last register row
+    1985,        # M = 31
+    2047, 2049,  # M = 32, three rows short of full and one row short
+]
+EDGE_N_LONG = [
+    2051,        # first long length; n mod 768 = 513, n mod 384 = 129 (both = 1 mod 8); (N - 1) % 16 = 2: two-grid start off
+    2305,        # n mod 768 = 767: the last count chunk one row short; two-grid start on
+    2307,        # n mod 768 = n mod 384 = 1: one row in the last chunk of both sizes; two-grid start off
+    2313,        # the reference's grid rule N = 8 mpol ntor + 1 with mpol = ntor = 17: (N - 1) % 16 = 8, two-grid start off
+    2889,        # the same with mpol = ntor = 19: (N - 1) % 16 = 8
+    3073,        # n mod 384 = 383: the last vector chunk one row short; two-grid start on
+    3075,        # n mod 768 = n mod 384 = 1 again, one count chunk further; two-grid start off
+    65535,       # largest odd length below the limit; (N - 1) % 16 = 14: two-grid start off
+]
+EDGE_N_COUNT = [
+    66, 130, 2050,   # even: every lane full (N - 2 = 64 M, M = 1, 2, 32); 66 is the one-row-per-lane sweep
+    2052,            # first even long length
+    2306, 3074,      # even and long: N - 2 = 3 * 768 and 4 * 768 fill the last chunk exactly
+]
+# (no (N, target) case is dropped: on every length above the two CPU oracles agree to far less than a tenth of each tolerance the GPU
+#  tests apply -- tests/test_edge_cases_cpu.py::test_the_two_oracles_agree_on_the_moving_well)
+
+
+def rows_per_lane(N):
+    return (N - 2 + 63) // 64
+
+
+def lanes_allowed(N):
+    """the lanes-per-system forms pick_lanes (csrc/ibs_api.hip) admits at this length besides 64"""
+    n = N - 2
+    return [P for P, lo, hi in ((32, 97, 640), (16, 49, 256)) if lo <= n <= hi]
+
+
+def theta_grid(N):
+    return np.linspace(-4 * np.pi, 4 * np.pi, N)
+
+
+def well_rows(theta, j_star, wr=6.0, depth=0.3):
+    """(g, c, f) of the moving well: g = 1, f = depth / h^2, c = (depth / h^2) exp(-((j - j_star) / wr)^2) - 0.5 over the grid index
+    j.  One Gaussian well, wr grid rows wide, centred on grid point j_star: lam_max is 0.40 ... 0.73, ||A|| about 13.5 and the mode
+    peaks on j_star at every N (X is zero at the ends, so a well centred next to an end peaks 4 to 6 points inside)."""
+    theta = np.asarray(theta, dtype=np.float64)
+    N = len(theta)
+    h = theta[1] - theta[0]
+    j = np.arange(N, dtype=np.float64)
+    a = depth / h ** 2
+    return np.ones(N), a * np.exp(-((j - j_star) / wr) ** 2) - 0.5, np.full(N, a)
+
+
+def two_wells(theta, j_deep, j_shallow, wr=6.0):
+    """the moving well of depth 0.3 on j_deep plus one of depth 0.27 on j_shallow (at least 40 rows apart; f as in well_rows): the top
+    mode sits on j_deep, the second on j_shallow, the third eigenvalue lies well below both"""
+    assert abs(j_deep - j_shallow) >= 40
+    g, c, f = well_rows(theta, j_deep, wr, 0.3)
+    h = theta[1] - theta[0]
+    j = np.arange(len(theta), dtype=np.float64)
+    return g, c + (0.27 / h ** 2) * np.exp(-((j - j_shallow) / wr) ** 2), f
+
+
+def to_geometry(g, c, f, dPdrho=-1.0):
+    """the geometry arrays (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22) whose coefficients (utils.py:1560-1562) are the rows
+    (g, c, f): bmag = 1, gradpar = sqrt(g / f), gds2 = g / gradpar, cvdrift = -c gradpar / dPdrho, the theta0 terms zero"""
+    g, c, f = (np.asarray(a, dtype=np.float64) for a in (g, c, f))
+    gradpar = np.sqrt(g / f)
+    z = np.zeros_like(g)
+    return np.ones_like(g), gradpar, -c * gradpar / dPdrho, z, g / gradpar, z.copy(), z.copy()
+
+
+def twist_targets(N, cap=24):
+    """the j_star list of a length: grid points 1 and N - 2 (the mode then peaks 4 to 6 points from that end: one direction of the
+    twisted split has almost no rows) and, for multiples m of 384 below N - 8, the points m - 1, m, m + 1, m + 2 (the row index is the
+    point index minus one, so the twist row lands on and next to a chunk edge counted either way).  At most `cap` per N: the first and
+    the last multiples are taken first."""
+    ms = list(range(VEC_CHUNK, N - 8, VEC_CHUNK))
+    order = []
+    lo, hi = 0, len(ms) - 1
+    while lo <= hi:
+        order.append(ms[lo])
+        if hi != lo:
+            order.append(ms[hi])
+        lo += 1; hi -= 1
+    out = [1, N - 2]
+    for m in order:
+        if len(out) + 4 > cap:
+            break
+        out += [m - 1, m, m + 1, m + 2]
+    return out
+
+
+def is_end_target(N, j_star):
+    return j_star < 6 or j_star > N - 7
+
+
+def norm_a(h, g, c, f):
+    """the solver's bound on ||A||: max over the rows of (|d| + e_lo + e_hi) / f (utils.py:1574-1592 with the half-grid g the mean of
+    neighbours); g, c, f (n_sys, N)"""
+    g, c, f = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (g, c, f))
+    ee = (g[:, :-2] + 2 * g[:, 1:-1] + g[:, 2:]) / (2 * h * h)
+    return ((np.abs(c[:, 1:-1] - ee) + ee) / f[:, 1:-1]).max(axis=1)
+
+
+def top_pairs(theta, g, c, f, k=2):
+    """(w, V): the k largest eigenvalues of the pencil (ascending) and their vectors as grid functions (N, k) with zero ends, by LAPACK
+    on the symmetrised tridiagonal (as bo.top_eigenpair); any N, even lengths included"""
+    from scipy.linalg import eigh_tridiagonal
+    from oracle import ballooning_oracle as bo
+    d, e, fd = bo.assemble(theta, g, c, f)[:3]
+    n = len(d)
+    w, v = eigh_tridiagonal(d / fd, e[1:n] / np.sqrt(fd[:-1] * fd[1:]), select="i", select_range=(n - k, n - 1))
+    V = np.zeros((n + 2, k))
+    V[1:-1] = v / np.sqrt(fd)[:, None]
+    return w, V

@@ -1,0 +1,149 @@
+"""CPU: the inputs of tests/test_gpu_edge_lengths.py pinned with the oracle alone (tests/edge_cases.py), so that a GPU failure there
+cannot be blamed on the systems: the moving well keeps its gap and puts the mode on the chosen grid point at every edge length, the
+second mode of two_wells sits on the shallow well, the geometry mapping reproduces the rows, the length lists cover the lane / chunk /
+path edges they claim, and the two CPU oracles (LAPACK on the symmetrised pencil; division-form bisection + twisted factorisation in
+C) agree on this family far inside every tolerance the GPU tests apply."""
+import numpy as np
+import pytest
+
+from oracle import ballooning_oracle as bo
+from tests import edge_cases as ec
+
+ALL_N = ec.EDGE_N_SHORT + ec.EDGE_N_LONG + ec.EDGE_N_COUNT
+
+
+@pytest.mark.parametrize("N", ALL_N)
+def test_moving_well_keeps_its_gap_and_peaks_on_the_target(N):
+    th = ec.theta_grid(N)
+    h = th[1] - th[0]
+    for j in ec.twist_targets(N):
+        g, c, f = ec.well_rows(th, j)
+        w, V = ec.top_pairs(th, g, c, f)
+        nA = ec.norm_a(h, g, c, f)[0]
+        assert 13.3 < nA < 13.6 and 0.1 < w[1] < 0.74, (N, j, nA, w)
+        assert w[1] - w[0] >= 0.02 * nA, (N, j, (w[1] - w[0]) / nA)
+        k = int(np.argmax(np.abs(V[:, 1])))
+        if ec.is_end_target(N, j):
+            assert min(k, N - 1 - k) <= 6 and (k < N // 2) == (j < N // 2), (N, j, k)
+        else:
+            assert k == j, (N, j, k)
+
+
+def shallow_partner(N, j_shallow):
+    """a deep-well position at least 40 rows from the shallow one and 8 points inside the grid"""
+    d = 40 if N < 200 else 60
+    return j_shallow + d if j_shallow + d < N - 8 else j_shallow - d
+
+
+@pytest.mark.parametrize("N", [67, 131, 2049] + ec.EDGE_N_LONG)
+def test_two_wells_second_mode_sits_on_the_shallow_well(N):
+    th = ec.theta_grid(N)
+    h = th[1] - th[0]
+    for js in ec.twist_targets(N):
+        jd = shallow_partner(N, js)
+        g, c, f = ec.two_wells(th, jd, js)
+        w, V = ec.top_pairs(th, g, c, f, 3)
+        nA = ec.norm_a(h, g, c, f)[0]
+        assert min(w[2] - w[1], w[1] - w[0]) >= 0.003 * nA, (N, js, w)
+        k1, k0 = int(np.argmax(np.abs(V[:, 1]))), int(np.argmax(np.abs(V[:, 2])))
+        assert k0 == jd, (N, js, jd, k0)
+        if ec.is_end_target(N, js):
+            assert min(k1, N - 1 - k1) <= 6 and (k1 < N // 2) == (js < N // 2), (N, js, k1)
+        else:
+            assert k1 == js, (N, js, k1)
+            assert w[0] < 0.28 and w[1] > 0.6, (N, js, w)
+
+
+@pytest.mark.parametrize("N", [67, 643, 2307])
+def test_geometry_mapping_reproduces_the_rows(N):
+    th = ec.theta_grid(N)
+    for j in ec.twist_targets(N)[:4]:
+        for rows in (ec.well_rows(th, j), ec.two_wells(th, shallow_partner(N, j), j)):
+            bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22 = ec.to_geometry(*rows)
+            for a, b in zip(bo.gcf(-1.0, bmag, gradpar, cvdrift, gds2), rows):
+                assert np.abs(a - b).max() <= 1e-14 * np.abs(b).max()
+            cv, gd = bo.fold_theta0(0.7, cvdrift, cvdrift0, gds2, gds21, gds22)       # (no theta0 dependence)
+            assert np.array_equal(cv, cvdrift) and np.array_equal(gd, gds2)
+            gam_geo = bo.gamma_ball_full(-1.0, th, bmag, gradpar, cvdrift, gds2)[0]
+            assert abs(gam_geo - bo.solve_gcf(th, *rows)[0]) < 1e-14
+
+
+def test_length_lists_cover_the_edges_they_claim():
+    S, L, Cn = ec.EDGE_N_SHORT, ec.EDGE_N_LONG, ec.EDGE_N_COUNT
+    assert all(N % 2 == 1 and 67 <= N <= 2049 for N in S) and all(N % 2 == 1 and 2050 < N <= 65537 for N in L)
+    assert all(N % 2 == 0 and 66 <= N for N in Cn) and len(set(S + L + Cn)) == len(S + L + Cn)
+    # every rows-per-lane instantiation of the geometry-fed register kernels
+    assert {ec.rows_per_lane(N) for N in S} == set(range(2, 33))
+    assert ec.rows_per_lane(129) == 2 and ec.rows_per_lane(131) == 3 and {ec.rows_per_lane(N) for N in (66, 130, 2050)} == {1, 2, 32}
+    assert all((N - 2) % 64 == 0 for N in (66, 130, 2050))
+    # the sub-wave forms on both sides of their limits
+    assert ec.lanes_allowed(97) == [16] and ec.lanes_allowed(99) == [32, 16]
+    assert ec.lanes_allowed(257) == [32, 16] and ec.lanes_allowed(259) == [32]
+    assert ec.lanes_allowed(641) == [32] and ec.lanes_allowed(643) == []
+    # last chunk of the long path: one row, one row short, exactly full; tails of the unroll by 8 other than 7
+    m768 = {N: (N - 2) % ec.LONG_CHUNK for N in L + Cn if N > 2050}
+    m384 = {N: (N - 2) % ec.VEC_CHUNK for N in L + Cn if N > 2050}
+    assert m768[2307] == 1 and m384[2307] == 1 and m768[3075] == 1 and m384[3075] == 1
+    assert m768[2305] == 767 and m384[3073] == 383 and m384[2305] == 383
+    assert m768[2306] == 0 and m768[3074] == 0 and m384[2306] == 0
+    assert {1, 767, 0} <= set(m768.values()) and {1, 383, 0} <= set(m384.values())
+    assert {m % 8 for m in m768.values()} >= {0, 1, 7} and {m % 8 for m in m384.values()} >= {0, 1, 7}
+    # both branches of the two-grid start
+    on = {N for N in L if (N - 1) % 16 == 0}
+    assert on == {2305, 3073} and {(N - 1) % 16 for N in (2313, 2889)} == {8}
+    assert 2313 == 8 * 17 * 17 + 1 and 2889 == 8 * 19 * 19 + 1
+    # twist targets: both ends, and the points about every multiple of 384 taken
+    for N in [67, 131, 1985, 2049] + L:
+        t = ec.twist_targets(N)
+        assert t[:2] == [1, N - 2] and len(t) <= 24 and len(set(t)) == len(t) and all(1 <= j <= N - 2 for j in t)
+        ms = sorted({j for j in t if j % ec.VEC_CHUNK == 0})
+        assert ms == [m for m in range(ec.VEC_CHUNK, N - 8, ec.VEC_CHUNK)] or (len(t) > 20 and ms[0] == ec.VEC_CHUNK and ms[-1] == (N - 9) // ec.VEC_CHUNK * ec.VEC_CHUNK)
+        for m in ms:
+            assert {m - 1, m, m + 1, m + 2} <= set(t)
+    assert len(ec.twist_targets(67)) == 2 and len(ec.twist_targets(2049)) == 22 and len(ec.twist_targets(65535)) == 22
+
+
+@pytest.mark.parametrize("N", [67, 2307, 65535])
+def test_the_two_oracles_agree_on_the_moving_well(N):
+    """two independent references: their agreement is what licenses the fast one on the GPU side.  lam to 4 N eps ||A||, gam to
+    1e-10; and X, dX, the count at lam +- 4 N eps ||A|| far inside the GPU tests' tolerances (a tenth of each)"""
+    from oracle import c_oracle as co
+    th = ec.theta_grid(N)
+    h = float(th[1] - th[0])
+    targets = ec.twist_targets(N)[:10]
+    rows = [ec.well_rows(th, j) for j in targets] + [ec.two_wells(th, shallow_partner(N, targets[-1]), targets[-1])]
+    g, c, f = (np.stack([r[i] for r in rows]) for i in range(3))
+    nA = ec.norm_a(h, g, c, f)
+    gam_b, lam_b, _ = co.solve_gcf_batch(h, g, c, f)
+    tol = 4 * N * ec.EPS * nA
+    assert (co.count_above_batch(h, g, c, f, np.zeros(len(rows))) >= 1).all()
+    for k in range(len(rows)):
+        gam, lam, X, dX = bo.solve_gcf(th, g[k], c[k], f[k])
+        gc, lc, Xc, dXc = co.solve_gcf(h, g[k], c[k], f[k])
+        assert abs(lam - lc) <= tol[k] and abs(lam - lam_b[k]) <= tol[k], (N, k, abs(lam - lc) / tol[k])
+        assert abs(gam - gc) < 1e-10 and abs(gam - gam_b[k]) < 1e-10, (N, k, gam - gc)
+        short = N <= 2050
+        assert np.abs(X - Xc).max() < 0.1 * (1e-7 if short else 1e-6)
+        assert np.abs(dX - dXc).max() < 0.1 * ((1e-7 * np.abs(dX).max() + 1e-7) if short else 1e-5 * max(1.0, np.abs(dX).max()))
+    lam = np.array([bo.solve_gcf(th, g[k], c[k], f[k])[1] for k in range(len(rows))])
+    assert np.array_equal(co.count_above_batch(h, g, c, f, lam + tol), np.zeros(len(rows), dtype=np.int32))
+    assert np.array_equal(co.count_above_batch(h, g, c, f, lam - tol), np.ones(len(rows), dtype=np.int32))
+
+
+@pytest.mark.parametrize("N", [131, 2307])
+def test_window_reference_of_the_nearest_eigenpair_equals_the_dense_one(N):
+    """tests/nearest_oracle.py: window_nearest (the eigenvalues above sigma - radius alone; used at 65,535 points, where the full
+    spectrum takes minutes per system) returns what dense_nearest returns"""
+    from tests.nearest_oracle import dense_nearest, window_nearest
+    th = ec.theta_grid(N)
+    g1, c1 = bo.salpha_gc(th, 1.0, 0.8, 0.0)
+    cases = [((g1, 4.0 * c1, g1.copy()), 0.42)]
+    for js in ec.twist_targets(N)[:3]:
+        rows = ec.two_wells(th, shallow_partner(N, js), js)
+        w = ec.top_pairs(th, *rows)[0]
+        cases.append((rows, w[0] + (w[1] - w[0]) / 3.0))
+    for rows, sigma in cases:
+        a, b = dense_nearest(th, *rows, sigma), window_nearest(th, *rows, sigma, radius=0.25)
+        assert a["idx"] == b["idx"] >= 1 and a["tie"] == b["tie"] and a["nA"] == b["nA"]
+        assert abs(a["lam"] - b["lam"]) <= 4 * N * ec.EPS * a["nA"] and abs(a["lam_max"] - b["lam_max"]) <= 4 * N * ec.EPS * a["nA"]
+        assert abs(a["gam"] - b["gam"]) < 1e-12 and np.abs(a["X"] - b["X"]).max() < 1e-10
