@@ -1109,6 +1109,37 @@ int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double 
   return staged(ctx, mem, decl, [&] { return points_nearest_device(ctx, a, false); });
 }
 
+// ---- geometry-fed points with the exact gradient of gam (ibs_exact_grad.hip): utils.py:1632-1728 with the derivative of the gam
+// returned in place of the Hellmann-Feynman formulas, one wave per point on the persistent grid of long_waves()
+// the per-wave workspace (ibs::exact_points_ws) in ctx->long_ws
+static int points_exact_device(ibs_ctx* ctx, ibs::ExactPointsArgs a) {
+  const int nw = long_waves(ctx, a.n_pts);
+  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::exact_points_ws(a.N).total * sizeof(double))) return r;
+  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+  HIPCHK(ibs::launch_obj_w_grad_exact(a, ctx->stream));
+  return 0;
+}
+
+int ibs_obj_w_grad_exact_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
+                             const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
+                             double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_pts < 0 || !geo || !theta0 || !val || !jac || ld < N || !(del_alpha > 0))
+    return fail(IBS_ERR_ARG, "bad arguments (n_pts=%d ld=%lld N=%d del_alpha=%g)", n_pts, (long long)ld, N, del_alpha);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_pts == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n = (size_t)n_pts, geo_elems = n * 3 * 8 * (size_t)ld;
+  ibs::ExactPointsArgs a{};
+  a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld; a.del_alpha = del_alpha;
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, geo_elems); a.theta0 = s.in(theta0, n); a.sigma = s.in(sigma, n);
+    a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.gam = s.out(gam, n); a.lam = s.out(lam, n); a.idx = s.out(idx, n);
+    a.info = s.status(info, n);
+  };
+  return staged(ctx, mem, decl, [&] { return points_exact_device(ctx, a); });
+}
+
 // Geometry-fed scan on a grid beyond 2050 points: the (g, c, f) rows of every (line, theta0) system -- and their theta0 tangents when
 // dgam/dtheta0 is wanted -- are written out (k_assemble_gcf_long: the arithmetic the scan kernels do while staging), solved by the
 // generic long-grid kernel, and the Hellmann-Feynman sums (utils.py:1676-1680) taken by k_hf_grad.  Warm-start guesses are not

@@ -100,6 +100,27 @@ struct NearestPointsArgs {
 };
 hipError_t launch_obj_w_grad_nearest(const NearestPointsArgs& a, hipStream_t st);
 hipError_t launch_points_nearest(const NearestPointsArgs& a, hipStream_t st);
+// geometry-fed points with the EXACT gradient of gam (ibs_exact_grad.hip): one wave per point on the persistent grid of
+// min(n_pts, n_waves) waves.  Per-wave workspace, in this order (ExactPointsWs: the kernel carves it, the host sizes it): three work
+// rows -- the solver's (D+, D-, z: nearest_ws_doubles(N)) until X is out, then the adjoint's (V, B, Y: vjp_ws_doubles(N)), the first two
+// of which receive g_bar and c_bar once V and B are dead (stage C of vjp_one reads Y alone) --, the centre line's g, c, f rows, the
+// eigenfunction X, f_bar, and eight doubles of scalars (lam; the status words of the solve and of the adjoint).
+struct ExactPointsWs {
+  size_t work, gb, cb, g, c, f, X, fb, scal, total;
+};
+constexpr ExactPointsWs exact_points_ws(int N) {
+  const size_t n = (size_t)N, w = nearest_ws_doubles(N) > vjp_ws_doubles(N) ? nearest_ws_doubles(N) : vjp_ws_doubles(N);
+  return ExactPointsWs{0, 0, n, w, w + n, w + 2 * n, w + 3 * n, w + 4 * n, w + 5 * n, w + 5 * n + 8};
+}
+struct ExactPointsArgs {
+  int n_pts, N; double h; long ld;
+  const double* geo;                                                  // [n_pts][3][8][ld], as NearestPointsArgs::geo
+  const double* theta0; const double* sigma; double del_alpha;        // theta0 [n_pts]; sigma [n_pts] or null = lam_max's eigenpair
+  double *val, *jac;                                                  // [n_pts], [n_pts][2] (required)
+  double* gam; double* lam; int* idx; int* info;                      // optional
+  double* work; size_t work_doubles; long n_waves;                    // the launch refuses less than min(n_pts, n_waves) waves' worth
+};
+hipError_t launch_obj_w_grad_exact(const ExactPointsArgs& a, hipStream_t st);
 hipError_t launch_sturm_long(const SturmArgs<double>& a, hipStream_t st);
 hipError_t launch_sturm_div(const SturmArgs<double>& a, hipStream_t st);     // lanes as systems, division form, any N
 template <typename T> struct ScanArgs;

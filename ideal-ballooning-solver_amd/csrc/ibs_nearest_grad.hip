@@ -14,24 +14,10 @@
 //   5. outputs     GRAD: val = -gam, jac = (-dgam/dalpha, -dgam/dtheta0) (utils.py:1728); else gam (and X, dX) as the solve gives them
 // Per-wave workspace: nearest_points_ws(N, GRAD) (ibs_launch.hpp), in global memory.
 #include "ibs_nearest.hpp"
+#include "ibs_geo_line.hpp"
 #include "ibs_launch.hpp"
 
 namespace ibs {
-
-// one field line: array k (bmag gradpar cvdrift cvdrift0 gds2 gds21 gds22 gbdrift) at p + k * ld
-struct GeoLine {
-  const double* p; long ld;
-  __device__ __forceinline__ double at(int k, int j) const { return p[(long)k * ld + j]; }
-};
-// (g, c, f) of a line at theta0 (the arithmetic of k_assemble_gcf_long: ball_scan.py:267-268, utils.py:1560-1562)
-__device__ __forceinline__ void line_gcf(const GeoLine& L, int j, double mdP, double th0, double& g, double& c, double& f) {
-  const double B = L.at(0, j), gp = xabs(L.at(1, j));
-  const double inv = 1.0 / (gp * B);
-  const double A1 = gp / B, A3 = inv / (B * B);
-  const double C0 = mdP * L.at(2, j) * inv, C1 = mdP * L.at(3, j) * inv;
-  const double d = L.at(4, j) + (2.0 * th0) * L.at(5, j) + (th0 * th0) * L.at(6, j);
-  g = A1 * d; c = C0 + th0 * C1; f = A3 * d;
-}
 
 template <bool GRAD>
 __global__ void __launch_bounds__(64) k_nearest_points(const NearestPointsArgs a) {

@@ -67,6 +67,7 @@ class AdjointStep:
     per boundary DOF (BASELINE configs[3]: 73 x 5 surfaces x 24 alpha x 15 theta0, N = 969).  Like the scan driver it works on
     lam_max's eigenpair by default; eigenpair="nearest" runs every equilibrium's scan in upstream's mode (the eigenpair nearest
     sigma = 1.0 / 1.3 |gam| + 0.05 / 0.42: BallooningScan's eigenpair="nearest"), with the same chunking, gather and objective.
+    jac="exact" refines every surface on the exact gradient of gam (BallooningScan's jac="exact"); "reference" is the default.
 
     Upstream this is ball_submit.py:64-95 (one `srun ball_scan.py iter dof ngroups` per DOF-perturbed equilibrium, each
     running vmec_splines -> coarse scan -> argmax -> L-BFGS-B -> final solve, ball_scan.py:190-347) followed by
@@ -81,9 +82,11 @@ class AdjointStep:
     (dof_steps / ScanConfig.dof_step)."""
 
     def __init__(self, ctx, theta, svals, device, nalpha=24, ntheta0=15, del_alpha=0.004, gamma_thresh=-2.0e-4, prefac=50.0,
-                 rank=0, world=1, dist=None, n_threads=0, n_chunks=4, gather_device=None, chunk_growth=1.0, eigenpair="max"):
-        from .scan import check_eigenpair
+                 rank=0, world=1, dist=None, n_threads=0, n_chunks=4, gather_device=None, chunk_growth=1.0, eigenpair="max",
+                 jac="reference"):
+        from .scan import check_eigenpair, check_jac
         self.eigenpair = check_eigenpair(eigenpair)
+        self.jac = check_jac(jac)
         self.ctx, self.device = ctx, device
         self.theta = np.asarray(theta, dtype=np.float64)
         self.svals = np.atleast_1d(np.asarray(svals, dtype=np.float64))       # ball_scan.py:197
@@ -107,7 +110,7 @@ class AdjointStep:
         if self._scan is None or len(self._scan.rho_arr) != n:
             self._scan = BallooningScan(self.ctx, None, self.theta, np.tile(self.svals, n_eq_local), nalpha=self.nalpha,
                                         ntheta0=self.ntheta0, del_alpha=self.del_alpha, tables=tables, device=self.device,
-                                        surf_index=np.arange(n), eigenpair=self.eigenpair)
+                                        surf_index=np.arange(n), eigenpair=self.eigenpair, jac=self.jac)
         self._scan.tables = tables
         return self._scan
 

@@ -86,24 +86,39 @@ def check_eigenpair(eigenpair):
     return eigenpair
 
 
+JACS = ("reference", "exact")
+
+
+def check_jac(jac):
+    if jac not in JACS:
+        raise ValueError("jac must be 'reference' or 'exact', not %r" % (jac,))
+    return jac
+
+
 class BallooningScan:
     """Coarse (alpha, theta0) scan -> argmax -> L-BFGS-B refinement -> final solve, per surface.
     eigenpair="max" (the default): every stage returns lam_max's eigenpair (the physical growth rate).  eigenpair="nearest":
     every stage returns the eigenpair nearest upstream's shift, as ball_scan.py's eigs(A, 1, sigma=sigma0) does (utils.py:1597):
     sigma = 1.0 in the coarse scan, 1.3 |gam| + 0.05 of the surface's coarse maximum in the refinement, 0.42 in the final solve.
-    The two agree wherever lam_max lies below the shifts; on strongly driven surfaces they differ."""
+    The two agree wherever lam_max lies below the shifts; on strongly driven surfaces they differ.
+    jac="reference" (the default): the refinement runs on upstream's Hellmann-Feynman gradient (utils.py:1676-1680, 1721-1725), which
+    puts gam in place of lam and is 0.1-5 % off the gam it comes with.  jac="exact": it runs on the exact derivative of that gam,
+    batched on the device (ibs_obj_w_grad_exact_f64), for either eigenpair; the coarse scan and the final solve are the same."""
 
     def __init__(self, ctx, fieldlines, theta, rho_arr, nalpha=24, ntheta0=15, del_alpha=0.004,
-                 rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None, eigenpair="max"):
+                 rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None, eigenpair="max",
+                 jac="reference"):
         """fieldlines: host geometry callable (see module docstring), or None together with
         tables=SurfaceTables (row F1): then the geometry is produced on `device` by the HIP geometry kernel and consumed
         there -- coarse scan, per-surface maximum, start points, refinement and final solve all stay in HBM and ONE small
         copy returns the rows.  surf_index[k] = index of surface k (of rho_arr) in `tables`; default: the surface of
         tables.s nearest to rho_arr[k].  Table sets that hold several equilibria (SurfaceTables.from_wouts: s repeats
         per equilibrium) need the explicit index.
-        eigenpair: "max" or "nearest" (see the class docstring); anything else raises ValueError."""
+        eigenpair: "max" or "nearest"; jac: "reference" or "exact" (see the class docstring); anything else raises ValueError."""
         self.eigenpair = check_eigenpair(eigenpair)
         self.nearest = eigenpair == "nearest"
+        self.jac = check_jac(jac)
+        self.exact = jac == "exact"
         self.ctx = ctx
         self.tables = tables
         self.device = device
@@ -174,12 +189,28 @@ class BallooningScan:
             raise IbsError("%d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)" % r["nbad"])
         return np.asarray(r["gam"]).reshape(len(self.own), len(self.alpha_scan), len(self.theta0_scan))
 
+    # -- jac="exact": val and the exact gradient at a batch of points (numpy or device tensors in, numpy out); sigma None = lam_max's pair
+    def _obj_exact(self, geo, t0, sigma):
+        from .solver import EXACT_VJP_SHIFT, vjp_status_message
+        val, jac, r = self.ctx.obj_w_grad_exact(self.h, geo, t0, self.del_alpha, sigma=sigma, want_info=True)
+        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        val, jac = host(val), host(jac)
+        vst = (host(r["info"]) >> EXACT_VJP_SHIFT) & 3
+        if np.any(vst):
+            raise IbsError(vjp_status_message(int(np.sum(vst & 1)), int(np.sum(vst >> 1))))
+        bad = ~(np.isfinite(val) & np.isfinite(jac).all(axis=1))
+        if bad.any():
+            raise IbsError("%d objective solves of the refinement were flagged (invalid data or iteration cap)" % int(bad.sum()))
+        return val, jac
+
     # -- A6: objective with gradient at one point of one surface (utils.py:1632-1728); sigma0: the shift of eigenpair="nearest"
     def obj_w_grad(self, x, s, sigma0=None):
         a, t0 = float(x[0]), float(x[1])
         d = self.del_alpha
         geo = np.asarray(self.fieldlines(s, np.array([a - 0.5 * d, a, a + 0.5 * d])))
-        if self.nearest:
+        if self.exact:
+            val, jac = self._obj_exact(geo[None], np.array([t0]), float(sigma0) if self.nearest else None)
+        elif self.nearest:
             val, jac = self.ctx.obj_w_grad_nearest(self.h, geo[None], np.array([t0]), float(sigma0), d)
             if not (np.isfinite(val[0]) and np.all(np.isfinite(jac[0]))):
                 raise IbsError("the objective's solve at (alpha, theta0) = (%g, %g) was flagged (invalid data or iteration cap)" % (a, t0))
@@ -208,7 +239,8 @@ class BallooningScan:
     def batched_obj_w_grad(self, surf_idx, X, sigma=None):
         """objective and gradient at X[k] = (alpha, theta0) of surface surf_idx[k] for all k at once
         (device geometry for the 3 n lines, then the fused obj_w_grad kernel; eigenpair="nearest": the eigenpair nearest
-        sigma[k], ibs_obj_w_grad_nearest_f64).  Returns (val (n,), jac (n, 2))."""
+        sigma[k], ibs_obj_w_grad_nearest_f64; jac="exact": ibs_obj_w_grad_exact_f64, for either eigenpair).
+        Returns (val (n,), jac (n, 2))."""
         n = len(surf_idx)
         d = self.del_alpha
         al = np.stack([X[:, 0] - 0.5 * d, X[:, 0], X[:, 0] + 0.5 * d], axis=1).reshape(-1)
@@ -217,6 +249,9 @@ class BallooningScan:
         geo = r["geo"].view(8, n, 3, N).permute(1, 2, 0, 3).contiguous()
         import torch
         t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
+        if self.exact:
+            sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device) if self.nearest else None
+            return self._obj_exact(geo, t0, sg)
         if self.nearest:
             sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device)
             val, jac = self.ctx.obj_w_grad_nearest(self.h, geo, t0, sg, d)
@@ -243,6 +278,8 @@ class BallooningScan:
             lib.ibs_lbfgsb2_init(states[k], p(x[k]), p(lo), p(hi), float(ftol), float(gtol), int(maxiter), 20)
         active = np.ones(n, dtype=bool)
         rounds = 0
+        if self.exact:
+            self._batched_evals = np.zeros(n, dtype=np.int32)   # evaluations per surface of this call (diagnostic)
         while active.any():
             idx = np.nonzero(active)[0]
             if not self.nearest:
@@ -253,6 +290,8 @@ class BallooningScan:
                     raise IbsError("%d objective solves of the refinement were flagged (invalid data or iteration cap)"
                                    % int(np.sum(~(np.isfinite(f) & np.isfinite(g).all(axis=1)))))
             rounds += 1
+            if self.exact:
+                self._batched_evals[idx] += 1
             for q, k in enumerate(idx):
                 gk = np.ascontiguousarray(g[q], dtype=np.float64)
                 if not lib.ibs_lbfgsb2_step(states[k], float(f[q]), p(gk), p(x[k])):
@@ -314,6 +353,8 @@ class BallooningScan:
         maximum (ibs_surface_argmax_pack_f64) -> start points and each surface's shift 1.3 |max| + 0.05 (ibs_scan_starts_f64) ->
         the host-driven L-BFGS-B (refine_batched: one geometry + ibs_obj_w_grad_nearest_f64 launch per round) -> final geometry +
         ibs_gamma_points_nearest_f64 at 0.42.  A solve counts as failed on status bits 0-1 only (bit 5, a tie, is informational).
+        jac="exact": the refinement is the host-driven one as well, for either eigenpair (ibs_refine_f64 has no exact form): one
+        geometry + ibs_obj_w_grad_exact_f64 launch per round; everything else as above.
         chunks: optional list of (c0, c1) ranges of owned surfaces: the coarse part (geometry, scan, starts) runs chunk by chunk,
         and fill(c0, c1) -- if given -- is called on the host before a chunk's launches (AdjointStep: the tables of the next
         equilibria are computed and uploaded while the GPU works on the previous ones).
@@ -373,14 +414,15 @@ class BallooningScan:
             fin = ctx.gamma_points_nearest(self.h, *[gf["geo"][k] for k in range(7)], gf["dPdrho"], xt, SIGMA_FINAL, want_info=True)
             rows = torch.stack([xt, xa, fin["gam"]], dim=1)
             bad = bad + (((fin["info"] >> 16) & 3) != 0).sum()
-            self.last_refine = dict(n_evals=None, rounds=rounds)
+            self.last_refine = dict(n_evals=self._batched_evals if self.exact else None, rounds=rounds)
         elif refine:
-            if len(self.theta) > 2050:
+            if len(self.theta) > 2050 or self.exact:
+                # (jac="exact": ibs_refine_f64 has no exact form -- refine_batched with one ibs_obj_w_grad_exact_f64 launch per round)
                 # ibs_refine_f64 holds the register-resident evaluation kernel (N <= 2050): beyond, the same L-BFGS-B state machines
                 # run on the host (ibs_lbfgsb2_*) and every round is ONE batched geometry + ibs_obj_w_grad_f64 launch for the
                 # surfaces still running (refine_batched: the form refine_device is tested against)
                 xh, fh, rounds = self.refine_batched(start.cpu().numpy())
-                xo = torch.from_numpy(xh).to(dev); ne = None
+                xo = torch.from_numpy(xh).to(dev); ne = self._batched_evals if self.exact else None
             else:
                 xo, fo, ne, rounds = ctx.refine_device(self.tables, res["pt_surf"], start, res["th"], self.del_alpha)
             mark("r1")

@@ -23,6 +23,11 @@ def vjp_status_message(n_pivot, n_bad):
             "eigenpair of their rows or with invalid data (status bit 1: NaN rows)" % (n_pivot, n_bad))
 
 
+# ibs_obj_w_grad_exact_f64: (info >> EXACT_VJP_SHIFT) & 3 = the status of its adjoint solve in solve_gcf_vjp's convention (bit 0 a replaced
+# pivot, bit 1 refused), i.e. status bits 6 and 7 of the info word
+EXACT_VJP_SHIFT = 16 + 6
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -442,6 +447,32 @@ class Context:
         check(self._lib.ibs_obj_w_grad_nearest_f64(self._h, n_pts, N, float(h), pg, N, pt, psig, float(del_alpha), pval, pjac,
                                                    plam, pidx, pinfo, ar.mem), "ibs_obj_w_grad_nearest_f64")
         return (val, jac, dict(lam=lam, idx=idx, info=info)) if want_info else (val, jac)
+
+    def obj_w_grad_exact(self, h, geo, theta0, del_alpha=0.004, sigma=None, want_info=False):
+        """obj_w_grad with the EXACT gradient of the gam it returns (ibs_obj_w_grad_exact_f64: utils.py:1632-1728 with the exact
+        derivative in place of the Hellmann-Feynman formulas of utils.py:1676-1680 / 1721-1725), batched on the device.
+        geo (n_pts, 3, 8, N), theta0 (n_pts,); sigma None: lam_max's eigenpair, else a scalar or (n_pts,): the eigenpair nearest it.
+        Returns (val, jac) or, with want_info, (val, jac, dict(gam, lam, idx, info)).  A failed solve (status bits 0-1) gives NaN
+        val and jac; an adjoint that refuses the pair (status bit 7) NaN jac alone; bit 6 (a replaced pivot of the adjoint solve) is
+        informational.  EXACT_VJP_SHIFT moves info's status to solve_gcf_vjp's two bits."""
+        ar = _Args()
+        n_pts, three, eight, N = geo.shape
+        if three != 3 or eight != 8:
+            raise IbsError("geo must be (n_pts, 3, 8, N)")
+        pg, pt = ar.inp(geo), ar.inp(theta0)
+        ref = geo if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        psig = self._sigma_rows(ar, sigma, (n_pts,), ref) if sigma is not None else C.c_void_p(None)
+        val, pval = ar.out((n_pts,), ref)
+        jac, pjac = ar.out((n_pts, 2), ref)
+        gam, pgam = ar.out((n_pts,), ref, want=want_info)
+        lam, plam = ar.out((n_pts,), ref, want=want_info)
+        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        check(self._lib.ibs_obj_w_grad_exact_f64(self._h, n_pts, N, float(h), pg, N, pt, psig, float(del_alpha), pval, pjac, pgam,
+                                                 plam, pidx, pinfo, ar.mem), "ibs_obj_w_grad_exact_f64")
+        return (val, jac, dict(gam=gam, lam=lam, idx=idx, info=info)) if want_info else (val, jac)
 
     def gamma_points_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma,
                              want_X=False, want_info=False):

@@ -37,6 +37,9 @@
  *     bit 5, nearest-sigma entry points (ibs_*_nearest_f64): "nearest not determined" -- the eigenvalues on either side of
  *            sigma lie at distances that differ by less than 4 N eps ||A||; the larger one is returned
  *            (these entry points never set bit 3, whose re-close diagnostic occupies bits 5 and up on the lam_max entry points).
+ *     bits 6-7, ibs_obj_w_grad_exact_f64 only: the two status bits of its adjoint solve (ibs_solve_gcf_vjp_f64's bits 0 and 1), moved
+ *            clear of bits 0-5 -- bit 6: a pivot of the adjoint solve fell below pivmin and was replaced (informational: jac may be
+ *            inaccurate); bit 7: the adjoint refused the pair (jac = NaN, val is good).  Neither is counted by return values > 0.
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
  *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
  *     for every sigma, lam_max's among them; they never set bit 4.
@@ -216,6 +219,23 @@ int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double 
                                  const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
                                  const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, const double* sigma,
                                  double* gam, double* lam, int32_t* idx, double* X, double* dX, int32_t* info, int32_t mem);
+
+/* The objective of the refinement with the EXACT gradient of the gam it returns: utils.py:1632-1728 with the exact derivative in place
+ * of the Hellmann-Feynman formulas of utils.py:1676-1680 / 1721-1725 (which put gam in place of lam and are 0.1-5 % off the gam they
+ * come with).  geo [n_pts][3][8][ld], theta0 [n_pts], del_alpha, val [n_pts] and jac [n_pts][2] as in ibs_obj_w_grad_f64: val = -gam,
+ * jac = (-dgam/dalpha, -dgam/dtheta0) (utils.py:1728).  sigma [n_pts]: the eigenpair nearest sigma (as ibs_obj_w_grad_nearest_f64), or
+ * NULL: lam_max's (as ibs_obj_w_grad_f64).  gam, lam, idx (0 with sigma = NULL) and info [n_pts] optional.  FP64, any odd N in
+ * [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED): one wavefront per point forms dPdrho of the three lines, the centre line's
+ * rows, the eigenpair in division form (lam_max: as the long-grid path of ibs_solve_gcf_f64, at every N), d gam / d (g, c, f) (as
+ * ibs_solve_gcf_vjp_f64 with gam_bar = 1) and its contractions with the theta0 tangent (utils.py:1669-1673) and the alpha tangent
+ * (right minus left line, each with its own dPdrho, over del_alpha: utils.py:1683-1718) in one kernel (csrc/ibs_exact_grad.hip); the
+ * derivative in theta0 is exact, in alpha that of the reference's central difference of the rows.  No floating-point atomics: results
+ * are bitwise repeatable and independent of the batch.  Status (conventions above): a point whose solve fails (bits 0-1; also theta0 or
+ * sigma not finite) gets val = jac = NaN; bit 7 (the adjoint refused the pair) gives jac = NaN with val kept; bits 5 and 6 are
+ * informational. */
+int ibs_obj_w_grad_exact_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
+                             const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
+                             double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem);
 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
