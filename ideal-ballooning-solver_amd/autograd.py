@@ -57,6 +57,28 @@ def solve_gcf(h, g, c, f, eigenpair="max", sigma=None, ctx=None):
     return _SolveGcf.apply(float(h), g, c, f, eigenpair, sigma, ctx or default_context(g.device.index or 0))
 
 
+class _MarginalScale(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, h, g, c, ictx):
+        r = ictx.marginal_gcf(h, g, c, want_grad=True)
+        fctx.save_for_backward(r["g_bar"], r["c_bar"])
+        return r["scale"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, s_bar):
+        g_bar, c_bar = fctx.saved_tensors
+        return None, g_bar * s_bar[:, None], c_bar * s_bar[:, None], None
+
+
+def marginal_scale(h, g, c, ctx=None):
+    """s* (n_sys,) of the raw rows g, c (n_sys, N): the critical scale of c at fixed g (Context.marginal_gcf; s* < 1 = unstable
+    now).  Differentiable in g and c: the backward is the cotangent times the derivative rows the forward's kernel returns
+    (Hellmann-Feynman on the discrete pencil, exact for it).  Systems with an infinite margin (no c_j > 0) get zero gradients,
+    flagged ones (invalid data) NaN."""
+    return _MarginalScale.apply(float(h), g, c, ctx or default_context(g.device.index or 0))
+
+
 def growth_rate(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, eigenpair="max", sigma=None, ctx=None):
     """gam (n_lines, n_theta0) of the lines (geometry arrays (n_lines, N), dPdrho (n_lines,)) at theta0 ((n_theta0,), shared by all
     lines as in Context.gamma_scan, or (n_lines, n_theta0)): the theta0 fold of ball_scan.py:267-268 and the coefficients of

@@ -981,6 +981,66 @@ int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, cons
   });
 }
 
+// ---- marginal stability: the critical scale s* of the pressure gradient at fixed rows (ibs_marginal.hip; nothing upstream corresponds:
+// c is linear in dPdrho, utils.py:1560-1562, and the quantity generalises the scan of bishop_ball_s-alpha.py:90-115)
+// the persistent grid of long_waves() with its workspace in ctx->long_ws (ibs::marginal_ws per wave)
+int ibs_marginal_gcf_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c, int64_t ld,
+                         double* scale, double* mu, double* X, double* gam0, double* g_bar, double* c_bar, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!g || !c || !scale) return fail(IBS_ERR_ARG, "null argument (g, c and scale are required)");
+  if (n_sys < 0 || ld < N) return fail(IBS_ERR_ARG, "bad arguments (n_sys=%lld ld=%lld N=%d)", (long long)n_sys, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_sys == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t in_elems = (size_t)n_sys * ld, out_elems = (size_t)n_sys * N;
+  ibs::MarginalArgs a{};
+  a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld;
+  auto decl = [&](Stage& s) {
+    a.g = s.in(g, in_elems); a.c = s.in(c, in_elems);
+    a.scale = s.out(scale, n_sys); a.mu = s.out(mu, n_sys); a.gam0 = s.out(gam0, n_sys);
+    a.X = s.out(X, out_elems); a.g_bar = s.out(g_bar, out_elems); a.c_bar = s.out(c_bar, out_elems);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    const int nw = long_waves(ctx, a.n_sys);
+    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, false).total * sizeof(double))) return r;
+    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    HIPCHK(ibs::launch_marginal_gcf(a, ctx->stream));
+    return 0;
+  });
+}
+
+int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                          const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                          const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                          double* scale, double* mu, double* dscale_dtheta0, double* dscale_ddPdrho, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho || !theta0 || !scale)
+    return fail(IBS_ERR_ARG, "null argument (the geometry arrays, dPdrho, theta0 and scale are required)");
+  if (n_lines < 0 || n_theta0 < 0 || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
+  ibs::MarginalScanArgs a{};
+  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld;
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
+    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_theta0);
+    a.scale = s.out(scale, n_sys); a.mu = s.out(mu, n_sys); a.dth0 = s.out(dscale_dtheta0, n_sys); a.ddP = s.out(dscale_ddPdrho, n_sys);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    const int nw = long_waves(ctx, (long)n_sys);
+    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, true).total * sizeof(double))) return r;
+    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    HIPCHK(ibs::launch_marginal_scan(a, ctx->stream));
+    return 0;
+  });
+}
+
 // Coarse scan with the nearest eigenpair: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
 // arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and solved by k_solve_gcf_nearest; chunks are
 // bounded by kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".

@@ -121,6 +121,33 @@ struct ExactPointsArgs {
   double* work; size_t work_doubles; long n_waves;                    // the launch refuses less than min(n_pts, n_waves) waves' worth
 };
 hipError_t launch_obj_w_grad_exact(const ExactPointsArgs& a, hipStream_t st);
+// marginal stability (ibs_marginal.hip): the critical scale s* of the pressure gradient at fixed rows, FP64, any odd N in
+// [66, kMaxLongN]: one wave per system on the persistent grid of min(n_sys, n_waves) waves.  Per-wave workspace, in this order
+// (MarginalWs: the kernels carve it, the host sizes it): the eigenvector stage's nearest_ws_doubles(N), the marginal mode X, and in
+// the geometry-fed kernel the g and c rows of the wave's (line, theta0).
+struct MarginalWs {
+  size_t work, X, g, c, total;
+};
+constexpr MarginalWs marginal_ws(int N, bool scan) {
+  const size_t n = (size_t)N, w = nearest_ws_doubles(N);
+  return MarginalWs{0, w, scan ? w + n : 0, scan ? w + 2 * n : 0, w + (scan ? 3 : 1) * n};
+}
+struct MarginalArgs {
+  long n_sys; int N; double h;
+  const double *g, *c; long ld;                                     // rows ld apart
+  double *scale, *mu, *gam0; int* info;                             // [n_sys]; scale required
+  double *X, *g_bar, *c_bar;                                        // [n_sys][N], optional
+  double* work; size_t work_doubles; long n_waves;                  // the launch refuses a workspace below min(n_sys, n_waves) waves
+};
+hipError_t launch_marginal_gcf(const MarginalArgs& a, hipStream_t st);
+struct MarginalScanArgs {
+  int n_lines, n_theta0, N; double h;
+  const double* geo7[7]; long ld;                                   // the seven arrays of ibs_gamma_scan_f64, [n_lines][ld]
+  const double *dPdrho, *theta0;                                    // [n_lines], [n_theta0]
+  double *scale, *mu, *dth0, *ddP; int* info;                       // [n_lines][n_theta0]; scale required
+  double* work; size_t work_doubles; long n_waves;
+};
+hipError_t launch_marginal_scan(const MarginalScanArgs& a, hipStream_t st);
 hipError_t launch_sturm_long(const SturmArgs<double>& a, hipStream_t st);
 hipError_t launch_sturm_div(const SturmArgs<double>& a, hipStream_t st);     // lanes as systems, division form, any N
 template <typename T> struct ScanArgs;

@@ -137,6 +137,27 @@ def _gamma_ball_nearest(ctx, dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, sigm
     return float(r["gam"][0]), r["X"][0], r["dX"][0], g, c, f
 
 
+def marginal_dPdrho(dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, ctx=None):
+    """The pressure gradient at which the line of gamma_ball_full's arguments is marginally stable, at FIXED geometry arrays:
+    returns (dPdrho_crit, s*, X) with dPdrho_crit = s* dPdrho, s* the critical scale of Context.marginal_gcf (s* < 1: the line is
+    unstable at dPdrho; s* = inf: no scale makes it unstable) and X the marginal mode.  Nothing upstream corresponds: c is linear in
+    dPdrho (utils.py:1561) and the quantity generalises the scan of bishop_ball_s-alpha.py:90-115.  A real equilibrium's geometry
+    moves with its pressure, so s* = 1 marks the true boundary and s* != 1 is a local, frozen-geometry margin.  Uniform grids only
+    (the half-grid g is the mean of neighbours): a non-uniform theta_PEST raises ValueError."""
+    theta = np.asarray(theta_PEST, dtype=np.float64)
+    if not is_uniform(theta):
+        raise ValueError("marginal_dPdrho needs a uniform theta_PEST grid")
+    B = np.asarray(B, dtype=np.float64)
+    gp = np.abs(np.asarray(gradpar, dtype=np.float64))
+    g = gp * np.asarray(gds2, dtype=np.float64) / B                                   # utils.py:1560
+    c = -1 * dPdrho * np.asarray(cvdrift, dtype=np.float64) * 1 / (gp * B)            # utils.py:1561
+    r = (ctx or default_context()).marginal_gcf(uniform_spacing(theta), g[None], c[None], want_X=True)
+    if r["nbad"]:
+        raise IbsError("marginal_dPdrho: the solve was flagged (invalid data or the multisection did not close)")
+    s = float(r["scale"][0])
+    return s * float(dPdrho), s, r["X"][0]
+
+
 def dPdrho_of(cvdrift, gbdrift, bmag):
     """ball_scan.py:262 / utils.py:1657"""
     return -1.0 * 0.5 * np.mean((cvdrift - gbdrift) * bmag ** 2)

@@ -189,6 +189,40 @@ class BallooningScan:
             raise IbsError("%d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)" % r["nbad"])
         return np.asarray(r["gam"]).reshape(len(self.own), len(self.alpha_scan), len(self.theta0_scan))
 
+    # -- marginal stability on the coarse grid of the surfaces this rank owns, one launch
+    def marginal(self):
+        """per owned surface, the smallest critical scale s* of dPdrho over the coarse (alpha, theta0) grid and where it sits
+        (Context.marginal_scan): dict(scale (n_own,), alpha, theta0, index (n_own, 2) = (i_alpha, i_theta0) of the first minimum,
+        table (n_own, nalpha, ntheta0)).  s* < 1: some line of the surface is unstable now; s* scales dPdrho at FIXED geometry
+        arrays, so away from 1 it is a local margin.  No refinement in (alpha, theta0).  Raises IbsError on status bits 0-1."""
+        na, nt = len(self.alpha_scan), len(self.theta0_scan)
+        if not self.own:
+            tab = np.zeros((0, na, nt))
+        elif self.tables is not None and self.device is not None:
+            import torch
+            surf = np.repeat(self._own_surf(), na)
+            r = self.ctx.fieldline_geometry(self.tables, surf, np.tile(self.alpha_scan, len(self.own)), self.theta,
+                                            device=self.device)
+            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
+            out = self.ctx.marginal_scan(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, want_info=True)
+            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())          # (bit 8, an infinite margin, is informational)
+            if nbad:
+                raise IbsError("%d of %d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)"
+                               % (nbad, out["info"].numel()))
+            tab = out["scale"].cpu().numpy().reshape(len(self.own), na, nt)
+        else:
+            geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
+            dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
+            out = self.ctx.marginal_scan(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan)
+            if out.get("nbad", 0):
+                raise IbsError("%d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)" % out["nbad"])
+            tab = np.asarray(out["scale"]).reshape(len(self.own), na, nt)
+        flat = tab.reshape(len(tab), -1)
+        k = np.argmin(flat, axis=1) if len(tab) else np.zeros(0, dtype=np.int64)
+        ia, it = k // nt, k % nt
+        return dict(scale=flat[np.arange(len(tab)), k], alpha=self.alpha_scan[ia], theta0=self.theta0_scan[it],
+                    index=np.stack([ia, it], axis=1), table=tab)
+
     # -- jac="exact": val and the exact gradient at a batch of points (numpy or device tensors in, numpy out); sigma None = lam_max's pair
     def _obj_exact(self, geo, t0, sigma):
         from .solver import EXACT_VJP_SHIFT, vjp_status_message

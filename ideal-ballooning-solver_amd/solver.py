@@ -282,6 +282,63 @@ class Context:
             out.update(info=info)
         return out
 
+    # ---- marginal stability -----------------------------------------------------------------
+    def marginal_gcf(self, h, g, c, want_X=False, want_grad=False, want_info=False):
+        """the critical scale s* of c at fixed g (ibs_marginal_gcf_f64): the factor by which the pressure gradient of a line may be
+        scaled, at fixed geometry arrays, before the line goes unstable; s* < 1 = unstable now.  g, c: (n_sys, N).
+        Returns dict(scale, mu = 1 / s*[, X, gam0][, g_bar, c_bar][, info], nbad): X the marginal mode (zero ends, largest entry +1),
+        gam0 its FD4 / Simpson quotient (O(h^2) from 0), g_bar / c_bar = d s* / d g, d s* / d c (n_sys, N).  info status bit 8: no
+        c_j > 0, scale = inf and mu = 0 (not counted in nbad)."""
+        ar = _Args()
+        n_sys, N = g.shape
+        pg, pc = ar.inp(g), ar.inp(c)
+        ref = g if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        scale, pscale = ar.out((n_sys,), ref)
+        mu, pmu = ar.out((n_sys,), ref)
+        X, pX = ar.out((n_sys, N), ref, want=want_X)
+        gam0, pgam0 = ar.out((n_sys,), ref, want=want_X)
+        gb, pgb = ar.out((n_sys, N), ref, want=want_grad)
+        cb, pcb = ar.out((n_sys, N), ref, want=want_grad)
+        info, pinfo = ar.out((n_sys,), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_marginal_gcf_f64(self._h, n_sys, N, float(h), pg, pc, N, pscale, pmu, pX, pgam0, pgb, pcb, pinfo,
+                                                  ar.mem), "ibs_marginal_gcf_f64")
+        out = dict(scale=scale, mu=mu, nbad=rc)
+        if want_X:
+            out.update(X=X, gam0=gam0)
+        if want_grad:
+            out.update(g_bar=gb, c_bar=cb)
+        if want_info:
+            out.update(info=info)
+        return out
+
+    def marginal_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_grad=False, want_info=False):
+        """the critical scale of dPdrho of every (line, theta0), at fixed geometry arrays (ibs_marginal_scan_f64): arrays as in
+        gamma_scan.  Returns dict(scale, mu[, dscale_dtheta0, dscale_ddPdrho][, info], nbad) shaped (n_lines, n_theta0);
+        dPdrho_crit = scale * dPdrho[:, None]."""
+        ar = _Args()
+        n_lines, N = bmag.shape
+        n_t0 = int(theta0.shape[0])
+        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
+        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
+        ref = bmag if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        scale, pscale = ar.out((n_lines, n_t0), ref)
+        mu, pmu = ar.out((n_lines, n_t0), ref)
+        dth, pdth = ar.out((n_lines, n_t0), ref, want=want_grad)
+        ddP, pddP = ar.out((n_lines, n_t0), ref, want=want_grad)
+        info, pinfo = ar.out((n_lines, n_t0), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_marginal_scan_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, pscale, pmu, pdth, pddP,
+                                                   pinfo, ar.mem), "ibs_marginal_scan_f64")
+        out = dict(scale=scale, mu=mu, nbad=rc)
+        if want_grad:
+            out.update(dscale_dtheta0=dth, dscale_ddPdrho=ddP)
+        if want_info:
+            out.update(info=info)
+        return out
+
     def gamma_scan_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma, want_info=False):
         """the coarse scan of ball_scan.py:248-273 with the eigenpair nearest sigma, as upstream (sigma = 1.0 there: ball_scan.py:230);
         ibs_gamma_scan_nearest_f64.  Geometry arrays (n_lines, N); dPdrho (n_lines,); theta0 (n_theta0,); sigma a scalar or

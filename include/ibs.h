@@ -40,6 +40,9 @@
  *     bits 6-7, ibs_obj_w_grad_exact_f64 only: the two status bits of its adjoint solve (ibs_solve_gcf_vjp_f64's bits 0 and 1), moved
  *            clear of bits 0-5 -- bit 6: a pivot of the adjoint solve fell below pivmin and was replaced (informational: jac may be
  *            inaccurate); bit 7: the adjoint refused the pair (jac = NaN, val is good).  Neither is counted by return values > 0.
+ *     bit 8, marginal-stability entry points (ibs_marginal_*_f64) only: no row has c_j > 0, so no scale of the pressure gradient makes
+ *            the line unstable -- scale = +inf, mu = 0, the derivatives are 0 and X, gam0 are NaN (informational: not counted by
+ *            return values > 0).
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
  *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
  *     for every sigma, lam_max's among them; they never set bit 4.
@@ -236,6 +239,32 @@ int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double 
 int ibs_obj_w_grad_exact_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
                              const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
                              double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem);
+
+/* Marginal stability of raw systems: the factor s* by which c (i.e. the pressure gradient: c is linear in dPdrho, utils.py:1560-1562)
+ * may be scaled, at fixed g, before the system goes unstable; s* < 1 = unstable now.  Nothing upstream corresponds: the quantity
+ * generalises the marginal-stability scan of the reference's s-alpha test (bishop_ball_s-alpha.py:90-115), which only reports a
+ * boolean per (shat, alpha).  With D the stiffness matrix of utils.py:1574-1592 on a uniform grid (e_k = (g_k + g_{k+1}) / 2 h^2,
+ * D_jj = e_{j-1} + e_j, D_{j,j+-1} = -e) and C = diag(c_j) on the interior points, s* = inf { s > 0 : lam_max(s C - D) >= 0 } =
+ * 1 / mu_max of C x = mu D x; f plays no part (f > 0 only scales rows).
+ *   g, c [n_sys][ld]; scale [n_sys] (required); mu [n_sys] = 1 / s* (0 with status bit 8); gam0 [n_sys]: the FD4 / Simpson quotient
+ *   of utils.py:1601-1621 of the marginal mode on the rows (g, s* c, 1), O(h^2) from 0 (a diagnostic); X [n_sys][N]: the marginal
+ *   mode, zero ends, largest entry +1; g_bar, c_bar [n_sys][N]: d s* / d g and d s* / d c, exact for the discrete pencil
+ *   (Hellmann-Feynman: no adjoint solve, no floating-point atomics, bitwise repeatable and independent of the batch); info [n_sys]:
+ *   bits 0-15 = multisection passes, status bits 0, 1 (invalid data: a non-finite entry or g <= 0; c may have any sign) and 8.
+ * Everything but scale is optional.  FP64, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED), one wavefront per
+ * system in division form (csrc/ibs_marginal.hip): 64-way multisection on "s C - D has a positive eigenvalue" to a width of 8 eps s*. */
+int ibs_marginal_gcf_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c, int64_t ld,
+                         double* scale, double* mu, double* X, double* gam0, double* g_bar, double* c_bar, int32_t* info, int32_t mem);
+/* The same margin of every (line, theta0) of a geometry-fed scan: arrays as in ibs_gamma_scan_f64, outputs [n_lines][n_theta0];
+ * s* scales dPdrho[line] at fixed geometry arrays (dPdrho_crit = s* dPdrho).  Nothing upstream corresponds (utils.py:1560-1562 and
+ * bishop_ball_s-alpha.py:90-115 are what the quantity generalises).  scale required; mu, dscale_dtheta0 (the derivative rows of
+ * ibs_marginal_gcf_f64 contracted with the theta0 tangent of utils.py:1669-1673), dscale_ddPdrho (= -s* / dPdrho) and info optional.
+ * One wavefront per (line, theta0) forms the rows and solves them in one kernel.  A real equilibrium's geometry moves with its
+ * pressure: s* = 1 marks the true boundary, s* != 1 is a local, frozen-geometry margin. */
+int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                          const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                          const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                          double* scale, double* mu, double* dscale_dtheta0, double* dscale_ddPdrho, int32_t* info, int32_t mem);
 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
