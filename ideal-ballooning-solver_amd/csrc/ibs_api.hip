@@ -1041,6 +1041,35 @@ int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
   });
 }
 
+// the objective of the margin's refinement in (alpha, theta0): val = -mu = -1 / s* and its gradient at geometry-fed points (k_marginal_points)
+int ibs_marginal_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
+                                const double* theta0, double del_alpha, double* val, double* jac, double* scale, double* dscale,
+                                double* dPdrho, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!geo || !theta0 || !val) return fail(IBS_ERR_ARG, "null argument (geo, theta0 and val are required)");
+  if (n_pts < 0 || ld < N || !(del_alpha > 0))
+    return fail(IBS_ERR_ARG, "bad arguments (n_pts=%d ld=%lld N=%d del_alpha=%g)", n_pts, (long long)ld, N, del_alpha);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_pts == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n = (size_t)n_pts, geo_elems = n * 3 * 8 * (size_t)ld;
+  ibs::MarginalPointsArgs a{};
+  a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld; a.del_alpha = del_alpha;
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, geo_elems); a.theta0 = s.in(theta0, n);
+    a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.scale = s.out(scale, n); a.dscale = s.out(dscale, 2 * n);
+    a.dPdrho = s.out(dPdrho, n);
+    a.info = s.status(info, n);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    const int nw = long_waves(ctx, a.n_pts);
+    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, true).total * sizeof(double))) return r;
+    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    HIPCHK(ibs::launch_marginal_points(a, ctx->stream));
+    return 0;
+  });
+}
+
 // Coarse scan with the nearest eigenpair: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
 // arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and solved by k_solve_gcf_nearest; chunks are
 // bounded by kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".

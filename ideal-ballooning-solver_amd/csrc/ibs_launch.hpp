@@ -148,6 +148,15 @@ struct MarginalScanArgs {
   double* work; size_t work_doubles; long n_waves;
 };
 hipError_t launch_marginal_scan(const MarginalScanArgs& a, hipStream_t st);
+// geometry-fed points with the gradient of s* in (alpha, theta0) (ibs_marginal_points.hip): one wave per point, workspace marginal_ws(N, true)
+struct MarginalPointsArgs {
+  int n_pts, N; double h; long ld;
+  const double* geo;                                                // [n_pts][3][8][ld], as ExactPointsArgs::geo
+  const double* theta0; double del_alpha;                           // theta0 [n_pts]
+  double *val, *jac, *scale, *dscale, *dPdrho; int* info;           // [n_pts] ([n_pts][2]: jac, dscale); val required
+  double* work; size_t work_doubles; long n_waves;                  // the launch refuses less than min(n_pts, n_waves) waves' worth
+};
+hipError_t launch_marginal_points(const MarginalPointsArgs& a, hipStream_t st);
 hipError_t launch_sturm_long(const SturmArgs<double>& a, hipStream_t st);
 hipError_t launch_sturm_div(const SturmArgs<double>& a, hipStream_t st);     // lanes as systems, division form, any N
 template <typename T> struct ScanArgs;

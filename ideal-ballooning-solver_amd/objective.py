@@ -172,3 +172,51 @@ class AdjointStep:
         if phases is not None:
             phases["gather_copy_objective_ms"] = (time.perf_counter() - t0) * 1e3
         return out
+
+    def marginal(self, wouts, steps=None, refine=True):
+        """the marginal-stability scale s* of every surface of every equilibrium of the step (BallooningScan.marginal: the smallest
+        critical scale of dPdrho over (alpha, theta0), refined from the coarse minimum unless refine=False), on the SurfaceTables
+        frame, the sharding of equilibria over ranks and the ONE all-gather of run().  wouts as in run().
+        Returns dict(scale, alpha, theta0: (n_eq, n_surf)), identical on every rank; with steps (n_eq,), entry 0 unused, also dscale
+        (n_dof, n_surf) = (scale[1:] - scale[0]) / steps[1:, None]: the forward differences of sims_runner_NCSX.py:258-261 applied
+        to the margin.  scale = inf (no scale makes the surface unstable) is a result, not a failure."""
+        import torch
+        from .geometry import SurfaceTables
+        from .scan import gather_rows_tensor
+        n_eq, ns = len(wouts), len(self.svals)
+        own = shard_dofs(n_eq, self.rank, self.world)
+        err = None
+        try:                               # row of an equilibrium: n_surf x (scale, alpha, theta0)
+            if own:
+                mine = [wouts[q] for q in own]
+                fr = self._frame
+                pinned = str(self.device).startswith("cuda")
+                if fr is None or fr.n_equilibria != len(own) or not np.array_equal(fr._svals, self.svals) or \
+                        fr._ns != int(mine[0]["ns"]) or len(fr.xm) != len(mine[0]["xm"]) or len(fr.xm_nyq) != len(mine[0]["xm_nyq"]):
+                    fr = self._frame = SurfaceTables.frame(mine[0], self.svals, len(own), pinned=pinned)
+                    self._scan = None
+                scan = self._scan_for(fr, len(own))
+                r0, r1 = fr.fill(0, mine, self.n_threads)
+                if pinned:
+                    self.ctx.upload_tables_rows(fr, self.device, r0, r1)
+                m = scan.marginal(refine=refine)
+                local = np.stack([m["scale"], m["alpha"], m["theta0"]], axis=1).reshape(len(own), 3 * ns)
+                rows = torch.from_numpy(np.ascontiguousarray(local, dtype=np.float64)).to(self.device)
+            else:
+                rows = torch.zeros((0, 3 * ns), dtype=torch.float64, device=self.device)
+        except Exception as e:             # (carried through the gather as NaN rows and raised on every rank afterwards)
+            err = e
+            rows = torch.full((len(own), 3 * ns), float("nan"), dtype=torch.float64, device=self.device)
+        if self.gather_device is not None and self.world > 1:
+            rows = rows.to(self.gather_device)
+        full = gather_rows_tensor(rows, n_eq, self.rank, self.world, self.dist, self.ctx if getattr(self.ctx, "_comm_world", 0) == self.world else None)
+        host = full.cpu().numpy()
+        if err is not None:
+            raise err
+        if np.any(np.isnan(host)):
+            raise IbsError("the marginal-stability scan of %d equilibria failed (see that rank's error)" % int(np.sum(np.isnan(host).any(axis=1))))
+        tab = host.reshape(n_eq, ns, 3)
+        out = dict(scale=tab[:, :, 0], alpha=tab[:, :, 1], theta0=tab[:, :, 2])
+        if steps is not None:
+            out["dscale"] = (out["scale"][1:] - out["scale"][0]) / np.asarray(steps, dtype=np.float64)[1:, None]
+        return out

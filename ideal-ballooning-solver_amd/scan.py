@@ -86,6 +86,9 @@ def check_eigenpair(eigenpair):
     return eigenpair
 
 
+# lanes per grid point of the geometry kernel in the rounds of marginal(refine=True) (option "geo_lpp"; BallooningScan._marginal_points)
+MARGINAL_GEO_LPP = 1
+
 JACS = ("reference", "exact")
 
 
@@ -190,11 +193,20 @@ class BallooningScan:
         return np.asarray(r["gam"]).reshape(len(self.own), len(self.alpha_scan), len(self.theta0_scan))
 
     # -- marginal stability on the coarse grid of the surfaces this rank owns, one launch
-    def marginal(self):
+    def marginal(self, refine=False, maxiter=30, ftol=5.0e-11, gtol=2.0e-8):
         """per owned surface, the smallest critical scale s* of dPdrho over the coarse (alpha, theta0) grid and where it sits
         (Context.marginal_scan): dict(scale (n_own,), alpha, theta0, index (n_own, 2) = (i_alpha, i_theta0) of the first minimum,
         table (n_own, nalpha, ntheta0)).  s* < 1: some line of the surface is unstable now; s* scales dPdrho at FIXED geometry
-        arrays, so away from 1 it is a local margin.  No refinement in (alpha, theta0).  Raises IbsError on status bits 0-1."""
+        arrays, so away from 1 it is a local margin.  Raises IbsError on status bits 0-1.
+        refine=True: every surface's minimum is refined in (alpha, theta0) from that grid node, as run() refines the growth rate:
+        -mu = -1 / s* (finite where no scale makes a line unstable) is minimised over [0, pi] x [0, pi/2] by the L-BFGS-B state
+        machines (ibs_lbfgsb2_*) in lockstep, every round ONE batched geometry step + ONE Context.marginal_obj_w_grad launch for the
+        surfaces still running, and one more launch at the refined points fills the result.  scale, alpha, theta0 are then the
+        refined ones (index and table stay the coarse ones) and the dict gains coarse_scale (n_own,), start (n_own, 2), dscale
+        (n_own, 2) = (d s* / d alpha, d s* / d theta0) at the refined point, dPdrho (n_own,) of the refined line, evals (n_own,),
+        task (n_own,) = the L-BFGS-B task codes (lbfgsb.TASKS) and rounds.  A surface's refinement does not depend on the surfaces
+        refined beside it (the rounds' geometry runs in one form of the geometry kernel: MARGINAL_GEO_LPP).  A surface whose coarse table is all +inf stays at its
+        start point with scale = inf and no evaluation (its gradient is 0)."""
         na, nt = len(self.alpha_scan), len(self.theta0_scan)
         if not self.own:
             tab = np.zeros((0, na, nt))
@@ -220,8 +232,81 @@ class BallooningScan:
         flat = tab.reshape(len(tab), -1)
         k = np.argmin(flat, axis=1) if len(tab) else np.zeros(0, dtype=np.int64)
         ia, it = k // nt, k % nt
-        return dict(scale=flat[np.arange(len(tab)), k], alpha=self.alpha_scan[ia], theta0=self.theta0_scan[it],
-                    index=np.stack([ia, it], axis=1), table=tab)
+        res = dict(scale=flat[np.arange(len(tab)), k], alpha=self.alpha_scan[ia], theta0=self.theta0_scan[it],
+                   index=np.stack([ia, it], axis=1), table=tab)
+        return self._marginal_refine(res, maxiter, ftol, gtol) if refine else res
+
+    # -- the margin's objective at X[q] = (alpha, theta0) of owned surface own_idx[q], all at once: one geometry step (the three
+    # lines of every point: the geometry kernel on `device`, staged through the host without one, or the host callable) and one
+    # ibs_marginal_obj_w_grad_f64 launch; numpy out
+    def _marginal_points(self, own_idx, X):
+        n, N, d = len(own_idx), len(self.theta), self.del_alpha
+        al = np.stack([X[:, 0] - 0.5 * d, X[:, 0], X[:, 0] + 0.5 * d], axis=1)
+        if self.tables is not None:
+            surf = np.repeat(self._own_surf()[own_idx], 3)
+            # the geometry kernel picks its form from the size of the batch, and the forms differ in the last bits of the rows: left
+            # to that, a surface's trajectory (and its refined point, to 1e-10) would depend on how many others run beside it.  One
+            # form for every round makes the refinement of a surface the same in any batch, bit for bit
+            with self.ctx.option_default("geo_lpp", MARGINAL_GEO_LPP):
+                r = self.ctx.fieldline_geometry(self.tables, surf, al.reshape(-1), self.theta, device=self.device)
+            if self.device is not None:
+                import torch
+                geo = r["geo"].view(8, n, 3, N).permute(1, 2, 0, 3).contiguous()
+                t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
+            else:
+                geo = np.ascontiguousarray(r["geo"].reshape(8, n, 3, N).transpose(1, 2, 0, 3))
+                t0 = np.ascontiguousarray(X[:, 1])
+        else:
+            geo = np.stack([np.asarray(self.fieldlines(self.rho_arr[self.own[k]], al[q])) for q, k in enumerate(own_idx)])
+            t0 = np.ascontiguousarray(X[:, 1])
+        out = self.ctx.marginal_obj_w_grad(self.h, geo, t0, d, want_grad=True, want_info=True)
+        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        out = {key: host(v) for key, v in out.items() if key != "nbad"}
+        bad = (((out["info"] >> 16) & 3) != 0) | ~np.isfinite(out["val"]) | ~np.isfinite(out["jac"]).all(axis=1)
+        if bad.any():
+            raise IbsError("%d of %d marginal-stability solves of the refinement were flagged (status bits 0-1: iteration cap or "
+                           "invalid data) or gave a non-finite objective" % (int(bad.sum()), n))
+        return out
+
+    def _marginal_refine(self, res, maxiter, ftol, gtol):
+        """the lockstep loop of refine_batched on the margin's objective, from the first minimum of every coarse table"""
+        import ctypes as C
+        from . import _lib
+        lib = _lib.lib()
+        lo = np.array([0.0, 0.0]); hi = np.array([np.pi, 0.5 * np.pi])
+        n = len(self.own)
+        p = lambda a: C.c_void_p(a.ctypes.data)
+        start = np.stack([res["alpha"], res["theta0"]], axis=1).astype(np.float64).reshape(n, 2)
+        x = np.clip(start, lo, hi)
+        states = [C.create_string_buffer(lib.ibs_lbfgsb2_state_bytes()) for _ in range(n)]
+        for k in range(n):
+            lib.ibs_lbfgsb2_init(states[k], p(x[k]), p(lo), p(hi), float(ftol), float(gtol), int(maxiter), 20)
+        active = np.isfinite(res["scale"])                  # (an all-inf table: mu = 0 with a zero gradient all around the start)
+        evals = np.zeros(n, dtype=np.int32)
+        task = np.full(n, 10, dtype=np.int32)
+        rounds = 0
+        while active.any():
+            idx = np.nonzero(active)[0]
+            r = self._marginal_points(idx, x[idx])
+            rounds += 1
+            evals[idx] += 1
+            for q, k in enumerate(idx):
+                gk = np.ascontiguousarray(r["jac"][q], dtype=np.float64)
+                if not lib.ibs_lbfgsb2_step(states[k], float(r["val"][q]), p(gk), p(x[k])):
+                    active[k] = False
+        for k in range(n):
+            if evals[k]:
+                fk = C.c_double(0.0); cnt = np.zeros(5, dtype=np.int32)
+                lib.ibs_lbfgsb2_result(states[k], p(x[k]), C.byref(fk), p(cnt))
+                task[k] = cnt[2]
+        out = dict(res, coarse_scale=res["scale"], start=start, alpha=x[:, 0].copy(), theta0=x[:, 1].copy(), evals=evals, task=task,
+                   rounds=rounds)
+        if n:
+            fin = self._marginal_points(np.arange(n), x)
+            out.update(scale=fin["scale"], dscale=fin["dscale"], dPdrho=fin["dPdrho"])
+        else:
+            out.update(scale=np.zeros(0), dscale=np.zeros((0, 2)), dPdrho=np.zeros(0))
+        return out
 
     # -- jac="exact": val and the exact gradient at a batch of points (numpy or device tensors in, numpy out); sigma None = lam_max's pair
     def _obj_exact(self, geo, t0, sigma):

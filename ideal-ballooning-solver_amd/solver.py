@@ -4,6 +4,7 @@ Accepts numpy arrays (host memory: staged by the library) or torch CUDA tensors 
 zero-copy, asynchronous on the torch current stream).  Mirrors the reference operators'
 argument meaning; see operators.py for the exact drop-in signatures.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -184,6 +185,26 @@ class Context:
         value None = back to the context's default"""
         check(self._lib.ibs_set_option(self._h, name.encode(), float("nan") if value is None else float(value)),
               "ibs_set_option")
+        mine = self.__dict__.setdefault("_options", {})      # what the caller holds overridden (option_default() leaves those alone)
+        if name == "all":
+            mine.clear()
+        elif value is None:
+            mine.pop(name, None)
+        elif name != "forget_rows":
+            mine[name] = float(value)
+
+    @contextlib.contextmanager
+    def option_default(self, name, value):
+        """`name` = value inside the block unless the caller holds the option overridden through set_option (then theirs stands);
+        afterwards the option is back at the context's default"""
+        if name in self.__dict__.get("_options", {}):
+            yield
+            return
+        self.set_option(name, value)
+        try:
+            yield
+        finally:
+            self.set_option(name, None)
 
     def reset_options(self):
         self.set_option("all", None)
@@ -335,6 +356,35 @@ class Context:
         out = dict(scale=scale, mu=mu, nbad=rc)
         if want_grad:
             out.update(dscale_dtheta0=dth, dscale_ddPdrho=ddP)
+        if want_info:
+            out.update(info=info)
+        return out
+
+    def marginal_obj_w_grad(self, h, geo, theta0, del_alpha=0.004, want_grad=True, want_info=False):
+        """the objective of the margin's refinement in (alpha, theta0) (ibs_marginal_obj_w_grad_f64): geo (n_pts, 3, 8, N) -- the
+        lines alpha - del_alpha / 2, alpha, alpha + del_alpha / 2 --, theta0 (n_pts,).  Returns dict(val = -1 / s*, scale = s*,
+        dPdrho (the centre line's)[, jac = dscale / s*^2, dscale = (d s* / d alpha, d s* / d theta0): (n_pts, 2)][, info], nbad).
+        want_grad=False: the side lines are not read and no mode is formed.  info status bit 8: scale = inf, val = 0, jac = dscale = 0
+        (not counted in nbad); bits 0-1: NaN outputs -- or, where only a side line held invalid data, NaN jac and dscale alone."""
+        ar = _Args()
+        n_pts, three, eight, N = geo.shape
+        if three != 3 or eight != 8:
+            raise IbsError("geo must be (n_pts, 3, 8, N)")
+        pg, pt = ar.inp(geo), ar.inp(theta0)
+        ref = geo if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        val, pval = ar.out((n_pts,), ref)
+        jac, pjac = ar.out((n_pts, 2), ref, want=want_grad)
+        scale, pscale = ar.out((n_pts,), ref)
+        dscale, pdscale = ar.out((n_pts, 2), ref, want=want_grad)
+        dP, pdP = ar.out((n_pts,), ref)
+        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_marginal_obj_w_grad_f64(self._h, n_pts, N, float(h), pg, N, pt, float(del_alpha), pval, pjac, pscale,
+                                                         pdscale, pdP, pinfo, ar.mem), "ibs_marginal_obj_w_grad_f64")
+        out = dict(val=val, scale=scale, dPdrho=dP, nbad=rc)
+        if want_grad:
+            out.update(jac=jac, dscale=dscale)
         if want_info:
             out.update(info=info)
         return out

@@ -42,7 +42,8 @@
  *            inaccurate); bit 7: the adjoint refused the pair (jac = NaN, val is good).  Neither is counted by return values > 0.
  *     bit 8, marginal-stability entry points (ibs_marginal_*_f64) only: no row has c_j > 0, so no scale of the pressure gradient makes
  *            the line unstable -- scale = +inf, mu = 0, the derivatives are 0 and X, gam0 are NaN (informational: not counted by
- *            return values > 0).
+ *            return values > 0).  ibs_marginal_obj_w_grad_f64 writes val = 0 and jac = dscale = 0 with it, and sets bit 1 with val
+ *            and scale kept (jac = dscale = NaN) where the centre line solved but a side line of the alpha tangent held invalid data.
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
  *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
  *     for every sigma, lam_max's among them; they never set bit 4.
@@ -265,6 +266,23 @@ int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
                           const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
                           const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
                           double* scale, double* mu, double* dscale_dtheta0, double* dscale_ddPdrho, int32_t* info, int32_t mem);
+/* The objective of the refinement of the margin in (alpha, theta0), at geometry-fed points: geo, theta0 and del_alpha as in
+ * ibs_obj_w_grad_exact_f64 (geo [n_pts][3][8][ld]: the lines alpha - del_alpha / 2, alpha, alpha + del_alpha / 2).  The objective is
+ * the marginal eigenvalue mu = 1 / s*, not s*: mu is finite everywhere (0 where no scale makes the line unstable), so a minimiser
+ * can cross a stable region.  Nothing upstream corresponds; the tangents are those of utils.py:1669-1673 (theta0) and 1683-1718
+ * (alpha: each side line with its own dPdrho, divided by del_alpha).
+ *   val [n_pts] = -mu (required); jac [n_pts][2] = -(d mu / d alpha, d mu / d theta0) = dscale / s*^2; scale [n_pts] = s*;
+ *   dscale [n_pts][2] = (d s* / d alpha, d s* / d theta0), Hellmann-Feynman on the discrete pencil (fixed-order sums: bitwise
+ *   repeatable and independent of the batch); dPdrho [n_pts]: the centre line's, so that dPdrho_crit = s* dPdrho; info [n_pts]:
+ *   bits 0-15 = multisection passes, status bits 0, 1 and 8.  Everything but val is optional; with jac and dscale both NULL the side
+ *   lines are not read and no mode is formed (the point-evaluation form).
+ *   Status bit 8: scale = +inf, val = 0, jac = dscale = 0 (not counted).  Bits 0-1 of the centre solve: every floating-point output of
+ *   the point is NaN.  A gradient that is not finite after a good centre solve: bit 1, jac = dscale = NaN, val and scale kept.
+ * FP64, any odd N in [66, 65537], one wavefront per point (k_marginal_points, csrc/ibs_marginal_points.hip).  The frozen-geometry caveat of
+ * ibs_marginal_scan_f64 applies. */
+int ibs_marginal_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
+                                const double* theta0, double del_alpha, double* val, double* jac, double* scale, double* dscale,
+                                double* dPdrho, int32_t* info, int32_t mem);
 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
