@@ -64,6 +64,7 @@ struct ibs_options {
   int geo_lpp = 0;        // lanes per grid point of the geometry kernel: 1 | 2 | 4
   int gcf_rows = -1;      // raw systems on long grids: -1 / 1 = row-streamed kernel, 0 = the 3-row staging of k_solve_gcf
   int gcf_direct = -1;    // raw systems, one wave per system: rows read straight from global memory (k_solve_gcf_direct): -1 = by batch size, 0 = never, 1 = always
+  int scan_resident = -1; // k_gamma_scan, 3 <= rows per lane <= 8: -1 = the resident form up to two waves per SIMD and k_gamma_scan_lean above, 0 = lean everywhere, 1 = resident wherever built
   int pack_mode = 0;      // hand-off of the fused scan + argmax: 1 = write-through + sc1 loads, 2 = release / acquire fences
   int f32_lam = 0;        // FP32 eigenvalue-only requests: 0 = by grid size, 1 = all-FP32 iteration + FP64 certificate, 2 = FP32 in HBM + FP64 solver
   double sigma0 = std::numeric_limits<double>::quiet_NaN();   // not NaN: solves that return lam AND info flag lam_max >= sigma0 (informational status bit 4: utils.py:1597 would have taken the eigenpair nearest sigma0)
@@ -719,6 +720,7 @@ int ibs_set_option(ibs_ctx* c, const char* name, double value) {
   else if (n == "geo_lpp") c->opt.geo_lpp = reset ? c->opt_created.geo_lpp : (int)value;
   else if (n == "gcf_rows") c->opt.gcf_rows = reset ? c->opt_created.gcf_rows : (int)value;
   else if (n == "gcf_direct") c->opt.gcf_direct = reset ? c->opt_created.gcf_direct : (int)value;
+  else if (n == "scan_resident") c->opt.scan_resident = reset ? c->opt_created.scan_resident : (int)value;
   else if (n == "pack_mode") c->opt.pack_mode = reset ? c->opt_created.pack_mode : (int)value;
   else if (n == "f32_lam") c->opt.f32_lam = reset ? c->opt_created.f32_lam : (int)value;
   else if (n == "reclose") c->opt.reclose = reset ? c->opt_created.reclose : (int)value;
@@ -1390,7 +1392,15 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
       }
     }
   }
+  // One wave per system, unchained, 3 <= M <= 8: the resident form of k_gamma_scan (186 VGPRs at M = 8: two waves per SIMD) while the
+  // launch holds no more than that -- its time is then a lone wave's latency --, k_gamma_scan_lean (four at M = 8) above.
+  if (fn == ibs::launch_table().scan_f64[M] && G == 1) {
+    const long grid_waves = (long)((n_theta0 + a.wpb - 1) / a.wpb) * n_lines * a.wpb;
+    a.resident = ctx->opt.scan_resident == 0 ? 0 : (ctx->opt.scan_resident == 1 ? 1 : (grid_waves <= 2L * 4 * ctx->n_cu ? 1 : 0));
+  }
   }   // (!lng)
+  // (the divisions of the kernel's set-up and growth-rate stage, done once here: correctly rounded on both sides)
+  a.ih2 = 1.0 / (h * h); a.ih = 1.0 / h;
   const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
   const size_t n_t0_vals = t0_per_line ? (size_t)n_lines : (size_t)n_theta0;
   a.guess_width = guess_width;

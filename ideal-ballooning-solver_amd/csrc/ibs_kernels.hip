@@ -4,6 +4,7 @@
 //
 //  k_solve_gcf   : raw (g, c, f) systems            -> lam, gam, [X, dX]        (config 5 / C1)
 //  k_gamma_scan  : field-line geometry x theta0 grid -> gam, lam, [X, dX, dgam/dtheta0]
+//                  (3 <= M <= 8: the register-resident form; k_gamma_scan_lean = the rebuild-and-replay form, see gamma_scan_body)
 //                  (ball_scan.py:248-275 inner loops, utils.py:1556-1624, utils.py:1666-1680)
 //  k_sturm_count : inertia of T - lam F at given shifts (pins the s-alpha stability test)
 #include "ibs_wave.hpp"
@@ -103,6 +104,15 @@ struct SrcGeo {
     const T g1 = G1[q], g2 = G2[q], a1 = A1[q], a3 = A3[q], c1 = C1[q];
     const T d = G0[q] + two_th0 * g1 + th0sq * g2, dp = T(2) * g1 + two_th0 * g2;
     g_ = a1 * d; c_ = sc(C0[q] + th0 * c1); f_ = a3 * d;
+    gt = a1 * dp; ct = sc(c1); ft = a3 * dp;
+  }
+  // the resident form of k_gamma_scan: the two factors of g = a1 * d_ at a point (kept in registers from set-up on), and the
+  // theta0 tangents alone, given a1
+  __device__ __forceinline__ void g_factors(int j, T& a1, T& d_) const { a1 = A1[lpos(j)]; d_ = gd(j); }
+  __device__ __forceinline__ void tangent(int j, T a1, T& gt, T& ct, T& ft) const {
+    const int q = lpos(j);
+    const T g1 = G1[q], g2 = G2[q], a3 = A3[q], c1 = C1[q];
+    const T dp = T(2) * g1 + two_th0 * g2;
     gt = a1 * dp; ct = sc(c1); ft = a3 * dp;
   }
 };
@@ -237,6 +247,25 @@ __device__ __forceinline__ void simpson_point(const Src& src, int j, T w, T X, T
   y1 = xfma(f_, X2, y1);                                             // utils.py:1619
 }
 
+// ... with the factors of g, c and f of the point carried in registers since set-up (WaveSolver<T, M, true>); only the
+// tangents are read
+template <typename T, class Src, bool WT>
+__device__ __forceinline__ void simpson_point_carried(const Src& src, int j, T a1, T d_, T c_, T f_, T w, T X, T dX, T& y0, T& y1,
+                                                      T& hc, T& hg, T& hf) {
+  const T X2 = w * (X * X), dX2 = w * (dX * dX);
+  // (the product is formed HERE, from a factor the compiler cannot trace: merged with set-up's own a1 * d it would be one more use
+  //  of that product, and the number of uses decides which product of set-up's half-grid means is contracted into an fma)
+  asm volatile("" : "+v"(d_));
+  const T g_ = a1 * d_;
+  if constexpr (WT) {
+    T gt, ct, ft;
+    src.tangent(j, a1, gt, ct, ft);
+    hc = xfma(ct, X2, hc); hg = xfma(gt, dX2, hg); hf = xfma(ft, X2, hf);
+  }
+  y0 += c_ * X2 - g_ * dX2;                                          // utils.py:1618
+  y1 = xfma(f_, X2, y1);                                             // utils.py:1619
+}
+
 // Growth rate without an LDS round trip: the eigenfunction stays in the lanes' row chunks, the four stencil neighbours beyond a chunk come from the adjacent lanes (wave_shr / wave_shl),
 // and every lane sums its own rows of the Simpson integrals; the two end points j = 0, N-1 (X = 0, one-sided dX)
 // are added by the first and last lane.  Same per-point arithmetic as finish() (utils.py:1601-1621).  X and dX, when
@@ -245,8 +274,10 @@ __device__ __forceinline__ void simpson_point(const Src& src, int j, T w, T X, T
 // PASSES > 1 (row-streamed raw systems, k_solve_gcf_rows): the Simpson sums are separable in (g, c, f), so they are
 // accumulated in PASSES sweeps over the rows, `src.begin_pass(p)` putting the p-th coefficient array into the wave's one
 // LDS row in between (the other two read as zero).
-template <typename T, int M, class Src, bool HF, int PASSES = 1, typename TO = T>
-__device__ __forceinline__ void finish_chunk(WaveSolver<T, M>& ws, Src& src, int N, T h, T* Xs, T lam,
+// RES (the resident form of k_gamma_scan): g (as its two factors), c and f of the lane's rows are the values set-up formed and
+// kept; only the two end points, and the theta0 tangents when they are wanted, are read from `src`.
+template <typename T, int M, class Src, bool HF, int PASSES = 1, typename TO = T, bool RES = false>
+__device__ __forceinline__ void finish_chunk(WaveSolver<T, M, RES>& ws, Src& src, int N, T h, T* Xs, T lam,
                                              const SolveInfo& inf, long sys, typename TypeId<TO>::type* lam_out,
                                              typename TypeId<TO>::type* gam_out, typename TypeId<TO>::type* X_out,
                                              typename TypeId<TO>::type* dX_out, typename TypeId<TO>::type* dth0_out,
@@ -279,7 +310,8 @@ __device__ __forceinline__ void finish_chunk(WaveSolver<T, M>& ws, Src& src, int
   for (int i = 0; i < M - 1; ++i) xe[i + 2] = x[i];
   xe[M + 1] = hl ? x[M - 1] : xp1; xe[M + 2] = hl ? xp1 : xp2; xe[M + 3] = xp2;
   IBS_PROBE_AT(13);
-  const T ih = T(1) / h;
+  T ih;
+  if constexpr (RES) ih = ws.rr.ih; else ih = T(1) / h;
   const T A_in = (T(2) / T(3)) * ih, B_in = -ih / T(12), A_e1 = T(0.5) * ih, A_e0 = T(2) * ih, B_e0 = T(-0.5) * ih;
   bool do_hf = false;
   if constexpr (HF) do_hf = dth0_out != nullptr;
@@ -299,8 +331,14 @@ __device__ __forceinline__ void finish_chunk(WaveSolver<T, M>& ws, Src& src, int
       const T A = e1 ? A_e1 : A_in, B = e1 ? T(0) : B_in;
       const T dX = xfma(A, xe[i + 3] - xe[i + 1], B * (xe[i + 4] - xe[i]));           // utils.py:1616
       const T w = act ? ((i & 1) ? w_odd : w_even) : T(0);
-      simpson_point<T, Src, HF && decltype(with_tangent)::value>(src, a + i + 1, w, xe[i + 2], dX, y0, y1, hc, hg, hf);
-      if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // at most 4 rows of LDS reads in flight (registers)
+      if constexpr (RES) {
+        simpson_point_carried<T, Src, HF && decltype(with_tangent)::value>(src, a + i + 1, ws.rr.a1[i], ws.rr.d[i], ws.rr.c[i],
+                                                                           ws.rr.f[i], w, xe[i + 2], dX, y0, y1, hc, hg, hf);
+        if constexpr (HF && decltype(with_tangent)::value) { if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0); }
+      } else {
+        simpson_point<T, Src, HF && decltype(with_tangent)::value>(src, a + i + 1, w, xe[i + 2], dX, y0, y1, hc, hg, hf);
+        if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // at most 4 rows of LDS reads in flight (registers)
+      }
     }
   };
   if constexpr (HF) {
@@ -1060,8 +1098,12 @@ __global__ void __launch_bounds__(256) k_solve_gcf_rows(long n_sys, int N, T h, 
 // ---------------------------------------------------------------- geometry-fed theta0 scan
 // grid = n_lines * ceil(n_theta0 / wpb) blocks; block = wpb waves; wave w solves theta0 index part*wpb + w.
 // dynamic LDS = (7 + wpb) * lds_pitch(N) * sizeof(T).  Geometry arrays are [n_lines][ld].
-template <typename T, int M>
-__global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines, int n_theta0, int N, T h,
+// Two forms of one body.  RES (k_gamma_scan<T, M>, 3 <= M <= 8): the rows set-up forms stay in registers up to the growth-rate
+// stage (WaveSolver<T, M, true>; 186 VGPRs at M = 8, two waves per SIMD) -- for launches of at most two waves per SIMD, whose
+// time is the latency of a lone wave.  Lean (k_gamma_scan_lean<T, M>, and k_gamma_scan at every other M): rebuilt and replayed
+// (126 VGPRs at M = 8), for launches that want the occupancy.  ih2 = 1 / (h * h), ih = 1 / h from the host (RES only).
+template <typename T, int M, bool RES>
+__device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N, T h,
                                                      const T* __restrict__ bmag, const T* __restrict__ gradpar,
                                                      const T* __restrict__ cvdrift, const T* __restrict__ cvdrift0,
                                                      const T* __restrict__ gds2, const T* __restrict__ gds21,
@@ -1070,7 +1112,7 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines,
                                                      T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
                                                      int* info_out, const T* __restrict__ lam_guess, T guess_width,
                                                      int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
-                                                     int t0_stride) {
+                                                     int t0_stride, T ih2, T ih) {
   // t0_stride: 0 = the theta0 grid is shared by all lines; 1 (with n_theta0 = 1) = one theta0 per line (ibs_gamma_points_f64)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
@@ -1118,7 +1160,8 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines,
   __syncthreads();
   IBS_PROBE_AT(1);
   SrcGeo<T> src{A1, A3, C0, C1, G0, G1, G2, th0, T(2) * th0, th0 * th0};
-  WaveSolver<T, M> ws;
+  WaveSolver<T, M, RES> ws;
+  if constexpr (RES) { ws.rr.ih2 = ih2; ws.rr.ih = ih; }
   SolveInfo inf{0, 0};
 #ifdef IBS_PROBE_TWICE
   // experiment (round 5, tools/scan_probe.py): the set-up executed twice, the first result discarded -- is its time the code's
@@ -1141,6 +1184,7 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines,
                                         valid ? gam_out : nullptr, valid ? X_out : nullptr, valid ? dX_out : nullptr,
                                         valid ? dth0_out : nullptr, valid ? info_out : nullptr);
   } else {
+    static_assert(M >= 3 || !RES, "the resident form lives in finish_chunk");
     finish<T, M, SrcGeo<T>, true>(ws, src, N, h, Xs, lam, inf, sys, valid ? lam_out : nullptr,
                                   valid ? gam_out : nullptr, valid ? X_out : nullptr, valid ? dX_out : nullptr,
                                   valid ? dth0_out : nullptr, valid ? info_out : nullptr);
@@ -1205,6 +1249,40 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines,
       }
     }
   }
+}
+
+constexpr bool scan_resident_built(int M) { return M >= 3 && M <= 8; }
+
+template <typename T, int M>
+__global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines, int n_theta0, int N, T h,
+                                                     const T* __restrict__ bmag, const T* __restrict__ gradpar,
+                                                     const T* __restrict__ cvdrift, const T* __restrict__ cvdrift0,
+                                                     const T* __restrict__ gds2, const T* __restrict__ gds21,
+                                                     const T* __restrict__ gds22, long ld,
+                                                     const T* __restrict__ dPdrho, const T* __restrict__ theta0,
+                                                     T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
+                                                     int* info_out, const T* __restrict__ lam_guess, T guess_width,
+                                                     int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
+                                                     int t0_stride, T ih2, T ih) {
+  gamma_scan_body<T, M, scan_resident_built(M)>(n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld,
+                                                dPdrho, theta0, gam_out, lam_out, X_out, dX_out, dth0_out, info_out, lam_guess,
+                                                guess_width, lines_per_surf, surf_counter, pack, pack_mode, t0_stride, ih2, ih);
+}
+// the lean form under a name of its own (3 <= M <= 8: launches above two waves per SIMD, option scan_resident = 0)
+template <typename T, int M>
+__global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan_lean(int n_lines, int n_theta0, int N, T h,
+                                                     const T* __restrict__ bmag, const T* __restrict__ gradpar,
+                                                     const T* __restrict__ cvdrift, const T* __restrict__ cvdrift0,
+                                                     const T* __restrict__ gds2, const T* __restrict__ gds21,
+                                                     const T* __restrict__ gds22, long ld,
+                                                     const T* __restrict__ dPdrho, const T* __restrict__ theta0,
+                                                     T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
+                                                     int* info_out, const T* __restrict__ lam_guess, T guess_width,
+                                                     int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
+                                                     int t0_stride) {
+  gamma_scan_body<T, M, false>(n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho, theta0,
+                               gam_out, lam_out, X_out, dX_out, dth0_out, info_out, lam_guess, guess_width, lines_per_surf,
+                               surf_counter, pack, pack_mode, t0_stride, T(0), T(0));
 }
 
 
@@ -1825,14 +1903,27 @@ template <typename T>
 static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb;
   const size_t lds = (size_t)(7 + wpb) * lds_pitch(a.N) * sizeof(T) + (a.pack ? 128 : 0);
+  dim3 grid((unsigned)(((a.n_theta0 + wpb - 1) / wpb) * a.n_lines));
+  if constexpr (scan_resident_built(IBS_M)) {
+    if (!a.resident) {
+      auto lean = k_gamma_scan_lean<T, IBS_M>;
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lean), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(lean, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
+                         a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
+                         a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
+                         a.t0_stride);
+      note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan_lean<%s, %d>", type_name<T>(), IBS_M);
+      return hipGetLastError();
+    }
+  }
   auto kern = k_gamma_scan<T, IBS_M>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  dim3 grid((unsigned)(((a.n_theta0 + wpb - 1) / wpb) * a.n_lines));
   hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
                      a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
                      a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
-                     a.t0_stride);
+                     a.t0_stride, a.ih2, a.ih);
   note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan<%s, %d>", type_name<T>(), IBS_M);
   return hipGetLastError();
 }

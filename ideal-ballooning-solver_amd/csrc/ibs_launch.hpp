@@ -36,6 +36,9 @@ struct ScanArgs {
   int lines_per_surf; int* surf_counter; T* pack;
   int pack_mode;                         // 1 = write-through stores + sc1 loads (one block per CU), 2 = release / acquire fences
   int t0_stride;                         // k_gamma_scan only: 0 = theta0[n_theta0] shared by all lines, 1 = theta0[n_lines] (n_theta0 = 1)
+  // k_gamma_scan, 3 <= M <= 8: 1 = the resident form (set-up rows carried in registers, 186 VGPRs at M = 8: launches of at most two waves
+  // per SIMD), 0 = the lean form k_gamma_scan_lean (126 VGPRs at M = 8).  ih2 = 1 / (h * h), ih = 1 / h: divided once, on the host
+  int resident; T ih2, ih;
 };
 template <typename T>
 struct SturmArgs {

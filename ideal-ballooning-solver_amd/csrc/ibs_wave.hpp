@@ -452,12 +452,35 @@ struct SolveInfo {
   int status;   // 0 ok, bit0 = iteration cap hit, bit1 = non-finite data / non-positive g or f
 };
 
+// Rows a wave carries in registers from set-up to the growth-rate stage (WaveSolver<T, M, true>): per owned row i the two
+// factors of g at its grid point (Src::g_factors: g = a1 * d), c and f there, and -- from pass A of twisted() on -- the forward
+// solution at the final shift.  ih2 = 1 / (h * h) and ih = 1 / h are formed once on the host (correctly rounded divisions on
+// both sides).  g is kept as its factors, and the scaling s is NOT kept, for the sake of the bits: the half-grid mean
+// 0.5 * (g_j + g_j+1) adds two products, the compiler contracts one of them into an fma, and WHICH one depends on how many
+// uses each product has -- a kept copy of g is one more use and moves D and Ph by an ulp, and set-up and assemble() contract
+// their (identical) expressions differently to begin with, so that the s of set-up is not the s assemble() has always used.
+template <typename T, int M, bool RES>
+struct ResidentRows {};
 template <typename T, int M>
+struct ResidentRows<T, M, true> {
+  T a1[M], d[M], c[M], f[M], zu[M];
+  T ih2, ih;
+};
+
+template <typename T, int M, bool RES = false>
 struct WaveSolver {
   // chunk of this lane, symmetric scaling (see header comment).  Register budget: during the shift iteration only D and
   // Ph (4M VGPRs) are live; the backward solution zw is stored once, after convergence; the forward solution is never
   // stored but replayed from its incoming pair (M fma per replay), and the diagonal scaling s is rebuilt from g when the
   // eigenvector is assembled -- so the peak is 6M + temporaries instead of 10M (256 VGPRs + scratch at M = 16 before).
+  // That replay-and-rebuild economy is what M > 8 needs and keeps.  At M <= 8 the registers are there (126 VGPRs at M = 8,
+  // and the latency-bound launches this form is for hold at most two waves per SIMD: 256 VGPRs each), while every
+  // instruction of the lone wave's path is step time -- so RES = true (k_gamma_scan, 3 <= M <= 8) CARRIES instead: set-up
+  // keeps g (as its two factors), c and f of the lane's rows (4M doubles, live across the shift iteration), pass A of
+  // twisted() keeps the forward solution (M more, live from convergence on), and pass B, assemble() and the Simpson sums
+  // read them back: one replay instead of three, no coefficient read in the sums.  Each carried value is bit for bit the
+  // value the lean form recomputes (see ResidentRows for the two that are not carried because they would not be).
+  ResidentRows<T, M, RES> rr;
   T D[M], Ph[M];
   T kap, ikap;
   bool has_last;   // this lane owns M rows (else M-1)
@@ -500,7 +523,8 @@ struct WaveSolver {
     const int rem = n - kWave * (M - 1);
     has_last = lane < rem;
     const int a = rows_start(lane, n);
-    const T ih2 = T(1) / (h * h);
+    T ih2;
+    if constexpr (RES) ih2 = rr.ih2; else ih2 = T(1) / (h * h);
     T sc = T(1);
     // half-grid g between grid points k and k+1 (utils.py:1574-1576): the mean of the neighbours on a uniform
     // grid, or a caller-supplied array when the input grid was regridded (Src::kHasGh)
@@ -550,10 +574,12 @@ struct WaveSolver {
         vna = xmax(vna, (xabs(d) + e_lo + e_hi) * rf);
         sum_c += cj; sum_f += fj;
         bad = bad || !(fj > T(0)) || !(e_hi > T(0)) || !finite_of(cj);
+        if constexpr (RES) { src.g_factors(j, rr.a1[i], rr.d[i]); rr.c[i] = cj; rr.f[i] = fj; }
         sc = fast_rcp(e_hi * sc);           // e s_i s_{i+1} = 1 to rounding (two Newton steps on the hardware seed)
         gcur = gnext; e_lo = e_hi;
       } else {
         D[i] = T(0); Ph[i] = T(0);
+        if constexpr (RES) { rr.a1[i] = T(0); rr.d[i] = T(0); rr.c[i] = T(0); rr.f[i] = T(0); }
       }
       // the rows hang on one dependent chain (sc), so the scheduler would put EVERY row's LDS reads in flight first
       // (3 to 7 values per row: > 400 VGPRs at M = 32); at most kSetupRows rows at a time
@@ -717,6 +743,7 @@ struct WaveSolver {
         best = better ? a : best; bi = better ? i : bi;
         zu_b = better ? zc : zu_b; zum_b = better ? zp : zum_b; t_b = better ? t : t_b;
         zw_b = better ? zw[i] : zw_b; zwp_b = better ? (i == M - 1 ? zw_p1 : zw[i < M - 1 ? i + 1 : M - 1]) : zwp_b;
+        if constexpr (RES) rr.zu[i] = zc;
         const T zn = xfma(-t, zc, -zp);
         if (act) { zp = zc; zc = zn; }
       }
@@ -747,7 +774,7 @@ struct WaveSolver {
     fu = xldexp(fast_rcp(zu_k), du);
     fw = xldexp(fast_rcp(zw_k), dw);
     thr = (lane < Lk) ? M : ((lane > Lk) ? -1 : ik);
-    // pass B: sum f x^2 over the twisted vector (forward solution replayed again)
+    // pass B: sum f x^2 over the twisted vector (forward solution replayed again; RES: taken from pass A)
     T acc = T(0);
     using SignWord = typename std::conditional<(M + 2 <= 32), unsigned, unsigned long long>::type;
     SignWord su = sign_word(zu_m1) >> 31, sw = 0;      // CNT: sign bits of (u_-1, u_0 .. u_{M-1}) and of (w_0 .. w_{M-1})
@@ -757,8 +784,8 @@ struct WaveSolver {
       T zc = u0_in, zp = zu_m1;
 #pragma unroll
       for (int i = 0; i < M; ++i) {
-        const T t = xfma(-sig, Ph[i], D[i]);
         const bool act = (i < M - 1) || has_last;
+        if constexpr (RES) zc = rr.zu[i];
         const T xu = zc * fu, xw = zw[i] * fw;
         const T x = (i <= thr) ? xu : xw;
         if (act) acc = xfma(Ph[i] * x, x, acc);
@@ -774,8 +801,10 @@ struct WaveSolver {
             sw_b = (unsigned)__builtin_amdgcn_alignbit(sw_b, sign_word(zw[i]), 31);
           }
         }
-        const T zn = xfma(-t, zc, -zp);
-        if (act) { zp = zc; zc = zn; }
+        if constexpr (!RES) {
+          const T zn = xfma(-xfma(-sig, Ph[i], D[i]), zc, -zp);
+          if (act) { zp = zc; zc = zn; }
+        }
       }
     }
     if constexpr (CNT) {
@@ -808,17 +837,20 @@ struct WaveSolver {
   // rebuilt here from g with the arithmetic of setup() (s_0 = 1, s_{i+1} = 1 / (e_{i+1} s_i)), the forward solution is
   // replayed at the shift of the last twisted() call.  D, Ph and zw are consumed row by row: x[] replaces them.
   // gh: the caller-supplied half-grid g of setup() (Src::kHasGh), or null = mean of the neighbouring g.
+  // RES: the forward solution is the one pass A of twisted() kept; nothing is replayed.
   template <class Src>
   __device__ __forceinline__ void assemble(const Src& src, const T* gh, int N, T h, T (&x)[M]) {
     int a = rows_start(lane, N - 2);
     asm volatile("" : "+v"(a));          // (keeps the compiler from carrying setup()'s LDS addresses across the iteration)
-    const T ih2 = T(1) / (h * h);
+    T ih2;
+    if constexpr (RES) ih2 = rr.ih2; else ih2 = T(1) / (h * h);
     T sc = T(1);
     T gcur = src.g(a + 1);
     T zc = u0_in, zp = zu_m1;
 #pragma unroll
     for (int i = 0; i < M; ++i) {
       const bool act = (i < M - 1) || has_last;
+      if constexpr (RES) zc = rr.zu[i];
       const T xu = sc * zc * fu, xw = sc * zw[i] * fw;
       x[i] = act ? ((i <= thr) ? xu : xw) : T(0);
       if (act) {
@@ -826,8 +858,10 @@ struct WaveSolver {
         if (gh) e_hi = gh[a + i + 1] * ih2;                    // (wave-uniform branch)
         else { const T gnext = src.g(a + i + 2); e_hi = T(0.5) * (gcur + gnext) * ih2; gcur = gnext; }
         sc = fast_rcp(e_hi * sc);
-        const T zn = xfma(-xfma(-sig_vec, Ph[i], D[i]), zc, -zp);
-        zp = zc; zc = zn;
+        if constexpr (!RES) {
+          const T zn = xfma(-xfma(-sig_vec, Ph[i], D[i]), zc, -zp);
+          zp = zc; zc = zn;
+        }
       }
       if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // at most 4 rows of LDS reads in flight (registers)
     }

@@ -138,8 +138,11 @@ int ibs_comm_destroy(ibs_ctx* ctx);
  * "sturm_form" (ibs_sturm_count_f64: 1 = prefix-product sweep, 2 = division form with lanes as systems, 3 = division form with one wave
  * per system; 0 = by grid length and batch size, see ibs_sturm_count_f64), "forget_rows" (an action: drop the remembered verdicts on device-resident mode rows, see ibs_fieldline_geometry_f64),
  * "pack_mode" (1|2: hand-off of the fused argmax), "refine_tangent" (refinement: the alpha-tangent of a point
- * staged in LDS, 1, or read from global memory by the sums, 0: two blocks per CU instead of one at N = 969; -1 = by batch size);
- * value 0 = automatic (refine_tangent, gcf_direct: -1); value NaN = back to what ibs_create() read from the environment
+ * staged in LDS, 1, or read from global memory by the sums, 0: two blocks per CU instead of one at N = 969; -1 = by batch size),
+ * "scan_resident" (the one-wave-per-system theta0 scan at 3 to 8 rows per lane, N = 131 .. 514: 1 = k_gamma_scan, which carries the rows
+ * of its set-up in registers up to the growth-rate stage, wherever it is built; 0 = k_gamma_scan_lean, which rebuilds them, everywhere;
+ * -1 = the default: the former while the launch holds at most two waves per SIMD, the latter above; same results bit for bit);
+ * value 0 = automatic (refine_tangent, gcf_direct, scan_resident: -1); value NaN = back to what ibs_create() read from the environment
  * (IBS_FORCE_P, IBS_SCAN_CHAIN, IBS_CHAIN_W1, IBS_CHAIN_W2, IBS_GEO_LPP are read once, there); name "all" with NaN
  * resets every option.  Results never depend on these switches beyond rounding; only the kernel variant does. */
 int ibs_set_option(ibs_ctx* ctx, const char* name, double value);
