@@ -17,6 +17,7 @@
 #include "ibs_wave.hpp"
 #include "ibs_lbfgsb2.hpp"
 #include "ibs_refine.hpp"
+#include "ibs_certify.hpp"
 #include <chrono>
 #include <thread>
 
@@ -1780,6 +1781,158 @@ int ibs_sturm_count_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const 
     HIPCHK(fn(a, ctx->stream));
     return 0;
   });
+}
+
+// ---- geometry-fed Sturm count and the count-pair certificate of geometry-fed growth rates (ibs_certify.hip).  The argument checks
+// come before any device use.
+static int geo_cert_check(const ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, int64_t ld, const double* const src[7],
+                          const double* dPdrho, const double* theta0, bool even_ok) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  for (int k = 0; k < 7; ++k) if (!src[k]) return fail(IBS_ERR_ARG, "null argument (the seven geometry arrays are required)");
+  if (!dPdrho || !theta0) return fail(IBS_ERR_ARG, "null argument (dPdrho and theta0 are required)");
+  if (n_lines < 0 || n_theta0 < 0 || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  if ((int64_t)n_lines * n_theta0 > (int64_t)std::numeric_limits<int32_t>::max())
+    return fail(IBS_ERR_ARG, "n_lines * n_theta0 = %lld exceeds 2^31 - 1", (long long)((int64_t)n_lines * n_theta0));
+  if (!even_ok) return check_grid(N, h, true);
+  if (N < 66 || N > ibs::kMaxLongN) return fail(IBS_ERR_UNSUPPORTED, "N=%d outside [66, %d]", N, ibs::kMaxLongN);
+  if (!(h > 0)) return fail(IBS_ERR_ARG, "h must be > 0");
+  return 0;
+}
+
+int ibs_geo_sturm_count_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                            const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                            const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                            const double* shift, int32_t* count, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, ld, src, dPdrho, theta0, true)) return r;   // (no Simpson stage: even N is fine)
+  if (!shift || !count) return fail(IBS_ERR_ARG, "null argument (shift and count are required)");
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
+  ibs::CertifyArgs a{};
+  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld;
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
+    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_theta0); a.shift = s.in(shift, n_sys);
+    a.count = s.out(count, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    HIPCHK(ibs::launch_geo_count(a, ctx->stream));
+    return 0;
+  });
+}
+
+// per_line: n_theta0 = 1 and theta0[n_lines] holds one value per line (the points form)
+static int geo_certify_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const src[7], int64_t ld,
+                            const double* dPdrho, const double* theta0, const double* lam, double tol_factor, int32_t* cert,
+                            int32_t mem, bool per_line) {
+  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, ld, src, dPdrho, theta0, false)) return r;
+  if (!lam || !cert) return fail(IBS_ERR_ARG, "null argument (lam and cert are required)");
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
+  ibs::CertifyArgs a{};
+  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld; a.t0_stride = per_line ? 1 : 0;
+  a.tol_factor = tol_factor > 0 ? tol_factor : 4.0;
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
+    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, per_line ? (size_t)n_lines : (size_t)n_theta0); a.lam = s.in(lam, n_sys);
+    a.cert = s.out(cert, n_sys);
+  };
+  const int rc = staged(ctx, mem, decl, [&]() -> int {
+    HIPCHK(ibs::launch_geo_certify(a, ctx->stream));
+    return 0;
+  });
+  if (rc != 0 || mem != IBS_MEM_HOST) return rc;
+  int n_open = 0;
+  for (size_t i = 0; i < n_sys; ++i) n_open += cert[i] != 0;
+  return n_open;
+}
+
+int ibs_gamma_scan_certify_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                               const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                               const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                               const double* lam, double tol_factor, int32_t* cert, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  return geo_certify_impl(ctx, n_lines, n_theta0, N, h, src, ld, dPdrho, theta0, lam, tol_factor, cert, mem, false);
+}
+
+int ibs_gamma_points_certify_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
+                                 const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
+                                 const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, const double* lam,
+                                 double tol_factor, int32_t* cert, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  return geo_certify_impl(ctx, n_pts, 1, N, h, src, ld, dPdrho, theta0, lam, tol_factor, cert, mem, true);
+}
+
+// Device pointers: list, solve and second certificate are queued back to back; nothing is read back in between (the list and its
+// counter stay on the device: ibs_certify.hip).  Host pointers: the in-out arrays go up with the inputs and come back as outputs.
+static int geo_reclose_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const src[7], int64_t ld,
+                            const double* dPdrho, const double* theta0, double tol_factor, int32_t* cert, double* lam, double* gam,
+                            double* X, double* dX, int32_t mem, bool per_line) {
+  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, ld, src, dPdrho, theta0, false)) return r;
+  if (!cert || !lam || !gam) return fail(IBS_ERR_ARG, "null argument (cert, lam and gam are required)");
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * (size_t)N;
+  ibs::RecloseArgs a{};
+  ibs::CertifyArgs& c = a.c;
+  c.n_lines = n_lines; c.n_theta0 = n_theta0; c.N = N; c.h = h; c.ld = (long)ld; c.t0_stride = per_line ? 1 : 0;
+  c.tol_factor = tol_factor > 0 ? tol_factor : 4.0;
+  const int *cert_up = nullptr;
+  const double *lam_up = nullptr, *gam_up = nullptr, *X_up = nullptr, *dX_up = nullptr;
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) c.geo7[k] = s.in(src[k], in_elems);
+    c.dPdrho = s.in(dPdrho, n_lines); c.theta0 = s.in(theta0, per_line ? (size_t)n_lines : (size_t)n_theta0);
+    if (s.host) {
+      cert_up = s.in((const int*)cert, n_sys); lam_up = s.in((const double*)lam, n_sys); gam_up = s.in((const double*)gam, n_sys);
+      X_up = s.in((const double*)X, out_elems); dX_up = s.in((const double*)dX, out_elems);
+    }
+    c.cert = s.out(cert, n_sys); a.lam = s.out(lam, n_sys); a.gam = s.out(gam, n_sys); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
+  };
+  const int rc = staged(ctx, mem, decl, [&]() -> int {
+    if (mem == IBS_MEM_HOST) {
+      HIPCHK(hipMemcpyAsync(c.cert, cert_up, n_sys * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(a.lam, lam_up, n_sys * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(a.gam, gam_up, n_sys * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      if (X) HIPCHK(hipMemcpyAsync(a.X, X_up, out_elems * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      if (dX) HIPCHK(hipMemcpyAsync(a.dX, dX_up, out_elems * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    // re-closing is rare: at most one wave per CU, and at most 256 MiB of row workspace
+    const size_t per_wave = ibs::reclose_ws_doubles(N) * sizeof(double);
+    long nw = (long)n_sys < ctx->n_cu ? (long)n_sys : ctx->n_cu;
+    const long fit = (long)((size_t(256) << 20) / per_wave);
+    if (nw > fit) nw = fit;
+    if (nw < 1) nw = 1;
+    if (int r = carve_long(ctx, [&](Carve& cv) {
+          a.list = cv.take<int>(1 + n_sys);
+          a.work = cv.take<double>((size_t)nw * ibs::reclose_ws_doubles(N));
+        })) return r;
+    a.n_waves = (int)nw;
+    HIPCHK(ibs::launch_geo_reclose(a, ctx->stream));
+    return 0;
+  });
+  if (rc != 0 || mem != IBS_MEM_HOST) return rc;
+  int n_open = 0;
+  for (size_t i = 0; i < n_sys; ++i) n_open += (cert[i] & (ibs::kCertNotMax | ibs::kCertNoEig)) != 0;
+  return n_open;
+}
+
+int ibs_gamma_scan_reclose_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                               const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                               const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                               double tol_factor, int32_t* cert, double* lam, double* gam, double* X, double* dX, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  return geo_reclose_impl(ctx, n_lines, n_theta0, N, h, src, ld, dPdrho, theta0, tol_factor, cert, lam, gam, X, dX, mem, false);
+}
+
+int ibs_gamma_points_reclose_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
+                                 const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
+                                 const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, double tol_factor,
+                                 int32_t* cert, double* lam, double* gam, double* X, double* dX, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  return geo_reclose_impl(ctx, n_pts, 1, N, h, src, ld, dPdrho, theta0, tol_factor, cert, lam, gam, X, dX, mem, true);
 }
 
 int ibs_surface_argmax_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per, const double* gam, int32_t* idx,

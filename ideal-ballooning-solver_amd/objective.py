@@ -68,6 +68,9 @@ class AdjointStep:
     lam_max's eigenpair by default; eigenpair="nearest" runs every equilibrium's scan in upstream's mode (the eigenpair nearest
     sigma = 1.0 / 1.3 |gam| + 0.05 / 0.42: BallooningScan's eigenpair="nearest"), with the same chunking, gather and objective.
     jac="exact" refines every surface on the exact gradient of gam (BallooningScan's jac="exact"); "reference" is the default.
+    certify=True (eigenpair="max" only, else ValueError) certifies and re-closes the coarse tables and the final solves of every
+    equilibrium (BallooningScan's certify=True; the refinement's own evaluations are not certified): the counts travel with the rows'
+    one copy into .last_certificate = dict(checked, reclosed, failed), summed over the ranks; failed > 0 raises IbsError.
 
     Upstream this is ball_submit.py:64-95 (one `srun ball_scan.py iter dof ngroups` per DOF-perturbed equilibrium, each
     running vmec_splines -> coarse scan -> argmax -> L-BFGS-B -> final solve, ball_scan.py:190-347) followed by
@@ -83,10 +86,14 @@ class AdjointStep:
 
     def __init__(self, ctx, theta, svals, device, nalpha=24, ntheta0=15, del_alpha=0.004, gamma_thresh=-2.0e-4, prefac=50.0,
                  rank=0, world=1, dist=None, n_threads=0, n_chunks=4, gather_device=None, chunk_growth=1.0, eigenpair="max",
-                 jac="reference"):
+                 jac="reference", certify=False):
         from .scan import check_eigenpair, check_jac
         self.eigenpair = check_eigenpair(eigenpair)
         self.jac = check_jac(jac)
+        self.certify = bool(certify)
+        if self.certify and self.eigenpair == "nearest":
+            raise ValueError("certify=True applies to eigenpair='max': eigenpair='nearest' runs in division form with its a-priori bound")
+        self.last_certificate = None
         self.ctx, self.device = ctx, device
         self.theta = np.asarray(theta, dtype=np.float64)
         self.svals = np.atleast_1d(np.asarray(svals, dtype=np.float64))       # ball_scan.py:197
@@ -110,7 +117,8 @@ class AdjointStep:
         if self._scan is None or len(self._scan.rho_arr) != n:
             self._scan = BallooningScan(self.ctx, None, self.theta, np.tile(self.svals, n_eq_local), nalpha=self.nalpha,
                                         ntheta0=self.ntheta0, del_alpha=self.del_alpha, tables=tables, device=self.device,
-                                        surf_index=np.arange(n), eigenpair=self.eigenpair, jac=self.jac)
+                                        surf_index=np.arange(n), eigenpair=self.eigenpair, jac=self.jac,
+                                        **(dict(certify=True) if self.certify else {}))
         self._scan.tables = tables
         return self._scan
 
@@ -124,6 +132,7 @@ class AdjointStep:
         from .scan import gather_rows_tensor
         n_eq, ns = len(wouts), len(self.svals)
         own = shard_dofs(n_eq, self.rank, self.world)
+        ncc = 3 if self.certify else 0     # trailing columns (checked, reclosed, failed): a rank's counts ride on its first row
         err = None
         try:                               # row of an equilibrium: n_surf x (theta0*, alpha*, gam) + the count of what went wrong
             if own:
@@ -149,11 +158,15 @@ class AdjointStep:
                 r, bad = scan.device_rows(refine, phases, chunks=[(cuts[k] * ns, cuts[k + 1] * ns) for k in range(nch)],
                                           fill=fill if pinned_upload else None)
                 rows = torch.cat([r.reshape(len(own), 3 * ns), bad.reshape(1, 1).expand(len(own), 1)], dim=1)
+                if ncc:
+                    cc = torch.zeros((len(own), 3), dtype=torch.float64, device=rows.device)
+                    cc[0] = scan._cert_dev
+                    rows = torch.cat([rows, cc], dim=1)
             else:
-                rows = torch.zeros((0, 3 * ns + 1), dtype=torch.float64, device=self.device)
+                rows = torch.zeros((0, 3 * ns + 1 + ncc), dtype=torch.float64, device=self.device)
         except Exception as e:             # (carried through the gather as NaN rows and raised on every rank afterwards)
             err = e
-            rows = torch.full((len(own), 3 * ns + 1), float("nan"), dtype=torch.float64, device=self.device)
+            rows = torch.full((len(own), 3 * ns + 1 + ncc), float("nan"), dtype=torch.float64, device=self.device)
         t0 = time.perf_counter()
         if self.gather_device is not None and self.world > 1:
             rows = rows.to(self.gather_device)
@@ -161,9 +174,17 @@ class AdjointStep:
         host = full.cpu().numpy()                                          # the one copy (and synchronisation)
         if err is not None:
             raise err
+        if ncc:
+            cc, host = np.nansum(host[:, -3:], axis=0), host[:, :-3]
+            self.last_certificate = dict(checked=int(cc[0]), reclosed=int(cc[1]), failed=int(cc[2]))
+            if self._scan is not None:
+                self._scan.last_certificate = dict(self.last_certificate)
         if not np.all(np.isfinite(host)) or np.any(host[:, -1] != 0):
             raise IbsError("the scan of %d equilibria was flagged or produced non-finite growth rates" %
                            int(np.sum(~np.isfinite(host).all(axis=1) | (host[:, -1] != 0))))
+        if ncc and self.last_certificate["failed"]:
+            raise IbsError("%d of %d eigenvalues could not be certified (cert bits 0-2 after the re-close)"
+                           % (self.last_certificate["failed"], self.last_certificate["checked"]))
         tab = host[:, :-1].reshape(n_eq, ns, 3)
         gam = tab[:, :, 2]
         f0 = ballooning_objective(f_other, gam, self.gamma_thresh, self.prefac)        # sims_runner_NCSX.py:254-257

@@ -106,11 +106,18 @@ class BallooningScan:
     The two agree wherever lam_max lies below the shifts; on strongly driven surfaces they differ.
     jac="reference" (the default): the refinement runs on upstream's Hellmann-Feynman gradient (utils.py:1676-1680, 1721-1725), which
     puts gam in place of lam and is 0.1-5 % off the gam it comes with.  jac="exact": it runs on the exact derivative of that gam,
-    batched on the device (ibs_obj_w_grad_exact_f64), for either eigenpair; the coarse scan and the final solve are the same."""
+    batched on the device (ibs_obj_w_grad_exact_f64), for either eigenpair; the coarse scan and the final solve are the same.
+    certify=True (eigenpair="max" only; "nearest" already runs in division form with its a-priori bound: ValueError): every eigenvalue
+    of the coarse scan's table is certified by a division-form Sturm count pair at lam +- 4 N eps ||A|| and re-closed in division form
+    where the pair refuses it (Context.certify_scan / reclose_scan), the per-surface maximum is then taken again from the table
+    (surface_argmax_pack), and the final solves are certified and re-closed the same way.  The solves inside the refinement's objective
+    are NOT certified: they only steer the optimizer, and the final solve at its end point is what is reported.  The counts of the
+    last run are in .last_certificate = dict(checked, reclosed, failed); failed > 0 raises IbsError.  certify=False (the default)
+    takes exactly the code path it took before the option existed."""
 
     def __init__(self, ctx, fieldlines, theta, rho_arr, nalpha=24, ntheta0=15, del_alpha=0.004,
                  rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None, eigenpair="max",
-                 jac="reference"):
+                 jac="reference", certify=False):
         """fieldlines: host geometry callable (see module docstring), or None together with
         tables=SurfaceTables (row F1): then the geometry is produced on `device` by the HIP geometry kernel and consumed
         there -- coarse scan, per-surface maximum, start points, refinement and final solve all stay in HBM and ONE small
@@ -122,6 +129,10 @@ class BallooningScan:
         self.nearest = eigenpair == "nearest"
         self.jac = check_jac(jac)
         self.exact = jac == "exact"
+        self.certify = bool(certify)
+        if self.certify and self.nearest:
+            raise ValueError("certify=True applies to eigenpair='max': eigenpair='nearest' runs in division form with its a-priori bound")
+        self.last_certificate = None
         self.ctx = ctx
         self.tables = tables
         self.device = device
@@ -171,15 +182,18 @@ class BallooningScan:
                 out = self.ctx.gamma_scan_nearest(self.h, *geo7, r["dPdrho"], t0, SIGMA_COARSE, want_info=True)
                 nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())      # (bit 5, a tie, is informational)
             else:
-                out = self.ctx.gamma_scan(self.h, *geo7, r["dPdrho"], t0, want_info=True)
+                out = self.ctx.gamma_scan(self.h, *geo7, r["dPdrho"], t0, want_info=True, **self._certify_kw())
                 # device-pointer calls are asynchronous and return no count of flagged systems: read the info words
                 nbad = int(((out["info"] >> 16) != 0).sum().item())
             if nbad:
                 raise IbsError("%d of %d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)"
                                % (nbad, out["info"].numel()))
+            if self.certify:
+                self._coarse_cert = out["cert"]
             return out["gam"].cpu().numpy().reshape(len(self.own), na, len(self.theta0_scan))
         geos = [np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own]
         if not geos:
+            self._coarse_cert = np.zeros(0, dtype=np.int32)
             return np.zeros((0, len(self.alpha_scan), len(self.theta0_scan)))
         geo = np.concatenate(geos, axis=0)                                 # (n_own*nalpha, 8, N)
         dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
@@ -187,10 +201,35 @@ class BallooningScan:
         if self.nearest:
             r = self.ctx.gamma_scan_nearest(self.h, *geo7, dP, self.theta0_scan, SIGMA_COARSE)
         else:
-            r = self.ctx.gamma_scan(self.h, *geo7, dP, self.theta0_scan)
+            r = self.ctx.gamma_scan(self.h, *geo7, dP, self.theta0_scan, **self._certify_kw())
         if r.get("nbad", 0):
             raise IbsError("%d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)" % r["nbad"])
+        if self.certify:
+            self._coarse_cert = r["cert"]
         return np.asarray(r["gam"]).reshape(len(self.own), len(self.alpha_scan), len(self.theta0_scan))
+
+    def _certify_kw(self):
+        """keyword of the solver calls: nothing at all without certify (the calls are then exactly what they were)"""
+        return dict(certify=True) if self.certify else {}
+
+    # -- unstable modes on the coarse grid of the surfaces this rank owns, one launch
+    def mode_count(self, shift=0.0):
+        """the number of eigenvalues above `shift` of every (alpha, theta0) of the coarse grid, int (n_own, nalpha, ntheta0)
+        (Context.geo_sturm_count: at shift 0 the number of unstable modes, bishop_ball_s-alpha.py:110-115 for real field lines)"""
+        na, nt = len(self.alpha_scan), len(self.theta0_scan)
+        if not self.own:
+            return np.zeros((0, na, nt), dtype=np.int32)
+        if self.tables is not None and self.device is not None:
+            import torch
+            r = self.ctx.fieldline_geometry(self.tables, np.repeat(self._own_surf(), na), np.tile(self.alpha_scan, len(self.own)),
+                                            self.theta, device=self.device)
+            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
+            cnt = self.ctx.geo_sturm_count(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, shift)
+            return cnt.cpu().numpy().reshape(len(self.own), na, nt)
+        geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
+        dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
+        cnt = self.ctx.geo_sturm_count(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan, shift)
+        return np.asarray(cnt).reshape(len(self.own), na, nt)
 
     # -- marginal stability on the coarse grid of the surfaces this rank owns, one launch
     def marginal(self, refine=False, maxiter=30, ftol=5.0e-11, gtol=2.0e-8):
@@ -351,7 +390,9 @@ class BallooningScan:
             if r.get("nbad", 0):
                 raise IbsError("the final solve at (alpha, theta0) = (%g, %g) was flagged (invalid data or iteration cap)" % (a, t))
             return t, a, float(np.asarray(r["gam"])[0]), res
-        r = self.ctx.gamma_scan(self.h, *[geo[k][None] for k in range(7)], np.array([dP]), np.array([t]))
+        r = self.ctx.gamma_scan(self.h, *[geo[k][None] for k in range(7)], np.array([dP]), np.array([t]), **self._certify_kw())
+        if self.certify:
+            self._count_certificate(r["cert"])
         return t, a, float(np.asarray(r["gam"])[0, 0]), res
 
     # -- F2: all owned surfaces refined in lockstep; every evaluation of every surface is ONE batched launch
@@ -444,7 +485,7 @@ class BallooningScan:
         if self.nearest:
             out = self.ctx.gamma_points_nearest(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, SIGMA_FINAL)
         else:
-            out = self.ctx.gamma_points(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0)
+            out = self.ctx.gamma_points(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, **self._certify_kw())
         return out["gam"].cpu().numpy()
 
     # -- the whole per-surface worker of ball_scan.py:248-339 for the owned surfaces, resident in HBM
@@ -497,6 +538,7 @@ class BallooningScan:
         gmax = torch.empty((n,), dtype=torch.float64, device=dev)
         sig0 = torch.empty((n,), dtype=torch.float64, device=dev) if self.nearest else None
         bad = res["n_bad"][0] * 0
+        ccount = torch.zeros(3, dtype=torch.float64, device=dev) if self.certify else None
         t_fill = 0.0
         for c0, c1 in chunks:
             if fill is not None:
@@ -513,6 +555,13 @@ class BallooningScan:
                 flagged = ((sc["info"] >> 16) & 3) != 0
             else:
                 sc = ctx.gamma_scan_argmax(self.h, [geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], c1 - c0)
+                if self.certify:
+                    # the table's eigenvalues are certified and re-closed in place, the per-surface maximum taken again from it
+                    g7 = [geo["geo"][k] for k in range(7)]
+                    cert = ctx.certify_scan(self.h, *g7, geo["dPdrho"], res["t0"], sc["lam"])
+                    ctx.reclose_scan(self.h, *g7, geo["dPdrho"], res["t0"], cert, sc["lam"], sc["gam"])
+                    sc["pack"] = ctx.surface_argmax_pack(sc["gam"].view(c1 - c0, -1))
+                    ccount = ccount + self._cert_counts(cert)
                 st = ctx.scan_starts(res["alpha"], res["t0"], sc["pack"], res["n_bad"])
                 flagged = (sc["info"] >> 16) != 0
             mark("s1")
@@ -547,7 +596,9 @@ class BallooningScan:
             mark("r1")
             xa, xt = xo[:, 0].contiguous(), xo[:, 1].contiguous()
             gf = ctx.fieldline_geometry(self.tables, res["pt_surf"], xa, res["th"], device=dev)
-            fin = ctx.gamma_points(self.h, *[gf["geo"][k] for k in range(7)], gf["dPdrho"], xt, want_info=True)
+            fin = ctx.gamma_points(self.h, *[gf["geo"][k] for k in range(7)], gf["dPdrho"], xt, want_info=True, **self._certify_kw())
+            if self.certify:
+                ccount = ccount + self._cert_counts(fin["cert"])
             rows = torch.stack([xt, xa, fin["gam"]], dim=1)
             bad = bad + ((fin["info"] >> 16) != 0).sum()
             self.last_refine = dict(n_evals=ne, rounds=rounds)
@@ -555,6 +606,7 @@ class BallooningScan:
             mark("r1")
             rows = torch.stack([start[:, 1], start[:, 0], gmax], dim=1)
         bad = bad + res["n_bad"][0]
+        self._cert_dev = ccount          # (checked, reclosed, failed) of this call, on the device: read with the rows' one copy
         mark("f1")
         if phases is not None:
             torch.cuda.synchronize()
@@ -566,9 +618,44 @@ class BallooningScan:
                 phases["coarse_chunks"] = len(chunks)
         return rows, bad.to(torch.float64)
 
+    @staticmethod
+    def _cert_counts(cert):
+        """(checked, reclosed, failed) of a device tensor of cert words, as a device tensor"""
+        import torch
+        return torch.stack([torch.full((), float(cert.numel()), dtype=torch.float64, device=cert.device),
+                            (cert == 8).sum().to(torch.float64), ((cert & 7) != 0).sum().to(torch.float64)])
+
+    def _count_certificate(self, cert):
+        """host-side paths: add a call's cert words to .last_certificate"""
+        c = np.asarray(cert.cpu().numpy() if hasattr(cert, "cpu") else cert)
+        if self.last_certificate is None:          # (refine() called on its own, outside local_rows)
+            self.last_certificate = dict(checked=0, reclosed=0, failed=0)
+        lc = self.last_certificate
+        lc["checked"] += int(c.size); lc["reclosed"] += int(np.sum(c == 8)); lc["failed"] += int(np.sum((c & 7) != 0))
+
+    def _raise_uncertified(self):
+        if self.last_certificate["failed"]:
+            raise IbsError("%d of %d eigenvalues could not be certified (cert bits 0-2 after the re-close)"
+                           % (self.last_certificate["failed"], self.last_certificate["checked"]))
+
     def local_rows(self, refine=True):
         """(theta0*, alpha*, gam) of the surfaces this rank owns, (n_own, 3): coarse scan -> argmax -> refinement -> final
         solve (ball_scan.py:248-339), no collective"""
+        if self.certify:
+            self.last_certificate = dict(checked=0, reclosed=0, failed=0)
+        if self.certify and self.tables is not None and self.device is not None:
+            import torch
+            rows, bad = self.device_rows(refine)
+            if not len(self.own):
+                return rows.cpu().numpy().reshape(0, 3)
+            host = torch.cat([rows.reshape(-1), bad.reshape(1), self._cert_dev]).cpu().numpy()    # the one copy (and synchronisation)
+            self.last_certificate = dict(checked=int(host[-3]), reclosed=int(host[-2]), failed=int(host[-1]))
+            host = host[:-3]
+            if host[-1] != 0 or not np.all(np.isfinite(host[:-1])):
+                raise IbsError("%d solves of this rank's scan were flagged or produced non-finite growth rates (status word != 0: "
+                               "invalid data or iteration cap)" % int(host[-1]))
+            self._raise_uncertified()
+            return host[:-1].reshape(len(self.own), 3)
         if self.tables is not None and self.device is not None:
             import torch
             rows, bad = self.device_rows(refine)
@@ -579,6 +666,8 @@ class BallooningScan:
             return host[:-1].reshape(len(self.own), 3)
         tabs = self.coarse()
         rows = []
+        if self.certify:
+            self._count_certificate(self._coarse_cert)
         for k, tab in zip(self.own, tabs):
             a0, t0, sigma0, ij = pick_start(tab, self.alpha_scan, self.theta0_scan)
             if refine:
@@ -586,6 +675,8 @@ class BallooningScan:
             else:
                 t, a, gam = t0, a0, float(np.max(tab))
             rows.append((t, a, gam))
+        if self.certify:
+            self._raise_uncertified()
         return np.array(rows, dtype=np.float64).reshape(len(self.own), 3)
 
     def run(self, refine=True):

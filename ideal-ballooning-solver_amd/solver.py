@@ -415,9 +415,21 @@ class Context:
 
     # ---- geometry x theta0 scan ---------------------------------------------------------------
     def gamma_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0,
-                   want_X=False, want_dtheta0=False, want_info=False, lam_guess=None, guess_width=None):
+                   want_X=False, want_dtheta0=False, want_info=False, lam_guess=None, guess_width=None, certify=False):
         """geometry arrays: (n_lines, N); dPdrho: (n_lines,); theta0: (n_theta0,).
-        Returns dict(gam, lam[, X, dX][, dgam_dtheta0]) shaped (n_lines, n_theta0[, N])."""
+        Returns dict(gam, lam[, X, dX][, dgam_dtheta0]) shaped (n_lines, n_theta0[, N]).
+        certify=True: every lam is then certified by a division-form Sturm count pair at lam +- 4 N eps ||A|| (certify_scan), a system
+        that fails is solved again in division form (reclose_scan: lam, gam, X, dX replaced; dgam_dtheta0 is not), and out["cert"]
+        (int32: 0 = certified, 8 = re-closed and certified, bits 0-2 = open, see certify_scan) and out["ncert_failed"] (host arrays
+        only) are added.  certify=False makes today's calls only."""
+        if certify:
+            out = self.gamma_scan(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_X=want_X,
+                                  want_dtheta0=want_dtheta0, want_info=want_info, lam_guess=lam_guess, guess_width=guess_width)
+            geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+            out["cert"] = self.certify_scan(h, *geo, dPdrho, theta0, out["lam"])
+            out["ncert_failed"] = self.reclose_scan(h, *geo, dPdrho, theta0, out["cert"], out["lam"], out["gam"], out.get("X"),
+                                                    out.get("dX"))
+            return out
         ar = _Args()
         n_lines, N = bmag.shape
         n_t0 = int(theta0.shape[0])
@@ -472,9 +484,18 @@ class Context:
         return dict(gam=gam, lam=lam, pack=pack, info=info)
 
     def gamma_points(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0,
-                     want_X=False, want_dtheta0=False, want_info=False):
+                     want_X=False, want_dtheta0=False, want_info=False, certify=False):
         """one (line, theta0) pair per point (ibs_gamma_points_f64: the final solve of ball_scan.py:322-339 for many
-        surfaces at once).  geometry arrays (n_pts, N); dPdrho, theta0 (n_pts,).  Returns dict(gam, lam[, X, dX][, ...])."""
+        surfaces at once).  geometry arrays (n_pts, N); dPdrho, theta0 (n_pts,).  Returns dict(gam, lam[, X, dX][, ...]).
+        certify=True: as in gamma_scan (certify_points, reclose_points; out["cert"], out["ncert_failed"])."""
+        if certify:
+            out = self.gamma_points(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_X=want_X,
+                                    want_dtheta0=want_dtheta0, want_info=want_info)
+            geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+            out["cert"] = self.certify_points(h, *geo, dPdrho, theta0, out["lam"])
+            out["ncert_failed"] = self.reclose_points(h, *geo, dPdrho, theta0, out["cert"], out["lam"], out["gam"], out.get("X"),
+                                                      out.get("dX"))
+            return out
         ar = _Args()
         n_pts, N = bmag.shape
         ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
@@ -797,6 +818,96 @@ class Context:
         check(self._lib.ibs_sturm_count_f64(self._h, n_sys, N, float(h), pg, pc, pf, N, ps, pcnt, ar.mem),
               "ibs_sturm_count_f64")
         return cnt
+
+    # ---- geometry-fed Sturm count, count-pair certificate and re-close (ibs_certify.hip) ------
+    def _geo_inputs(self, ar, geo7, dPdrho, theta0, points):
+        n_lines, N = geo7[0].shape
+        n_t0 = 1 if points else int(theta0.shape[0])
+        if points and int(theta0.shape[0]) != n_lines:
+            raise IbsError("theta0 must hold one value per point (%d), got %d" % (n_lines, int(theta0.shape[0])))
+        ptrs = [ar.inp(a) for a in geo7]
+        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
+        ref = geo7[0] if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        return n_lines, n_t0, N, ptrs, pdP, pt0, ref
+
+    def geo_sturm_count(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, shift=0.0):
+        """eigenvalues above shift for every (line, theta0) of a geometry-fed scan (ibs_geo_sturm_count_f64: the number of unstable
+        modes at shift 0, bishop_ball_s-alpha.py:110-115 for real field lines).  Arrays as in gamma_scan; shift a scalar or
+        (n_lines, n_theta0).  Returns int32 (n_lines, n_theta0).  Even N is accepted."""
+        ar = _Args()
+        n_lines, n_t0, N, ptrs, pdP, pt0, ref = self._geo_inputs(ar, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho,
+                                                                 theta0, False)
+        ps = self._sigma_rows(ar, shift, (n_lines, n_t0), ref)
+        cnt, pcnt = ar.out((n_lines, n_t0), ref, dtype=np.int32)
+        check(self._lib.ibs_geo_sturm_count_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, ps, pcnt, ar.mem),
+              "ibs_geo_sturm_count_f64")
+        return cnt
+
+    def _certify(self, points, h, geo7, dPdrho, theta0, lam, tol_factor):
+        ar = _Args()
+        n_lines, n_t0, N, ptrs, pdP, pt0, ref = self._geo_inputs(ar, geo7, dPdrho, theta0, points)
+        plam = ar.inp(lam)
+        cert, pcert = ar.out((n_lines,) if points else (n_lines, n_t0), ref, dtype=np.int32)
+        if points:
+            check(self._lib.ibs_gamma_points_certify_f64(self._h, n_lines, N, float(h), *ptrs, N, pdP, pt0, plam, float(tol_factor),
+                                                         pcert, ar.mem), "ibs_gamma_points_certify_f64")
+        else:
+            check(self._lib.ibs_gamma_scan_certify_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, plam,
+                                                       float(tol_factor), pcert, ar.mem), "ibs_gamma_scan_certify_f64")
+        return cert
+
+    def certify_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, lam, tol_factor=0.0):
+        """count-pair certificate of the eigenvalues lam (n_lines, n_theta0) of a geometry-fed scan (ibs_gamma_scan_certify_f64): with
+        tol = tol_factor N eps ||A|| (tol_factor <= 0: 4) the division-form Sturm counts must read 0 above lam + tol and >= 1 above
+        lam - tol.  Returns cert, int32 (n_lines, n_theta0): 0 = certified; bit 0 = lam is not the largest eigenvalue; bit 1 = no
+        eigenvalue at lam; bit 2 = not checked (lam not finite or invalid data)."""
+        return self._certify(False, h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0, lam, tol_factor)
+
+    def certify_points(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, lam, tol_factor=0.0):
+        """certify_scan for the points of gamma_points: theta0, lam (n_pts,) -> cert (n_pts,) (ibs_gamma_points_certify_f64)"""
+        return self._certify(True, h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0, lam, tol_factor)
+
+    def _reclose(self, points, h, geo7, dPdrho, theta0, cert, lam, gam, X, dX, tol_factor):
+        ar = _Args()
+        n_lines, n_t0, N, ptrs, pdP, pt0, ref = self._geo_inputs(ar, geo7, dPdrho, theta0, points)
+        # in-out arrays: updated in place, so they must already be what the library reads
+        io = []
+        for name, a, dt in (("cert", cert, np.int32), ("lam", lam, np.float64), ("gam", gam, np.float64), ("X", X, np.float64),
+                            ("dX", dX, np.float64)):
+            if a is None:
+                if name in ("X", "dX"):
+                    io.append(C.c_void_p(None))
+                    continue
+                raise IbsError("reclose: %s is required" % name)
+            if _is_torch(a):
+                ok = a.is_cuda and a.is_contiguous() and a.dtype == ar._torch_dtype()[np.dtype(dt)]
+            else:
+                ok = isinstance(a, np.ndarray) and a.flags.c_contiguous and a.flags.writeable and a.dtype == np.dtype(dt)
+            if not ok:
+                raise IbsError("reclose: %s is updated in place and must be a contiguous %s array" % (name, np.dtype(dt).name))
+            io.append(ar.inp(a, dtype=dt))
+        fn = self._lib.ibs_gamma_points_reclose_f64 if points else self._lib.ibs_gamma_scan_reclose_f64
+        dims = (n_lines,) if points else (n_lines, n_t0)
+        return check(fn(self._h, *dims, N, float(h), *ptrs, N, pdP, pt0, float(tol_factor), *io, ar.mem),
+                     "ibs_gamma_points_reclose_f64" if points else "ibs_gamma_scan_reclose_f64")
+
+    def reclose_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, cert, lam, gam, X=None, dX=None,
+                     tol_factor=0.0):
+        """re-close of the systems certify_scan refused (ibs_gamma_scan_reclose_f64), IN PLACE: every system whose cert has bit 0 or
+        1 is solved again in division form and certified again; on success its lam, gam (X, dX) are replaced and its cert becomes 8,
+        else it keeps its bits; all other entries stay untouched bit for bit.  cert int32, lam, gam (n_lines, n_theta0), X, dX
+        (n_lines, n_theta0, N) optional: contiguous arrays of exactly those types.  Device tensors: nothing is read back, returns 0;
+        numpy arrays: returns the number of systems that still carry bit 0 or 1."""
+        return self._reclose(False, h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0, cert, lam, gam, X, dX,
+                             tol_factor)
+
+    def reclose_points(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, cert, lam, gam, X=None, dX=None,
+                       tol_factor=0.0):
+        """reclose_scan for the points of gamma_points (ibs_gamma_points_reclose_f64): cert, lam, gam (n_pts,), X, dX (n_pts, N)"""
+        return self._reclose(True, h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0, cert, lam, gam, X, dX,
+                             tol_factor)
 
     def surface_argmax_pack(self, gam):
         """gam: device tensor (n_surf, n_per_surf) -> pack (n_surf, 2) = (max, first row-major index) on the device

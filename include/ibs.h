@@ -461,6 +461,56 @@ int ibs_last_launch(char* name, int32_t len, int64_t* blocks, int32_t* threads);
 int ibs_sturm_count_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c,
                         const double* f, int64_t ld, const double* shift, int32_t* count, int32_t mem);
 
+/* The same count for every (line, theta0) of a geometry-fed scan: the number of unstable modes per field line and theta0 at shift 0.
+ * Replaces: tests/shifted-circle-s-alpha/bishop_ball_s-alpha.py:110-115 (isunstable <=> count(0) > 0) for real field lines: arrays,
+ * dPdrho and theta0 as in ibs_gamma_scan_f64, shift and count [n_lines][n_theta0].  The rows are folded and assembled on the device
+ * (ball_scan.py:267-268, utils.py:1560-1562, 1574-1592) and counted in division form with lanes as systems (csrc/ibs_certify.hip):
+ * exact for a pencil a few ulp away, any N in [66, 65537].  Even N is accepted, as in ibs_sturm_count_f64. */
+int ibs_geo_sturm_count_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                            const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                            const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                            const double* shift, int32_t* count, int32_t mem);
+
+/* Certificate of the eigenvalues a geometry-fed scan returned.  Nothing upstream corresponds.  The scan, objective and refinement
+ * kernels close lam_max with the scaled-row shift iteration and state no a-priori bound; this call states one afterwards, independent
+ * of their arithmetic: with tol = tol_factor N eps ||A|| (tol_factor <= 0: 4, the bound of the raw entry points; ||A|| as under status
+ * bit 3 above) the division-form Sturm counts of the system's rows must read 0 above lam + tol and >= 1 above lam - tol.
+ *   arrays, dPdrho, theta0 as in ibs_gamma_scan_f64; lam [n_lines][n_theta0] (in); cert [n_lines][n_theta0] (out), per system:
+ *   bit 0 = an eigenvalue lies above lam + tol: lam is not the largest eigenvalue; bit 1 = no eigenvalue lies above lam - tol: there
+ *   is none at lam; bit 2 = not checked: lam is not finite or the data are invalid (non-finite, g <= 0 or f <= 0); 0 = certified:
+ *   |lam - lam_max| <= tol.  (Bit 3 is set by the re-close below.)
+ * N as for ibs_gamma_scan_f64 (odd, 66 .. 65537; else IBS_ERR_UNSUPPORTED).  Host pointers: returns the number of systems with a
+ * non-zero cert word.  One kernel, lanes as systems, two passes over each line (csrc/ibs_certify.hip). */
+int ibs_gamma_scan_certify_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                               const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                               const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                               const double* lam, double tol_factor, int32_t* cert, int32_t mem);
+/* The same certificate for the points of ibs_gamma_points_f64: one (line, theta0) pair per point, theta0, lam and cert [n_pts].
+ * Nothing upstream corresponds. */
+int ibs_gamma_points_certify_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
+                                 const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
+                                 const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, const double* lam,
+                                 double tol_factor, int32_t* cert, int32_t mem);
+/* Re-close of the systems a certificate refused.  Nothing upstream corresponds.  Every system whose cert word has bit 0 or 1 (and not
+ * bit 2) is solved again on its rows in division form -- bounds, 64-way multisection to 2 eps ||A||, twisted-factorisation
+ * eigenvector and the growth rate of utils.py:1601-1621, the pieces of the long-grid path of ibs_solve_gcf_f64 -- and certified again
+ * with tol_factor (as above).  On success lam, gam (and X, dX [n_lines][n_theta0][N] where given) of that system are replaced and its
+ * cert word becomes bit 3 alone (re-closed: informational); a system that still fails keeps its bits.  Every other entry of cert, lam,
+ * gam, X, dX is left untouched bit for bit.  cert, lam, gam are in-out and required; X, dX optional.
+ * Device pointers: list, solve and second certificate are queued on the context's stream; nothing is read back in between (the list of
+ * refused systems and its counter live on the device).  Host pointers: returns the number of systems that still carry bit 0 or 1.
+ * The composition for a C caller: ibs_gamma_scan_f64 (lam requested) -> ibs_gamma_scan_certify_f64 -> ibs_gamma_scan_reclose_f64. */
+int ibs_gamma_scan_reclose_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                               const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                               const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                               double tol_factor, int32_t* cert, double* lam, double* gam, double* X, double* dX, int32_t mem);
+/* The same re-close for the points of ibs_gamma_points_f64 (theta0, cert, lam, gam [n_pts]; X, dX [n_pts][N]).  Nothing upstream
+ * corresponds. */
+int ibs_gamma_points_reclose_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
+                                 const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
+                                 const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, double tol_factor,
+                                 int32_t* cert, double* lam, double* gam, double* X, double* dX, int32_t mem);
+
 /* Per-surface reduction of a scan: first (row-major) index of the maximum and its value, the rule of
  * ball_scan.py:279-295.  gam is [n_surf][n_per_surf]. */
 int ibs_surface_argmax_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per_surf, const double* gam,
