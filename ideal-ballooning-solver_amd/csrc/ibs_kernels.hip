@@ -223,9 +223,10 @@ __device__ __forceinline__ void finish(WaveSolver<T, M>& ws, const Src& src, int
     if (lane == 0 && dalpha_out) dalpha_out[sys] = (TO)jac;
   }
   if (lane == 0) {
-    if (lam_out) lam_out[sys] = (TO)lam;
-    // (write-through, agent scope: the fused per-surface reduction of k_gamma_scan reads it from another CU)
+    // (write-through, agent scope: the fused per-surface reduction of k_gamma_scan reads it from another CU; issued first, so
+    //  that its acknowledgement is the oldest one the drain before that reduction waits for)
     if (gam_out) __hip_atomic_store(gam_out + sys, (TO)gam, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lam_out) lam_out[sys] = (TO)lam;
     if (info_out) info_out[sys] = inf.iters | (inf.status << 16);
   }
 }
@@ -362,9 +363,10 @@ __device__ __forceinline__ void finish_chunk(WaveSolver<T, M, RES>& ws, Src& src
     }
   }
   if (lane == 0) {
-    if (lam_out) lam_out[sys] = (TO)lam;
-    // (write-through, agent scope: the fused per-surface reduction of k_gamma_scan reads it from another CU)
+    // (write-through, agent scope: the fused per-surface reduction of k_gamma_scan reads it from another CU; issued first, so
+    //  that its acknowledgement is the oldest one the drain before that reduction waits for)
     if (gam_out) __hip_atomic_store(gam_out + sys, (TO)gam, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lam_out) lam_out[sys] = (TO)lam;
     if (info_out) info_out[sys] = inf.iters | (inf.status << 16);
   }
   if (X_out || dX_out) {                   // wave-uniform
@@ -1191,63 +1193,68 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
   }
   IBS_PROBE_AT(4);
   // ---- fused per-surface argmax (ball_scan.py:279-295: first maximum of the surface's (alpha, theta0) table).
-  // Last-block-done: every block publishes its growth rates (plain stores -> each wave drains its stores -> block
-  // barrier -> ONE lane: agent-scope release, drain, relaxed agent-scope add on the surface's counter); the block whose
-  // add completes the surface acquires (agent scope), then reduces the table.  Placement-independent (no assumption
-  // on dispatch order or XCD co-location: cdna_hip_programming.md G16); the counter word is reset by the last arriver.
+  // Last-block-done, finished by ONE wave: every wave has stored its growth rate write-through (sc1, finish()) and drains its
+  // stores; one block barrier, behind which only wave 0 goes on; its lane 0 adds to the surface's arrival counter and the
+  // returned count reaches the wave through readfirstlane.  The wave whose add completes the surface reads the table back -- after
+  // its own add has returned, so no second barrier and no flag in LDS --, reduces it in registers (DPP), stores the pair and
+  // resets the counter.  pack_mode 1 (one block per CU: the regime MI355X_MICROARCH.md measured this hand-off in): relaxed add,
+  // sc1 loads, no fences.  pack_mode 2 (any placement): agent-scope release before the add, agent-scope acquire behind it.
+  // Placement-independent either way (no assumption on dispatch order or XCD co-location: cdna_hip_programming.md G16).
   if (pack) {                                   // (kernel argument: uniform over the grid)
-    int* flag = reinterpret_cast<int*>(smem + (size_t)(7 + wpb) * P);   // 128 B behind the staging rows (launcher adds them)
-    double* sv = reinterpret_cast<double*>(flag + 4);
-    int* si = flag + 4 + 2 * 8;
-    const int surf = line / lines_per_surf;
+    int surf = line / lines_per_surf;
+    asm volatile("" : "+s"(surf));              // (the division's scalar chain runs here, beside the drain, not behind the barrier)
     const int nblk_surf = lines_per_surf * nparts;
-    // pack_mode 1 (one block per CU: the regime MI355X_MICROARCH.md measured this hand-off in): the growth rates were
-    // stored write-through (sc1) by finish(), every storing wave drains its stores, and the add follows the block barrier;
-    // the last arriver reads them back with sc1 loads -- no fences.  pack_mode 2 (any placement): agent-scope release
-    // before the add, agent-scope acquire in the block that completes the surface.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
+    IBS_PROBE_AT(16);
+    if (wave != 0) return;
+    int old = 0;
+    if (lane == 0) {
       if (pack_mode != 1) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      const int old = __hip_atomic_fetch_add(&surf_counter[surf], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = (old == nblk_surf - 1) ? 1 : 0;
-      if (last) {
-        __hip_atomic_store(&surf_counter[surf], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (pack_mode != 1) {
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-      }
-      flag[0] = last;
+      old = __hip_atomic_fetch_add(&surf_counter[surf], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __syncthreads();
-    if (flag[0]) {                              // block-uniform
-      const int n_per = lines_per_surf * n_theta0;
-      const T* gsurf = gam_out + (size_t)surf * n_per;
-      T best = -T(1.7976931348623157e308);
-      int bi = 0x7fffffff;
-      for (int i = threadIdx.x; i < n_per; i += blockDim.x) {
+    old = __builtin_amdgcn_readfirstlane(old);
+    const long long t_add = IBS_PROBE_NOW();
+    if (old != nblk_surf - 1) { IBS_PROBE_PUT(17, t_add); return; }   // (wave-uniform) not the block that completes the surface
+    if (pack_mode != 1) {
+      // (all 64 lanes run it, though only lane 0 read the counter: the acquire is ONE wave instruction -- buffer_inv sc1 drops this
+      //  CU's L1 lines for the whole wave -- behind the wait for the atomic's return, and the loads below bypass that L1 anyway)
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const int n_per = lines_per_surf * n_theta0;
+    const T* gsurf = gam_out + (size_t)surf * n_per;
+    T best = -T(1.7976931348623157e308);
+    int bi = 0x7fffffff;
+    // lane l takes i = l, l + 64, ...: four loads in flight before the first compare (one group covers n_per <= 256; the
+    // headline's 64 values are one load per lane).  A slot past the end re-reads the last value and is not compared: a load
+    // under a condition of its own would be branched around and waited for one at a time.
+    for (int i0 = lane; i0 < n_per; i0 += 4 * kWave) {
+      T v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * kWave;
         // (agent-scope loads: served by L2, never by this CU's L1, which other CUs' stores do not refresh)
-        const T v = __hip_atomic_load(gsurf + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+        v[k] = __hip_atomic_load(gsurf + (i < n_per ? i : n_per - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
 #pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) {
-        const T v2 = __shfl_xor(best, d);
-        const int i2 = __shfl_xor(bi, d);
-        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-      }
-      if (lane == 0) { sv[wave] = best; si[wave] = bi; }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        for (int k = 1; k < wpb; ++k)
-          if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-        pack[2 * surf] = best; pack[2 * surf + 1] = (T)bi;
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * kWave;
+        const bool take = (i < n_per) & ((v[k] > best) | ((v[k] == best) & (i < bi)));     // (no short circuit: selects, not branches)
+        best = take ? v[k] : best; bi = take ? i : bi;
       }
     }
+    wave_argmax_first(best, bi);
+    if (lane == 0) {
+      pack[2 * surf] = best; pack[2 * surf + 1] = (T)bi;
+      // the counter's reset, for the next launch on this stream: behind the loads, whose waits would otherwise wait for it too
+      __hip_atomic_store(&surf_counter[surf], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    IBS_PROBE_PUT(17, t_add);
+    IBS_PROBE_AT(18);
   }
 }
 
@@ -1902,7 +1909,7 @@ static hipError_t launch_gcf_rows_wide(const GcfArgs<float>& a, hipStream_t st) 
 template <typename T>
 static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb;
-  const size_t lds = (size_t)(7 + wpb) * lds_pitch(a.N) * sizeof(T) + (a.pack ? 128 : 0);
+  const size_t lds = (size_t)(7 + wpb) * lds_pitch(a.N) * sizeof(T);
   dim3 grid((unsigned)(((a.n_theta0 + wpb - 1) / wpb) * a.n_lines));
   if constexpr (scan_resident_built(IBS_M)) {
     if (!a.resident) {

@@ -35,10 +35,21 @@ __device__ double ibs_trace_all[404];
 #endif
 // phase timestamps for tools/phase_probe.hip (debug builds only; the library is built without IBS_PROBE)
 #ifdef IBS_PROBE
-__device__ long long ibs_probe_buf[16 * 4096];
-#define IBS_PROBE_AT(k) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) ibs_probe_buf[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (k)] = wall_clock64(); } while (0)
+// a wave's row: 16 slots, all taken; slots 16 .. 19 (the hand-off at the end of the scan kernels, tools/scan_probe.py) lie in a
+// second table behind the first, so that every reader of the 16-slot rows finds them where they were.  Blocks 0 .. 1023 and
+// waves 0 .. 3 of a block stamp; a block's further waves do not (their rows would be the next block's, and past the end of the
+// table for the last block).
+__device__ long long ibs_probe_buf[(16 + 4) * 4096];
+#define IBS_PROBE_SLOT(k) ibs_probe_buf[(k) < 16 ? (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (k) \
+                                                 : 16 * 4096 + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + ((k) - 16)]
+// a stamp taken at one place (NOW) and written at a later one (PUT: where its store would sit in front of loads that are waited for)
+#define IBS_PROBE_NOW() wall_clock64()
+#define IBS_PROBE_PUT(k, t) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024 && threadIdx.x < 256) IBS_PROBE_SLOT(k) = (t); } while (0)
+#define IBS_PROBE_AT(k) IBS_PROBE_PUT(k, wall_clock64())
 #else
 #define IBS_PROBE_AT(k) do {} while (0)
+#define IBS_PROBE_NOW() 0LL
+#define IBS_PROBE_PUT(k, t) do { (void)(t); } while (0)
 #endif
 
 
@@ -201,6 +212,23 @@ __device__ __forceinline__ T wave_max(T v) {  // identity for missing lanes: the
   v = xmax(v, dpp_t<0x142, 0xA>(v, v));
   v = xmax(v, dpp_t<0x143, 0xC>(v, v));
   return readlane_t(v, 63);
+}
+// wave-wide FIRST maximum of (value, index) pairs: the larger value wins, on equal values the lower index (comparisons and selects
+// only: the winning pair keeps its bits; a NaN never wins).  The ladder of wave_max -- a lane without a source meets its own pair
+// again, which changes nothing.  The result is wave-uniform.
+template <typename T>
+__device__ __forceinline__ void wave_argmax_first(T& v, int& idx) {
+  auto meet = [&](T v2, int i2) {
+    const bool take = (v2 > v) | ((v2 == v) & (i2 < idx));      // (no short circuit: selects, not branches)
+    v = take ? v2 : v; idx = take ? i2 : idx;
+  };
+  meet(dpp_t<0x111, 0xF>(v, v), dpp_i<0x111, 0xF>(idx, idx));
+  meet(dpp_t<0x112, 0xF>(v, v), dpp_i<0x112, 0xF>(idx, idx));
+  meet(dpp_t<0x114, 0xF>(v, v), dpp_i<0x114, 0xF>(idx, idx));
+  meet(dpp_t<0x118, 0xF>(v, v), dpp_i<0x118, 0xF>(idx, idx));
+  meet(dpp_t<0x142, 0xA>(v, v), dpp_i<0x142, 0xA>(idx, idx));
+  meet(dpp_t<0x143, 0xC>(v, v), dpp_i<0x143, 0xC>(idx, idx));
+  v = readlane_t(v, 63); idx = readlane_i(idx, 63);
 }
 template <typename T>
 __device__ __forceinline__ T uniform(T v) {  // value is already identical in all lanes: make it scalar

@@ -2,7 +2,7 @@
 """Workload for the rocprofv3 --pmc passes: the legs of bench.py, each at the size the bench runs it, so that
 tools/pmc_summary.py (entries keyed by kernel AND launch size) yields exactly the entries bench.py looks up.
    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out -o fetch -- python3 tools/profile_run.py [leg ...]
-legs (default: all but `refine`): headline stress sturm scan_large ncsx c5 refine"""
+legs (default: all but `headline_plain` and `refine`): headline headline_plain stress sturm scan_large ncsx c5 refine"""
 import os
 import sys
 
@@ -23,6 +23,13 @@ if "headline" in legs:
         plan.scan_argmax()
     torch.cuda.synchronize()
     print("headline", ctx.last_launch(), flush=True)
+if "headline_plain" in legs:
+    # the same kernel without the per-surface maximum at its end (ScanPlan.scan(): no pack): headline minus this = the hand-off
+    plan = ibs_amd.ScanPlan(ctx, h, geo7, dP, th0, bench.N_SURF)
+    for _ in range(20):
+        plan.scan()
+    torch.cuda.synchronize()
+    print("headline_plain", ctx.last_launch(), flush=True)
 n = int(os.environ.get("IBS_STRESS_N", "262144"))
 if "stress" in legs:
     s = bench.stress(ctx, dev, n, "smooth", reps=2)
