@@ -6,6 +6,10 @@ Simpson quotient of utils.py:1601-1621), not the Hellmann-Feynman formulas of ut
     gam = iag.growth_rate(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0)
     gam.sum().backward()            # gradients in every geometry array, dPdrho and theta0
 
+    geo, dP = iag.fieldline_geometry(tables, line_surf, line_alpha, theta, tab_mn=tm, tab_nyq=tq, scal=sc)
+    gam = iag.growth_rate(h, *geo[:7], dP, theta0)
+    gam.sum().backward()            # gradients in the surface tables tm, tq, the scalars sc and line_alpha
+
 Float64 CUDA tensors throughout; uniform grids, odd N in [66, 65537] (the limits of the kernels).  A backward whose VJP flags a system
 (status bits 0-1 of ibs_solve_gcf_vjp_f64) issues a VjpStatusWarning.  `import ibs_amd` does not import
 this module, nor torch."""
@@ -101,3 +105,44 @@ def growth_rate(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho,
         sigma = sigma.expand(n_lines, n_t0).reshape(-1) if sigma.dim() == 0 else sigma.reshape(-1)
     gam, _ = solve_gcf(h, g.reshape(-1, N), c.reshape(-1, N), f.reshape(-1, N), eigenpair, sigma, ctx)
     return gam.reshape(n_lines, n_t0)
+
+
+class _FieldlineGeometry(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, tables, line_surf, line_alpha, theta, tab_mn, tab_nyq, scal, ictx):
+        r = ictx.fieldline_geometry(tables, line_surf, line_alpha, theta, device=line_alpha.device, tabs=(tab_mn, tab_nyq, scal))
+        fctx.save_for_backward(line_surf, line_alpha, theta, tab_mn, tab_nyq, scal)
+        fctx.tables, fctx.ictx = tables, ictx
+        return r["geo"], r["dPdrho"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, geo_bar, dP_bar):
+        line_surf, line_alpha, theta, tab_mn, tab_nyq, scal = fctx.saved_tensors
+        need = fctx.needs_input_grad
+        want = [k for k, i in (("alpha", 2), ("tab_mn", 4), ("tab_nyq", 5), ("scal", 6)) if need[i]]
+        if not want:
+            return (None,) * 8
+        r = fctx.ictx.fieldline_geometry_vjp(fctx.tables, line_surf, line_alpha, theta, geo_bar.contiguous(), dP_bar.contiguous(),
+                                             device=line_alpha.device, want=want, tabs=(tab_mn, tab_nyq, scal))
+        return None, None, r["alpha_bar"], None, r["tab_mn_bar"], r["tab_nyq_bar"], r["scal_bar"], None
+
+
+def fieldline_geometry(tables, line_surf, line_alpha, theta, tab_mn=None, tab_nyq=None, scal=None, ctx=None):
+    """(geo (8, n_lines, N), dPdrho (n_lines,)) of the field lines (surface line_surf[i], label line_alpha[i]) on the grid theta:
+    Context.fieldline_geometry on the device.  Differentiable in line_alpha and in tab_mn (n_surf, 6, mnmax), tab_nyq (n_surf, 7,
+    mnmax_nyq), scal (n_surf, 6) when these are given as device tensors; each defaults to the values of `tables` (its resident
+    device copy), then without gradient.  line_surf then indexes the tensors given; the mode tables are those of `tables`.  The
+    backward is the library's exact vector-Jacobian product (Context.fieldline_geometry_vjp, ibs_fieldline_geometry_vjp_f64): the
+    root solve of utils.py:391-416 by the implicit-function theorem.  theta gets no gradient.
+    line_surf: int tensor (n_lines,); line_alpha, theta: float64 device tensors."""
+    ictx = ctx or default_context(line_alpha.device.index or 0)
+    if tab_mn is None or tab_nyq is None or scal is None:
+        d = ictx._device_tables(tables, line_alpha.device)
+        given = [t for t in (tab_mn, tab_nyq, scal) if t is not None]
+        if given and any(int(t.shape[0]) != len(tables.s) for t in given):
+            raise ValueError("tab_mn, tab_nyq and scal must hold the same surfaces: give all three or the tables' own count")
+        tab_mn, tab_nyq, scal = (d[4] if tab_mn is None else tab_mn, d[5] if tab_nyq is None else tab_nyq,
+                                 d[6] if scal is None else scal)
+    line_surf = torch.as_tensor(line_surf, device=line_alpha.device).to(torch.int32)
+    return _FieldlineGeometry.apply(tables, line_surf, line_alpha, theta, tab_mn, tab_nyq, scal, ictx)

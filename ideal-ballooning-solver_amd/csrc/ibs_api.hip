@@ -1714,6 +1714,44 @@ int ibs_fieldline_geometry_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int3
   });
 }
 
+int ibs_fieldline_geometry_vjp_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_nyq, const double* xm,
+                                   const double* xn, const double* xm_nyq, const double* xn_nyq, const double* tab_mn,
+                                   const double* tab_nyq, const double* scal, int32_t n_lines, const int32_t* line_surf,
+                                   const double* line_alpha, int32_t N, const double* theta, int64_t ld,
+                                   const double* geo_bar, const double* dPdrho_bar, double* tab_mn_bar,
+                                   double* tab_nyq_bar, double* scal_bar, double* alpha_bar, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_lines < 0) return fail(IBS_ERR_ARG, "n_lines=%d < 0", n_lines);
+  if (ld < N) return fail(IBS_ERR_ARG, "ld=%lld < N=%d", (long long)ld, N);
+  if (n_surf <= 0 || mnmax <= 0 || mnmax_nyq <= 0 || N < 2 || !xm || !xn || !xm_nyq || !xn_nyq || !tab_mn || !tab_nyq ||
+      !scal || !line_surf || !line_alpha || !theta || !geo_bar)
+    return fail(IBS_ERR_ARG, "bad arguments");
+  if (!tab_mn_bar && !tab_nyq_bar && !scal_bar && !alpha_bar) return fail(IBS_ERR_ARG, "no output requested");
+  if (n_lines > 65535 || n_surf > 65535) return fail(IBS_ERR_UNSUPPORTED, "n_lines=%d, n_surf=%d: at most 65535 each", n_lines, n_surf);
+  const bool host = mem == IBS_MEM_HOST;
+  if (host)
+    for (int i = 0; i < n_lines; ++i)
+      if (line_surf[i] < 0 || line_surf[i] >= n_surf) return fail(IBS_ERR_ARG, "line_surf[%d]=%d out of range", i, line_surf[i]);
+  ON_DEVICE(ctx);
+  ibs::GeoVjpArgs a{};
+  a.n_surf = n_surf; a.mnmax = mnmax; a.mnmax_nyq = mnmax_nyq; a.n_lines = n_lines; a.N = N; a.ld = ld;
+  const size_t n_mn = (size_t)n_surf * 6 * mnmax, n_nyq = (size_t)n_surf * 7 * mnmax_nyq, n_geo = (size_t)8 * n_lines * ld;
+  auto decl = [&](Stage& s) {
+    a.xm = s.in(xm, mnmax); a.xn = s.in(xn, mnmax); a.xm_nyq = s.in(xm_nyq, mnmax_nyq); a.xn_nyq = s.in(xn_nyq, mnmax_nyq);
+    a.tab_mn = s.in(tab_mn, n_mn); a.tab_nyq = s.in(tab_nyq, n_nyq); a.scal = s.in(scal, (size_t)n_surf * 6);
+    a.line_surf = s.in(line_surf, n_lines); a.line_alpha = s.in(line_alpha, n_lines); a.theta = s.in(theta, N);
+    a.geo_bar = s.in(geo_bar, n_geo); a.dPdrho_bar = s.in(dPdrho_bar, n_lines);
+    a.tab_mn_bar = s.out(tab_mn_bar, n_mn); a.tab_nyq_bar = s.out(tab_nyq_bar, n_nyq);
+    a.scal_bar = s.out(scal_bar, (size_t)n_surf * 6); a.alpha_bar = s.out(alpha_bar, n_lines);
+    a.ws = s.scratch<double>((size_t)n_lines * ibs::kGeoVjpW * N);
+  };
+  // (without lines the points kernel has nothing to do; the reductions still write the zeros)
+  return staged(ctx, mem, decl, [&]() -> int {
+    HIPCHK(ibs::launch_geometry_vjp(a, ctx->stream));
+    return 0;
+  });
+}
+
 int ibs_hf_grad_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, const double* X, const double* dX, const double* f,
                     const double* g_p, const double* c_p, const double* f_p, int64_t ld, const double* gam,
                     double* jac, int32_t mem) {

@@ -207,6 +207,23 @@ size_t geo_image_doubles(const GeoArgs& a, int lpp);      // per surface
 bool geo_rows_usable(const GeoArgs& a, int lpp);
 hipError_t launch_geometry(GeoArgs& a, hipStream_t st, int n_cu);
 
+// vector-Jacobian product of the geometry (ibs_geometry_vjp.hip)
+constexpr int kGeoVjpW = 29;   // workspace doubles per grid point
+constexpr int kGeoVjpG = 8;    // modes per wave of the table reduction
+struct GeoVjpArgs {
+  int n_surf, mnmax, mnmax_nyq, n_lines, N;
+  const double *xm, *xn, *xm_nyq, *xn_nyq;
+  const double *tab_mn, *tab_nyq, *scal;       // as GeoArgs
+  const int* line_surf; const double* line_alpha; const double* theta;
+  long ld;
+  size_t plane;                // distance between the 8 planes of geo_bar in elements; 0 = n_lines * ld
+  const double* geo_bar;       // [8][n_lines][ld]
+  const double* dPdrho_bar;    // optional [n_lines]
+  double* ws;                  // [n_lines][kGeoVjpW][N]
+  double *tab_mn_bar, *tab_nyq_bar, *scal_bar, *alpha_bar;   // each optional
+};
+hipError_t launch_geometry_vjp(GeoVjpArgs& a, hipStream_t st);
+
 template <typename T> struct RefineEvalArgs;
 struct LaunchTable {
   hipError_t (*gcf_f64[kMaxM + 1])(const GcfArgs<double>&, hipStream_t);

@@ -204,5 +204,46 @@ class SurfaceTables:
                         ev(wout["bsubvmnc"], True)], axis=1)
         pres_h = np.asarray(wout["pres"], dtype=np.float64)[1:]        # utils.py:112
         iota_h = np.asarray(wout["iotas"], dtype=np.float64)[1:]       # utils.py:118
-        return cls(svals, wout["xm"], wout["xn"], wout["xm_nyq"], wout["xn_nyq"], mn, nyq, Wh @ iota_h,
-                   Whd @ iota_h, Whd @ pres_h, float(np.asarray(wout["phi"])[-1]), float(wout["Aminor_p"]))
+        out = cls(svals, wout["xm"], wout["xn"], wout["xm_nyq"], wout["xn_nyq"], mn, nyq, Wh @ iota_h,
+                  Whd @ iota_h, Whd @ pres_h, float(np.asarray(wout["phi"])[-1]), float(wout["Aminor_p"]))
+        out.n_equilibria, out.n_surf_per_equilibrium, out._ns, out._svals = 1, len(svals), ns, svals      # (pullback)
+        return out
+
+    def pullback(self, tab_mn_bar, tab_nyq_bar, scal_bar, per_surface=False):
+        """transpose of from_wout / frame().fill(): cotangents of the packed tables -> cotangents of the wout data they were
+        built from.  tab_mn_bar (n_surf, 6, mnmax), tab_nyq_bar (n_surf, 7, mnmax_nyq), scal_bar (n_surf, 6), host numpy, for the
+        n_surf = n_equilibria * n_surf_per_equilibrium surfaces of this set.  Returns one dict per equilibrium: the nine wout
+        arrays (modes, ns) by name, "iotas", "pres", "phi" (ns,; only phi[-1], the edge flux, is read) and "Aminor_p" -- so that
+        sum_k <dict[k], d wout[k]> is the change of <bar, tables> to first order (exactly: the radial step is linear, four
+        weight matrices).  Half-mesh arrays get a zero first column (utils.py:66, 83-118 read columns 1..ns-1); lmns and bmnc
+        collect both their value and their derivative column; the surface label s gets no cotangent (it is not wout data).
+        per_surface=True: no sum over the surfaces of an equilibrium -- every array gains a leading axis n_surf_per_equilibrium
+        (the cotangents of one surface's tables each: BallooningScan.sensitivity / AdjointStep.sensitivity)."""
+        if not hasattr(self, "_ns"):
+            raise ValueError("SurfaceTables.pullback: this table set was not built from wout tables (from_wout, from_wouts, frame)")
+        n_eq, n_s, ns = self.n_equilibria, self.n_surf_per_equilibrium, self._ns
+        Wf, Wfd, Wh, Whd = _radial_weights(ns, np.ascontiguousarray(self._svals, dtype=np.float64).tobytes())
+        mnb = np.asarray(tab_mn_bar, dtype=np.float64).reshape(n_eq, n_s, 6, -1)
+        nqb = np.asarray(tab_nyq_bar, dtype=np.float64).reshape(n_eq, n_s, 7, -1)
+        scb = np.asarray(scal_bar, dtype=np.float64).reshape(n_eq, n_s, 6)
+        full = lambda v, d=None: np.einsum("sm,sn->smn", v, Wf) + (0.0 if d is None else np.einsum("sm,sn->smn", d, Wfd))
+
+        def half(v, d=None):                   # (s, modes) -> (s, modes, ns) with the zero first column
+            out = np.zeros(v.shape + (ns,))
+            out[:, :, 1:] = np.einsum("sm,sn->smn", v, Wh)
+            if d is not None:
+                out[:, :, 1:] += np.einsum("sm,sn->smn", d, Whd)
+            return out
+        res = []
+        for q in range(n_eq):
+            a, b, c = mnb[q], nqb[q], scb[q]
+            d = dict(rmnc=full(a[:, 0], a[:, 3]), zmns=full(a[:, 1], a[:, 4]), lmns=half(a[:, 2], a[:, 5]),
+                     gmnc=half(b[:, 0]), bmnc=half(b[:, 1], b[:, 2]), bsupvmnc=half(b[:, 3]), bsubsmns=full(b[:, 4]),
+                     bsubumnc=half(b[:, 5]), bsubvmnc=half(b[:, 6]))
+            io = np.zeros((n_s, ns)); pr = np.zeros((n_s, ns)); ph = np.zeros((n_s, ns))
+            io[:, 1:] = c[:, 1, None] * Wh + c[:, 2, None] * Whd              # utils.py:118
+            pr[:, 1:] = c[:, 3, None] * Whd                                    # utils.py:112
+            ph[:, -1] = c[:, 4]
+            d.update(iotas=io, pres=pr, phi=ph, Aminor_p=c[:, 5].copy())
+            res.append(d if per_surface else {k: v.sum(axis=0) for k, v in d.items()})
+        return res

@@ -606,6 +606,7 @@ class BallooningScan:
             mark("r1")
             rows = torch.stack([start[:, 1], start[:, 0], gmax], dim=1)
         bad = bad + res["n_bad"][0]
+        self._last_rows = rows           # (sensitivity()'s default points)
         self._cert_dev = ccount          # (checked, reclosed, failed) of this call, on the device: read with the rows' one copy
         mark("f1")
         if phases is not None:
@@ -617,6 +618,41 @@ class BallooningScan:
                 phases["host_tables_ms"] = t_fill * 1e3
                 phases["coarse_chunks"] = len(chunks)
         return rows, bad.to(torch.float64)
+
+    def sensitivity(self, points=None, eigenpair=None):
+        """exact derivatives of every owned surface's gam at ONE point (alpha, theta0) of that surface, with respect to the point and
+        to the surface's own tables.  tables= + device= scans only.  points (n_own, 2) = (alpha, theta0); None: the rows of the last
+        local_rows() / device_rows() / run().  eigenpair None: this scan's mode ("nearest": the eigenpair nearest SIGMA_FINAL, as in
+        the final solve).  One geometry launch, one solve (autograd.growth_rate), one rows-VJP (ibs_solve_gcf_vjp_f64) and one
+        geometry-VJP launch (ibs_fieldline_geometry_vjp_f64) in which every surface's point works on its own copy of the surface's
+        tables, so that the cotangents stay per point.  Returns device tensors dict(gam, dgam_dalpha, dgam_dtheta0: (n_own,);
+        tab_mn_bar (n_own, 6, mnmax), tab_nyq_bar (n_own, 7, mnmax_nyq), scal_bar (n_own, 6))."""
+        import torch
+        from . import autograd as iag
+        if self.tables is None or self.device is None:
+            raise IbsError("sensitivity() needs a scan built with tables= and device=")
+        mode = self.eigenpair if eigenpair is None else check_eigenpair(eigenpair)
+        dev, own = self.device, self._own_surf()
+        n = len(own)
+        if points is None:
+            rows = getattr(self, "_last_rows", None)
+            if rows is None or rows.shape[0] != n:
+                raise IbsError("sensitivity(): no points given and no rows of an earlier run on this object")
+            al, t0 = rows[:, 1].detach().clone(), rows[:, 0].detach().clone()
+        else:
+            pts = np.asarray(points, dtype=np.float64).reshape(n, 2)
+            al, t0 = (torch.from_numpy(np.ascontiguousarray(pts[:, k])).to(dev) for k in (0, 1))
+        d = self.ctx._device_tables(self.tables, dev)
+        idx = torch.from_numpy(own.astype(np.int64)).to(dev)
+        tm, tq, sc = (d[k][idx].clone().requires_grad_(True) for k in (4, 5, 6))
+        al.requires_grad_(True); t0.requires_grad_(True)
+        geo, dP = iag.fieldline_geometry(self.tables, torch.arange(n, dtype=torch.int32, device=dev), al, self._resident_inputs()["th"],
+                                         tab_mn=tm, tab_nyq=tq, scal=sc, ctx=self.ctx)
+        gam = iag.growth_rate(self.h, *geo[:7], dP, t0[:, None], eigenpair=mode, sigma=SIGMA_FINAL if mode == "nearest" else None,
+                              ctx=self.ctx)
+        gam.sum().backward()
+        return dict(gam=gam.detach().reshape(n), dgam_dalpha=al.grad, dgam_dtheta0=t0.grad, tab_mn_bar=tm.grad, tab_nyq_bar=tq.grad,
+                    scal_bar=sc.grad)
 
     @staticmethod
     def _cert_counts(cert):

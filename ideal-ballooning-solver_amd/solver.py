@@ -630,10 +630,12 @@ class Context:
             out.update(info=info)
         return out
 
-    def fieldline_geometry(self, tables, line_surf, line_alpha, theta, device=None, use_rows=True):
+    def fieldline_geometry(self, tables, line_surf, line_alpha, theta, device=None, use_rows=True, tabs=None):
         """geometry of the field lines (tables.s[line_surf[i]], line_alpha[i]) on the grid theta (row F1).
         Returns dict(geo=(8, n_lines, N), dPdrho=(n_lines,)); geo[0..6] + dPdrho feed gamma_scan directly.
-        device=None: numpy in / numpy out (staged);  device=torch.device(...): results stay in HBM."""
+        device=None: numpy in / numpy out (staged);  device=torch.device(...): results stay in HBM.
+        tabs (device calls): (tab_mn, tab_nyq, scal) device tensors to use in place of the tables' resident copies, for any
+        number of surfaces (ibs_amd.autograd.fieldline_geometry); the mode tables stay those of `tables`."""
         n_lines = len(line_surf)
         N = len(theta)
         resident = device is not None and all(_is_torch(a) for a in (line_surf, line_alpha, theta))
@@ -657,7 +659,7 @@ class Context:
         # tables are uploaded once and stay resident; the device copies live ON the tables object (a cache keyed by
         # id(tables) would hand a later object that re-uses the id the previous object's tables)
         allc = self._device_tables(tables, device)
-        dev = allc[:7]
+        dev = allc[:7] if tabs is None else allc[:4] + [t.contiguous() for t in tabs]
         d_rows = allc[7:]
         if resident:      # index / angle / grid tensors already in HBM (int32, float64, float64): no upload, no host check
             #               (the geometry kernel clamps the surface index itself)
@@ -669,13 +671,67 @@ class Context:
         self._stream_from_torch(geo)
         p = lambda t: C.c_void_p(t.data_ptr())
         nr = (len(tables.rows_mn), len(tables.rows_nyq)) if use_rows else (0, 0)
-        check(self._lib.ibs_fieldline_geometry_f64(self._h, len(tables.s), len(tables.xm), len(tables.xm_nyq),
+        check(self._lib.ibs_fieldline_geometry_f64(self._h, len(tables.s) if tabs is None else int(tabs[2].shape[0]), len(tables.xm), len(tables.xm_nyq),
                                                    *[p(t) for t in dev], n_lines, p(d_ls), p(d_la), N, p(d_th), N, p(geo),
                                                    p(dP), nr[0], p(d_rows[0]), nr[1], p(d_rows[1]), float(tables.dn_mn), float(tables.dn_nyq),
                                                    MEM_DEVICE),
               "ibs_fieldline_geometry_f64")
         self._keep = (d_ls, d_la, d_th)
         return dict(geo=geo, dPdrho=dP)
+
+    def fieldline_geometry_vjp(self, tables, line_surf, line_alpha, theta, geo_bar, dPdrho_bar=None, device=None,
+                               want=("tab_mn", "tab_nyq", "scal", "alpha"), tabs=None):
+        """vector-Jacobian product of fieldline_geometry (ibs_fieldline_geometry_vjp_f64): cotangents geo_bar (8, n_lines, N)
+        and, optionally, dPdrho_bar (n_lines,) -> dict(tab_mn_bar (n_surf, 6, mnmax), tab_nyq_bar (n_surf, 7, mnmax_nyq),
+        scal_bar (n_surf, 6), alpha_bar (n_lines,)); entries not named in `want` are None.  Exact: the root solve of
+        utils.py:391-416 by the implicit-function theorem.  Sums run in a fixed order: repeatable bit for bit.
+        device=None: numpy in / numpy out (staged);  device=torch.device(...): device tensors in, device tensors out.
+        tabs: as in fieldline_geometry."""
+        want = set(want)
+        if not want or not want <= {"tab_mn", "tab_nyq", "scal", "alpha"}:
+            raise IbsError("want must name at least one of tab_mn, tab_nyq, scal, alpha")
+        n_lines, N = len(line_surf), len(theta)
+        n_surf, mnmax, mnq = len(tables.s) if tabs is None else int(tabs[2].shape[0]), len(tables.xm), len(tables.xm_nyq)
+        if tuple(geo_bar.shape) != (8, n_lines, N):
+            raise IbsError("geo_bar must be (8, n_lines, N)")
+        shapes = dict(tab_mn=(n_surf, 6, mnmax), tab_nyq=(n_surf, 7, mnq), scal=(n_surf, 6), alpha=(n_lines,))
+        names = ("tab_mn", "tab_nyq", "scal", "alpha")
+        head = (self._h, n_surf, mnmax, mnq)
+        if device is None:
+            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
+            la = np.ascontiguousarray(line_alpha, dtype=np.float64)
+            th = np.ascontiguousarray(theta, dtype=np.float64)
+            gb = np.ascontiguousarray(geo_bar, dtype=np.float64)
+            db = None if dPdrho_bar is None else np.ascontiguousarray(dPdrho_bar, dtype=np.float64)
+            host = [tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal]
+            outs = {k: (np.empty(shapes[k]) if k in want else None) for k in names}
+            p = lambda a: C.c_void_p(None if a is None else a.ctypes.data)
+            check(self._lib.ibs_fieldline_geometry_vjp_f64(*head, *[p(a) for a in host], n_lines, p(ls), p(la), N, p(th), N,
+                                                           p(gb), p(db), *[p(outs[k]) for k in names], MEM_HOST),
+                  "ibs_fieldline_geometry_vjp_f64")
+            return {k + "_bar": outs[k] for k in names}
+        import torch
+        allc = self._device_tables(tables, device)
+        dev = allc[:7] if tabs is None else allc[:4] + [t.contiguous() for t in tabs]
+        if all(_is_torch(a) for a in (line_surf, line_alpha, theta)):
+            d_ls, d_la, d_th = line_surf.to(torch.int32).contiguous(), line_alpha.to(torch.float64).contiguous(), theta.to(torch.float64).contiguous()
+        else:
+            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
+            if ls.size and (ls.min() < 0 or ls.max() >= n_surf):
+                raise IbsError("line_surf out of range")
+            d_ls = torch.from_numpy(ls).to(device)
+            d_la = torch.from_numpy(np.ascontiguousarray(line_alpha, dtype=np.float64)).to(device)
+            d_th = torch.from_numpy(np.ascontiguousarray(theta, dtype=np.float64)).to(device)
+        gb = geo_bar.to(torch.float64).contiguous()
+        db = None if dPdrho_bar is None else dPdrho_bar.to(torch.float64).contiguous()
+        outs = {k: (torch.empty(shapes[k], dtype=torch.float64, device=device) if k in want else None) for k in names}
+        self._stream_from_torch(gb)
+        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        check(self._lib.ibs_fieldline_geometry_vjp_f64(*head, *[p(t) for t in dev], n_lines, p(d_ls), p(d_la), N, p(d_th), N,
+                                                       p(gb), p(db), *[p(outs[k]) for k in names], MEM_DEVICE),
+              "ibs_fieldline_geometry_vjp_f64")
+        self._keep = (d_ls, d_la, d_th, gb, db, dev)
+        return {k + "_bar": outs[k] for k in names}
 
     def _device_tables(self, tables, device):
         """the surface/mode/row tables of `tables` resident on `device` (uploaded once, cached on the object)"""

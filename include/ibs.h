@@ -394,6 +394,31 @@ int ibs_fieldline_geometry_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int3
                                double* dPdrho, int32_t nrows_mn, const int32_t* rows_mn, int32_t nrows_nyq,
                                const int32_t* rows_nyq, double dn_mn, double dn_nyq, int32_t mem);
 
+/* Vector-Jacobian product of ibs_fieldline_geometry_f64: from cotangents of the eight arrays (and of dPdrho) to cotangents
+ * of the surface tables, the surface scalars and the line labels.
+ * Replaces: nothing.  Nothing upstream corresponds: the reference obtains sensitivities to the equilibrium by re-scanning
+ * perturbed equilibria (sims_runner_NCSX.py:151-276) and its alpha-derivative by a central difference of the rows
+ * (utils.py:1641-1646).  The arithmetic differentiated is utils.py:359-720 as the forward call restates it; the
+ * theta_pest -> theta_vmec root solve (utils.py:391-416) is differentiated by the implicit-function theorem at the
+ * converged root theta_vmec + Lambda(theta_vmec, phi) = theta_pest, not through the secant iterations; sgn(Psi') is a
+ * constant and d|Psi'| = sgn(Psi') dPsi' (utils.py:474, 654-665).
+ *   every forward input as for ibs_fieldline_geometry_f64 (mode rows are not needed: any mode ordering);
+ *   geo_bar [8][n_lines][ld]: cotangents of the eight arrays, entries N..ld-1 of a row are never read;
+ *   dPdrho_bar [n_lines] (optional): cotangent of dPdrho, folded into planes 0, 2 and 7 (ball_scan.py:262);
+ *   tab_mn_bar [n_surf][6][mnmax], tab_nyq_bar [n_surf][7][mnmax_nyq], scal_bar [n_surf][6], alpha_bar [n_lines]: each
+ *   optional, at least one required.  A surface no line refers to gets zeros.  theta gets no cotangent (the grid is fixed).
+ * A line whose forward evaluation is not finite gives NaN in alpha_bar[line] and in the rows of its surface.
+ * No floating-point atomics: every sum runs in a fixed order (lines of a surface by index), so the same call gives the same
+ * bits on every run, with host or device pointers, whichever outputs are requested.
+ * n_lines and n_surf <= 65535.  IBS_MEM_HOST: synchronous; IBS_MEM_DEVICE: asynchronous on the context's stream, nothing is
+ * read back (device-resident line_surf is clamped to [0, n_surf), like the forward call's). */
+int ibs_fieldline_geometry_vjp_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_nyq, const double* xm,
+                                   const double* xn, const double* xm_nyq, const double* xn_nyq, const double* tab_mn,
+                                   const double* tab_nyq, const double* scal, int32_t n_lines, const int32_t* line_surf,
+                                   const double* line_alpha, int32_t N, const double* theta, int64_t ld,
+                                   const double* geo_bar, const double* dPdrho_bar, double* tab_mn_bar,
+                                   double* tab_nyq_bar, double* scal_bar, double* alpha_bar, int32_t mem);
+
 /* Host part of the geometry producer: the per-surface Fourier coefficient vectors of n_eq equilibria at n_s surfaces.
  * Replaces: vmec_splines (utils.py:58-119: one InterpolatedUnivariateSpline per mode and array) + their evaluation at the
  * surface (utils.py:311-357) for all equilibria of an optimizer step (sims_runner_NCSX.py:151-276) at once.  Cubic
