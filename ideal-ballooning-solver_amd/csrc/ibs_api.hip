@@ -334,6 +334,15 @@ class Stage {
     if (hs_ && dst) hs_->down(dst, d, n * sizeof(T));
     return d;
   }
+  // output of `rows` rows of n elements that lie ld >= n apart in dst.  Host pointers: the device buffer holds the rows packed (pitch
+  // n: the launch must use rows_ld(n, ld)) and each comes back on its own, so the caller's entries n .. ld-1 of a row are never written
+  template <typename T> T* out_rows(T* dst, size_t rows, size_t n, size_t ld) {
+    if (!host || !dst || ld == n) return out(dst, rows * ld);
+    T* d = out_.take<T>(rows * n);
+    if (hs_) for (size_t r = 0; r < rows; ++r) hs_->down(dst + r * ld, d + r * n, n * sizeof(T));
+    return d;
+  }
+  size_t rows_ld(size_t n, size_t ld) const { return host ? n : ld; }
   // workspace of the device code alone, in either mode
   template <typename T> T* scratch(size_t n, bool when = true) { return when ? scr_.take<T>(n) : nullptr; }
   // status words: host pointers always get a device buffer, whose count of bad words is what staged() returns
@@ -1698,13 +1707,15 @@ int ibs_fieldline_geometry_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int3
   // a device-pointer call whose lines touch few of the surfaces (a large table set worked through piece by piece) builds their
   // images only
   const bool mark = !host && img_bytes && n_surf >= 32 && (long)n_lines < 8L * n_surf;
-  const size_t n_mn = (size_t)n_surf * 6 * mnmax, n_nyq = (size_t)n_surf * 7 * mnmax_nyq, n_geo = (size_t)8 * n_lines * ld;
+  const size_t n_mn = (size_t)n_surf * 6 * mnmax, n_nyq = (size_t)n_surf * 7 * mnmax_nyq;
   auto decl = [&](Stage& s) {
     a.xm = s.in(xm, mnmax); a.xn = s.in(xn, mnmax); a.xm_nyq = s.in(xm_nyq, mnmax_nyq); a.xn_nyq = s.in(xn_nyq, mnmax_nyq);
     a.tab_mn = s.in(tab_mn, n_mn); a.tab_nyq = s.in(tab_nyq, n_nyq); a.scal = s.in(scal, (size_t)n_surf * 6);
     a.line_surf = s.in(line_surf, n_lines); a.line_alpha = s.in(line_alpha, n_lines); a.theta = s.in(theta, N);
     if (rows) { a.rows_mn = s.in(rows_mn, (size_t)2 * nrows_mn); a.rows_nyq = s.in(rows_nyq, (size_t)2 * nrows_nyq); }
-    a.geo = s.out(geo, n_geo); a.dPdrho = s.out(dPdrho, n_lines, true);
+    // (host pointers with ld > N: the padding of the caller's rows stays as it was, as it does with device pointers)
+    a.ld = (long)s.rows_ld(N, ld);
+    a.geo = s.out_rows(geo, (size_t)8 * n_lines, N, ld); a.dPdrho = s.out(dPdrho, n_lines, true);
     if (img_bytes) a.img[ibs::geo_lpp_index(a.form.lpp)] = s.scratch<double>(img_bytes / sizeof(double));
     a.surf_used = s.scratch<int>(n_surf, mark);
   };

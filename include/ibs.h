@@ -375,7 +375,8 @@ int ibs_hf_grad_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, const double* X, con
  *   tab_nyq [n_surf][7][mnmax_nyq]  gmnc bmnc d_bmnc_d_s bsupvmnc bsubsmns bsubumnc bsubvmnc
  *   scal    [n_surf][6]             s iota d_iota_d_s d_pressure_d_s phiedge Aminor_p
  * and the mode numbers xm, xn [mnmax], xm_nyq, xn_nyq [mnmax_nyq] (xn includes nfp).
- *   geo [8][n_lines][ld]: bmag gradpar_theta_pest cvdrift cvdrift0 gds2 gds21 gds22 gbdrift
+ *   geo [8][n_lines][ld]: bmag gradpar_theta_pest cvdrift cvdrift0 gds2 gds21 gds22 gbdrift; entries N..ld-1 of a row are
+ *   never written, with host pointers as with device pointers
  *   dPdrho[n_lines] (optional): -0.5 mean((cvdrift - gbdrift) bmag^2), ball_scan.py:262.
  *   rows_mn [nrows_mn][2], rows_nyq [nrows_nyq][2] (optional, nrows = 0 to omit): {first mode, count} of each
  *   run of modes with equal m and n advancing by the common step dn_mn / dn_nyq (= nfp in VMEC's own

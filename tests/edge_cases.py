@@ -1,5 +1,6 @@
 """Grid lengths on lane, chunk and path edges, and two families of raw systems whose mode sits where the caller puts it: the inputs of
-tests/test_gpu_edge_lengths.py, pinned with the oracle alone in tests/test_edge_cases_cpu.py.  Test infrastructure only.
+tests/test_gpu_edge_lengths.py, pinned with the oracle alone in tests/test_edge_cases_cpu.py; below them the item, tail, block and
+ballot edges of the field-line geometry kernels, the inputs of tests/test_gpu_geometry_edges.py.  Test infrastructure only.
 
 Rows per lane of the register kernels: M = ceil((N - 2) / 64), N <= 2050.  Beyond that the long path (csrc/ibs_long.hpp) passes the
 n = N - 2 rows through LDS in chunks of 768 (counts) and 384 (pivots, eigenvector, adjoint solve, nearest sigma): the last chunk
@@ -152,3 +153,116 @@ def top_pairs(theta, g, c, f, k=2):
     V = np.zeros((n + 2, k))
     V[1:-1] = v / np.sqrt(fd)[:, None]
     return w, V
+
+
+# ---- field-line geometry (csrc/ibs_geometry.hip, csrc/ibs_geometry_vjp.hip): the inputs of tests/test_gpu_geometry_edges.py ----------
+# A wave-item of k_geo_rows<PPL, LPP, MAXR> is 64 PPL / LPP consecutive grid points of one line, a unit eight items of one line (one
+# per wave of a 512-thread block).  launch_geometry hands the rem = N % pts points beyond a multiple of the item to the
+# one-point-per-wave tail kernel only if LPP == 1, 0 < rem <= 16 and N > pts; otherwise the last item of a line is partial.
+GEO_FORMS = {"1": (1, 1), "-2": (2, 1), "2": (1, 2), "4": (1, 4), "8": (1, 8)}     # option geo_lpp -> (PPL, LPP)
+GEO_TAIL_MAX = 16
+GEO_WAVES_PER_BLOCK = 8
+GEO_PTS = sorted({64 * p // l for p, l in GEO_FORMS.values()})                     # 8, 16, 32, 64, 128
+
+
+def geo_dispatch(N, ppl, lpp):
+    """launch_geometry's arithmetic for one line of N points in the form (ppl, lpp): item size, remainder, the points the tail kernel
+    takes, the end of the row kernel's range, and the row kernel's items and units per line"""
+    pts = 64 * ppl // lpp
+    rem = N % pts
+    tail = rem if (lpp == 1 and 0 < rem <= GEO_TAIL_MAX and N > pts) else 0
+    j_end = N - tail
+    items = (j_end + pts - 1) // pts
+    return dict(pts=pts, rem=rem, tail=tail, j_end=j_end, items=items, units=(items + GEO_WAVES_PER_BLOCK - 1) // GEO_WAVES_PER_BLOCK,
+                spare=(-items) % GEO_WAVES_PER_BLOCK, last=j_end - (items - 1) * pts)
+
+
+def geo_pick_form(n_lines, N, n_cu, lpp_opt=0):
+    """geo_pick_form: the option if set, else the smallest item that gives none of the 8 n_cu wave slots a second item"""
+    if str(lpp_opt) in GEO_FORMS:
+        return GEO_FORMS[str(lpp_opt)]
+    pts, slots = n_lines * N, 8 * n_cu
+    for k, form in ((64, (2, 1)), (32, (1, 1)), (16, (1, 2)), (8, (1, 4))):
+        if pts > slots * k:
+            return form
+    return (1, 8)
+
+
+def geo_kernel_name(ppl, lpp, nrows_mn=11):
+    """what ibs_last_launch reports for the row kernel of a form (tables of more than 12 rows run <1, 1, 24> whatever the form)"""
+    return "ibs::k_geo_rows<1, 1, 24>" if nrows_mn > 12 else "ibs::k_geo_rows<%d, %d, 12>" % (ppl, lpp)
+
+
+def geo_threshold_lines(N, n_cu):
+    """[(points per wave slot k, line count just below, line count just above)]: the largest n_lines with n_lines N <= 8 n_cu k (the
+    form of the smaller item still serves it) and the next one, for the four thresholds of geo_pick_form"""
+    return [(k, (8 * n_cu * k) // N, (8 * n_cu * k) // N + 1) for k in (8, 16, 32, 64)]
+
+
+GEO_EDGE_REASONS = {
+    -1: "pts - 1: one item, one lane (lane group) short of full; N < pts, so no tail kernel in any form",
+    0: "pts: exactly one full item, rem = 0",
+    1: "pts + 1: rem = 1; one lane per point: the tail kernel takes one point; else a second item with one live point",
+    16: "pts + 16: rem = 16, the most the tail kernel takes",
+    17: "pts + 17: rem = 17, the first remainder that stays a partial item in every form",
+}
+GEO_EDGE_REASONS_8 = {
+    0: "8 pts: exactly one unit per line, no spare item, rem = 0",
+    1: "8 pts + 1: one lane per point: the tail kernel keeps the line at 8 items; else 9 items = two units, seven spare items",
+    17: "8 pts + 17: two units in every form, the second with one item (two / three with items of 16 / 8 points), the last one partial",
+}
+GEO_EDGE_N = sorted(
+    {pts + d for pts in GEO_PTS for d in GEO_EDGE_REASONS} | {8 * pts + d for pts in GEO_PTS for d in GEO_EDGE_REASONS_8}
+    | {2, 3,     # the shortest grids the entry point takes: two and three live points in the only item
+       7,        # one point short of the smallest item
+       66})      # an even length that is no edge of any item size (the lists above hold even lengths on the edges)
+GEO_EDGE_SURF = [1, 0, 1, 1, 0]                       # two surfaces, the staged image changes on every line but one
+GEO_EDGE_ALPHA = [0.3, 2.9, 1.1, 0.0, 2.2]
+
+# alpha and theta outside [0, pi] and off the symmetric window (the kernels see theta[j] and alpha only through
+# phi = (theta - alpha) / iota and the root solve started at theta)
+GEO_WINDOWS = [(-4 * np.pi, 4 * np.pi),               # the scan's window
+               (2 * np.pi, 10 * np.pi),               # all theta > 0: |phi| up to ~70, the angles m theta - n phi up to ~2e3
+               (-np.pi, np.pi)]                       # one poloidal turn
+GEO_ALPHAS = [-3 * np.pi, -7.3, 0.0, np.pi, 9.1]      # negative, beyond one turn, and the two ends of the box tested so far
+GEO_WINDOW_N = [131, 65]                              # 65 = 64 + 1: a tail point for LPP = 1, N < pts for two points per lane
+GEO_WINDOW_FORMS = ["1", "-2", "4"]
+
+
+def geo_nonuniform_grid(N=131, seed=5):
+    """an increasing grid on [-4 pi, 4 pi] with spacings between 0.2 and 1.8 of the uniform one"""
+    rng = np.random.default_rng(seed)
+    d = rng.uniform(0.2, 1.8, N - 1)
+    return -4 * np.pi + 8 * np.pi * np.concatenate([[0.0], np.cumsum(d)]) / d.sum()
+
+
+# many lines on alternating surfaces: (n_lines, N); more units than an MI355X has CUs (256) in both forms, so blocks own two or three
+# lines and re-stage on every unit
+GEO_MANY = [(700, 67),      # one item per line; one lane per point: 64 points + 3 tail points, two points per lane: N < pts
+            (300, 145)]     # rem = 17 in both forms: 3 / 2 items, the last one partial
+GEO_MANY_FORMS = ["1", "-2"]
+GEO_PITCH = [(145, 150), (67, 72)]                    # (N, ld = N + 5)
+GEO_MARK = dict(n_surf=40, first=[3, 39, 17, 3, 39], second=[0, 5, 5, 0, 5])      # k_geo_mark: n_surf >= 32, n_lines < 8 n_surf
+
+# VJP: for_points_of_surface ballots line_surf 64 entries at a time; k_geo_vjp_modes gives a wave 8 modes and a block 4 waves
+GEO_VJP_G = 8
+GEO_VJP_LINES = [63, 64, 65, 130]      # one word one short, one word full, a second word with one entry, a third word
+GEO_VJP_LINES_N = 35
+GEO_VJP_N = [2, 63, 64, 65]            # the points of a line are strided over 64 lanes: two lanes, one short, full, one lane twice
+GEO_VJP_MODES = {"odd_groups": (41, 50),   # 6 + 7 = 13 groups: the last block of k_geo_vjp_modes has one wave with work
+                 "few": (7, 7)}            # fewer than 8 modes in each table: min(k0 + g, n - 1) clamps in the only group
+
+
+def geo_vjp_line_surf(n_lines):
+    """four surfaces: surface 1 holds no line, surface 3 only lines at index >= 64 (the even ones), surface 2 every third line below
+    64 and the odd ones from 64 on (both sides of a ballot word), surface 0 the rest"""
+    i = np.arange(n_lines)
+    return np.where(i >= 64, np.where(i % 2 == 0, 3, 2), np.where(i % 3 == 0, 2, 0)).astype(np.int32)
+
+
+def geo_vjp_line_alpha(n_lines):
+    return np.linspace(-3 * np.pi, 3 * np.pi, n_lines)
+
+
+def geo_vjp_groups(mnmax, mnmax_nyq):
+    return (mnmax + GEO_VJP_G - 1) // GEO_VJP_G + (mnmax_nyq + GEO_VJP_G - 1) // GEO_VJP_G

@@ -2,7 +2,8 @@
 cannot be blamed on the systems: the moving well keeps its gap and puts the mode on the chosen grid point at every edge length, the
 second mode of two_wells sits on the shallow well, the geometry mapping reproduces the rows, the length lists cover the lane / chunk /
 path edges they claim, and the two CPU oracles (LAPACK on the symmetrised pencil; division-form bisection + twisted factorisation in
-C) agree on this family far inside every tolerance the GPU tests apply."""
+C) agree on this family far inside every tolerance the GPU tests apply.  For tests/test_gpu_geometry_edges.py: the dispatch arithmetic of
+the geometry kernels restated, and every edge class its lists claim found in them."""
 import numpy as np
 import pytest
 
@@ -147,3 +148,101 @@ def test_window_reference_of_the_nearest_eigenpair_equals_the_dense_one(N):
         assert a["idx"] == b["idx"] >= 1 and a["tie"] == b["tie"] and a["nA"] == b["nA"]
         assert abs(a["lam"] - b["lam"]) <= 4 * N * ec.EPS * a["nA"] and abs(a["lam_max"] - b["lam_max"]) <= 4 * N * ec.EPS * a["nA"]
         assert abs(a["gam"] - b["gam"]) < 1e-12 and np.abs(a["X"] - b["X"]).max() < 1e-10
+
+
+# ---- the inputs of tests/test_gpu_geometry_edges.py -----------------------------------------------------------------------------------
+def test_geometry_dispatch_arithmetic():
+    """geo_dispatch / geo_pick_form restate launch_geometry, k_geo_rows and geo_pick_form (csrc/ibs_geometry.hip) on known values"""
+    assert ec.GEO_PTS == [8, 16, 32, 64, 128] and {k: 64 * p // l for k, (p, l) in ec.GEO_FORMS.items()} == {"1": 64, "-2": 128, "2": 32, "4": 16, "8": 8}
+    # N = 1025 = 8 * 128 + 1 (test_F1_geometry_lanes_per_point_variants_agree): one tail point per line with one lane per point
+    assert ec.geo_dispatch(1025, 2, 1) == dict(pts=128, rem=1, tail=1, j_end=1024, items=8, units=1, spare=0, last=128)
+    assert ec.geo_dispatch(1025, 1, 1) == dict(pts=64, rem=1, tail=1, j_end=1024, items=16, units=2, spare=0, last=64)
+    assert ec.geo_dispatch(1025, 1, 4) == dict(pts=16, rem=1, tail=0, j_end=1025, items=65, units=9, spare=7, last=1)
+    assert ec.geo_dispatch(67, 2, 1)["tail"] == 0 and ec.geo_dispatch(67, 1, 1)["tail"] == 3 and ec.geo_dispatch(2, 1, 8)["last"] == 2
+    # tools/geo_form_sweep.py: 30 / 54 / 84 / 201 lines of 969 points on 256 CUs -> 4 / 2 / 1 lanes per point / two points per lane
+    assert [ec.geo_pick_form(n, 969, 256) for n in (16, 30, 54, 84, 201)] == [(1, 8), (1, 4), (1, 2), (1, 1), (2, 1)]
+    assert ec.geo_pick_form(5, 131, 256, "-2") == (2, 1) and ec.geo_pick_form(10 ** 6, 131, 256, 8) == (1, 8)
+    assert ec.geo_kernel_name(2, 1) == "ibs::k_geo_rows<2, 1, 12>" and ec.geo_kernel_name(1, 4, 13) == "ibs::k_geo_rows<1, 1, 24>"
+
+
+def test_geometry_length_list_covers_the_edges_it_claims():
+    Ns = ec.GEO_EDGE_N
+    assert Ns == sorted(set(Ns)) and min(Ns) == 2 and max(Ns) == 1041 and {2, 3, 7} <= set(Ns) and sum(N < 150 for N in Ns) > len(Ns) // 2
+    assert any(N % 2 == 0 and all(N % p for p in ec.GEO_PTS[1:]) for N in Ns)
+    for key, (ppl, lpp) in ec.GEO_FORMS.items():
+        d = {N: ec.geo_dispatch(N, ppl, lpp) for N in Ns}
+        pts = 64 * ppl // lpp
+        for N in (pts - 1, pts, pts + 1, pts + 16, pts + 17, 8 * pts, 8 * pts + 1, 8 * pts + 17):
+            assert N in d, (key, N)
+        tails = {v["tail"] for v in d.values()}
+        assert tails >= ({0, 1, 16} if lpp == 1 else {0}) and max(tails) <= (16 if lpp == 1 else 0), (key, tails)
+        for N, v in d.items():             # the tail kernel runs exactly where the item arithmetic says, and never on a whole line
+            assert v["tail"] == (N % pts if lpp == 1 and N > pts and 1 <= N % pts <= 16 else 0) and v["j_end"] >= min(N, pts)
+            assert v["tail"] + v["j_end"] == N and (v["items"] - 1) * pts < v["j_end"] <= v["items"] * pts and 1 <= v["last"] <= pts
+        assert d[pts - 1]["items"] == 1 and d[pts - 1]["last"] == pts - 1 and d[pts - 1]["tail"] == 0        # N < pts
+        assert d[pts]["rem"] == 0 and d[pts]["items"] == 1 and d[pts]["last"] == pts                          # N = pts
+        assert d[pts + 17]["tail"] == 0 and d[pts + 16]["tail"] == (16 if lpp == 1 else 0)
+        if pts > 17:                           # (items of 8 and 16 points, four and eight lanes per point: 16 and 17 more points are whole items)
+            assert d[pts + 16]["rem"] == 16 and d[pts + 17]["rem"] == 17 and d[pts + 17]["items"] == 2 and d[pts + 17]["last"] == 17
+        else:
+            assert d[pts + 16]["rem"] == 0 and d[pts + 17]["last"] == 1 and d[pts + 17]["items"] == 2 + 16 // pts
+        assert d[8 * pts]["rem"] == 0 and (d[8 * pts]["items"], d[8 * pts]["units"], d[8 * pts]["spare"]) == (8, 1, 0)
+        more = (17 + pts - 1) // pts             # 1, or 2 / 3 with items of 16 / 8 points
+        assert (d[8 * pts + 17]["items"], d[8 * pts + 17]["units"], d[8 * pts + 17]["spare"]) == (8 + more, 2, 8 - more)
+        assert d[8 * pts + 1]["items"] == (8 if lpp == 1 else 9)
+        assert {v["items"] for v in d.values()} >= {1, 2, 8, 9}
+        assert any(N < pts for N in Ns) and d[2]["last"] == 2 and d[3]["last"] == 3
+    # the window cases: a tail point with one lane per point, a line shorter than the item with two points per lane
+    assert ec.geo_dispatch(65, 1, 1)["tail"] == 1 and ec.geo_dispatch(65, 2, 1)["items"] == 1 and ec.geo_dispatch(65, 1, 4)["last"] == 1
+    assert ec.GEO_WINDOW_N == [131, 65] and 65 in Ns and ec.GEO_WINDOW_FORMS == ["1", "-2", "4"]
+    assert min(ec.GEO_ALPHAS) < -np.pi and max(ec.GEO_ALPHAS) > 2 * np.pi and {0.0, np.pi} <= set(ec.GEO_ALPHAS)
+    assert any(lo > 0 for lo, hi in ec.GEO_WINDOWS) and any(hi - lo < 7 for lo, hi in ec.GEO_WINDOWS)
+    th = ec.geo_nonuniform_grid()
+    dth = np.diff(th)
+    assert len(th) == 131 and abs(th[0] + 4 * np.pi) < 1e-12 and abs(th[-1] - 4 * np.pi) < 1e-12 and dth.min() > 0 and dth.max() > 3 * dth.min()
+
+
+def test_geometry_batches_cover_the_block_and_threshold_edges():
+    n_cu = 256                                               # MI355X; the GPU test takes the count from the device
+    for n_lines, N in ec.GEO_MANY:
+        for key in ec.GEO_MANY_FORMS:
+            d = ec.geo_dispatch(N, *ec.GEO_FORMS[key])
+            U = n_lines * d["units"]
+            own = {U * (b + 1) // n_cu - U * b // n_cu for b in range(n_cu)}         # units of block b: [U b / B, U (b + 1) / B)
+            assert U > n_cu and len(own) == 2 and min(own) >= 1, (n_lines, N, key, own)
+            assert d["spare"] > 0                            # every unit has spare items: item < ipl decides
+    assert {ec.geo_dispatch(67, *ec.GEO_FORMS[k])["tail"] for k in ec.GEO_MANY_FORMS} == {3, 0}
+    assert {ec.geo_dispatch(145, *ec.GEO_FORMS[k])["last"] for k in ec.GEO_MANY_FORMS} == {17}
+    # default form: every threshold from both sides, the item doubling across it
+    seen = []
+    for k, below, above in ec.geo_threshold_lines(131, n_cu):
+        fb, fa = ec.geo_pick_form(below, 131, n_cu), ec.geo_pick_form(above, 131, n_cu)
+        assert below * 131 <= 8 * n_cu * k < above * 131 and above == below + 1
+        assert 64 * fa[0] // fa[1] == 2 * (64 * fb[0] // fb[1])
+        seen += [fb, fa]
+    assert [k for k, _, _ in ec.geo_threshold_lines(131, n_cu)] == [8, 16, 32, 64] and set(seen) == set(ec.GEO_FORMS.values())
+    assert [(b, a) for _, b, a in ec.geo_threshold_lines(131, n_cu)] == [(125, 126), (250, 251), (500, 501), (1000, 1001)]
+    assert all(ld == N + 5 for N, ld in ec.GEO_PITCH) and {N for N, _ in ec.GEO_PITCH} == {145, 67}
+    m = ec.GEO_MARK                                          # ibs_fieldline_geometry_f64: marks when n_surf >= 32 and n_lines < 8 n_surf
+    assert m["n_surf"] >= 32 and len(m["first"]) == len(m["second"]) == 5 < 8 * m["n_surf"]
+    assert set(m["first"]) == {3, 39, 17} and set(m["second"]) == {0, 5} and max(m["first"]) == m["n_surf"] - 1
+
+
+def test_geometry_vjp_cases_cover_the_ballot_and_group_edges():
+    assert ec.GEO_VJP_LINES == [63, 64, 65, 130] and ec.GEO_VJP_N == [2, 63, 64, 65]
+    assert {(n + 63) // 64 for n in ec.GEO_VJP_LINES} == {1, 2, 3}
+    for n in ec.GEO_VJP_LINES:
+        ls, la = ec.geo_vjp_line_surf(n), ec.geo_vjp_line_alpha(n)
+        assert len(ls) == len(la) == n and 1 not in ls and set(ls) <= {0, 2, 3}
+        assert la.min() == -3 * np.pi and la.max() == 3 * np.pi
+        at3, at2 = np.flatnonzero(ls == 3), np.flatnonzero(ls == 2)
+        assert (at3 >= 64).all() and (at2 < 64).any()
+        if n > 64:
+            assert len(at3) >= 1
+        if n == 130:                                         # lines of one surface in all three ballot words, of another in two
+            assert {i // 64 for i in at2} == {0, 1, 2} and {i // 64 for i in at3} == {1, 2}
+    assert list(ec.geo_vjp_line_surf(65)[63:]) == [2, 3]
+    # mode tables: the two in use so far fill the last block of four waves, the new ones do not
+    assert ec.geo_vjp_groups(242, 392) % 4 == 0 and ec.geo_vjp_groups(37, 53) % 4 == 0
+    assert ec.geo_vjp_groups(*ec.GEO_VJP_MODES["odd_groups"]) == 13 and ec.geo_vjp_groups(*ec.GEO_VJP_MODES["few"]) == 2
+    assert max(ec.GEO_VJP_MODES["few"]) < ec.GEO_VJP_G
