@@ -1,5 +1,6 @@
 """Grid lengths on lane, chunk and path edges, and two families of raw systems whose mode sits where the caller puts it: the inputs of
-tests/test_gpu_edge_lengths.py, pinned with the oracle alone in tests/test_edge_cases_cpu.py; below them the item, tail, block and
+tests/test_gpu_edge_lengths.py, pinned with the oracle alone in tests/test_edge_cases_cpu.py, and the lane edges of the register kernels the
+same well is put on in tests/test_gpu_lane_edges.py (lane_rows_start, lane_targets); below them the item, tail, block and
 ballot edges of the field-line geometry kernels, the inputs of tests/test_gpu_geometry_edges.py.  Test infrastructure only.
 
 Rows per lane of the register kernels: M = ceil((N - 2) / 64), N <= 2050.  Beyond that the long path (csrc/ibs_long.hpp) passes the
@@ -132,6 +133,49 @@ def twist_targets(N, cap=24):
 
 def is_end_target(N, j_star):
     return j_star < 6 or j_star > N - 7
+
+
+def lane_rows_start(L, n, P=64):
+    """first row (0-based, row r = grid point r + 1) of lane L when P lanes share the n rows: WaveSolver::rows_start (csrc/ibs_wave.hpp)
+    and GroupSolver::rows_start (csrc/ibs_group.hpp) restated with M = ceil(n / P): rem = n - P (M - 1) lanes of M rows, then lanes of
+    M - 1 rows; L = P gives n"""
+    M = (n + P - 1) // P
+    rem = n - P * (M - 1)
+    return L * (M - 1) + min(L, rem)
+
+
+def lane_edge_lanes(N, P=64):
+    """the lanes whose first row is an edge of the register kernels: lane 1 and the last lane, the lane where the chunk length drops
+    from M to M - 1 and the one after it, the lanes at which the DPP scan changes its step (row_shr within 16 lanes, row_bcast at 16,
+    32 and 48), and the middle lane of a 16-lane group; all within 1 ... P - 1"""
+    rem = N - 2 - P * ((N - 2 + P - 1) // P - 1)
+    lanes = {1, rem, rem + 1, P - 1} | set(range(16, P, 16)) | ({P // 2} if P == 16 else set())
+    return sorted(L for L in lanes if 1 <= L <= P - 1)
+
+
+def lane_targets(N, P=64):
+    """the j_star list that puts the twist row of the eigenvector stage on the lane edges of the P-lane register kernels: for every
+    lane L of lane_edge_lanes the grid points rows_start(L) (the last row of lane L - 1) and rows_start(L) + 1 (the first row of lane
+    L), within 1 ... N - 2, without duplicates: at most 14 per (N, P)"""
+    out = []
+    for L in lane_edge_lanes(N, P):
+        a = lane_rows_start(L, N - 2, P)
+        out += [j for j in (a, a + 1) if 1 <= j <= N - 2 and j not in out]
+    return out
+
+
+def lane_forms(N):
+    """the lanes-per-system forms whose lane edges a length is tested on: the full wave and what lanes_allowed admits"""
+    return [64] + lanes_allowed(N)
+
+
+def fp32_inputs(h, g, c, f):
+    """what the FP32 entry point sees: (h, g, c, f) rounded to float32, and the same values widened again -- (h32, (g, c, f) as
+    float32 arrays, (g, c, f) as float64 arrays, a theta grid whose spacing is h32) -- the reference of an FP32 call solves THESE"""
+    h32 = float(np.float32(h))
+    r32 = tuple(np.ascontiguousarray(a, dtype=np.float32) for a in (g, c, f))
+    N = r32[0].shape[-1]
+    return h32, r32, tuple(a.astype(np.float64) for a in r32), np.linspace(-0.5 * h32 * (N - 1), 0.5 * h32 * (N - 1), N)
 
 
 def norm_a(h, g, c, f):

@@ -246,3 +246,120 @@ def test_geometry_vjp_cases_cover_the_ballot_and_group_edges():
     assert ec.geo_vjp_groups(242, 392) % 4 == 0 and ec.geo_vjp_groups(37, 53) % 4 == 0
     assert ec.geo_vjp_groups(*ec.GEO_VJP_MODES["odd_groups"]) == 13 and ec.geo_vjp_groups(*ec.GEO_VJP_MODES["few"]) == 2
     assert max(ec.GEO_VJP_MODES["few"]) < ec.GEO_VJP_G
+
+
+# ---- the inputs of tests/test_gpu_lane_edges.py ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", ec.EDGE_N_SHORT)
+def test_lane_rows_start_tiles_the_rows(N):
+    """lane_rows_start restates rows_start (csrc/ibs_wave.hpp, csrc/ibs_group.hpp): the chunks tile [0, n), the first rem lanes hold M
+    rows and the others M - 1; the edge lanes and the targets drawn from them are what tests/edge_cases.py says"""
+    n = N - 2
+    for P in ec.lane_forms(N):
+        M = (n + P - 1) // P
+        rem = n - P * (M - 1)
+        assert 1 <= rem <= P and (P != 64 or M == ec.rows_per_lane(N))
+        start = [ec.lane_rows_start(L, n, P) for L in range(P + 1)]
+        assert start[0] == 0 and start[P] == n
+        assert [b - a for a, b in zip(start, start[1:])] == [M] * rem + [M - 1] * (P - rem), (N, P)
+        assert start == [L * (M - 1) + (L if L < rem else rem) for L in range(P + 1)]          # the kernels' own expression
+        lanes = ec.lane_edge_lanes(N, P)
+        want = {1, rem, rem + 1, P - 1} | {16, 32, 48} | ({8} if P == 16 else set())
+        assert lanes == sorted(L for L in want if 1 <= L <= P - 1), (N, P, lanes)
+        t = ec.lane_targets(N, P)
+        assert len(t) == len(set(t)) and 2 <= len(t) <= 14 and all(1 <= j <= N - 2 for j in t), (N, P, t)
+        assert set(t) == {j for L in lanes for j in (start[L], start[L] + 1) if 1 <= j <= N - 2}
+        for L in lanes:          # grid point start[L] is row start[L] - 1, the last of lane L - 1; start[L] + 1 the first row of lane L
+            assert start[L] - 1 == start[L - 1] + (M if L - 1 < rem else M - 1) - 1
+    if N == ec.EDGE_N_SHORT[0]:
+        assert sum(len(ec.lane_targets(K, P)) for K in ec.EDGE_N_SHORT for P in ec.lane_forms(K)) == 555
+        assert max(len(ec.lane_targets(K)) for K in ec.EDGE_N_SHORT) == 14
+        assert ec.lane_targets(2049) == [32, 33, 512, 513, 1024, 1025, 1536, 1537, 2016, 2017]
+        assert ec.lane_targets(131, 16) == [9, 10, 17, 18, 65, 66, 121, 122]
+
+
+def lane_edge_systems(N):
+    """[(P, targets)] of a length and the union of the targets (several forms share grid points)"""
+    forms = [(P, ec.lane_targets(N, P)) for P in ec.lane_forms(N)]
+    return forms, sorted({j for _, t in forms for j in t})
+
+
+@pytest.mark.parametrize("N", ec.EDGE_N_SHORT)
+def test_moving_well_on_lane_edges_keeps_its_gap_and_peaks_on_the_target(N):
+    """every (N, P, target) case of tests/test_gpu_lane_edges.py, none left out: the oracle's mode peaks on the target (within 6 points of
+    an end for end targets), lam_max lies in [0.149, 0.732] and the second eigenvalue at least 0.39 below it"""
+    th = ec.theta_grid(N)
+    forms, union = lane_edge_systems(N)
+    seen = {}
+    for j in union:
+        g, c, f = ec.well_rows(th, j)
+        gam, lam, X, dX = bo.solve_gcf(th, g, c, f)
+        w = ec.top_pairs(th, g, c, f)[0]
+        # (the interval and the gap are figures printed to three and two digits: the smallest lam_max is 0.14895 at N = 67, j = 65)
+        assert abs(w[1] - lam) < 1e-12 and 0.149 <= round(lam, 3) <= 0.732, (N, j, lam)
+        assert round(w[1] - w[0], 2) >= 0.39, (N, j, w)
+        seen[j] = int(np.argmax(np.abs(X)))
+    for P, targets in forms:
+        for j in targets:
+            k = seen[j]
+            if ec.is_end_target(N, j):
+                assert min(k, N - 1 - k) <= 6 and (k < N // 2) == (j < N // 2), (N, P, j, k)
+            else:
+                assert k == j, (N, P, j, k)
+
+
+@pytest.mark.parametrize("N", ec.EDGE_N_SHORT)
+def test_the_two_oracles_agree_on_the_lane_edge_wells(N):
+    """the pattern of test_the_two_oracles_agree_on_the_moving_well on the lane-edge systems, in FP64 and on the FP32-valued inputs
+    of the FP32 entry point (g, c, f rounded to float32 and widened, h = float(float32(h))): a tenth of each bound
+    tests/test_gpu_lane_edges.py applies -- lam 4 N eps ||A||, gam 1e-10, X 1e-7, dX 1e-7 max|dX| + 1e-7, and for the FP32 eigenvalues
+    (N + 3) eps32 ||A||"""
+    from oracle import c_oracle as co
+    th = ec.theta_grid(N)
+    h = float(th[1] - th[0])
+    _, union = lane_edge_systems(N)
+    rows = [ec.well_rows(th, j) for j in union]
+    g, c, f = (np.stack([r[i] for r in rows]) for i in range(3))
+    h32, _, (gw, cw, fw), th32 = ec.fp32_inputs(h, g, c, f)
+    assert abs((th32[1] - th32[0]) - h32) <= 4 * ec.EPS * h32 and abs(h32 - h) <= 2.0 ** -24 * h
+    assert np.array_equal(gw, g) and np.abs(cw - c).max() <= 2.0 ** -24 * np.abs(c).max() and not np.array_equal(cw, c)
+    for what, (thx, hx, gx, cx, fx) in (("FP64", (th, h, g, c, f)), ("FP32 values", (th32, h32, gw, cw, fw))):
+        nA = ec.norm_a(hx, gx, cx, fx)
+        lam_c = co.lam_batch(hx, gx, cx, fx)
+        for k, j in enumerate(union):
+            gam, lam, X, dX = bo.solve_gcf(thx, gx[k], cx[k], fx[k])
+            gc, lc, Xc, dXc = co.solve_gcf(hx, gx[k], cx[k], fx[k])
+            assert abs(lam - lc) <= 0.4 * N * ec.EPS * nA[k] and abs(lam - lam_c[k]) <= 0.4 * N * ec.EPS * nA[k], (N, what, j)
+            assert abs(lam - lam_c[k]) <= 0.1 * (N + 3) * 2.0 ** -23 * nA[k]
+            assert abs(gam - gc) < 1e-11, (N, what, j, gam - gc)
+            assert np.abs(X - Xc).max() < 1e-8 and np.abs(dX - dXc).max() < 0.1 * (1e-7 * np.abs(dX).max() + 1e-7), (N, what, j)
+            kk = int(np.argmax(np.abs(Xc)))
+            assert (min(kk, N - 1 - kk) <= 6) if ec.is_end_target(N, j) else (kk == j), (N, what, j, kk)
+
+
+def test_check_pair_notices_a_shift_by_one_point_and_one_entry_off():
+    """the checker of the GPU tests (tests/test_gpu_edge_lengths.py: check_pair) passes on the reference itself and fails when X is
+    the reference shifted by one grid point, or has one entry off by 1e-6"""
+    from tests.test_gpu_edge_lengths import check_pair
+    N = 259
+    th = ec.theta_grid(N)
+    for j in ec.lane_targets(N)[:4]:
+        g, c, f = ec.well_rows(th, j)
+        nA = ec.norm_a(float(th[1] - th[0]), g, c, f)[0]
+        ref = bo.solve_gcf(th, g, c, f)
+        gam, lam, X, dX = ref
+        check_pair(N, "reference", lam, gam, X.copy(), dX.copy(), ref, nA)
+        for shift in (1, -1):
+            with pytest.raises(AssertionError):
+                check_pair(N, "X one point off", lam, gam, X, dX, (gam, lam, np.roll(X, shift), np.roll(dX, shift)), nA)
+            Xs = np.roll(X, shift)
+            with pytest.raises(AssertionError):
+                check_pair(N, "GPU X one point off", lam, gam, Xs, np.roll(dX, shift), ref, nA)
+        for k in (j, j + 1, 1, N - 2):
+            Xb = X.copy()
+            Xb[k] += 1e-6 if k != j else -1e-6                    # (at the peak downwards: max |X| stays one)
+            with pytest.raises(AssertionError):
+                check_pair(N, "one entry off", lam, gam, Xb, dX, ref, nA)
+        dXb = dX.copy()
+        dXb[j + 1] += 2 * (1e-7 * np.abs(dX).max() + 1e-7)
+        with pytest.raises(AssertionError):
+            check_pair(N, "one dX entry off", lam, gam, X, dXb, ref, nA)
