@@ -66,6 +66,9 @@ SYMBOLS = {
                                              _I64, _P, _P, _I32, _P, _I32, _P, _D, _D, _I32]),
     "ibs_fieldline_geometry_vjp_f64": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P,
                                                  _I64, _P, _P, _P, _P, _P, _P, _I32]),
+    "ibs_fieldline_geometry_dalpha_f64": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P,
+                                                    _I64, _P, _I32]),
+    "ibs_obj_w_grad_exact_tangent_f64": (C.c_int, [_P, _I32, _I32, _D, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_surface_tables_f64": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_refine_f64": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _D, _D, _I32, _P, _P,
                                  _I32, _P, _D, _I32, _D, _D, _P, _P, _P, _I32]),

@@ -1241,6 +1241,36 @@ int ibs_obj_w_grad_exact_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, c
   return staged(ctx, mem, decl, [&] { return points_exact_device(ctx, a); });
 }
 
+// ---- the same from ONE line per point and the alpha-tangent of its geometry (ibs_exact_tangent.hip): exact in alpha as well; the
+// per-wave workspace is that of points_exact_device
+static int points_exact_tangent_device(ibs_ctx* ctx, ibs::ExactTangentArgs a) {
+  const int nw = long_waves(ctx, a.n_pts);
+  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::exact_points_ws(a.N).total * sizeof(double))) return r;
+  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+  HIPCHK(ibs::launch_obj_w_grad_exact_tangent(a, ctx->stream));
+  return 0;
+}
+
+int ibs_obj_w_grad_exact_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, const double* geo_da,
+                                     int64_t ld, const double* theta0, const double* sigma, double* val, double* jac,
+                                     double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_pts < 0 || !geo || !geo_da || !theta0 || !val || !jac || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_pts=%d ld=%lld N=%d)", n_pts, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_pts == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n = (size_t)n_pts, geo_elems = n * 8 * (size_t)ld;
+  ibs::ExactTangentArgs a{};
+  a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld;
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, geo_elems); a.geo_da = s.in(geo_da, geo_elems); a.theta0 = s.in(theta0, n); a.sigma = s.in(sigma, n);
+    a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.gam = s.out(gam, n); a.lam = s.out(lam, n); a.idx = s.out(idx, n);
+    a.info = s.status(info, n);
+  };
+  return staged(ctx, mem, decl, [&] { return points_exact_tangent_device(ctx, a); });
+}
+
 // Geometry-fed scan on a grid beyond 2050 points: the (g, c, f) rows of every (line, theta0) system -- and their theta0 tangents when
 // dgam/dtheta0 is wanted -- are written out (k_assemble_gcf_long: the arithmetic the scan kernels do while staging), solved by the
 // generic long-grid kernel, and the Hellmann-Feynman sums (utils.py:1676-1680) taken by k_hf_grad.  Warm-start guesses are not
@@ -1759,6 +1789,40 @@ int ibs_fieldline_geometry_vjp_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, 
   // (without lines the points kernel has nothing to do; the reductions still write the zeros)
   return staged(ctx, mem, decl, [&]() -> int {
     HIPCHK(ibs::launch_geometry_vjp(a, ctx->stream));
+    return 0;
+  });
+}
+
+int ibs_fieldline_geometry_dalpha_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_nyq, const double* xm,
+                                      const double* xn, const double* xm_nyq, const double* xn_nyq, const double* tab_mn,
+                                      const double* tab_nyq, const double* scal, int32_t n_lines, const int32_t* line_surf,
+                                      const double* line_alpha, int32_t N, const double* theta, int64_t ld, double* geo_da,
+                                      int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_lines < 0) return fail(IBS_ERR_ARG, "n_lines=%d < 0", n_lines);
+  if (ld < N) return fail(IBS_ERR_ARG, "ld=%lld < N=%d", (long long)ld, N);
+  if (n_surf <= 0 || mnmax <= 0 || mnmax_nyq <= 0 || N < 2 || !xm || !xn || !xm_nyq || !xn_nyq || !tab_mn || !tab_nyq ||
+      !scal || !line_surf || !line_alpha || !theta || !geo_da)
+    return fail(IBS_ERR_ARG, "bad arguments");
+  if (n_lines > 65535 || n_surf > 65535) return fail(IBS_ERR_UNSUPPORTED, "n_lines=%d, n_surf=%d: at most 65535 each", n_lines, n_surf);
+  const bool host = mem == IBS_MEM_HOST;
+  if (host)
+    for (int i = 0; i < n_lines; ++i)
+      if (line_surf[i] < 0 || line_surf[i] >= n_surf) return fail(IBS_ERR_ARG, "line_surf[%d]=%d out of range", i, line_surf[i]);
+  if (n_lines == 0) return 0;
+  ON_DEVICE(ctx);
+  ibs::GeoDalphaArgs a{};
+  a.n_surf = n_surf; a.mnmax = mnmax; a.mnmax_nyq = mnmax_nyq; a.n_lines = n_lines; a.N = N; a.ld = ld;
+  const size_t n_mn = (size_t)n_surf * 6 * mnmax, n_nyq = (size_t)n_surf * 7 * mnmax_nyq;
+  // (host pointers: the rows are packed on the device and come back one by one, so the caller's entries N..ld-1 stay as they were)
+  auto decl = [&](Stage& s) {
+    a.xm = s.in(xm, mnmax); a.xn = s.in(xn, mnmax); a.xm_nyq = s.in(xm_nyq, mnmax_nyq); a.xn_nyq = s.in(xn_nyq, mnmax_nyq);
+    a.tab_mn = s.in(tab_mn, n_mn); a.tab_nyq = s.in(tab_nyq, n_nyq); a.scal = s.in(scal, (size_t)n_surf * 6);
+    a.line_surf = s.in(line_surf, n_lines); a.line_alpha = s.in(line_alpha, n_lines); a.theta = s.in(theta, N);
+    a.geo_da = s.out_rows(geo_da, (size_t)8 * n_lines, N, ld); a.ld = (long)s.rows_ld(N, ld);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    HIPCHK(ibs::launch_geometry_dalpha(a, ctx->stream));
     return 0;
   });
 }

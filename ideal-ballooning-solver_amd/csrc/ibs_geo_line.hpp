@@ -19,5 +19,20 @@ __device__ __forceinline__ void line_gcf(const GeoLine& L, int j, double mdP, do
   const double d = L.at(4, j) + (2.0 * th0) * L.at(5, j) + (th0 * th0) * L.at(6, j);
   g = A1 * d; c = C0 + th0 * C1; f = A3 * d;
 }
+// alpha-tangent of those rows: L the line, T the alpha-derivative of its eight arrays (ibs_fieldline_geometry_dalpha_f64), dPdrho
+// held fixed (a surface constant: (cvdrift - gbdrift) bmag^2 does not depend on alpha); d|gradpar| = sgn(gradpar) d gradpar
+__device__ __forceinline__ void line_gcf_tangent(const GeoLine& L, const GeoLine& T, int j, double mdP, double th0, double& ga,
+                                                 double& ca, double& fa) {
+  const double B = L.at(0, j), gpr = L.at(1, j), gp = xabs(gpr);
+  const double dB = T.at(0, j), dgp = gpr > 0.0 ? T.at(1, j) : (gpr < 0.0 ? -T.at(1, j) : 0.0 * T.at(1, j));
+  const double iBv = 1.0 / B;
+  const double inv = 1.0 / (gp * B), dinv = -inv * inv * (dgp * B + gp * dB);
+  const double A1 = gp * iBv, dA1 = (dgp - A1 * dB) * iBv;
+  const double A3 = inv * iBv * iBv, dA3 = (dinv - 2.0 * inv * dB * iBv) * iBv * iBv;
+  const double dC0 = mdP * (T.at(2, j) * inv + L.at(2, j) * dinv), dC1 = mdP * (T.at(3, j) * inv + L.at(3, j) * dinv);
+  const double d = L.at(4, j) + (2.0 * th0) * L.at(5, j) + (th0 * th0) * L.at(6, j);
+  const double dd = T.at(4, j) + (2.0 * th0) * T.at(5, j) + (th0 * th0) * T.at(6, j);
+  ga = dA1 * d + A1 * dd; ca = dC0 + th0 * dC1; fa = dA3 * d + A3 * dd;
+}
 
 }  // namespace ibs

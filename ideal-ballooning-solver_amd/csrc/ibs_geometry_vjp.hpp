@@ -46,26 +46,13 @@ __host__ __device__ inline double dot(const V3& a, const V3& b) { return a.x * b
 __host__ __device__ inline V3 operator*(double s, const V3& a) { return V3{s * a.x, s * a.y, s * a.z}; }
 __host__ __device__ inline V3 operator+(const V3& a, const V3& b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 
-// One grid point: forward recomputed, reverse pass, workspace written.  Plain C++ (host and device): the arithmetic can be
-// checked on a CPU.
-__host__ __device__ inline void geo_vjp_point(const GeoVjpArgs& a, int line, int j) {
-  const int ls_raw = a.line_surf[line];
-  const int js = ls_raw < 0 ? 0 : (ls_raw >= a.n_surf ? a.n_surf - 1 : ls_raw);
-  const double* sc = a.scal + 6 * js;
-  const double s = sc[0], iota = sc[1], diota = sc[2], dp = sc[3], phiedge = sc[4], L = sc[5];
-  const double alpha = a.line_alpha[line];
-  const double tp = a.theta[j];
-  const double phi = (tp - alpha) / iota;                                    // utils.py:373 (phi_center = 0)
-  const int n1 = a.mnmax, n2 = a.mnmax_nyq;
-  const double* rmnc = a.tab_mn + (size_t)js * 6 * n1;
-  const double* zmns = rmnc + n1; const double* lmns = zmns + n1;
-  const double* drmnc = lmns + n1; const double* dzmns = drmnc + n1; const double* dlmns = dzmns + n1;
-  // ---- theta_vmec: the forward's secant from (theta_p, theta_p + 0.1)       utils.py:391-416
+// theta_vmec of one grid point: the forward's secant from (theta_p, theta_p + 0.1)       utils.py:391-416
+__host__ __device__ inline double geo_theta_vmec(const double* xm, const double* xn, const double* lmns, int n1, double tp, double phi) {
   auto resid = [&](double tv) {
     double acc = 0.0;
     for (int k = 0; k < n1; ++k) {
       double sa, ca;
-      vjp_sincos(a.xm[k] * tv - a.xn[k] * phi, &sa, &ca);
+      vjp_sincos(xm[k] * tv - xn[k] * phi, &sa, &ca);
       acc += lmns[k] * sa;
     }
     return tp - (tv + acc);
@@ -83,7 +70,24 @@ __host__ __device__ inline void geo_vjp_point(const GeoVjpArgs& a, int line, int
     last = fabs(step) <= 1e-9 * fmax(1.0, fabs(p1));
     q1 = resid(p1);
   }
-  const double tv = p1;
+  return p1;
+}
+
+// One grid point: forward recomputed, reverse pass, workspace written.  Plain C++ (host and device): the arithmetic can be
+// checked on a CPU.
+__host__ __device__ inline void geo_vjp_point(const GeoVjpArgs& a, int line, int j) {
+  const int ls_raw = a.line_surf[line];
+  const int js = ls_raw < 0 ? 0 : (ls_raw >= a.n_surf ? a.n_surf - 1 : ls_raw);
+  const double* sc = a.scal + 6 * js;
+  const double s = sc[0], iota = sc[1], diota = sc[2], dp = sc[3], phiedge = sc[4], L = sc[5];
+  const double alpha = a.line_alpha[line];
+  const double tp = a.theta[j];
+  const double phi = (tp - alpha) / iota;                                    // utils.py:373 (phi_center = 0)
+  const int n1 = a.mnmax, n2 = a.mnmax_nyq;
+  const double* rmnc = a.tab_mn + (size_t)js * 6 * n1;
+  const double* zmns = rmnc + n1; const double* lmns = zmns + n1;
+  const double* drmnc = lmns + n1; const double* dzmns = drmnc + n1; const double* dlmns = dzmns + n1;
+  const double tv = geo_theta_vmec(a.xm, a.xn, lmns, n1, tp, phi);
   // ---- forward syntheses                                                    utils.py:420-468
   double R = 0, R_s = 0, R_t = 0, R_p = 0, Z_s = 0, Z_t = 0, Z_p = 0, l_s = 0, l_t = 0, l_p = 0;
   for (int k = 0; k < n1; ++k) {

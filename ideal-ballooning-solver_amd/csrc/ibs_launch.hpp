@@ -224,6 +224,30 @@ struct GeoVjpArgs {
 };
 hipError_t launch_geometry_vjp(GeoVjpArgs& a, hipStream_t st);
 
+// alpha-tangent of the geometry (ibs_geometry_tangent.hip): d/d alpha of the eight arrays of every line, one lane per grid point
+struct GeoDalphaArgs {
+  int n_surf, mnmax, mnmax_nyq, n_lines, N;
+  const double *xm, *xn, *xm_nyq, *xn_nyq;
+  const double *tab_mn, *tab_nyq, *scal;       // as GeoArgs
+  const int* line_surf; const double* line_alpha; const double* theta;
+  long ld;
+  size_t plane;                // distance between the 8 planes of geo_da in elements; 0 = n_lines * ld
+  double* geo_da;              // [8][n_lines][ld]
+};
+hipError_t launch_geometry_dalpha(GeoDalphaArgs& a, hipStream_t st);
+
+// geometry-fed points with the exact gradient of gam from ONE line per point and its alpha-tangent (ibs_exact_tangent.hip): the
+// stages, the persistent grid and the per-wave workspace (exact_points_ws) of k_exact_points
+struct ExactTangentArgs {
+  int n_pts, N; double h; long ld;
+  const double *geo, *geo_da;                                         // both [8][n_pts][ld]: the layout of the two geometry calls
+  const double* theta0; const double* sigma;                          // theta0 [n_pts]; sigma [n_pts] or null = lam_max's eigenpair
+  double *val, *jac;                                                  // [n_pts], [n_pts][2] (required)
+  double* gam; double* lam; int* idx; int* info;                      // optional
+  double* work; size_t work_doubles; long n_waves;                    // the launch refuses less than min(n_pts, n_waves) waves' worth
+};
+hipError_t launch_obj_w_grad_exact_tangent(const ExactTangentArgs& a, hipStream_t st);
+
 template <typename T> struct RefineEvalArgs;
 struct LaunchTable {
   hipError_t (*gcf_f64[kMaxM + 1])(const GcfArgs<double>&, hipStream_t);

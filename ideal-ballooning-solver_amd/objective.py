@@ -100,7 +100,8 @@ class AdjointStep:
     per boundary DOF (BASELINE configs[3]: 73 x 5 surfaces x 24 alpha x 15 theta0, N = 969).  Like the scan driver it works on
     lam_max's eigenpair by default; eigenpair="nearest" runs every equilibrium's scan in upstream's mode (the eigenpair nearest
     sigma = 1.0 / 1.3 |gam| + 0.05 / 0.42: BallooningScan's eigenpair="nearest"), with the same chunking, gather and objective.
-    jac="exact" refines every surface on the exact gradient of gam (BallooningScan's jac="exact"); "reference" is the default.
+    jac="exact" refines every surface on the exact gradient of gam (BallooningScan's jac="exact"), jac="exact_tangent" on the
+    gradient that is exact in alpha as well, from one line per point (BallooningScan's jac="exact_tangent"); "reference" is the default.
     certify=True (eigenpair="max" only, else ValueError) certifies and re-closes the coarse tables and the final solves of every
     equilibrium (BallooningScan's certify=True; the refinement's own evaluations are not certified): the counts travel with the rows'
     one copy into .last_certificate = dict(checked, reclosed, failed), summed over the ranks; failed > 0 raises IbsError.

@@ -89,12 +89,16 @@ def check_eigenpair(eigenpair):
 # lanes per grid point of the geometry kernel in the rounds of marginal(refine=True) (option "geo_lpp"; BallooningScan._marginal_points)
 MARGINAL_GEO_LPP = 1
 
-JACS = ("reference", "exact")
+JACS = ("reference", "exact", "exact_tangent")
+
+
+class JacError(IbsError, ValueError):
+    """an unknown jac value: an IbsError that is, like the drivers' other option errors (eigenpair, certify), a ValueError as well"""
 
 
 def check_jac(jac):
     if jac not in JACS:
-        raise ValueError("jac must be 'reference' or 'exact', not %r" % (jac,))
+        raise JacError("jac must be 'reference', 'exact' or 'exact_tangent', not %r" % (jac,))
     return jac
 
 
@@ -107,6 +111,10 @@ class BallooningScan:
     jac="reference" (the default): the refinement runs on upstream's Hellmann-Feynman gradient (utils.py:1676-1680, 1721-1725), which
     puts gam in place of lam and is 0.1-5 % off the gam it comes with.  jac="exact": it runs on the exact derivative of that gam,
     batched on the device (ibs_obj_w_grad_exact_f64), for either eigenpair; the coarse scan and the final solve are the same.
+    That derivative is exact in theta0 and, in alpha, the reference's central difference of the rows over del_alpha (three lines per
+    point).  jac="exact_tangent" (tables= and device= required, else IbsError: upstream's callback has no tangent): exact in alpha as
+    well, from ONE line per point -- every round is one forward geometry launch, one alpha-tangent launch
+    (ibs_fieldline_geometry_dalpha_f64) and one point launch (ibs_obj_w_grad_exact_tangent_f64); del_alpha plays no part.
     certify=True (eigenpair="max" only; "nearest" already runs in division form with its a-priori bound: ValueError): every eigenvalue
     of the coarse scan's table is certified by a division-form Sturm count pair at lam +- 4 N eps ||A|| and re-closed in division form
     where the pair refuses it (Context.certify_scan / reclose_scan), the per-surface maximum is then taken again from the table
@@ -124,11 +132,15 @@ class BallooningScan:
         copy returns the rows.  surf_index[k] = index of surface k (of rho_arr) in `tables`; default: the surface of
         tables.s nearest to rho_arr[k].  Table sets that hold several equilibria (SurfaceTables.from_wouts: s repeats
         per equilibrium) need the explicit index.
-        eigenpair: "max" or "nearest"; jac: "reference" or "exact" (see the class docstring); anything else raises ValueError."""
+        eigenpair: "max" or "nearest" (anything else raises ValueError); jac: "reference", "exact" or "exact_tangent" (see the class
+        docstring; anything else raises IbsError, which is a ValueError too)."""
         self.eigenpair = check_eigenpair(eigenpair)
         self.nearest = eigenpair == "nearest"
         self.jac = check_jac(jac)
-        self.exact = jac == "exact"
+        self.tangent = jac == "exact_tangent"
+        self.exact = jac == "exact" or self.tangent        # (the host-driven refinement on ibs_obj_w_grad_exact*_f64)
+        if self.tangent and (tables is None or device is None):
+            raise IbsError("jac='exact_tangent' needs tables= and device=: a host geometry callable has no alpha-tangent")
         self.certify = bool(certify)
         if self.certify and self.nearest:
             raise ValueError("certify=True applies to eigenpair='max': eigenpair='nearest' runs in division form with its a-priori bound")
@@ -348,9 +360,13 @@ class BallooningScan:
         return out
 
     # -- jac="exact": val and the exact gradient at a batch of points (numpy or device tensors in, numpy out); sigma None = lam_max's pair
-    def _obj_exact(self, geo, t0, sigma):
+    # (geo_da: the alpha-tangent planes of jac="exact_tangent", geo then being the (8, n, N) planes of the points' own lines)
+    def _obj_exact(self, geo, t0, sigma, geo_da=None):
         from .solver import EXACT_VJP_SHIFT, vjp_status_message
-        val, jac, r = self.ctx.obj_w_grad_exact(self.h, geo, t0, self.del_alpha, sigma=sigma, want_info=True)
+        if geo_da is not None:
+            val, jac, r = self.ctx.obj_w_grad_exact_tangent(self.h, geo, geo_da, t0, sigma=sigma, want_info=True)
+        else:
+            val, jac, r = self.ctx.obj_w_grad_exact(self.h, geo, t0, self.del_alpha, sigma=sigma, want_info=True)
         host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
         val, jac = host(val), host(jac)
         vst = (host(r["info"]) >> EXACT_VJP_SHIFT) & 3
@@ -365,6 +381,10 @@ class BallooningScan:
     def obj_w_grad(self, x, s, sigma0=None):
         a, t0 = float(x[0]), float(x[1])
         d = self.del_alpha
+        if self.tangent:
+            js = np.array([int(np.argmin(np.abs(self.tables.s - s)))], dtype=np.int32)
+            val, jac = self.batched_obj_w_grad(js, np.array([[a, t0]]), None if sigma0 is None else np.array([float(sigma0)]))
+            return float(val[0]), np.asarray(jac[0], dtype=np.float64)
         geo = np.asarray(self.fieldlines(s, np.array([a - 0.5 * d, a, a + 0.5 * d])))
         if self.exact:
             val, jac = self._obj_exact(geo[None], np.array([t0]), float(sigma0) if self.nearest else None)
@@ -399,10 +419,19 @@ class BallooningScan:
     def batched_obj_w_grad(self, surf_idx, X, sigma=None):
         """objective and gradient at X[k] = (alpha, theta0) of surface surf_idx[k] for all k at once
         (device geometry for the 3 n lines, then the fused obj_w_grad kernel; eigenpair="nearest": the eigenpair nearest
-        sigma[k], ibs_obj_w_grad_nearest_f64; jac="exact": ibs_obj_w_grad_exact_f64, for either eigenpair).
+        sigma[k], ibs_obj_w_grad_nearest_f64; jac="exact": ibs_obj_w_grad_exact_f64, for either eigenpair; jac="exact_tangent": the
+        geometry of the n lines themselves by the row kernels, their alpha-tangent, then ibs_obj_w_grad_exact_tangent_f64).
         Returns (val (n,), jac (n, 2))."""
         n = len(surf_idx)
         d = self.del_alpha
+        if self.tangent:
+            import torch
+            al = np.ascontiguousarray(X[:, 0])
+            r = self.ctx.fieldline_geometry(self.tables, surf_idx, al, self.theta, device=self.device)
+            ra = self.ctx.fieldline_geometry_dalpha(self.tables, surf_idx, al, self.theta, device=self.device)
+            t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
+            sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device) if self.nearest else None
+            return self._obj_exact(r["geo"], t0, sg, geo_da=ra["geo_da"])
         al = np.stack([X[:, 0] - 0.5 * d, X[:, 0], X[:, 0] + 0.5 * d], axis=1).reshape(-1)
         r = self.ctx.fieldline_geometry(self.tables, np.repeat(surf_idx, 3), al, self.theta, device=self.device)
         N = len(self.theta)
@@ -514,7 +543,8 @@ class BallooningScan:
         the host-driven L-BFGS-B (refine_batched: one geometry + ibs_obj_w_grad_nearest_f64 launch per round) -> final geometry +
         ibs_gamma_points_nearest_f64 at 0.42.  A solve counts as failed on status bits 0-1 only (bit 5, a tie, is informational).
         jac="exact": the refinement is the host-driven one as well, for either eigenpair (ibs_refine_f64 has no exact form): one
-        geometry + ibs_obj_w_grad_exact_f64 launch per round; everything else as above.
+        geometry + ibs_obj_w_grad_exact_f64 launch per round; everything else as above.  jac="exact_tangent": the same loop with one
+        geometry, one alpha-tangent and one ibs_obj_w_grad_exact_tangent_f64 launch per round, on one line per point.
         chunks: optional list of (c0, c1) ranges of owned surfaces: the coarse part (geometry, scan, starts) runs chunk by chunk,
         and fill(c0, c1) -- if given -- is called on the host before a chunk's launches (AdjointStep: the tables of the next
         equilibria are computed and uploaded while the GPU works on the previous ones).

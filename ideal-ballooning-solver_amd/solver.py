@@ -602,6 +602,30 @@ class Context:
                                                  plam, pidx, pinfo, ar.mem), "ibs_obj_w_grad_exact_f64")
         return (val, jac, dict(gam=gam, lam=lam, idx=idx, info=info)) if want_info else (val, jac)
 
+    def obj_w_grad_exact_tangent(self, h, geo, geo_da, theta0, sigma=None, want_info=False):
+        """obj_w_grad_exact with the derivative in alpha exact as well, from ONE line per point (ibs_obj_w_grad_exact_tangent_f64):
+        geo, geo_da (8, n_pts, N) as fieldline_geometry and fieldline_geometry_dalpha return them for the same lines, theta0 (n_pts,);
+        no del_alpha.  sigma, the return values and the status bits are obj_w_grad_exact's; val, jac[:, 1] and the info dict are the
+        bits obj_w_grad_exact gives on the same centre line."""
+        ar = _Args()
+        eight, n_pts, N = geo.shape
+        if eight != 8 or tuple(geo_da.shape) != (8, n_pts, N):
+            raise IbsError("geo and geo_da must both be (8, n_pts, N)")
+        pg, pd, pt = ar.inp(geo), ar.inp(geo_da), ar.inp(theta0)
+        ref = geo if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        psig = self._sigma_rows(ar, sigma, (n_pts,), ref) if sigma is not None else C.c_void_p(None)
+        val, pval = ar.out((n_pts,), ref)
+        jac, pjac = ar.out((n_pts, 2), ref)
+        gam, pgam = ar.out((n_pts,), ref, want=want_info)
+        lam, plam = ar.out((n_pts,), ref, want=want_info)
+        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        check(self._lib.ibs_obj_w_grad_exact_tangent_f64(self._h, n_pts, N, float(h), pg, pd, N, pt, psig, pval, pjac, pgam, plam, pidx,
+                                                         pinfo, ar.mem), "ibs_obj_w_grad_exact_tangent_f64")
+        return (val, jac, dict(gam=gam, lam=lam, idx=idx, info=info)) if want_info else (val, jac)
+
     def gamma_points_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma,
                              want_X=False, want_info=False):
         """gamma_points with the eigenpair NEAREST sigma (ibs_gamma_points_nearest_f64: the final solve of ball_scan.py:322-339,
@@ -732,6 +756,42 @@ class Context:
               "ibs_fieldline_geometry_vjp_f64")
         self._keep = (d_ls, d_la, d_th, gb, db, dev)
         return {k + "_bar": outs[k] for k in names}
+
+    def fieldline_geometry_dalpha(self, tables, line_surf, line_alpha, theta, device=None):
+        """alpha-tangent of fieldline_geometry (ibs_fieldline_geometry_dalpha_f64): dict(geo_da=(8, n_lines, N)), the derivative of the
+        eight arrays of every line in its own alpha -- the derivative in place of the central difference of utils.py:1641-1646 /
+        1683-1718.  dPdrho does not depend on alpha and has no tangent.  One lane per grid point: a line alone gives its batch bits.
+        device=None: numpy in / numpy out (staged);  device=torch.device(...): numpy or device tensors in, a device tensor out."""
+        n_lines, N = len(line_surf), len(theta)
+        head = (self._h, len(tables.s), len(tables.xm), len(tables.xm_nyq))
+        if device is None:
+            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
+            la = np.ascontiguousarray(line_alpha, dtype=np.float64)
+            th = np.ascontiguousarray(theta, dtype=np.float64)
+            host = [tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal]
+            out = np.empty((8, n_lines, N))
+            p = lambda a: C.c_void_p(a.ctypes.data)
+            check(self._lib.ibs_fieldline_geometry_dalpha_f64(*head, *[p(a) for a in host], n_lines, p(ls), p(la), N, p(th), N, p(out),
+                                                              MEM_HOST), "ibs_fieldline_geometry_dalpha_f64")
+            return dict(geo_da=out)
+        import torch
+        dev = self._device_tables(tables, device)[:7]
+        if all(_is_torch(a) for a in (line_surf, line_alpha, theta)):
+            d_ls, d_la, d_th = line_surf.to(torch.int32).contiguous(), line_alpha.to(torch.float64).contiguous(), theta.to(torch.float64).contiguous()
+        else:
+            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
+            if ls.size and (ls.min() < 0 or ls.max() >= len(tables.s)):
+                raise IbsError("line_surf out of range")
+            d_ls = torch.from_numpy(ls).to(device)
+            d_la = torch.from_numpy(np.ascontiguousarray(line_alpha, dtype=np.float64)).to(device)
+            d_th = torch.from_numpy(np.ascontiguousarray(theta, dtype=np.float64)).to(device)
+        out = torch.empty((8, n_lines, N), dtype=torch.float64, device=device)
+        self._stream_from_torch(out)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        check(self._lib.ibs_fieldline_geometry_dalpha_f64(*head, *[p(t) for t in dev], n_lines, p(d_ls), p(d_la), N, p(d_th), N, p(out),
+                                                          MEM_DEVICE), "ibs_fieldline_geometry_dalpha_f64")
+        self._keep = (d_ls, d_la, d_th, dev)
+        return dict(geo_da=out)
 
     def _device_tables(self, tables, device):
         """the surface/mode/row tables of `tables` resident on `device` (uploaded once, cached on the object)"""

@@ -244,6 +244,22 @@ int ibs_obj_w_grad_exact_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, c
                              const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
                              double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem);
 
+/* ibs_obj_w_grad_exact_f64 with the derivative in alpha exact as well, from ONE field line per point.
+ * Replaces: the central difference of the rows over del_alpha of utils.py:1683-1718 (and the two side lines of utils.py:1641-1646) by
+ * the contraction of d gam / d (g, c, f) with the alpha-derivative of the rows, formed from geo_da = the output of
+ * ibs_fieldline_geometry_dalpha_f64 for the same lines; d|gradpar| = sgn(gradpar) d gradpar, and dPdrho is held fixed (it does not
+ * depend on alpha).  There is no del_alpha.
+ *   geo, geo_da [8][n_pts][ld]: the layout both geometry calls write (plane k of point p at (k n_pts + p) ld), no permuted copy;
+ *   theta0, sigma, val, jac, gam, lam, idx, info: exactly as in ibs_obj_w_grad_exact_f64, status bits included.  val, gam, lam, idx,
+ *   info and jac[.][1] are the bits ibs_obj_w_grad_exact_f64 gives on the same centre line.  A non-finite entry of geo_da gives
+ *   jac[p][0] = NaN and nothing else.
+ * FP64, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED, checked before the context is touched): one wavefront
+ * per point, the stages and the workspace of ibs_obj_w_grad_exact_f64 (csrc/ibs_exact_tangent.hip).  No floating-point atomics:
+ * results are bitwise repeatable and independent of the batch. */
+int ibs_obj_w_grad_exact_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, const double* geo_da,
+                                     int64_t ld, const double* theta0, const double* sigma, double* val, double* jac,
+                                     double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem);
+
 /* Marginal stability of raw systems: the factor s* by which c (i.e. the pressure gradient: c is linear in dPdrho, utils.py:1560-1562)
  * may be scaled, at fixed g, before the system goes unstable; s* < 1 = unstable now.  Nothing upstream corresponds: the quantity
  * generalises the marginal-stability scan of the reference's s-alpha test (bishop_ball_s-alpha.py:90-115), which only reports a
@@ -419,6 +435,30 @@ int ibs_fieldline_geometry_vjp_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, 
                                    const double* line_alpha, int32_t N, const double* theta, int64_t ld,
                                    const double* geo_bar, const double* dPdrho_bar, double* tab_mn_bar,
                                    double* tab_nyq_bar, double* scal_bar, double* alpha_bar, int32_t mem);
+
+/* Tangent of ibs_fieldline_geometry_f64 in the line label: d/d alpha of the eight arrays of every line, in forward mode.
+ * Replaces: the central difference of the rows in utils.py:1641-1646 / 1683-1718 (three field lines per point, the side lines
+ * del_alpha / 2 away, an O(del_alpha^2) error of 1e-5 .. 3e-4 of an array's scale at upstream's 0.004) by their derivative.  The
+ * arithmetic differentiated is utils.py:359-720 in the plain form ibs_fieldline_geometry_vjp_f64 recomputes: phi = (theta - alpha) /
+ * iota so phi' = -1 / iota; the theta_pest -> theta_vmec root solve (utils.py:391-416) by the implicit-function theorem at the
+ * converged root, theta_vmec' = -Lambda_phi phi' / (1 + Lambda_theta), not through the secant iterations; every synthesised sum
+ * S' = sum coef trig'(m theta_vmec - n phi) (m theta_vmec' - n phi'), taken as two partial sums in the same pass over the modes as
+ * the values; then the metric algebra on (value, tangent) pairs.
+ * dPdrho has no alpha-tangent and none is returned: cvdrift - gbdrift is the pressure term -2 mu0 sgn(Psi') p' B_ref Aminor^2 sqrt(s)
+ * / (Psi' |B|^2) (utils.py:700-720) and bmag^2 = |B|^2 / B_ref^2, so (cvdrift - gbdrift) bmag^2 holds surface quantities alone and
+ * dPdrho = -1/2 mean(...) (ball_scan.py:262) is the same on every line of a surface; a caller that differentiates rows in alpha holds
+ * it fixed.
+ *   every forward input as for ibs_fieldline_geometry_vjp_f64 up to ld (mode rows are not needed: any mode ordering);
+ *   geo_da [8][n_lines][ld]: d/d alpha of bmag gradpar cvdrift cvdrift0 gds2 gds21 gds22 gbdrift; entries N..ld-1 of a row are
+ *   never written.  A grid point whose forward evaluation is not finite gets NaN in its eight entries, nothing else is touched.
+ * One lane per grid point, no atomics and no cross-lane sums: a line alone gives the bits it has in a batch, with host or device
+ * pointers (csrc/ibs_geometry_tangent.hip).  Any N >= 2; n_lines and n_surf <= 65535.  IBS_MEM_HOST: synchronous; IBS_MEM_DEVICE:
+ * asynchronous on the context's stream (device-resident line_surf is clamped to [0, n_surf), like the forward call's). */
+int ibs_fieldline_geometry_dalpha_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_nyq, const double* xm,
+                                      const double* xn, const double* xm_nyq, const double* xn_nyq, const double* tab_mn,
+                                      const double* tab_nyq, const double* scal, int32_t n_lines, const int32_t* line_surf,
+                                      const double* line_alpha, int32_t N, const double* theta, int64_t ld, double* geo_da,
+                                      int32_t mem);
 
 /* Host part of the geometry producer: the per-surface Fourier coefficient vectors of n_eq equilibria at n_s surfaces.
  * Replaces: vmec_splines (utils.py:58-119: one InterpolatedUnivariateSpline per mode and array) + their evaluation at the
