@@ -17,7 +17,7 @@ import warnings
 
 import torch
 
-from .solver import VjpStatusWarning, default_context, vjp_status_message
+from .solver import IbsError, VjpStatusWarning, default_context, vjp_status_message
 
 _MODES = ("max", "nearest")
 
@@ -81,6 +81,41 @@ def marginal_scale(h, g, c, ctx=None):
     (Hellmann-Feynman on the discrete pencil, exact for it).  Systems with an infinite margin (no c_j > 0) get zero gradients,
     flagged ones (invalid data) NaN."""
     return _MarginalScale.apply(float(h), g, c, ctx or default_context(g.device.index or 0))
+
+
+class _MarginalPoints(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, h, geo, geo_da, theta0, ictx):
+        r = ictx.marginal_obj_w_grad_tangent(h, geo, geo_da, theta0, want_grad=True, want_geo_bar=True, want_info=True)
+        nbad = int(((r["info"] >> 16) & 3).ne(0).sum().item())                 # (bit 8, an infinite margin, is informational)
+        if nbad:
+            raise IbsError("%d of %d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)"
+                           % (nbad, r["info"].numel()))
+        fctx.save_for_backward(r["geo_bar"], r["dscale"])
+        fctx.mark_non_differentiable(r["dscale"], r["dPdrho"])
+        return r["scale"], r["dscale"], r["dPdrho"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, s_bar, _ds_bar, _dP_bar):
+        geo_bar, dscale = fctx.saved_tensors
+        return None, geo_bar * s_bar[None, :, None], None, dscale[:, 1] * s_bar, None
+
+
+def marginal_points_full(h, geo, geo_da, theta0, ctx=None):
+    """marginal_points with the alpha-tangent planes geo_da (8, n_pts, N) of the lines given: (scale, dscale (n_pts, 2) = (d s* / d alpha,
+    d s* / d theta0), dPdrho), the last two without gradient (BallooningScan.marginal_sensitivity)"""
+    return _MarginalPoints.apply(float(h), geo, geo_da, theta0, ctx or default_context(geo.device.index or 0))
+
+
+def marginal_points(h, geo, theta0, ctx=None):
+    """s* (n_pts,) of the field lines geo (8, n_pts, N) -- the planes fieldline_geometry returns -- at theta0 (n_pts,), each line with
+    its own dPdrho: the critical scale of the pressure gradient at fixed geometry arrays (Context.marginal_obj_w_grad_tangent,
+    ibs_marginal_obj_w_grad_tangent_f64).  Differentiable in geo and theta0: the backward is the cotangent times the planes geo_bar and
+    the theta0 derivative the forward's kernel returns (Hellmann-Feynman on the discrete pencil, exact for it; the dependence through
+    the line's dPdrho is inside geo_bar).  Composes with fieldline_geometry, so that s.sum().backward() reaches tab_mn, tab_nyq, scal
+    and line_alpha.  Points with an infinite margin (no c_j > 0) get zero gradients; status bits 0-1 raise IbsError."""
+    return marginal_points_full(h, geo, torch.zeros_like(geo), theta0, ctx)[0]
 
 
 def growth_rate(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, eigenpair="max", sigma=None, ctx=None):

@@ -1082,6 +1082,38 @@ int ibs_marginal_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h
   });
 }
 
+// the same objective from ONE line per point and the alpha-tangent of its geometry: the gradient exact in alpha as well, and the
+// cotangent planes of s* for the geometry's VJP (k_marginal_tangent_points)
+int ibs_marginal_obj_w_grad_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, const double* geo_da,
+                                        int64_t ld, const double* theta0, double* val, double* jac, double* scale, double* dscale,
+                                        double* dPdrho, double* geo_bar, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!geo || !theta0 || !val) return fail(IBS_ERR_ARG, "null argument (geo, theta0 and val are required)");
+  if (!geo_da && (jac || dscale)) return fail(IBS_ERR_ARG, "null geo_da (required with jac or dscale)");
+  if (n_pts < 0 || ld < N) return fail(IBS_ERR_ARG, "bad arguments (n_pts=%d ld=%lld N=%d)", n_pts, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_pts == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n = (size_t)n_pts, geo_elems = n * 8 * (size_t)ld;
+  ibs::MarginalTangentArgs a{};
+  a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld;
+  // (host pointers: the rows of geo_bar are packed on the device and come back one by one, so the caller's entries N..ld-1 stay as they were)
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, geo_elems); a.geo_da = s.in(geo_da, geo_elems); a.theta0 = s.in(theta0, n);
+    a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.scale = s.out(scale, n); a.dscale = s.out(dscale, 2 * n);
+    a.dPdrho = s.out(dPdrho, n);
+    a.geo_bar = s.out_rows(geo_bar, 8 * n, N, ld); a.ld_bar = (long)s.rows_ld(N, ld);
+    a.info = s.status(info, n);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    const int nw = long_waves(ctx, a.n_pts);
+    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, true).total * sizeof(double))) return r;
+    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    HIPCHK(ibs::launch_marginal_tangent_points(a, ctx->stream));
+    return 0;
+  });
+}
+
 // Coarse scan with the nearest eigenpair: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
 // arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and solved by k_solve_gcf_nearest; chunks are
 // bounded by kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".

@@ -160,6 +160,17 @@ struct MarginalPointsArgs {
   double* work; size_t work_doubles; long n_waves;                  // the launch refuses less than min(n_pts, n_waves) waves' worth
 };
 hipError_t launch_marginal_points(const MarginalPointsArgs& a, hipStream_t st);
+// the same from ONE line per point and the alpha-tangent of its geometry, with the cotangent planes of s* (ibs_marginal_tangent.hip): the
+// persistent grid and the per-wave workspace of k_marginal_points
+struct MarginalTangentArgs {
+  int n_pts, N; double h; long ld;
+  const double *geo, *geo_da;                                       // both [8][n_pts][ld]; geo_da only with jac or dscale
+  const double* theta0;                                             // [n_pts]
+  double *val, *jac, *scale, *dscale, *dPdrho; int* info;           // as MarginalPointsArgs; val required
+  double* geo_bar; long ld_bar;                                     // optional [8][n_pts][ld_bar]: d scale / d geo, entries 0 .. N-1 of a row
+  double* work; size_t work_doubles; long n_waves;                  // the launch refuses less than min(n_pts, n_waves) waves' worth
+};
+hipError_t launch_marginal_tangent_points(const MarginalTangentArgs& a, hipStream_t st);
 hipError_t launch_sturm_long(const SturmArgs<double>& a, hipStream_t st);
 hipError_t launch_sturm_div(const SturmArgs<double>& a, hipStream_t st);     // lanes as systems, division form, any N
 template <typename T> struct ScanArgs;

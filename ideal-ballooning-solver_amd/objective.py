@@ -44,10 +44,18 @@ def linearised_dof_gradient(sens, wouts, f_other, steps, gam0, gamma_thresh=-2.0
     second-order terms in the step, a maximum that jumps to another (alpha, theta0) and the clipping of the maximiser to the scan's
     box are not seen.  72 dot products per surface in place of 72 scans; pure numpy."""
     gam0 = np.asarray(gam0, dtype=np.float64)
-    n_eq, n_s = len(wouts), len(gam0)
-    if len(sens) != n_s:
+    if len(sens) != len(gam0):
         raise ValueError("linearised_dof_gradient: one sensitivity per surface")
-    gam = np.tile(gam0, (n_eq, 1))
+    gam = _linearised_rows(sens, wouts, gam0, np.ones(len(gam0), dtype=bool))
+    f0 = ballooning_objective(f_other, gam, gamma_thresh, prefac)
+    return dof_fd_gradient(f0, steps)
+
+
+def _linearised_rows(sens, wouts, v0, use):
+    """(n_eq, n_surf): v0[s] + sum_keys <sens[s][key], wouts[k][key] - wouts[0][key]> for every equilibrium k (row 0 = v0), on the
+    surfaces with use[s]; the others keep v0[s] in every row"""
+    n_eq, n_s = len(wouts), len(v0)
+    val = np.tile(v0, (n_eq, 1))
     w0 = wouts[0]
     for k in range(1, n_eq):
         for key in WOUT_SENSITIVITY_KEYS:
@@ -55,9 +63,30 @@ def linearised_dof_gradient(sens, wouts, f_other, steps, gam0, gamma_thresh=-2.0
             if not np.any(d):
                 continue
             for si in range(n_s):
-                gam[k, si] += float(np.sum(np.asarray(sens[si][key]) * d))
-    f0 = ballooning_objective(f_other, gam, gamma_thresh, prefac)
-    return dof_fd_gradient(f0, steps)
+                if use[si]:
+                    val[k, si] += float(np.sum(np.asarray(sens[si][key]) * d))
+    return val
+
+
+def linearised_margin_gradient(sens, wouts, steps, scale0):
+    """the forward differences AdjointStep.marginal(wouts, steps)["dscale"] with the margins of the DOF-perturbed equilibria LINEARISED
+    about the base equilibrium instead of scanned and refined:
+        s*_s(k) = scale0[s] + sum_keys <sens[s][key], wouts[k][key] - wouts[0][key]>,     k = 1 .. n_dof,
+    then (s*(k) - s*(0)) / steps[k] -> (n_dof, n_surf).  sens: per surface, the cotangents d s*_s / d wout of the base equilibrium
+    (AdjointStep.marginal_sensitivity(...)["wout_bar"]); wouts: the n_dof + 1 equilibria, entry 0 = base; steps (n_dof + 1,), entry 0
+    unused; scale0 (n_surf,) the base equilibrium's margins.  A surface whose scale0 is not finite (no scale makes it unstable: its
+    sensitivities are zero) gets a zero column.
+    What it is: a first-order estimate at FIXED (alpha*, theta0*).  At a refined minimum that is a stationary point of the s* whose
+    derivative is taken (marginal(refine=True, jac="exact_tangent")), the derivative of the per-surface minimum equals the partial
+    derivative at the fixed minimiser (envelope theorem), so to first order nothing is lost by not re-scanning; second-order terms in
+    the step, a minimum that jumps to another (alpha, theta0) and the clipping of the minimiser to the scan's box are not seen.  s*
+    scales dPdrho at FROZEN geometry arrays: away from s* = 1 it is a local margin, and so is its derivative.  Pure numpy."""
+    scale0 = np.asarray(scale0, dtype=np.float64)
+    if len(sens) != len(scale0):
+        raise ValueError("linearised_margin_gradient: one sensitivity per surface")
+    ok = np.isfinite(scale0)
+    val = _linearised_rows(sens, wouts, np.where(ok, scale0, 0.0), ok)
+    return (val[1:] - val[0]) / np.asarray(steps, dtype=np.float64)[1:, None]
 
 
 def dof_steps(x0, isabs, abs_step=1.0e-3, rel_step=2.0e-3):
@@ -254,16 +283,46 @@ class AdjointStep:
         return dict(gam=host["gam"], alpha=pts[:, 0].copy(), theta0=pts[:, 1].copy(), dgam_dalpha=host["dgam_dalpha"],
                     dgam_dtheta0=host["dgam_dtheta0"], wout_bar=wout_bar)
 
-    def marginal(self, wouts, steps=None, refine=True):
+    def marginal_sensitivity(self, wout0, points=None, jac="exact_tangent"):
+        """exact derivatives of every surface's critical scale s* of the BASE equilibrium wout0, pulled back to its wout data: the
+        margin's counterpart of sensitivity().  points (n_surf, 2) = (alpha, theta0) per surface; None: the refined margin of each
+        surface (one BallooningScan.marginal(refine=True, jac=jac) of wout0; with jac="exact_tangent" the refined point is a
+        stationary point of the s* differentiated here, which the envelope theorem needs).  One geometry launch, one alpha-tangent
+        launch, one point launch with the cotangent planes, one geometry-VJP (BallooningScan.marginal_sensitivity), then
+        SurfaceTables.pullback per surface.  Returns dict(scale, alpha, theta0, dscale_dalpha, dscale_dtheta0: (n_surf,); wout_bar:
+        per surface a dict of d s*_s / d (rmnc, ..., bsubvmnc (modes, ns), iotas, pres, phi (ns,), Aminor_p) -- the `sens` of
+        linearised_margin_gradient).  Not sharded over ranks: every caller computes the same.  The frozen-geometry caveat of
+        BallooningScan.marginal applies."""
+        from .geometry import SurfaceTables
+        from .scan import BallooningScan
+        tables = SurfaceTables.from_wout(wout0, self.svals)
+        ns = len(self.svals)
+        scan = BallooningScan(self.ctx, None, self.theta, self.svals, nalpha=self.nalpha, ntheta0=self.ntheta0, del_alpha=self.del_alpha,
+                              tables=tables, device=self.device, surf_index=np.arange(ns))
+        if points is None:
+            m = scan.marginal(refine=True, jac=jac)
+            points = np.stack([m["alpha"], m["theta0"]], axis=1)
+        r = scan.marginal_sensitivity(points)
+        host = {k: v.detach().cpu().numpy() for k, v in r.items()}
+        bars = tables.pullback(host["tab_mn_bar"], host["tab_nyq_bar"], host["scal_bar"], per_surface=True)[0]
+        # (surface k of the scan is its own copy of table row k: its cotangents live in row k alone)
+        wout_bar = [{key: np.ascontiguousarray(v[k]) for key, v in bars.items()} for k in range(ns)]
+        pts = np.asarray(points, dtype=np.float64).reshape(ns, 2)
+        return dict(scale=host["scale"], alpha=pts[:, 0].copy(), theta0=pts[:, 1].copy(), dscale_dalpha=host["dscale_dalpha"],
+                    dscale_dtheta0=host["dscale_dtheta0"], wout_bar=wout_bar)
+
+    def marginal(self, wouts, steps=None, refine=True, jac="reference"):
         """the marginal-stability scale s* of every surface of every equilibrium of the step (BallooningScan.marginal: the smallest
         critical scale of dPdrho over (alpha, theta0), refined from the coarse minimum unless refine=False), on the SurfaceTables
         frame, the sharding of equilibria over ranks and the ONE all-gather of run().  wouts as in run().
         Returns dict(scale, alpha, theta0: (n_eq, n_surf)), identical on every rank; with steps (n_eq,), entry 0 unused, also dscale
         (n_dof, n_surf) = (scale[1:] - scale[0]) / steps[1:, None]: the forward differences of sims_runner_NCSX.py:258-261 applied
-        to the margin.  scale = inf (no scale makes the surface unstable) is a result, not a failure."""
+        to the margin.  scale = inf (no scale makes the surface unstable) is a result, not a failure.  jac: the gradient the
+        refinement runs on, as in BallooningScan.marginal ("reference", the default, or "exact_tangent")."""
         import torch
         from .geometry import SurfaceTables
-        from .scan import gather_rows_tensor
+        from .scan import check_marginal_jac, gather_rows_tensor
+        check_marginal_jac(jac)
         n_eq, ns = len(wouts), len(self.svals)
         own = shard_dofs(n_eq, self.rank, self.world)
         err = None
@@ -280,7 +339,7 @@ class AdjointStep:
                 r0, r1 = fr.fill(0, mine, self.n_threads)
                 if pinned:
                     self.ctx.upload_tables_rows(fr, self.device, r0, r1)
-                m = scan.marginal(refine=refine)
+                m = scan.marginal(refine=refine, jac=jac)
                 local = np.stack([m["scale"], m["alpha"], m["theta0"]], axis=1).reshape(len(own), 3 * ns)
                 rows = torch.from_numpy(np.ascontiguousarray(local, dtype=np.float64)).to(self.device)
             else:

@@ -102,6 +102,15 @@ def check_jac(jac):
     return jac
 
 
+MARGINAL_JACS = ("reference", "exact_tangent")
+
+
+def check_marginal_jac(jac):
+    if jac not in MARGINAL_JACS:
+        raise JacError("the margin's jac must be 'reference' or 'exact_tangent', not %r" % (jac,))
+    return jac
+
+
 class BallooningScan:
     """Coarse (alpha, theta0) scan -> argmax -> L-BFGS-B refinement -> final solve, per surface.
     eigenpair="max" (the default): every stage returns lam_max's eigenpair (the physical growth rate).  eigenpair="nearest":
@@ -244,7 +253,7 @@ class BallooningScan:
         return np.asarray(cnt).reshape(len(self.own), na, nt)
 
     # -- marginal stability on the coarse grid of the surfaces this rank owns, one launch
-    def marginal(self, refine=False, maxiter=30, ftol=5.0e-11, gtol=2.0e-8):
+    def marginal(self, refine=False, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, jac="reference"):
         """per owned surface, the smallest critical scale s* of dPdrho over the coarse (alpha, theta0) grid and where it sits
         (Context.marginal_scan): dict(scale (n_own,), alpha, theta0, index (n_own, 2) = (i_alpha, i_theta0) of the first minimum,
         table (n_own, nalpha, ntheta0)).  s* < 1: some line of the surface is unstable now; s* scales dPdrho at FIXED geometry
@@ -257,7 +266,17 @@ class BallooningScan:
         (n_own, 2) = (d s* / d alpha, d s* / d theta0) at the refined point, dPdrho (n_own,) of the refined line, evals (n_own,),
         task (n_own,) = the L-BFGS-B task codes (lbfgsb.TASKS) and rounds.  A surface's refinement does not depend on the surfaces
         refined beside it (the rounds' geometry runs in one form of the geometry kernel: MARGINAL_GEO_LPP).  A surface whose coarse table is all +inf stays at its
-        start point with scale = inf and no evaluation (its gradient is 0)."""
+        start point with scale = inf and no evaluation (its gradient is 0).
+        jac="reference" (the default): the rounds take d s* / d alpha from the del_alpha difference of the rows, three lines per point
+        (ibs_marginal_obj_w_grad_f64), exactly as before the option existed.  jac="exact_tangent" (tables= and device= required, else
+        IbsError; any other value is refused): d s* / d alpha is the derivative, from ONE line per point -- every round is one forward
+        geometry launch (in the same pinned form), one alpha-tangent launch (ibs_fieldline_geometry_dalpha_f64) and one point launch
+        (ibs_marginal_obj_w_grad_tangent_f64); the dict has the same keys and dscale is then exact in both variables, so the refined
+        point is a stationary point of the s* returned (marginal_sensitivity()).  Either mode leaves its (alpha, theta0) per owned
+        surface on the object for marginal_sensitivity()."""
+        tangent = check_marginal_jac(jac) == "exact_tangent"
+        if tangent and (self.tables is None or self.device is None):
+            raise IbsError("marginal(jac='exact_tangent') needs tables= and device=: a host geometry callable has no alpha-tangent")
         na, nt = len(self.alpha_scan), len(self.theta0_scan)
         if not self.own:
             tab = np.zeros((0, na, nt))
@@ -285,7 +304,10 @@ class BallooningScan:
         ia, it = k // nt, k % nt
         res = dict(scale=flat[np.arange(len(tab)), k], alpha=self.alpha_scan[ia], theta0=self.theta0_scan[it],
                    index=np.stack([ia, it], axis=1), table=tab)
-        return self._marginal_refine(res, maxiter, ftol, gtol) if refine else res
+        if refine:
+            res = self._marginal_refine(res, maxiter, ftol, gtol, tangent)
+        self._last_marginal_points = np.stack([res["alpha"], res["theta0"]], axis=1).astype(np.float64).reshape(len(tab), 2)
+        return res
 
     # -- the margin's objective at X[q] = (alpha, theta0) of owned surface own_idx[q], all at once: one geometry step (the three
     # lines of every point: the geometry kernel on `device`, staged through the host without one, or the host callable) and one
@@ -319,8 +341,28 @@ class BallooningScan:
                            "invalid data) or gave a non-finite objective" % (int(bad.sum()), n))
         return out
 
-    def _marginal_refine(self, res, maxiter, ftol, gtol):
+    # -- the same from ONE line per point (jac="exact_tangent"): the geometry of the points' own lines in the pinned form, their
+    # alpha-tangent, then one ibs_marginal_obj_w_grad_tangent_f64 launch; numpy out
+    def _marginal_points_tangent(self, own_idx, X):
+        import torch
+        n = len(own_idx)
+        surf = np.ascontiguousarray(self._own_surf()[own_idx])
+        al = np.ascontiguousarray(X[:, 0])
+        with self.ctx.option_default("geo_lpp", MARGINAL_GEO_LPP):
+            r = self.ctx.fieldline_geometry(self.tables, surf, al, self.theta, device=self.device)
+        ra = self.ctx.fieldline_geometry_dalpha(self.tables, surf, al, self.theta, device=self.device)
+        t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
+        out = self.ctx.marginal_obj_w_grad_tangent(self.h, r["geo"], ra["geo_da"], t0, want_grad=True, want_info=True)
+        out = {key: v.cpu().numpy() for key, v in out.items() if key != "nbad"}
+        bad = (((out["info"] >> 16) & 3) != 0) | ~np.isfinite(out["val"]) | ~np.isfinite(out["jac"]).all(axis=1)
+        if bad.any():
+            raise IbsError("%d of %d marginal-stability solves of the refinement were flagged (status bits 0-1: iteration cap or "
+                           "invalid data) or gave a non-finite objective" % (int(bad.sum()), n))
+        return out
+
+    def _marginal_refine(self, res, maxiter, ftol, gtol, tangent=False):
         """the lockstep loop of refine_batched on the margin's objective, from the first minimum of every coarse table"""
+        points = self._marginal_points_tangent if tangent else self._marginal_points
         import ctypes as C
         from . import _lib
         lib = _lib.lib()
@@ -338,7 +380,7 @@ class BallooningScan:
         rounds = 0
         while active.any():
             idx = np.nonzero(active)[0]
-            r = self._marginal_points(idx, x[idx])
+            r = points(idx, x[idx])
             rounds += 1
             evals[idx] += 1
             for q, k in enumerate(idx):
@@ -353,7 +395,7 @@ class BallooningScan:
         out = dict(res, coarse_scale=res["scale"], start=start, alpha=x[:, 0].copy(), theta0=x[:, 1].copy(), evals=evals, task=task,
                    rounds=rounds)
         if n:
-            fin = self._marginal_points(np.arange(n), x)
+            fin = points(np.arange(n), x)
             out.update(scale=fin["scale"], dscale=fin["dscale"], dPdrho=fin["dPdrho"])
         else:
             out.update(scale=np.zeros(0), dscale=np.zeros((0, 2)), dPdrho=np.zeros(0))
@@ -683,6 +725,44 @@ class BallooningScan:
         gam.sum().backward()
         return dict(gam=gam.detach().reshape(n), dgam_dalpha=al.grad, dgam_dtheta0=t0.grad, tab_mn_bar=tm.grad, tab_nyq_bar=tq.grad,
                     scal_bar=sc.grad)
+
+    def marginal_sensitivity(self, points=None):
+        """exact derivatives of every owned surface's critical scale s* at ONE point (alpha, theta0) of that surface, with respect to
+        the point and to the surface's own tables.  tables= + device= scans only.  points (n_own, 2) = (alpha, theta0); None: the
+        points of the last marginal() on this object (IbsError if there is none).  One geometry launch (in the pinned form of the
+        refinement's rounds), one alpha-tangent launch, one point launch with the cotangent planes (ibs_marginal_obj_w_grad_tangent_f64)
+        and one geometry-VJP launch (ibs_fieldline_geometry_vjp_f64) in which every surface's point works on its own copy of the
+        surface's tables, so that the cotangents stay per point.  s* is an eigenvalue of the discrete pencil: the derivatives are
+        those of the scale returned.  At a point refined with marginal(refine=True, jac="exact_tangent") that is interior to the box,
+        dscale_dalpha = dscale_dtheta0 = 0 and the table cotangents are d (min s*) / d tables by the envelope theorem.  A surface with
+        scale = inf has zero derivatives; status bits 0-1 raise IbsError.  The frozen-geometry caveat of marginal() applies.
+        Returns device tensors dict(scale, dscale_dalpha, dscale_dtheta0, dPdrho: (n_own,); tab_mn_bar (n_own, 6, mnmax), tab_nyq_bar
+        (n_own, 7, mnmax_nyq), scal_bar (n_own, 6))."""
+        import torch
+        from . import autograd as iag
+        if self.tables is None or self.device is None:
+            raise IbsError("marginal_sensitivity() needs a scan built with tables= and device=")
+        dev, own = self.device, self._own_surf()
+        n = len(own)
+        if points is None:
+            pts = getattr(self, "_last_marginal_points", None)
+            if pts is None or pts.shape[0] != n:
+                raise IbsError("marginal_sensitivity(): no points given and no marginal() on this object before")
+        else:
+            pts = np.asarray(points, dtype=np.float64).reshape(n, 2)
+        al, t0 = (torch.from_numpy(np.ascontiguousarray(pts[:, k])).to(dev) for k in (0, 1))
+        d = self.ctx._device_tables(self.tables, dev)
+        idx = torch.from_numpy(own.astype(np.int64)).to(dev)
+        tm, tq, sc = (d[k][idx].clone().requires_grad_(True) for k in (4, 5, 6))
+        th = self._resident_inputs()["th"]
+        with self.ctx.option_default("geo_lpp", MARGINAL_GEO_LPP):
+            geo, _ = iag.fieldline_geometry(self.tables, torch.arange(n, dtype=torch.int32, device=dev), al, th, tab_mn=tm, tab_nyq=tq,
+                                            scal=sc, ctx=self.ctx)
+        gda = self.ctx.fieldline_geometry_dalpha(self.tables, own, np.ascontiguousarray(pts[:, 0]), self.theta, device=dev)["geo_da"]
+        scale, dscale, dP = iag.marginal_points_full(self.h, geo, gda, t0, ctx=self.ctx)
+        scale.sum().backward()
+        return dict(scale=scale.detach(), dscale_dalpha=dscale[:, 0].contiguous(), dscale_dtheta0=dscale[:, 1].contiguous(), dPdrho=dP,
+                    tab_mn_bar=tm.grad, tab_nyq_bar=tq.grad, scal_bar=sc.grad)
 
     @staticmethod
     def _cert_counts(cert):

@@ -389,6 +389,43 @@ class Context:
             out.update(info=info)
         return out
 
+    def marginal_obj_w_grad_tangent(self, h, geo, geo_da, theta0, want_grad=True, want_geo_bar=False, want_info=False):
+        """marginal_obj_w_grad with the derivative in alpha exact as well, from ONE line per point (ibs_marginal_obj_w_grad_tangent_f64):
+        geo, geo_da (8, n_pts, N) as fieldline_geometry and fieldline_geometry_dalpha return them for the same lines, theta0 (n_pts,);
+        no del_alpha.  geo_da may be None with want_grad=False.  Returns dict(val = -1 / s*, scale = s*, dPdrho[, jac = dscale / s*^2,
+        dscale = (d s* / d alpha, d s* / d theta0): (n_pts, 2)][, geo_bar (8, n_pts, N) = d scale / d geo, the dependence through the
+        line's own dPdrho included: the cotangent to hand to fieldline_geometry_vjp][, info], nbad).  want_grad=False and
+        want_geo_bar=False: no mode is formed.  Status bits as marginal_obj_w_grad; geo_bar is zero with bit 8 and NaN with a failed
+        solve, and kept where only geo_da held invalid data (bit 1, NaN jac and dscale)."""
+        ar = _Args()
+        eight, n_pts, N = geo.shape
+        if eight != 8 or (geo_da is not None and tuple(geo_da.shape) != (8, n_pts, N)):
+            raise IbsError("geo and geo_da must both be (8, n_pts, N)")
+        if geo_da is None and want_grad:
+            raise IbsError("geo_da is required with want_grad")
+        pg, pt = ar.inp(geo), ar.inp(theta0)
+        pd = ar.inp(geo_da) if geo_da is not None else C.c_void_p(None)
+        ref = geo if ar.mem == MEM_DEVICE else None
+        if ref is not None:
+            self._stream_from_torch(ref)
+        val, pval = ar.out((n_pts,), ref)
+        jac, pjac = ar.out((n_pts, 2), ref, want=want_grad)
+        scale, pscale = ar.out((n_pts,), ref)
+        dscale, pdscale = ar.out((n_pts, 2), ref, want=want_grad)
+        dP, pdP = ar.out((n_pts,), ref)
+        gbar, pgbar = ar.out((8, n_pts, N), ref, want=want_geo_bar)
+        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
+        rc = check(self._lib.ibs_marginal_obj_w_grad_tangent_f64(self._h, n_pts, N, float(h), pg, pd, N, pt, pval, pjac, pscale, pdscale,
+                                                                 pdP, pgbar, pinfo, ar.mem), "ibs_marginal_obj_w_grad_tangent_f64")
+        out = dict(val=val, scale=scale, dPdrho=dP, nbad=rc)
+        if want_grad:
+            out.update(jac=jac, dscale=dscale)
+        if want_geo_bar:
+            out.update(geo_bar=gbar)
+        if want_info:
+            out.update(info=info)
+        return out
+
     def gamma_scan_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma, want_info=False):
         """the coarse scan of ball_scan.py:248-273 with the eigenpair nearest sigma, as upstream (sigma = 1.0 there: ball_scan.py:230);
         ibs_gamma_scan_nearest_f64.  Geometry arrays (n_lines, N); dPdrho (n_lines,); theta0 (n_theta0,); sigma a scalar or

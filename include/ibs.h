@@ -302,6 +302,31 @@ int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
 int ibs_marginal_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
                                 const double* theta0, double del_alpha, double* val, double* jac, double* scale, double* dscale,
                                 double* dPdrho, int32_t* info, int32_t mem);
+/* ibs_marginal_obj_w_grad_f64 with the derivative in alpha exact as well, from ONE field line per point, and the cotangent of s* in the
+ * geometry arrays.
+ * Replaces: the del_alpha difference of the rows of two side lines (utils.py:1683-1718 and the side lines of utils.py:1641-1646) by the
+ * contraction of d s* / d (g, c) with the alpha-derivative of the rows, formed from geo_da = the output of
+ * ibs_fieldline_geometry_dalpha_f64 for the same lines; d|gradpar| = sgn(gradpar) d gradpar, and dPdrho is held fixed (it does not
+ * depend on alpha).  There is no del_alpha.  s* is an eigenvalue of the discrete pencil, so Hellmann-Feynman is exact: dscale is the
+ * derivative of the scale returned in BOTH variables, with no adjoint solve.
+ *   geo, geo_da [8][n_pts][ld]: the layout both geometry calls write (plane k of point p at (k n_pts + p) ld), no permuted copy;
+ *   geo_da may be NULL only when jac and dscale both are (else IBS_ERR_ARG);
+ *   theta0, val (required), jac, scale, dscale, dPdrho, info: as in ibs_marginal_obj_w_grad_f64.  val, scale, dPdrho, info, jac[.][1]
+ *   and dscale[.][1] are what ibs_marginal_obj_w_grad_f64 gives on the same centre line;
+ *   geo_bar [8][n_pts][ld] (optional): the derivative of scale[p] in every entry of the eight arrays of point p that were read, the
+ *   dependence through the line's own dPdrho included -- pass it to ibs_fieldline_geometry_vjp_f64 with dPdrho_bar = NULL to get
+ *   d s* / d (tab_mn, tab_nyq, scal, alpha).  Closed form per grid point from the marginal mode (csrc/ibs_marginal_tangent.hip); entries
+ *   N .. ld-1 of a row are never written, with host pointers either.
+ *   With jac, dscale and geo_bar all NULL no mode is formed (the point-evaluation form).
+ *   Status bit 8: scale = +inf, val = 0, jac = dscale = 0, zero geo_bar rows (not counted).  Bits 0-1 of the solve: every floating-point
+ *   output of the point is NaN, its geo_bar rows (entries 0 .. N-1) included.  A gradient that is not finite after a good solve (a
+ *   non-finite entry of geo_da): bit 1, jac = dscale = NaN; val, scale and geo_bar kept.
+ * FP64, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED; this and the argument checks run before the context is
+ * touched), one wavefront per point (k_marginal_tangent_points), the workspace of ibs_marginal_obj_w_grad_f64.  No floating-point
+ * atomics: results are bitwise repeatable and independent of the batch.  The frozen-geometry caveat of ibs_marginal_scan_f64 applies. */
+int ibs_marginal_obj_w_grad_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, const double* geo_da,
+                                        int64_t ld, const double* theta0, double* val, double* jac, double* scale, double* dscale,
+                                        double* dPdrho, double* geo_bar, int32_t* info, int32_t mem);
 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
