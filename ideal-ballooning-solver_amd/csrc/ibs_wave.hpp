@@ -25,6 +25,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "ibs_sweep_count.hpp"
 
 namespace ibs {
 
@@ -182,6 +183,17 @@ __device__ __forceinline__ double dppz_t(double src) {
 template <int CTRL, int ROWMASK>
 __device__ __forceinline__ float dppz_t(float src) { return __int_as_float(dppz_i<CTRL, ROWMASK>(__float_as_int(src))); }
 
+// fetch into the rows of ROWMASK for a caller in which the lanes of the other rows never look at what they got: no previous value
+// is named, so none has to be set up in the destination (with `old = 0` and a partial row mask: one v_mov per dword and step)
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ int dppu_i(int src) { return __builtin_amdgcn_mov_dpp(src, CTRL, ROWMASK, 0xF, false); }
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ double dppu_t(double src) {
+  return __hiloint2double(dppu_i<CTRL, ROWMASK>(__double2hiint(src)), dppu_i<CTRL, ROWMASK>(__double2loint(src)));
+}
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ float dppu_t(float src) { return __int_as_float(dppu_i<CTRL, ROWMASK>(__float_as_int(src))); }
+
 // wave-wide reductions on the VALU (DPP row_shr / row_bcast: no LDS round trips); the result is
 // read from lane 63 into SGPRs, i.e. it is wave-uniform.
 template <typename T>
@@ -293,6 +305,15 @@ __device__ __forceinline__ M2<T> dpp_fetch(const M2<T>& s) {
   r.e = dppz_i<CTRL, ROWMASK>(s.e);
   return r;
 }
+// ... for the two row_bcast steps of scan_fwd_rows: lanes outside ROWMASK keep whatever the registers held (dppu_i)
+template <typename T, int CTRL, int ROWMASK>
+__device__ __forceinline__ M2<T> dpp_fetch_rows(const M2<T>& s) {
+  M2<T> r;
+  r.a = dppu_t<CTRL, ROWMASK>(s.a); r.b = dppu_t<CTRL, ROWMASK>(s.b);
+  r.c = dppu_t<CTRL, ROWMASK>(s.c); r.d = dppu_t<CTRL, ROWMASK>(s.d);
+  r.e = dppu_i<CTRL, ROWMASK>(s.e);
+  return r;
+}
 template <typename T>
 __device__ __forceinline__ M2<T> lane_bcast(const M2<T>& s, int src_lane) {  // src_lane is a constant
   M2<T> r;
@@ -324,6 +345,39 @@ __device__ __forceinline__ M2<T> scan_fwd(M2<T> P, int lane) {
   {                                                                                             // row_bcast:31 -> rows 2,3
     const T Fa = dppz_t<0x143, 0xC>(P.a), Fc = dppz_t<0x143, 0xC>(P.c);
     const int Fe = dppz_i<0x143, 0xC>(P.e);
+    if (row >= 2) {
+      const T na = xfma(P.a, Fa, P.b * Fc);
+      P.c = xfma(P.c, Fa, P.d * Fc);
+      P.a = na;
+      P.e += Fe;
+      if (RN) {                            // (first column only)
+        const T m = xmax(xabs(P.a), xabs(P.c));
+        int ex;
+        const T sc = pow2_scale_of(m, ex);
+        P.a *= sc; P.c *= sc; P.e += ex;
+      }
+    }
+  }
+  return P;
+}
+// The same scan for the resident solver (WaveSolver<T, M, true>), operation for operation; only the two row_bcast fetches differ:
+// they write the rows that consume them and nothing else.  The rows outside the row mask apply no product in those steps
+// (`row & 1`, `row >= 2`), so the zero fill scan_fwd gives them -- 9 + 5 register initialisations per scan -- is never read.  The
+// products stay under their conditions: an identity factor in the idle rows would not do (it can turn the sign of a zero, and
+// a renormalised one moves the split of the shooting value).  A form of its own, so that scan_fwd stays as every other kernel
+// compiles it today.
+template <typename T>
+__device__ __forceinline__ M2<T> scan_fwd_rows(M2<T> P, int lane) {
+  constexpr bool RN = ScanNorm<T>::v;
+  const int l16 = lane & 15, row = lane >> 4;
+  { const M2<T> F = dpp_fetch<T, 0x111, 0xF>(P); if (l16 >= 1) mul_inplace<T, false>(P, F); }   // row_shr:1
+  { const M2<T> F = dpp_fetch<T, 0x112, 0xF>(P); if (l16 >= 2) mul_inplace<T, RN>(P, F); }      // row_shr:2
+  { const M2<T> F = dpp_fetch<T, 0x114, 0xF>(P); if (l16 >= 4) mul_inplace<T, false>(P, F); }   // row_shr:4
+  { const M2<T> F = dpp_fetch<T, 0x118, 0xF>(P); if (l16 >= 8) mul_inplace<T, RN>(P, F); }      // row_shr:8
+  { const M2<T> F = dpp_fetch_rows<T, 0x142, 0xA>(P); if (row & 1) mul_inplace<T, false>(P, F); }   // row_bcast:15 -> rows 1,3
+  {                                                                                             // row_bcast:31 -> rows 2,3
+    const T Fa = dppu_t<0x143, 0xC>(P.a), Fc = dppu_t<0x143, 0xC>(P.c);
+    const int Fe = dppu_i<0x143, 0xC>(P.e);
     if (row >= 2) {
       const T na = xfma(P.a, Fa, P.b * Fc);
       P.c = xfma(P.c, Fa, P.d * Fc);
@@ -493,6 +547,7 @@ template <typename T, int M>
 struct ResidentRows<T, M, true> {
   T a1[M], d[M], c[M], f[M], zu[M];
   T ih2, ih;
+  unsigned own;      // the sign changes of a forward sweep this lane counts (sweep_count_mask): set-up forms it once
 };
 
 template <typename T, int M, bool RES = false>
@@ -550,6 +605,7 @@ struct WaveSolver {
     const int n = N - 2;
     const int rem = n - kWave * (M - 1);
     has_last = lane < rem;
+    if constexpr (RES) rr.own = sweep_count_mask(M, has_last, lane == kWave - 1);
     const int a = rows_start(lane, n);
     T ih2;
     if constexpr (RES) ih2 = rr.ih2; else ih2 = T(1) / (h * h);
@@ -695,6 +751,58 @@ struct WaveSolver {
     return count;
   }
 
+  // The forward sweep of the resident solver's shift iteration: sweep_fwd operation for operation in floating point and in
+  // every sign test, with two differences in what surrounds them.  (A body of its own, so that sweep_fwd stays as every other
+  // kernel compiles it today.)
+  //  * It returns min(count, 2) -- all that solve() asks (count == 0, != 0, == 1) -- NOT the Sturm count: every row shifts the
+  //    sign of its value into one word (one v_alignbit), the lane's changes are the bits of w ^ (w >> 1) it owns (rr.own: the
+  //    ownership rule of sweep_fwd as a mask, loop-invariant), and two ballots over the lanes' counts answer the wave's
+  //    question (ibs_sweep_count.hpp).  No exec region and no per-row scalar chain.
+  //  * The scan's row_bcast fetches initialise nothing (scan_fwd_rows).
+  // Builds that REPORT counts (IBS_TRACE, IBS_TRACE_ALL; IBS_PROBE unless IBS_PROBE_MIN2 asks for the library's own form to be
+  // timed) return the exact count, summed over the lanes.
+  __device__ __forceinline__ int sweep_fwd_min2(T sig) {
+    static_assert(RES && M + 2 <= 32, "one 32-bit sign word per lane");
+    T fA = T(1), fAp = T(0), fB = T(0), fBp = T(1);
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      const T tf = xfma(-sig, Ph[i], D[i]);
+      if ((i < M - 1) || has_last) {
+        const T nA = xfma(-tf, fA, -fAp), nB = xfma(-tf, fB, -fBp);
+        fAp = fA; fA = nA; fBp = fB; fB = nB;
+      }
+    }
+    M2<T> F;
+    F.a = fA * kap; F.b = fB * kap; F.c = fAp * ikap; F.d = fBp * ikap; F.e = 0;
+    renorm(F);
+    const M2<T> P = scan_fwd_rows(F, lane);
+    shoot_m = readlane_t(P.a, kWave - 1); shoot_e = readlane_i(P.e, kWave - 1);
+    const T u0 = dpp_t<0x138, 0xF>(T(1), P.a);   // wave_shr:1  (lane 0 reads the fill: (1, 0), exponent 0)
+    const T um = dpp_t<0x138, 0xF>(T(0), P.c);
+    Eu = dpp_i<0x138, 0xF>(0, P.e);
+    zu_m1 = um; u0_in = u0;
+    T zc = u0, zp = um;
+    unsigned w = sign_word(um) >> 31;
+    w = (unsigned)__builtin_amdgcn_alignbit(w, sign_word(u0), 31);                  // (w << 1) | sign(u_0)
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      const T t = xfma(-sig, Ph[i], D[i]);
+      const T zn = xfma(-t, zc, -zp);               // (a row the lane does not hold has D = Ph = 0: its bit is not owned)
+      w = (unsigned)__builtin_amdgcn_alignbit(w, sign_word(zn), 31);
+      if (i < M - 1) { zp = zc; zc = zn; }
+    }
+    const int c = sweep_count_lane(w, rr.own, M);
+#if defined(IBS_TRACE) || defined(IBS_TRACE_ALL) || (defined(IBS_PROBE) && !defined(IBS_PROBE_MIN2))
+    return wave_sum_i(c);
+#else
+    return sweep_count_min2(__builtin_amdgcn_ballot_w64(c != 0), __builtin_amdgcn_ballot_w64(c > 1));
+#endif
+  }
+  // the count as the shift iteration takes it: exact, or min(count, 2) in the resident form
+  __device__ __forceinline__ int sweep_fwd_iter(T sig) {
+    if constexpr (RES) return sweep_fwd_min2(sig); else return sweep_fwd(sig);
+  }
+
   // backward sweep at shift sig (solution from the right end); fills zw.  Returns the number of sign
   // changes of the backward solution w_{n-1}, ..., w_0, w_{-1} = the Sturm count (eigenvalues > sig) taken from the
   // other end of the matrix (the same theorem applied to the reversed index order).
@@ -731,8 +839,8 @@ struct WaveSolver {
     return count;
   }
 
-  __device__ __forceinline__ int sweep(T sig) {
-    const int c = sweep_fwd(sig);
+  __device__ __forceinline__ int sweep(T sig) {      // (returns what sweep_fwd_iter returns)
+    const int c = sweep_fwd_iter(sig);
     sweep_bwd(sig);
     return c;
   }
@@ -1076,7 +1184,7 @@ struct WaveSolver {
 #ifdef IBS_PROBE
       const long long tp0 = wall_clock64();
 #endif
-      const int C = sweep_fwd(sig);
+      const int C = sweep_fwd_iter(sig);            // (resident form: min(count, 2) -- only 0, 1 and "more" are told apart below)
 #ifdef IBS_PROBE
       const long long tp1 = wall_clock64(); t_sweep += tp1 - tp0;
 #endif
