@@ -1650,6 +1650,17 @@ __global__ void __launch_bounds__(256) k_refine_eval(RefineEvalArgs<T> a) {
 //     u[r+1] = -(d[r] - sig f[r]) u[r] - e[r]^2 u[r-1]
 // (signs only matter, so the 2x2 scan carries no exponent).  Each array is streamed through a per-wave
 // LDS row with 16-byte coalesced loads and handed to the lanes as contiguous chunks.
+// Range: the recurrence grows like max(|d - sig f|, e) per row, so inside a lane the chunk product is multiplied by an exact power
+// of two every kSturmRenormRows rows, and the replay by the same ones (a common positive factor changes no sign test; the replay is
+// the chunk product's state applied to a normalised pair, so it needs no exponent search of its own): 32 un-normalised rows of
+// s-alpha coefficients reach 1e202 at N = 2049 and overflow once (g, c) are given in units 4096 times smaller, with wrong counts
+// and no status.  Eight rows with a lag of two stay within 1e-138 .. 1e210 for (g, c) of order 1 scaled by 2^-40 ... 2^40 at shifts anywhere in
+// and around the spectrum (tests/test_count_spectrum_cpu.py restates this arithmetic; tests/test_gpu_count_spectrum.py).
+// The exponent search is taken off the recurrence's dependent chain (one wave per SIMD at 32 rows per lane: nothing else hides it):
+// the scale a row applies comes from the state kSturmRenormLag rows earlier and is folded into that row's coefficients.
+constexpr int kSturmRenormRows = 8, kSturmRenormLag = 2;
+static_assert(kSturmRenormLag >= 1 && kSturmRenormLag < kSturmRenormRows, "the scale of a row comes from an earlier row of its block");
+__host__ __device__ constexpr bool sturm_renorm_row(int i, int M) { return (i % kSturmRenormRows) == kSturmRenormRows - 1 && i + 1 < M; }
 // A wave's row of N values held in registers as KP 16-byte pieces per lane (coalesced: lane l owns pieces
 // l, l+64, ...), loaded from the first 16-byte aligned element on; the (at most one) head and tail elements
 // are loaded singly.  All three coefficient rows are put in flight before any of them is consumed.
@@ -1758,12 +1769,20 @@ __global__ void __launch_bounds__(256) k_sturm_count(long n_sys, int N, T h, con
     if ((i < M - 1) || has_last) t[i] = xfma(-sig, row[a + i + 1], t[i]);   // t = d - sig f
   // chunk transfer matrix: (u_a, u_{a-1}) -> (u_{a+cnt}, u_{a+cnt-1})
   T fA = T(1), fAp = T(0), fB = T(0), fBp = T(1);
+  constexpr int kRenorms = (M - 1) / kSturmRenormRows;
+  T rs[kRenorms > 0 ? kRenorms : 1];       // the powers of two the chunk product is multiplied by; the replay takes the same
+  T s_next = T(1);
 #pragma unroll
   for (int i = 0; i < M; ++i) {
+    const bool renorm = sturm_renorm_row(i, M);
+    if (renorm) { rs[i / kSturmRenormRows] = s_next; t[i] *= s_next; e2[i] *= s_next; }      // this row's step times s ...
     if ((i < M - 1) || has_last) {
       const T nA = xfma(-t[i], fA, -(e2[i] * fAp)), nB = xfma(-t[i], fB, -(e2[i] * fBp));
       fAp = fA; fA = nA; fBp = fB; fB = nB;
     }
+    if (renorm) { fAp *= s_next; fBp *= s_next; }                                             // ... and the row before it
+    if (sturm_renorm_row(i + kSturmRenormLag, M))
+      s_next = xldexp(T(1), -fexp(xmax(xmax(xabs(fA), xabs(fAp)), xmax(xabs(fB), xabs(fBp)))));
   }
   M2s<T> P{fA, fB, fAp, fBp};
   P = muls(P, M2s<T>{T(1), T(0), T(0), T(1)}, true);
@@ -1788,6 +1807,9 @@ __global__ void __launch_bounds__(256) k_sturm_count(long n_sys, int N, T h, con
     const bool flip = (i < M - 2 || i < ncount) && sign_differs(zn, zc);
     cnt += __popcll(__ballot(flip));
     if (act) { zp = zc; zc = zn; }
+    // (t, e2 of a renormalised row carry its scale already; (zc, zp) is the chunk product's state at this row applied to an incoming
+    //  pair of entries <= 2, so the chunk product's scales keep it in range)
+    if (sturm_renorm_row(i, M)) zp *= rs[i / kSturmRenormRows];
   }
   if (valid && lane == 0) count_out[sys] = cnt;
 }

@@ -548,7 +548,10 @@ int ibs_last_launch(char* name, int32_t len, int64_t* blocks, int32_t* threads);
  * systems or more against the sweep's 6 TB/s at N_zeta <= 512; Python: sturm_count(..., exact=True)); it is what grids beyond 2050
  * points get (batches under 64 systems: one wave per system) and, where it is also the faster one, what big batches get by default
  * (16 rows per lane = N in 963 .. 1026 from 65,536 systems, 32 rows = 1987 .. 2050 from 32,768: the sweep runs at 4.2 / 2.8 TB/s
- * there).  Even N is accepted here. */
+ * there).  Even N is accepted here.  Magnitudes: the sweep rescales its recurrence every 8 rows inside a lane, so g, c, f may be given in
+ * any units that keep the row magnitudes max(|d - shift f|, e) (d = c - (e_lo + e_hi), e = half-grid g / h^2) between about 1e-30 and
+ * 1e30 -- counts are tested exact for inputs of order 1 ... 1e3 with (g, c) scaled by 2^-40 ... 2^40 and f by 2^20, at shifts from
+ * below the spectrum to above it; the division forms take anything above about 1e-280. */
 int ibs_sturm_count_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c,
                         const double* f, int64_t ld, const double* shift, int32_t* count, int32_t mem);
 
