@@ -194,6 +194,14 @@ int ensure_fix(ibs_ctx* c, long n_sys) {
   return 0;
 }
 int long_waves(const ibs_ctx* c, long n_sys) { const long cap = 8L * c->n_cu; return (int)(n_sys < cap ? n_sys : cap); }   // (ibs_long.hip: kLongChunk)
+// the persistent grid of long_waves(n) with doubles_per_wave of ctx->long_ws each, entered into the launch arguments a of a
+// one-wave-per-system kernel (a.work, a.work_doubles, a.n_waves: ibs_launch.hpp, persistent_grid)
+template <class A> int with_wave_ws(ibs_ctx* c, A& a, long n, size_t doubles_per_wave) {
+  const int nw = long_waves(c, n);
+  if (int r = ensure_long_ws(c, (size_t)nw * doubles_per_wave * sizeof(double))) return r;
+  a.work = static_cast<double*>(c->long_ws); a.work_doubles = c->long_ws_bytes / sizeof(double); a.n_waves = nw;
+  return 0;
+}
 
 int ensure_ws(ibs_ctx* c, size_t bytes) {
   if (bytes <= c->ws_bytes) return 0;
@@ -928,15 +936,6 @@ int ibs_solve_gcf_f32(ibs_ctx* ctx, int64_t n_sys, int32_t N, float h, const flo
 
 // ---- the eigenpair nearest sigma (ibs_nearest.hip; utils.py:1597)
 // the persistent grid of long_waves() with its workspace in ctx->long_ws (nearest_ws_doubles(N) per wave)
-static int nearest_device(ibs_ctx* ctx, ibs::NearestArgs a) {
-  const int nw = long_waves(ctx, a.n_sys);
-  const size_t ws = (size_t)nw * ibs::nearest_ws_doubles(a.N);
-  if (int r = ensure_long_ws(ctx, ws * sizeof(double))) return r;
-  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
-  HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
-  return 0;
-}
-
 int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
                               const double* c, const double* f, int64_t ld, const double* sigma, double* lam,
                               int32_t* idx, double* gam, double* X, double* dX, int32_t* info, int32_t mem) {
@@ -954,19 +953,15 @@ int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, 
     a.lam = s.out(lam, n_sys); a.gam = s.out(gam, n_sys); a.idx = s.out(idx, n_sys); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
     a.info = s.status(info, n_sys);
   };
-  return staged(ctx, mem, decl, [&] { return nearest_device(ctx, a); });
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, a.n_sys, ibs::nearest_ws_doubles(N))) return r;
+    HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
+    return 0;
+  });
 }
 
 // ---- exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip)
 // the persistent grid of long_waves() with its workspace in ctx->long_ws (vjp_ws_doubles(N) per wave)
-static int vjp_device(ibs_ctx* ctx, ibs::VjpArgs a) {
-  const int nw = long_waves(ctx, a.n_sys);
-  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::vjp_ws_doubles(a.N) * sizeof(double))) return r;
-  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
-  HIPCHK(ibs::launch_gcf_vjp(a, ctx->stream));
-  return 0;
-}
-
 int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c, const double* f,
                           int64_t ld, const double* lam, const double* X, const double* gam_bar, const double* lam_bar, double* g_bar,
                           double* c_bar, double* f_bar, int32_t* info, int32_t mem) {
@@ -989,7 +984,9 @@ int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, cons
   return staged(ctx, mem, decl, [&]() -> int {
     if (mem == IBS_MEM_HOST && ld > N)                  // (host pointers: the padding columns come back as zero)
       for (double* o : {a.g_bar, a.c_bar, a.f_bar}) HIPCHK(hipMemsetAsync(o, 0, rows * sizeof(double), ctx->stream));
-    return vjp_device(ctx, a);
+    if (int r = with_wave_ws(ctx, a, a.n_sys, ibs::vjp_ws_doubles(N))) return r;
+    HIPCHK(ibs::launch_gcf_vjp(a, ctx->stream));
+    return 0;
   });
 }
 
@@ -1014,9 +1011,7 @@ int ibs_marginal_gcf_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const
     a.info = s.status(info, n_sys);
   };
   return staged(ctx, mem, decl, [&]() -> int {
-    const int nw = long_waves(ctx, a.n_sys);
-    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, false).total * sizeof(double))) return r;
-    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    if (int r = with_wave_ws(ctx, a, a.n_sys, ibs::marginal_ws(N, false).total)) return r;
     HIPCHK(ibs::launch_marginal_gcf(a, ctx->stream));
     return 0;
   });
@@ -1045,9 +1040,7 @@ int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
     a.info = s.status(info, n_sys);
   };
   return staged(ctx, mem, decl, [&]() -> int {
-    const int nw = long_waves(ctx, (long)n_sys);
-    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, true).total * sizeof(double))) return r;
-    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    if (int r = with_wave_ws(ctx, a, (long)n_sys, ibs::marginal_ws(N, true).total)) return r;
     HIPCHK(ibs::launch_marginal_scan(a, ctx->stream));
     return 0;
   });
@@ -1074,9 +1067,7 @@ int ibs_marginal_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h
     a.info = s.status(info, n);
   };
   return staged(ctx, mem, decl, [&]() -> int {
-    const int nw = long_waves(ctx, a.n_pts);
-    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, true).total * sizeof(double))) return r;
-    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    if (int r = with_wave_ws(ctx, a, a.n_pts, ibs::marginal_ws(N, true).total)) return r;
     HIPCHK(ibs::launch_marginal_points(a, ctx->stream));
     return 0;
   });
@@ -1106,9 +1097,7 @@ int ibs_marginal_obj_w_grad_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, 
     a.info = s.status(info, n);
   };
   return staged(ctx, mem, decl, [&]() -> int {
-    const int nw = long_waves(ctx, a.n_pts);
-    if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::marginal_ws(a.N, true).total * sizeof(double))) return r;
-    a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
+    if (int r = with_wave_ws(ctx, a, a.n_pts, ibs::marginal_ws(N, true).total)) return r;
     HIPCHK(ibs::launch_marginal_tangent_points(a, ctx->stream));
     return 0;
   });
@@ -1191,14 +1180,6 @@ int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
 // ---- geometry-fed points with the eigenpair nearest sigma[p] (ibs_nearest_grad.hip): the refinement's objective + gradient and
 // the final solve of ball_scan.py:305-339 in upstream's mode, one wave per point on the persistent grid of long_waves()
 // the per-wave workspace (ibs::nearest_points_ws) in ctx->long_ws
-static int points_nearest_device(ibs_ctx* ctx, ibs::NearestPointsArgs a, bool grad) {
-  const int nw = long_waves(ctx, a.n_pts);
-  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::nearest_points_ws(a.N, grad).total * sizeof(double))) return r;
-  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
-  HIPCHK(grad ? ibs::launch_obj_w_grad_nearest(a, ctx->stream) : ibs::launch_points_nearest(a, ctx->stream));
-  return 0;
-}
-
 int ibs_obj_w_grad_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
                                const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
                                double* lam, int32_t* idx, int32_t* info, int32_t mem) {
@@ -1215,7 +1196,11 @@ int ibs_obj_w_grad_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h,
     a.geo = s.in(geo, geo_elems); a.theta0 = s.in(theta0, n); a.sigma = s.in(sigma, n);
     a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.lam = s.out(lam, n); a.idx = s.out(idx, n); a.info = s.status(info, n);
   };
-  return staged(ctx, mem, decl, [&] { return points_nearest_device(ctx, a, true); });
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, a.n_pts, ibs::nearest_points_ws(N, true).total)) return r;
+    HIPCHK(ibs::launch_obj_w_grad_nearest(a, ctx->stream));
+    return 0;
+  });
 }
 
 int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
@@ -1239,20 +1224,16 @@ int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double 
     a.gam = s.out(gam, n); a.lam = s.out(lam, n); a.idx = s.out(idx, n); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
     a.info = s.status(info, n);
   };
-  return staged(ctx, mem, decl, [&] { return points_nearest_device(ctx, a, false); });
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, a.n_pts, ibs::nearest_points_ws(N, false).total)) return r;
+    HIPCHK(ibs::launch_points_nearest(a, ctx->stream));
+    return 0;
+  });
 }
 
 // ---- geometry-fed points with the exact gradient of gam (ibs_exact_grad.hip): utils.py:1632-1728 with the derivative of the gam
 // returned in place of the Hellmann-Feynman formulas, one wave per point on the persistent grid of long_waves()
 // the per-wave workspace (ibs::exact_points_ws) in ctx->long_ws
-static int points_exact_device(ibs_ctx* ctx, ibs::ExactPointsArgs a) {
-  const int nw = long_waves(ctx, a.n_pts);
-  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::exact_points_ws(a.N).total * sizeof(double))) return r;
-  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
-  HIPCHK(ibs::launch_obj_w_grad_exact(a, ctx->stream));
-  return 0;
-}
-
 int ibs_obj_w_grad_exact_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
                              const double* theta0, const double* sigma, double del_alpha, double* val, double* jac,
                              double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem) {
@@ -1270,19 +1251,15 @@ int ibs_obj_w_grad_exact_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, c
     a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.gam = s.out(gam, n); a.lam = s.out(lam, n); a.idx = s.out(idx, n);
     a.info = s.status(info, n);
   };
-  return staged(ctx, mem, decl, [&] { return points_exact_device(ctx, a); });
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, a.n_pts, ibs::exact_points_ws(N).total)) return r;
+    HIPCHK(ibs::launch_obj_w_grad_exact(a, ctx->stream));
+    return 0;
+  });
 }
 
 // ---- the same from ONE line per point and the alpha-tangent of its geometry (ibs_exact_tangent.hip): exact in alpha as well; the
-// per-wave workspace is that of points_exact_device
-static int points_exact_tangent_device(ibs_ctx* ctx, ibs::ExactTangentArgs a) {
-  const int nw = long_waves(ctx, a.n_pts);
-  if (int r = ensure_long_ws(ctx, (size_t)nw * ibs::exact_points_ws(a.N).total * sizeof(double))) return r;
-  a.work = static_cast<double*>(ctx->long_ws); a.work_doubles = ctx->long_ws_bytes / sizeof(double); a.n_waves = nw;
-  HIPCHK(ibs::launch_obj_w_grad_exact_tangent(a, ctx->stream));
-  return 0;
-}
-
+// per-wave workspace is the same (ibs::exact_points_ws)
 int ibs_obj_w_grad_exact_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, const double* geo_da,
                                      int64_t ld, const double* theta0, const double* sigma, double* val, double* jac,
                                      double* gam, double* lam, int32_t* idx, int32_t* info, int32_t mem) {
@@ -1293,14 +1270,18 @@ int ibs_obj_w_grad_exact_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, dou
   if (n_pts == 0) return 0;
   ON_DEVICE(ctx);
   const size_t n = (size_t)n_pts, geo_elems = n * 8 * (size_t)ld;
-  ibs::ExactTangentArgs a{};
+  ibs::ExactPointsArgs a{};
   a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld;
   auto decl = [&](Stage& s) {
     a.geo = s.in(geo, geo_elems); a.geo_da = s.in(geo_da, geo_elems); a.theta0 = s.in(theta0, n); a.sigma = s.in(sigma, n);
     a.val = s.out(val, n); a.jac = s.out(jac, 2 * n); a.gam = s.out(gam, n); a.lam = s.out(lam, n); a.idx = s.out(idx, n);
     a.info = s.status(info, n);
   };
-  return staged(ctx, mem, decl, [&] { return points_exact_tangent_device(ctx, a); });
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, a.n_pts, ibs::exact_points_ws(N).total)) return r;
+    HIPCHK(ibs::launch_obj_w_grad_exact_tangent(a, ctx->stream));
+    return 0;
+  });
 }
 
 // Geometry-fed scan on a grid beyond 2050 points: the (g, c, f) rows of every (line, theta0) system -- and their theta0 tangents when

@@ -21,6 +21,7 @@
 // rows the wave writes to its workspace with the arithmetic of k_assemble_gcf_long; k_geo_certify then looks at exactly those again.
 #include "ibs_certify.hpp"
 #include "ibs_long.hpp"
+#include "ibs_geo_line.hpp"
 #include "ibs_launch.hpp"
 
 namespace ibs {
@@ -204,17 +205,10 @@ __global__ void __launch_bounds__(64) k_geo_reclose(RecloseArgs a) {
   for (int k = blockIdx.x; k < n_list; k += gridDim.x) {
     const long sys = a.list[1 + k];
     const int line = (int)(sys / s.n_theta0), it0 = (int)(sys - (long)line * s.n_theta0);
-    const double th0 = s.theta0[s.t0_stride ? line : it0], two_th0 = 2.0 * th0, th0sq = th0 * th0;
+    const double th0 = s.theta0[s.t0_stride ? line : it0];
     const double mdP = -s.dPdrho[line];
-    const long off = (long)line * s.ld;
-    for (int j = lane; j < N; j += kWave) {                             // the rows, as k_assemble_gcf_long writes them
-      const double B = s.geo7[0][off + j], gp = xabs(s.geo7[1][off + j]);
-      const double inv = 1.0 / (gp * B);
-      const double A1 = gp / B, A3 = inv / (B * B);
-      const double C0 = mdP * s.geo7[2][off + j] * inv, C1 = mdP * s.geo7[3][off + j] * inv;
-      const double d = s.geo7[4][off + j] + two_th0 * s.geo7[5][off + j] + th0sq * s.geo7[6][off + j];
-      G[j] = A1 * d; Cc[j] = C0 + th0 * C1; F[j] = A3 * d;
-    }
+    const GeoLine7 ln = geo_line7(s.geo7, (long)line * s.ld);
+    for (int j = lane; j < N; j += kWave) line_gcf(ln, j, mdP, th0, G[j], Cc[j], F[j]);     // the rows, as k_assemble_gcf_long writes them
     long_fence();
     const SrcLong<double, false> src{G, Cc, F, nullptr};
     const LongBounds b = long_bounds<false>(src, N, ih2, lane);

@@ -18,10 +18,10 @@
 // repeatable and the same whatever the batch.  info = the solve's word (bits 0-15 passes, status from bit 16) with the adjoint's two
 // flags at status bits 6 (a replaced pivot: informational) and 7 (refused: jac = NaN, val kept).  A failed solve (status bits 0-1)
 // gives val = jac = NaN.  Per-wave workspace: exact_points_ws(N) (ibs_launch.hpp), in global memory.
-#include "ibs_nearest.hpp"
-#include "ibs_vjp.hpp"
+// Stages 1, 2 and the tangents of 5 are the per-line functions of ibs_geo_line.hpp (line_mdP, line_gcf, line_gcf_dtheta0); stages 3, 4
+// and 6 are exact_eigenpair, exact_adjoint and exact_store of ibs_exact_stages.hpp, shared with k_exact_tangent_points.
+#include "ibs_exact_stages.hpp"
 #include "ibs_geo_line.hpp"
-#include "ibs_launch.hpp"
 
 namespace ibs {
 
@@ -33,29 +33,16 @@ __global__ void __launch_bounds__(64) k_exact_points(const ExactPointsArgs a) {
   const int N = a.N;
   const ExactPointsWs L = exact_points_ws(N);
   double* my = a.work + (size_t)blockIdx.x * L.total;
-  double* G = my + L.g; double* C = my + L.c; double* F = my + L.f; double* Xw = my + L.X;
-  double* gb = my + L.gb; double* cb = my + L.cb; double* fb = my + L.fb;
-  double* s_lam = my + L.scal;                               // scalars of lane 0, read back by the wave behind a fence
-  int* s_info = reinterpret_cast<int*>(my + L.scal + 1);     // [0] the solve's word (NEAREST), [1] the adjoint's
+  double* G = my + L.g; double* C = my + L.c; double* F = my + L.f;
+  const double* gb = my + L.gb; const double* cb = my + L.cb; const double* fb = my + L.fb;
   for (long p = blockIdx.x; p < a.n_pts; p += gridDim.x) {
     const double th0 = uniform(a.theta0[p]);
     // ---- 1. dPdrho of the three lines
     GeoLine ln[3];
-    double mdP[3];
-    {
-      double s[3] = {0.0, 0.0, 0.0};
+    double mdP[3];                                          // -dPdrho
 #pragma unroll
-      for (int l = 0; l < 3; ++l) ln[l] = GeoLine{a.geo + ((size_t)p * 3 + l) * 8 * (size_t)a.ld, a.ld};
-      for (int j = lane; j < N; j += kWave) {
-#pragma unroll
-        for (int l = 0; l < 3; ++l) {
-          const double B = ln[l].at(0, j);
-          s[l] += (ln[l].at(2, j) - ln[l].at(7, j)) * B * B;
-        }
-      }
-#pragma unroll
-      for (int l = 0; l < 3; ++l) mdP[l] = 0.5 * wave_sum(s[l]) / (double)N;      // -dPdrho
-    }
+    for (int l = 0; l < 3; ++l) ln[l] = GeoLine{a.geo + ((size_t)p * 3 + l) * 8 * (size_t)a.ld, a.ld};
+    line_mdP<3>(ln, N, lane, mdP);
     // ---- 2. the centre line's rows
     for (int j = lane; j < N; j += kWave) {
       double g, c, f;
@@ -64,75 +51,36 @@ __global__ void __launch_bounds__(64) k_exact_points(const ExactPointsArgs a) {
     }
     long_fence();                                           // (rows written by every lane, read by every lane below)
     const SrcLong<double, false> src{G, C, F, nullptr};
-    // ---- 3. the eigenpair
-    double gam = __builtin_nan(""), lam = __builtin_nan("");
-    int word = 0, idx = -1;
-    if constexpr (NEAREST) {
-      gam = solve_nearest_one<false>(src, N, a.h, a.sigma[p], 0, my + L.work, s_lam, a.idx ? a.idx + p : nullptr, nullptr, Xw, nullptr,
-                                     s_info, lds);
-      long_fence();                                         // (X of every lane, lam and the word of lane 0)
-      lam = uniform(s_lam[0]);
-      word = __builtin_amdgcn_readfirstlane(s_info[0]);
-    } else {
-      const double ih2 = 1.0 / (a.h * a.h);
-      const LongBounds b = long_bounds<false>(src, N, ih2, lane);
-      int status = 0, passes = 0;
-      if (b.bad) status = 2;
-      else if (!long_lam_max(src, N, ih2, b.lo, b.hi, b.normA, lds, lane, lam, passes)) status = 1;
-      if (status == 0) {
-        gam = long_vector_growth<false, double>(src, N, a.h, lam, 0, my + L.work, Xw, (double*)nullptr, lds, lane);
-        idx = 0;
-      }
-      if (status == 2) lam = __builtin_nan("");           // (status 1: lam is where the multisection stopped, as solve_long_one leaves it)
-      word = passes | (status << 16);
-      long_fence();                                         // (X of every lane)
-    }
-    // ---- 4. d gam / d (g, c, f)
+    // ---- 3. the eigenpair, 4. d gam / d (g, c, f)
+    ExactPair e = exact_eigenpair<NEAREST>(src, a, p, my, L, lds, lane);
     double ja = __builtin_nan(""), jt = __builtin_nan("");
-    if (((word >> 16) & 3) == 0) {
-      vjp_one(src, N, a.h, lam, Xw, 1.0, 0.0, gb, cb, fb, s_info + 1, 0, my + L.work, lds, lane);
-      long_fence();                                         // (the cotangent rows of every lane, the adjoint's word of lane 0)
-      const int vw = __builtin_amdgcn_readfirstlane(s_info[1]) >> 16;
-      word |= (vw & 3) << (16 + 6);
+    if (((e.word >> 16) & 3) == 0 && (exact_adjoint(src, a, e, my, L, lds, lane) & 2) == 0) {
       // ---- 5. contraction with the theta0 and alpha tangents
-      if ((vw & 2) == 0) {
-        double st = 0.0, sa = 0.0;
-        for (int j = lane; j < N; j += kWave) {
-          const double gbj = gb[j], cbj = cb[j], fbj = fb[j];
-          // theta0 tangent of the centre line (utils.py:1669-1673)
-          const double B = ln[1].at(0, j), gp = xabs(ln[1].at(1, j));
-          const double inv = 1.0 / (gp * B);
-          const double A1 = gp / B, A3 = inv / (B * B);
-          const double dp = 2.0 * ln[1].at(5, j) + (2.0 * th0) * ln[1].at(6, j);
-          const double gt = A1 * dp, ct = mdP[1] * ln[1].at(3, j) * inv, ft = A3 * dp;
-          // alpha tangent (utils.py:1705-1719): each side line with its own dPdrho
-          double gl, cl, fl, gr, cr, fr;
-          line_gcf(ln[0], j, mdP[0], th0, gl, cl, fl);
-          line_gcf(ln[2], j, mdP[2], th0, gr, cr, fr);
-          st += gbj * gt + cbj * ct + fbj * ft;
-          sa += gbj * (gr - gl) + cbj * (cr - cl) + fbj * (fr - fl);
-        }
-        jt = wave_sum(st);
-        ja = wave_sum(sa) / a.del_alpha;
+      double st = 0.0, sa = 0.0;
+      for (int j = lane; j < N; j += kWave) {
+        const double gbj = gb[j], cbj = cb[j], fbj = fb[j];
+        double gt, ct, ft;                                  // theta0 tangent of the centre line
+        line_gcf_dtheta0(ln[1], j, mdP[1], th0, gt, ct, ft);
+        // alpha tangent (utils.py:1705-1719): each side line with its own dPdrho
+        double gl, cl, fl, gr, cr, fr;
+        line_gcf(ln[0], j, mdP[0], th0, gl, cl, fl);
+        line_gcf(ln[2], j, mdP[2], th0, gr, cr, fr);
+        st += gbj * gt + cbj * ct + fbj * ft;
+        sa += gbj * (gr - gl) + cbj * (cr - cl) + fbj * (fr - fl);
       }
+      jt = wave_sum(st);
+      ja = wave_sum(sa) / a.del_alpha;
     }
     // ---- 6. utils.py:1728
-    if (lane == 0) {
-      a.val[p] = -gam; a.jac[2 * p] = -ja; a.jac[2 * p + 1] = -jt;
-      if (a.gam) a.gam[p] = gam;
-      if (a.lam) a.lam[p] = lam;
-      if (!NEAREST && a.idx) a.idx[p] = idx;
-      if (a.info) a.info[p] = word;
-    }
+    if (lane == 0) exact_store<NEAREST>(a, p, e, ja, jt);
     long_fence();                                           // (the workspace is reused by this wave's next point)
   }
 }
 
 hipError_t launch_obj_w_grad_exact(const ExactPointsArgs& a, hipStream_t st) {
   if (a.n_pts <= 0) return hipSuccess;
-  const long grid = a.n_pts < a.n_waves ? a.n_pts : a.n_waves;
-  if (grid < 1 || !a.work || a.work_doubles < (size_t)grid * exact_points_ws(a.N).total) return hipErrorInvalidValue;
-  if (!a.geo || !a.theta0 || !a.val || !a.jac) return hipErrorInvalidValue;
+  const long grid = persistent_grid(a.n_pts, a.n_waves, a.work, a.work_doubles, exact_points_ws(a.N).total);
+  if (!grid || !a.geo || !a.theta0 || !a.val || !a.jac) return hipErrorInvalidValue;
   if (a.sigma) {
     hipLaunchKernelGGL(k_exact_points<true>, dim3((unsigned)grid), dim3(64), 0, st, a);
     note_launch(grid, 64, "ibs::k_exact_points<true>");

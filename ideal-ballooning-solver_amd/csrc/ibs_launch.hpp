@@ -60,6 +60,12 @@ struct LongGcfArgs {
   double* work; int n_waves;                // n_waves * 3 * N doubles of workspace; the grid is min(n_sys, n_waves) waves
 };
 hipError_t launch_gcf_long(const LongGcfArgs& a, hipStream_t st);
+// the persistent grid of the one-wave-per-system kernels below: min(n, n_waves) waves, each with per_wave doubles of workspace at
+// work + wave * per_wave; 0 = the workspace is missing or too short for that grid (the launch refuses)
+inline long persistent_grid(long n, long n_waves, const double* work, size_t work_doubles, size_t per_wave) {
+  const long grid = n < n_waves ? n : n_waves;
+  return grid >= 1 && work && work_doubles >= (size_t)grid * per_wave ? grid : 0;
+}
 // the eigenpair nearest sigma[sys] (ibs_nearest.hip), FP64, any N in [66, kMaxLongN]: one wave per system, persistent grid of
 // min(n_sys, n_waves) waves, each with nearest_ws_doubles(N) doubles of workspace at work + wave * nearest_ws_doubles(N)
 constexpr size_t nearest_ws_doubles(int N) { return 3 * (size_t)N; }
@@ -115,15 +121,18 @@ constexpr ExactPointsWs exact_points_ws(int N) {
   const size_t n = (size_t)N, w = nearest_ws_doubles(N) > vjp_ws_doubles(N) ? nearest_ws_doubles(N) : vjp_ws_doubles(N);
   return ExactPointsWs{0, 0, n, w, w + n, w + 2 * n, w + 3 * n, w + 4 * n, w + 5 * n, w + 5 * n + 8};
 }
+// The same struct feeds k_exact_tangent_points (ibs_exact_tangent.hip): ONE line per point and its alpha-tangent, same stages, grid and workspace.
 struct ExactPointsArgs {
   int n_pts, N; double h; long ld;
-  const double* geo;                                                  // [n_pts][3][8][ld], as NearestPointsArgs::geo
-  const double* theta0; const double* sigma; double del_alpha;        // theta0 [n_pts]; sigma [n_pts] or null = lam_max's eigenpair
+  const double* geo;                                                  // [n_pts][3][8][ld], as NearestPointsArgs::geo; tangent form: [8][n_pts][ld]
+  const double* geo_da;                                               // tangent form only: [8][n_pts][ld], the layout of the two geometry calls
+  const double* theta0; const double* sigma; double del_alpha;        // theta0 [n_pts]; sigma [n_pts] or null = lam_max's eigenpair; del_alpha: three-line form only
   double *val, *jac;                                                  // [n_pts], [n_pts][2] (required)
   double* gam; double* lam; int* idx; int* info;                      // optional
   double* work; size_t work_doubles; long n_waves;                    // the launch refuses less than min(n_pts, n_waves) waves' worth
 };
 hipError_t launch_obj_w_grad_exact(const ExactPointsArgs& a, hipStream_t st);
+hipError_t launch_obj_w_grad_exact_tangent(const ExactPointsArgs& a, hipStream_t st);
 // marginal stability (ibs_marginal.hip): the critical scale s* of the pressure gradient at fixed rows, FP64, any odd N in
 // [66, kMaxLongN]: one wave per system on the persistent grid of min(n_sys, n_waves) waves.  Per-wave workspace, in this order
 // (MarginalWs: the kernels carve it, the host sizes it): the eigenvector stage's nearest_ws_doubles(N), the marginal mode X, and in
@@ -246,18 +255,6 @@ struct GeoDalphaArgs {
   double* geo_da;              // [8][n_lines][ld]
 };
 hipError_t launch_geometry_dalpha(GeoDalphaArgs& a, hipStream_t st);
-
-// geometry-fed points with the exact gradient of gam from ONE line per point and its alpha-tangent (ibs_exact_tangent.hip): the
-// stages, the persistent grid and the per-wave workspace (exact_points_ws) of k_exact_points
-struct ExactTangentArgs {
-  int n_pts, N; double h; long ld;
-  const double *geo, *geo_da;                                         // both [8][n_pts][ld]: the layout of the two geometry calls
-  const double* theta0; const double* sigma;                          // theta0 [n_pts]; sigma [n_pts] or null = lam_max's eigenpair
-  double *val, *jac;                                                  // [n_pts], [n_pts][2] (required)
-  double* gam; double* lam; int* idx; int* info;                      // optional
-  double* work; size_t work_doubles; long n_waves;                    // the launch refuses less than min(n_pts, n_waves) waves' worth
-};
-hipError_t launch_obj_w_grad_exact_tangent(const ExactTangentArgs& a, hipStream_t st);
 
 template <typename T> struct RefineEvalArgs;
 struct LaunchTable {

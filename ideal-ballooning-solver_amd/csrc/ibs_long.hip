@@ -18,6 +18,7 @@
 // number of waves, each taking systems blockIdx.x, blockIdx.x + gridDim.x, ...  The device pieces of stages 1-4 live in ibs_long.hpp,
 // shared with the nearest-sigma kernel (ibs_nearest.hip).
 #include "ibs_long.hpp"
+#include "ibs_geo_line.hpp"
 #include "ibs_launch.hpp"
 
 namespace ibs {
@@ -161,19 +162,16 @@ __global__ void __launch_bounds__(256) k_assemble_gcf_long(int n_lines, int n_th
   const long n_sys = (long)n_lines * n_theta0;
   for (long sys = blockIdx.y; sys < n_sys; sys += gridDim.y) {
     const int line = (int)(sys / n_theta0), it0 = (int)(sys - (long)line * n_theta0);
-    const double th0 = theta0[(long)line * t0_stride + it0], two_th0 = 2.0 * th0, th0sq = th0 * th0;
+    const double th0 = theta0[(long)line * t0_stride + it0];
     const double mdP = -dPdrho[line];
-    const long off = (long)line * ld;
+    const GeoLine7 ln{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, (long)line * ld};
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < N; j += gridDim.x * blockDim.x) {
-      const double B = bmag[off + j], gp = xabs(gradpar[off + j]);
-      const double inv = 1.0 / (gp * B);
-      const double A1 = gp / B, A3 = inv / (B * B);
-      const double C0 = mdP * cvdrift[off + j] * inv, C1 = mdP * cvdrift0[off + j] * inv;
-      const double G0 = gds2[off + j], G1 = gds21[off + j], G2 = gds22[off + j];
-      const double d = G0 + two_th0 * G1 + th0sq * G2;
       const long o = sys * N + j;
-      g[o] = A1 * d; c[o] = C0 + th0 * C1; f[o] = A3 * d;
-      if (gt) { const double dp = 2.0 * G1 + two_th0 * G2; gt[o] = A1 * dp; ct[o] = C1; ft[o] = A3 * dp; }
+      double gj, cj, fj, gtj, ctj, ftj;                     // (all loads before the first store: the outputs are not __restrict__)
+      line_gcf(ln, j, mdP, th0, gj, cj, fj);
+      line_gcf_dtheta0(ln, j, mdP, th0, gtj, ctj, ftj);
+      g[o] = gj; c[o] = cj; f[o] = fj;
+      if (gt) { gt[o] = gtj; ct[o] = ctj; ft[o] = ftj; }
     }
   }
 }

@@ -19,6 +19,7 @@
 // NaN vectors and derivatives; with bit 8 the derivatives are 0 (s* is locally constant) and X, gam0 are NaN.
 // Per-wave workspace: marginal_ws(N, scan) (ibs_launch.hpp), in global memory.
 #include "ibs_marginal.hpp"
+#include "ibs_geo_line.hpp"
 #include "ibs_launch.hpp"
 
 namespace ibs {
@@ -88,16 +89,9 @@ __global__ void __launch_bounds__(64) k_marginal_scan(const MarginalScanArgs a) 
   for (long sys = blockIdx.x; sys < n_sys; sys += gridDim.x) {
     const int line = (int)(sys / a.n_theta0), it0 = (int)(sys - (long)line * a.n_theta0);
     const double th0 = uniform(a.theta0[it0]), dP = uniform(a.dPdrho[line]), mdP = -dP;
-    const long off = (long)line * a.ld;
-    // ---- the rows at theta0 (the arithmetic of line_gcf / k_assemble_gcf_long: ball_scan.py:267-268, utils.py:1560-1561)
-    for (int j = lane; j < N; j += kWave) {
-      const double B = a.geo7[0][off + j], gp = xabs(a.geo7[1][off + j]);
-      const double inv = 1.0 / (gp * B);
-      const double A1 = gp / B;
-      const double C0 = mdP * a.geo7[2][off + j] * inv, C1 = mdP * a.geo7[3][off + j] * inv;
-      const double d = a.geo7[4][off + j] + (2.0 * th0) * a.geo7[5][off + j] + (th0 * th0) * a.geo7[6][off + j];
-      G[j] = A1 * d; C[j] = C0 + th0 * C1;
-    }
+    const GeoLine7 ln = geo_line7(a.geo7, (long)line * a.ld);
+    // ---- the rows at theta0
+    for (int j = lane; j < N; j += kWave) line_gcf(ln, j, mdP, th0, G[j], C[j]);
     long_fence();                                           // (rows written by every lane, read by every lane below)
     int status, passes;
     double gam0;
@@ -108,12 +102,10 @@ __global__ void __launch_bounds__(64) k_marginal_scan(const MarginalScanArgs a) 
       double q = 0.0, sg = 0.0, sc = 0.0;
       for (int j = lane; j < N; j += kWave) {
         const double x0 = Xw[j], x2 = x0 * x0;
-        const double dm = j > 0 ? x0 - Xw[j - 1] : 0.0, dp = j < N - 1 ? Xw[j + 1] - x0 : 0.0;
-        const double B = a.geo7[0][off + j], gp = xabs(a.geo7[1][off + j]);
-        const double gt = (gp / B) * (2.0 * a.geo7[5][off + j] + (2.0 * th0) * a.geo7[6][off + j]);
-        const double ct = mdP * a.geo7[3][off + j] * (1.0 / (gp * B));
+        double gt, ct;
+        line_gcf_dtheta0(ln, j, mdP, th0, gt, ct);
         q = xfma(C[j], x2, q);
-        sg = xfma(gt, xfma(dm, dm, dp * dp), sg);
+        sg = xfma(gt, pencil_weight(Xw, j, N), sg);
         sc = xfma(ct, x2, sc);
       }
       q = wave_sum(q); sg = wave_sum(sg); sc = wave_sum(sc);
@@ -132,8 +124,8 @@ __global__ void __launch_bounds__(64) k_marginal_scan(const MarginalScanArgs a) 
 
 hipError_t launch_marginal_gcf(const MarginalArgs& a, hipStream_t st) {
   if (a.n_sys <= 0) return hipSuccess;
-  const long grid = a.n_sys < a.n_waves ? a.n_sys : a.n_waves;
-  if (grid < 1 || !a.g || !a.c || !a.scale || !a.work || a.work_doubles < (size_t)grid * marginal_ws(a.N, false).total) return hipErrorInvalidValue;
+  const long grid = persistent_grid(a.n_sys, a.n_waves, a.work, a.work_doubles, marginal_ws(a.N, false).total);
+  if (!grid || !a.g || !a.c || !a.scale) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_marginal_gcf, dim3((unsigned)grid), dim3(64), 0, st, a);
   note_launch(grid, 64, "ibs::k_marginal_gcf");
   return hipGetLastError();
@@ -142,8 +134,8 @@ hipError_t launch_marginal_gcf(const MarginalArgs& a, hipStream_t st) {
 hipError_t launch_marginal_scan(const MarginalScanArgs& a, hipStream_t st) {
   const long n_sys = (long)a.n_lines * a.n_theta0;
   if (n_sys <= 0) return hipSuccess;
-  const long grid = n_sys < a.n_waves ? n_sys : a.n_waves;
-  if (grid < 1 || !a.dPdrho || !a.theta0 || !a.scale || !a.work || a.work_doubles < (size_t)grid * marginal_ws(a.N, true).total) return hipErrorInvalidValue;
+  const long grid = persistent_grid(n_sys, a.n_waves, a.work, a.work_doubles, marginal_ws(a.N, true).total);
+  if (!grid || !a.dPdrho || !a.theta0 || !a.scale) return hipErrorInvalidValue;
   for (int k = 0; k < 7; ++k) if (!a.geo7[k]) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_marginal_scan, dim3((unsigned)grid), dim3(64), 0, st, a);
   note_launch(grid, 64, "ibs::k_marginal_scan");

@@ -131,4 +131,28 @@ __device__ __forceinline__ double marginal_one(const double* G, const double* C,
   return s;
 }
 
+// ---- 4: the weight of g_j in the pencil's quadratic form, w_j = (X_j - X_{j-1})^2 + (X_{j+1} - X_j)^2 (the end rows have one cell):
+// d s* / d g_j = 1/2 h^-2 w_j / q
+__device__ __forceinline__ double pencil_weight(const double* Xw, int j, int N) {
+  const double x0 = Xw[j];
+  const double dm = j > 0 ? x0 - Xw[j - 1] : 0.0, dp = j < N - 1 ? Xw[j + 1] - x0 : 0.0;
+  return xfma(dm, dm, dp * dp);
+}
+
+// lane-0 outputs of the margin's point kernels (A = MarginalPointsArgs | MarginalTangentArgs): val = -mu = -1 / s*, jac = dscale / s*^2,
+// scale, dscale = (dal, dth), dPdrho = -mdP, info.  A failed solve (s NaN or status bit 0): every floating-point output NaN; status
+// bit 8 (s* = +inf): val = 0, and dal = dth = 0 as the caller filled them
+template <class A>
+__device__ __forceinline__ void marginal_store(const A& a, long p, double s, int status, int passes, double dal, double dth, double mdP) {
+  const bool failed = s != s || (status & 1);               // (the centre solve: iteration cap or invalid data)
+  if (failed) s = __builtin_nan("");
+  const double rs = 1.0 / s;                                // mu: 0 with s* = +inf
+  a.val[p] = (status & 256) ? 0.0 : -rs;
+  if (a.jac) { a.jac[2 * p] = dal * rs * rs; a.jac[2 * p + 1] = dth * rs * rs; }
+  if (a.scale) a.scale[p] = s;
+  if (a.dscale) { a.dscale[2 * p] = dal; a.dscale[2 * p + 1] = dth; }
+  if (a.dPdrho) a.dPdrho[p] = failed ? __builtin_nan("") : -mdP;
+  if (a.info) a.info[p] = passes | (status << 16);
+}
+
 }  // namespace ibs

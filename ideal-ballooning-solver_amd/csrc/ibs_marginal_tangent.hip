@@ -1,12 +1,13 @@
 // Marginal stability at geometry-fed points with the EXACT gradient of s* in (alpha, theta0) and its cotangent planes: k_marginal_points
 // (ibs_marginal_points.hip) with the alpha-derivative of the rows taken from the alpha-tangent of the geometry
 // (ibs_fieldline_geometry_dalpha_f64) in place of the del_alpha difference of two side lines (utils.py:1683-1718): ONE field line per
-// point, on the data layout of k_exact_tangent_points (ibs_exact_tangent.hip).  A sibling kernel in its own translation unit;
-// k_marginal_points itself is untouched.  FP64, every odd N in [66, 65,537], one wavefront per point on the persistent grid of the
+// point, on the data layout of k_exact_tangent_points (ibs_exact_tangent.hip).  Stages 1, 2, the theta0 part of 4 and 6 are the
+// functions k_marginal_points calls too: line_mdP, line_gcf, line_gcf_dtheta0 (ibs_geo_line.hpp), pencil_weight, marginal_store
+// (ibs_marginal.hpp).  FP64, every odd N in [66, 65,537], one wavefront per point on the persistent grid of the
 // long path, division form throughout; per-wave workspace marginal_ws(N, true).
 // Per point p (geo and geo_da in the [8][n_pts][ld] layout of the two geometry calls) and theta0[p]:
 //   1. dPdrho      of the line, -1/2 mean((cvdrift - gbdrift) bmag^2) as a wave reduction (the centre line's sum of k_marginal_points)
-//   2. rows        the line's (g, c) at theta0 in the wave's workspace, the arithmetic of k_marginal_scan
+//   2. rows        the line's (g, c) at theta0 in the wave's workspace: line_gcf, as k_marginal_scan
 //   3. s*          marginal_one: s*, status, passes and, with a gradient or geo_bar, the marginal mode X
 //   4. gradient    Hellmann-Feynman on the discrete pencil, q = sum c_j X_j^2, w_j = (X_j - X_{j-1})^2 + (X_{j+1} - X_j)^2:
 //                  d s* / d theta0 as k_marginal_points (the same sums in the same order);
@@ -49,23 +50,9 @@ __global__ void __launch_bounds__(64) k_marginal_tangent_points(const MarginalTa
     const GeoLine ln{a.geo + (size_t)p * a.ld, plane};
     // ---- 1. dPdrho of the line
     double mdP;                                             // -dPdrho
-    {
-      double s = 0.0;
-      for (int j = lane; j < N; j += kWave) {
-        const double B = ln.at(0, j);
-        s += (ln.at(2, j) - ln.at(7, j)) * B * B;
-      }
-      mdP = 0.5 * wave_sum(s) / (double)N;
-    }
-    // ---- 2. the line's rows at theta0 (the arithmetic of k_marginal_scan)
-    for (int j = lane; j < N; j += kWave) {
-      const double B = ln.at(0, j), gp = xabs(ln.at(1, j));
-      const double inv = 1.0 / (gp * B);
-      const double A1 = gp / B;
-      const double C0 = mdP * ln.at(2, j) * inv, C1 = mdP * ln.at(3, j) * inv;
-      const double d = ln.at(4, j) + (2.0 * th0) * ln.at(5, j) + (th0 * th0) * ln.at(6, j);
-      G[j] = A1 * d; C[j] = C0 + th0 * C1;
-    }
+    line_mdP<1>(&ln, N, lane, &mdP);
+    // ---- 2. the line's rows at theta0
+    for (int j = lane; j < N; j += kWave) line_gcf(ln, j, mdP, th0, G[j], C[j]);
     long_fence();                                           // (rows written by every lane, read by every lane below)
     // ---- 3. s* and the marginal mode
     int status, passes;
@@ -80,13 +67,9 @@ __global__ void __launch_bounds__(64) k_marginal_tangent_points(const MarginalTa
       if (want_grad) {
         const GeoLine lt{a.geo_da + (size_t)p * a.ld, plane};
         for (int j = lane; j < N; j += kWave) {
-          const double x0 = Xw[j], x2 = x0 * x0;
-          const double dm = j > 0 ? x0 - Xw[j - 1] : 0.0, dp = j < N - 1 ? Xw[j + 1] - x0 : 0.0;
-          const double w = xfma(dm, dm, dp * dp);
-          // theta0 tangent of the line (utils.py:1669-1673)
-          const double B = ln.at(0, j), gp = xabs(ln.at(1, j));
-          const double gt = (gp / B) * (2.0 * ln.at(5, j) + (2.0 * th0) * ln.at(6, j));
-          const double ct = mdP * ln.at(3, j) * (1.0 / (gp * B));
+          const double x0 = Xw[j], x2 = x0 * x0, w = pencil_weight(Xw, j, N);
+          double gt, ct;                                    // theta0 tangent of the line
+          line_gcf_dtheta0(ln, j, mdP, th0, gt, ct);
           q = xfma(C[j], x2, q);
           sg = xfma(gt, w, sg);
           sc = xfma(ct, x2, sc);
@@ -123,9 +106,7 @@ __global__ void __launch_bounds__(64) k_marginal_tangent_points(const MarginalTa
       } else {
         const double iq = 1.0 / q, kap = -s / mdP, iN = 1.0 / (double)N;
         for (int j = lane; j < N; j += kWave) {
-          const double x0 = Xw[j];
-          const double dm = j > 0 ? x0 - Xw[j - 1] : 0.0, dp = j < N - 1 ? Xw[j + 1] - x0 : 0.0;
-          const double w = xfma(dm, dm, dp * dp);
+          const double x0 = Xw[j], w = pencil_weight(Xw, j, N);
           const double gbar = 0.5 * ih2 * w * iq, cbar = -s * (x0 * x0) * iq;
           const double B = ln.at(0, j), gpr = ln.at(1, j), gp = xabs(gpr);
           const double iB = 1.0 / B, ia = 1.0 / gp;
@@ -148,24 +129,15 @@ __global__ void __launch_bounds__(64) k_marginal_tangent_points(const MarginalTa
       }
     }
     // ---- 6. outputs
-    if (lane == 0) {
-      if (failed) s = __builtin_nan("");
-      const double rs = 1.0 / s;                            // mu: 0 with s* = +inf
-      a.val[p] = (status & 256) ? 0.0 : -rs;
-      if (a.jac) { a.jac[2 * p] = dal * rs * rs; a.jac[2 * p + 1] = dth * rs * rs; }
-      if (a.scale) a.scale[p] = s;
-      if (a.dscale) { a.dscale[2 * p] = dal; a.dscale[2 * p + 1] = dth; }
-      if (a.dPdrho) a.dPdrho[p] = failed ? __builtin_nan("") : -mdP;
-      if (a.info) a.info[p] = passes | (status << 16);
-    }
+    if (lane == 0) marginal_store(a, p, s, status, passes, dal, dth, mdP);
     long_fence();                                           // (the workspace is reused by this wave's next point)
   }
 }
 
 hipError_t launch_marginal_tangent_points(const MarginalTangentArgs& a, hipStream_t st) {
   if (a.n_pts <= 0) return hipSuccess;
-  const long grid = a.n_pts < a.n_waves ? a.n_pts : a.n_waves;
-  if (grid < 1 || !a.geo || !a.theta0 || !a.val || !a.work || a.work_doubles < (size_t)grid * marginal_ws(a.N, true).total) return hipErrorInvalidValue;
+  const long grid = persistent_grid(a.n_pts, a.n_waves, a.work, a.work_doubles, marginal_ws(a.N, true).total);
+  if (!grid || !a.geo || !a.theta0 || !a.val) return hipErrorInvalidValue;
   if (((a.jac || a.dscale) && !a.geo_da) || a.ld < a.N || (a.geo_bar && a.ld_bar < a.N)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_marginal_tangent_points, dim3((unsigned)grid), dim3(64), 0, st, a);
   note_launch(grid, 64, "ibs::k_marginal_tangent_points");

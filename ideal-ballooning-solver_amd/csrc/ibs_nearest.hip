@@ -39,8 +39,8 @@ __global__ void __launch_bounds__(64) k_solve_gcf_nearest(long n_sys, int N, dou
 
 hipError_t launch_gcf_nearest(const NearestArgs& a, hipStream_t st) {
   if (a.n_sys <= 0) return hipSuccess;
-  const long grid = a.n_sys < a.n_waves ? a.n_sys : a.n_waves;
-  if (grid < 1 || !a.work || a.work_doubles < (size_t)grid * nearest_ws_doubles(a.N)) return hipErrorInvalidValue;
+  const long grid = persistent_grid(a.n_sys, a.n_waves, a.work, a.work_doubles, nearest_ws_doubles(a.N));
+  if (!grid) return hipErrorInvalidValue;
   if (a.gh) {
     hipLaunchKernelGGL(k_solve_gcf_nearest<true>, dim3((unsigned)grid), dim3(64), 0, st, a.n_sys, a.N, a.h, a.g, a.c, a.f, a.gh, a.ld, a.sigma,
                        a.lam, a.idx, a.gam, a.X, a.dX, a.info, a.work);

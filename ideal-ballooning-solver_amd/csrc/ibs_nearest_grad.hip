@@ -12,7 +12,8 @@
 //                  line's cvdrift0 / gds21 / gds22, the alpha tangent (right - left) / del_alpha with each side line's own dPdrho.  The
 //                  tangents are formed from the geometry as they are summed, never written out
 //   5. outputs     GRAD: val = -gam, jac = (-dgam/dalpha, -dgam/dtheta0) (utils.py:1728); else gam (and X, dX) as the solve gives them
-// Per-wave workspace: nearest_points_ws(N, GRAD) (ibs_launch.hpp), in global memory.
+// Per-wave workspace: nearest_points_ws(N, GRAD) (ibs_launch.hpp), in global memory.  dPdrho, the rows and their theta0 tangent are
+// the per-line functions of ibs_geo_line.hpp (line_mdP, line_gcf on either layout, line_gcf_dtheta0).
 #include "ibs_nearest.hpp"
 #include "ibs_geo_line.hpp"
 #include "ibs_launch.hpp"
@@ -31,39 +32,21 @@ __global__ void __launch_bounds__(64) k_nearest_points(const NearestPointsArgs a
   for (long p = blockIdx.x; p < a.n_pts; p += gridDim.x) {
     const double th0 = uniform(a.theta0[p]);
     GeoLine ln[3];
-    double mdP[3];
+    double mdP[3];                                          // -dPdrho
     if constexpr (GRAD) {
       // ---- 1. dPdrho of the three lines
-      double s[3] = {0.0, 0.0, 0.0};
 #pragma unroll
       for (int l = 0; l < 3; ++l) ln[l] = GeoLine{a.geo + ((size_t)p * 3 + l) * 8 * (size_t)a.ld, a.ld};
-      for (int j = lane; j < N; j += kWave) {
-#pragma unroll
-        for (int l = 0; l < 3; ++l) {
-          const double B = ln[l].at(0, j);
-          s[l] += (ln[l].at(2, j) - ln[l].at(7, j)) * B * B;
-        }
-      }
-#pragma unroll
-      for (int l = 0; l < 3; ++l) mdP[l] = 0.5 * wave_sum(s[l]) / (double)N;      // -dPdrho
+      line_mdP<3>(ln, N, lane, mdP);
     } else {
-      ln[1] = GeoLine{nullptr, 0};
       mdP[1] = -uniform(a.dPdrho[p]);
     }
     // ---- 2. the centre line's rows
+    const GeoLine7 l7 = geo_line7(a.geo7, p * a.ld);        // (the points form without GRAD)
     for (int j = lane; j < N; j += kWave) {
       double g, c, f;
-      if constexpr (GRAD) {
-        line_gcf(ln[1], j, mdP[1], th0, g, c, f);
-      } else {
-        const long o = p * a.ld + j;
-        const double B = a.geo7[0][o], gp = xabs(a.geo7[1][o]);
-        const double inv = 1.0 / (gp * B);
-        const double A1 = gp / B, A3 = inv / (B * B);
-        const double C0 = mdP[1] * a.geo7[2][o] * inv, C1 = mdP[1] * a.geo7[3][o] * inv;
-        const double d = a.geo7[4][o] + (2.0 * th0) * a.geo7[5][o] + (th0 * th0) * a.geo7[6][o];
-        g = A1 * d; c = C0 + th0 * C1; f = A3 * d;
-      }
+      if constexpr (GRAD) line_gcf(ln[1], j, mdP[1], th0, g, c, f);
+      else line_gcf(l7, j, mdP[1], th0, g, c, f);
       G[j] = g; C[j] = c; F[j] = f;
     }
     long_fence();                                           // (rows written by every lane, read by every lane below)
@@ -82,12 +65,8 @@ __global__ void __launch_bounds__(64) k_nearest_points(const NearestPointsArgs a
         for (int j = lane; j < N; j += kWave) {
           const double w = (j == 0 || j == N - 1) ? 1.0 : ((j & 1) ? 4.0 : 2.0);
           const double x2 = w * Xw[j] * Xw[j], d2 = w * dXw[j] * dXw[j];
-          // theta0 tangent of the centre line (utils.py:1669-1673)
-          const double B = ln[1].at(0, j), gp = xabs(ln[1].at(1, j));
-          const double inv = 1.0 / (gp * B);
-          const double A1 = gp / B, A3 = inv / (B * B);
-          const double dp = 2.0 * ln[1].at(5, j) + (2.0 * th0) * ln[1].at(6, j);
-          const double gt = A1 * dp, ct = mdP[1] * ln[1].at(3, j) * inv, ft = A3 * dp;
+          double gt, ct, ft;                                // theta0 tangent of the centre line
+          line_gcf_dtheta0(ln[1], j, mdP[1], th0, gt, ct, ft);
           // alpha tangent (utils.py:1705-1719): each side line with its own dPdrho
           double gl, cl, fl, gr, cr, fr;
           line_gcf(ln[0], j, mdP[0], th0, gl, cl, fl);
@@ -119,8 +98,8 @@ __global__ void __launch_bounds__(64) k_nearest_points(const NearestPointsArgs a
 
 static hipError_t launch_points(const NearestPointsArgs& a, bool grad, hipStream_t st) {
   if (a.n_pts <= 0) return hipSuccess;
-  const long grid = a.n_pts < a.n_waves ? a.n_pts : a.n_waves;
-  if (grid < 1 || !a.work || a.work_doubles < (size_t)grid * nearest_points_ws(a.N, grad).total) return hipErrorInvalidValue;
+  const long grid = persistent_grid(a.n_pts, a.n_waves, a.work, a.work_doubles, nearest_points_ws(a.N, grad).total);
+  if (!grid) return hipErrorInvalidValue;
   if (grad) {
     if (!a.geo || !a.val || !a.jac) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_nearest_points<true>, dim3((unsigned)grid), dim3(64), 0, st, a);

@@ -39,8 +39,8 @@ __global__ void __launch_bounds__(64) k_solve_gcf_vjp(const VjpArgs a) {
 
 hipError_t launch_gcf_vjp(const VjpArgs& a, hipStream_t st) {
   if (a.n_sys <= 0) return hipSuccess;
-  const long grid = a.n_sys < a.n_waves ? a.n_sys : a.n_waves;
-  if (grid < 1 || !a.work || a.work_doubles < (size_t)grid * vjp_ws_doubles(a.N)) return hipErrorInvalidValue;
+  const long grid = persistent_grid(a.n_sys, a.n_waves, a.work, a.work_doubles, vjp_ws_doubles(a.N));
+  if (!grid) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_solve_gcf_vjp, dim3((unsigned)grid), dim3(64), 0, st, a);
   note_launch(grid, 64, "ibs::k_solve_gcf_vjp");
   return hipGetLastError();
