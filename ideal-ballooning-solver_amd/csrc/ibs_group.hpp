@@ -148,9 +148,12 @@ struct GroupSolver {
     const int a = rows_start(lg, n);
     const T ih2 = T(1) / (h * h);
     T sc = T(1);
-    const T g0 = src.g(a);
-    T gcur = src.g(a + 1);
-    T e_lo = T(0.5) * (g0 + gcur) * ih2;
+    // (g a product: the means of the chunk with the rounding of ibs_half_grid.hpp, through the walker, as WaveSolver::setup)
+    constexpr bool kWalk = HalfGridWalk<T, Src, M>::kFactors;
+    HalfGridWalk<T, Src, M> hg;
+    T g0, gcur, e_lo;
+    if constexpr (kWalk) { hg.begin(src, a); g0 = hg.g; e_lo = hg.next(src, 0, a) * ih2; gcur = hg.g; }
+    else { g0 = src.g(a); gcur = src.g(a + 1); e_lo = T(0.5) * (g0 + gcur) * ih2; }
     T vhi = -T(1e300), vlo = -T(1e300), vna = T(0), sum_c = T(0), sum_f = T(0);
     bool bad = !(g0 > T(0)) || !(gcur > T(0));   // non-finite data, g <= 0 or f <= 0 anywhere in this lane's rows
     const T e_first = e_lo;
@@ -167,9 +170,9 @@ struct GroupSolver {
       const bool act = (i < M - 1) || has_last;
       if (act) {
         const int j = a + i + 1;
-        const T gnext = src.g(j + 1);
-        bad = bad || !(gnext > T(0));
-        const T e_hi = T(0.5) * (gcur + gnext) * ih2;
+        T gnext, e_hi;
+        if constexpr (kWalk) { e_hi = hg.next(src, i + 1, j) * ih2; gnext = hg.g; bad = bad || !(gnext > T(0)); }
+        else { gnext = src.g(j + 1); bad = bad || !(gnext > T(0)); e_hi = T(0.5) * (gcur + gnext) * ih2; }
         const T cj = src.c(j), fj = src.f(j);
         const T d = cj - (e_lo + e_hi);
         const T s2 = sc * sc;
@@ -399,14 +402,17 @@ struct GroupSolver {
   }
 
   // eigenvector entries of this lane's rows up to a common factor per group (normalised by the caller);
-  // the diagonal scaling s is rebuilt here from g (s_0 = 1, s_{i+1} = 1/(e_{i+1} s_i)), the forward solution is
+  // the diagonal scaling s is rebuilt here from g (s_0 = 1, s_{i+1} = 1/(e_{i+1} s_i); set-up's numbers), the forward solution is
   // replayed at the shift of the last twisted() call
   template <class Src>
   __device__ __forceinline__ void assemble(const Src& src, int N, T h, T (&x)[M]) {
     const int a = rows_start(lg, N - 2);
     const T ih2 = T(1) / (h * h);
     T sc = T(1);
-    T gcur = src.g(a + 1);
+    constexpr bool kWalk = HalfGridWalk<T, Src, M>::kFactors;
+    HalfGridWalk<T, Src, M> hg;
+    T gcur = T(0);
+    if constexpr (kWalk) hg.begin(src, a + 1); else gcur = src.g(a + 1);
     T zc = u0_in, zp = zu_m1;
 #pragma unroll
     for (int i = 0; i < M; ++i) {
@@ -414,9 +420,14 @@ struct GroupSolver {
       const T xu = sc * zc * fu, xw = sc * zw[i] * fw;
       x[i] = act ? ((i <= thr) ? xu : xw) : T(0);
       if (act) {
-        const T gnext = src.g(a + i + 2);
-        sc = fast_rcp(T(0.5) * (gcur + gnext) * ih2 * sc);
-        gcur = gnext;
+        if constexpr (kWalk) {
+          const T e_hi = hg.next(src, i + 1, a + i + 1) * ih2;  // (the product as set-up writes it: the two are merged, and keep their flags)
+          sc = fast_rcp(e_hi * sc);
+        } else {
+          const T gnext = src.g(a + i + 2);
+          sc = fast_rcp(T(0.5) * (gcur + gnext) * ih2 * sc);
+          gcur = gnext;
+        }
         const T zn = xfma(-xfma(-sig_vec, Ph[i], D[i]), zc, -zp);
         zp = zc; zc = zn;
       }

@@ -254,10 +254,7 @@ template <typename T, class Src, bool WT>
 __device__ __forceinline__ void simpson_point_carried(const Src& src, int j, T a1, T d_, T c_, T f_, T w, T X, T dX, T& y0, T& y1,
                                                       T& hc, T& hg, T& hf) {
   const T X2 = w * (X * X), dX2 = w * (dX * dX);
-  // (the product is formed HERE, from a factor the compiler cannot trace: merged with set-up's own a1 * d it would be one more use
-  //  of that product, and the number of uses decides which product of set-up's half-grid means is contracted into an fma)
-  asm volatile("" : "+v"(d_));
-  const T g_ = a1 * d_;
+  const T g_ = a1 * d_;       // (set-up's means no longer depend on how often this product is used: ibs_half_grid.hpp)
   if constexpr (WT) {
     T gt, ct, ft;
     src.tangent(j, a1, gt, ct, ft);

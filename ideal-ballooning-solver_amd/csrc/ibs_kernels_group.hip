@@ -30,6 +30,7 @@ struct SrcGeoG {     // as SrcGeo (ibs_kernels.hip): 7 derived arrays of the lin
   // rows are padded: element j at lpos(j)
   __device__ __forceinline__ T gd(int j) const { const int q = lpos(j); return G0[q] + two_th0 * G1[q] + th0sq * G2[q]; }
   __device__ __forceinline__ T g(int j) const { return A1[lpos(j)] * gd(j); }
+  __device__ __forceinline__ void g_factors(int j, T& a1, T& d_) const { a1 = A1[lpos(j)]; d_ = gd(j); }   // g = a1 * d_ (HalfGridWalk)
   __device__ __forceinline__ T c(int j) const { const int q = lpos(j); return C0[q] + th0 * C1[q]; }
   __device__ __forceinline__ T f(int j) const { return A3[lpos(j)] * gd(j); }
   __device__ __forceinline__ T gdp(int j) const { const int q = lpos(j); return T(2) * G1[q] + two_th0 * G2[q]; }

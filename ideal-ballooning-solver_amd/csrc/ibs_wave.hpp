@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "ibs_sweep_count.hpp"
+#include "ibs_half_grid.hpp"
 
 namespace ibs {
 
@@ -528,6 +529,37 @@ __device__ __forceinline__ bool reclose_division(const Src& src, int N, T h, T c
   return multisect_division<T, Src>(src, N, h, center - T(2048) * epsA, center + T(2048) * epsA, normA, lane, lam, passes);
 }
 
+// ---------------------------------------------------------------- half-grid means of a lane's chunk
+// A source whose g is a product says so by giving its factors: g_factors(j, a1, d), g(j) = a1 * d.
+template <class Src, typename T, typename = void>
+struct SrcHasGFactors : std::false_type {};
+template <class Src, typename T>
+struct SrcHasGFactors<Src, T, std::void_t<decltype(std::declval<const Src&>().g_factors(0, std::declval<T&>(), std::declval<T&>()))>>
+    : std::true_type {};
+
+// Walks the chunk points of a lane upwards and gives the half-grid mean between each pair with the rounding of
+// ibs_half_grid.hpp: set-up, assemble() and the sub-wave solver all form their means here.  Holds chunk point k after begin(k, ..)
+// and k + 1 after next(k, ..); k is the chunk-local index (grid point minus the lane's rows_start), a constant of the unrolled
+// row loops; M = rows per lane.
+template <typename T, class Src, int M>
+struct HalfGridWalk {
+  static constexpr bool kFactors = SrcHasGFactors<Src, T>::value;   // (a source of stored g keeps its plain mean where it was)
+  T a1, d;     // factors of the held point
+  T g;         // its g: the rounded product
+  __device__ __forceinline__ void load(const Src& src, int j, T& a1_, T& d_, T& g_) const {
+    src.g_factors(j, a1_, d_); g_ = half_grid_product(a1_, d_);
+  }
+  __device__ __forceinline__ void begin(const Src& src, int j) { load(src, j, a1, d, g); }
+  // mean k, between the held chunk point k (grid point j) and the next one, which is held afterwards
+  __device__ __forceinline__ T next(const Src& src, int k, int j) {
+    T a1n, dn, gn;
+    load(src, j + 1, a1n, dn, gn);
+    const T m = half_grid_fuses_lower(k, M) ? half_grid_mean_fused(a1, d, gn) : half_grid_mean_fused(a1n, dn, g);
+    a1 = a1n; d = dn; g = gn;
+    return m;
+  }
+};
+
 // ---------------------------------------------------------------- per-wave solver state
 struct SolveInfo {
   int iters;    // fused double sweeps used
@@ -537,15 +569,14 @@ struct SolveInfo {
 // Rows a wave carries in registers from set-up to the growth-rate stage (WaveSolver<T, M, true>): per owned row i the two
 // factors of g at its grid point (Src::g_factors: g = a1 * d), c and f there, and -- from pass A of twisted() on -- the forward
 // solution at the final shift.  ih2 = 1 / (h * h) and ih = 1 / h are formed once on the host (correctly rounded divisions on
-// both sides).  g is kept as its factors, and the scaling s is NOT kept, for the sake of the bits: the half-grid mean
-// 0.5 * (g_j + g_j+1) adds two products, the compiler contracts one of them into an fma, and WHICH one depends on how many
-// uses each product has -- a kept copy of g is one more use and moves D and Ph by an ulp, and set-up and assemble() contract
-// their (identical) expressions differently to begin with, so that the s of set-up is not the s assemble() has always used.
+// both sides).  g is kept as its factors (every second chunk point never forms its product for a mean: ibs_half_grid.hpp).  s[i] is
+// the diagonal scaling of row i as set-up stepped it, s_0 = 1, s_{i+1} = 1 / (e_{i+1} s_i): the numbers D and Ph were scaled
+// with, and -- the means being formed by one rule -- bit for bit what the lean form's assemble() rebuilds from g.
 template <typename T, int M, bool RES>
 struct ResidentRows {};
 template <typename T, int M>
 struct ResidentRows<T, M, true> {
-  T a1[M], d[M], c[M], f[M], zu[M];
+  T a1[M], d[M], c[M], f[M], zu[M], s[M];
   T ih2, ih;
   unsigned own;      // the sign changes of a forward sweep this lane counts (sweep_count_mask): set-up forms it once
 };
@@ -612,12 +643,20 @@ struct WaveSolver {
     T sc = T(1);
     // half-grid g between grid points k and k+1 (utils.py:1574-1576): the mean of the neighbours on a uniform
     // grid, or a caller-supplied array when the input grid was regridded (Src::kHasGh)
+    // (g a product: the mean's rounding is ibs_half_grid.hpp's, through the walker; the product with ih2 stays here)
+    constexpr bool kWalk = HalfGridWalk<T, Src, M>::kFactors;
+    HalfGridWalk<T, Src, M> hg;
     T gcur = T(0);
     T e_lo;
     bool bad = false;                            // non-finite data, g <= 0 or f <= 0 anywhere in this lane's rows
     if constexpr (Src::kHasGh) {
       e_lo = src.gh(a) * ih2;
       bad = !(src.g(a) > T(0));
+    } else if constexpr (kWalk) {
+      hg.begin(src, a);
+      const T g0 = hg.g;
+      e_lo = hg.next(src, 0, a) * ih2;    // e_a
+      bad = !(g0 > T(0)) || !(hg.g > T(0));
     } else {
       const T g0 = src.g(a);
       gcur = src.g(a + 1);
@@ -640,7 +679,9 @@ struct WaveSolver {
       if (act) {
         const int j = a + i + 1;  // grid point of row a+i
         T gnext = T(0), e_hi;                           // e_{a+i+1}
+        if constexpr (RES) { rr.a1[i] = hg.a1; rr.d[i] = hg.d; rr.s[i] = sc; }
         if constexpr (Src::kHasGh) { e_hi = src.gh(j) * ih2; bad = bad || !(src.g(j + 1) > T(0)); }
+        else if constexpr (kWalk) { e_hi = hg.next(src, i + 1, j) * ih2; bad = bad || !(hg.g > T(0)); }
         else { gnext = src.g(j + 1); e_hi = T(0.5) * (gcur + gnext) * ih2; bad = bad || !(gnext > T(0)); }
         const T cj = src.c(j), fj = src.f(j);
         const T d = cj - (e_lo + e_hi);
@@ -658,12 +699,12 @@ struct WaveSolver {
         vna = xmax(vna, (xabs(d) + e_lo + e_hi) * rf);
         sum_c += cj; sum_f += fj;
         bad = bad || !(fj > T(0)) || !(e_hi > T(0)) || !finite_of(cj);
-        if constexpr (RES) { src.g_factors(j, rr.a1[i], rr.d[i]); rr.c[i] = cj; rr.f[i] = fj; }
+        if constexpr (RES) { rr.c[i] = cj; rr.f[i] = fj; }
         sc = fast_rcp(e_hi * sc);           // e s_i s_{i+1} = 1 to rounding (two Newton steps on the hardware seed)
         gcur = gnext; e_lo = e_hi;
       } else {
         D[i] = T(0); Ph[i] = T(0);
-        if constexpr (RES) { rr.a1[i] = T(0); rr.d[i] = T(0); rr.c[i] = T(0); rr.f[i] = T(0); }
+        if constexpr (RES) { rr.a1[i] = T(0); rr.d[i] = T(0); rr.c[i] = T(0); rr.f[i] = T(0); rr.s[i] = T(0); }
       }
       // the rows hang on one dependent chain (sc), so the scheduler would put EVERY row's LDS reads in flight first
       // (3 to 7 values per row: > 400 VGPRs at M = 32); at most kSetupRows rows at a time
@@ -970,34 +1011,44 @@ struct WaveSolver {
   }
 
   // eigenvector entries of this lane's rows up to a common factor (normalised by the caller).  The diagonal scaling s is
-  // rebuilt here from g with the arithmetic of setup() (s_0 = 1, s_{i+1} = 1 / (e_{i+1} s_i)), the forward solution is
-  // replayed at the shift of the last twisted() call.  D, Ph and zw are consumed row by row: x[] replaces them.
+  // rebuilt here from g with the arithmetic of setup() (s_0 = 1, s_{i+1} = 1 / (e_{i+1} s_i); the means by the one rule of
+  // ibs_half_grid.hpp, so these are set-up's numbers), the forward solution is replayed at the shift of the last twisted()
+  // call.  D, Ph and zw are consumed row by row: x[] replaces them.
   // gh: the caller-supplied half-grid g of setup() (Src::kHasGh), or null = mean of the neighbouring g.
-  // RES: the forward solution is the one pass A of twisted() kept; nothing is replayed.
+  // RES: s is set-up's own and the forward solution the one pass A of twisted() kept; nothing is read, rebuilt or replayed.
   template <class Src>
   __device__ __forceinline__ void assemble(const Src& src, const T* gh, int N, T h, T (&x)[M]) {
+    if constexpr (RES) {
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+        const bool act = (i < M - 1) || has_last;
+        const T xu = rr.s[i] * rr.zu[i] * fu, xw = rr.s[i] * zw[i] * fw;
+        x[i] = act ? ((i <= thr) ? xu : xw) : T(0);
+      }
+      return;
+    }
     int a = rows_start(lane, N - 2);
     asm volatile("" : "+v"(a));          // (keeps the compiler from carrying setup()'s LDS addresses across the iteration)
-    T ih2;
-    if constexpr (RES) ih2 = rr.ih2; else ih2 = T(1) / (h * h);
+    const T ih2 = T(1) / (h * h);
     T sc = T(1);
-    T gcur = src.g(a + 1);
+    constexpr bool kWalk = HalfGridWalk<T, Src, M>::kFactors;
+    HalfGridWalk<T, Src, M> hg;
+    T gcur = T(0);
+    if constexpr (kWalk) hg.begin(src, a + 1); else gcur = src.g(a + 1);
     T zc = u0_in, zp = zu_m1;
 #pragma unroll
     for (int i = 0; i < M; ++i) {
       const bool act = (i < M - 1) || has_last;
-      if constexpr (RES) zc = rr.zu[i];
       const T xu = sc * zc * fu, xw = sc * zw[i] * fw;
       x[i] = act ? ((i <= thr) ? xu : xw) : T(0);
       if (act) {
         T e_hi;
         if (gh) e_hi = gh[a + i + 1] * ih2;                    // (wave-uniform branch)
+        else if constexpr (kWalk) e_hi = hg.next(src, i + 1, a + i + 1) * ih2;   // (the product as set-up writes it: merged with set-up's, it keeps its flags)
         else { const T gnext = src.g(a + i + 2); e_hi = T(0.5) * (gcur + gnext) * ih2; gcur = gnext; }
         sc = fast_rcp(e_hi * sc);
-        if constexpr (!RES) {
-          const T zn = xfma(-xfma(-sig_vec, Ph[i], D[i]), zc, -zp);
-          zp = zc; zc = zn;
-        }
+        const T zn = xfma(-xfma(-sig_vec, Ph[i], D[i]), zc, -zp);
+        zp = zc; zc = zn;
       }
       if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // at most 4 rows of LDS reads in flight (registers)
     }
