@@ -9,6 +9,7 @@
 //  k_sturm_count : inertia of T - lam F at given shifts (pins the s-alpha stability test)
 #include "ibs_wave.hpp"
 #include "ibs_launch.hpp"
+#include "ibs_scan_map.hpp"
 #include "ibs_refine.hpp"
 #include <type_traits>
 
@@ -1094,8 +1095,16 @@ __global__ void __launch_bounds__(256) k_solve_gcf_rows(long n_sys, int N, T h, 
   }
 }
 
+// the block's place in a scan launch (ibs_scan_map.hpp): nparts_1d = 0: the 3-D grid launch_scan / launch_scan_chain launch (no
+// division); else the 1-D form of a launch too long for a 3-D grid, nparts_1d = the blocks of a line
+__device__ __forceinline__ ScanBlock scan_block(int n_lines, int nparts_1d) {
+  if (__builtin_expect(nparts_1d != 0, 0)) return scan_block_1d(n_lines, nparts_1d, blockIdx.x);
+  return scan_block_3d(n_lines, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y);
+}
+
 // ---------------------------------------------------------------- geometry-fed theta0 scan
-// grid = n_lines * ceil(n_theta0 / wpb) blocks; block = wpb waves; wave w solves theta0 index part*wpb + w.
+// grid = ceil(n_theta0 / wpb) blocks ("parts") per line, laid out by scan_grid (ibs_scan_map.hpp: 3-D, chunks of 8 lines); block =
+// wpb waves; wave w solves theta0 index part*wpb + w.
 // dynamic LDS = (7 + wpb) * lds_pitch(N) * sizeof(T).  Geometry arrays are [n_lines][ld].
 // Two forms of one body.  RES (k_gamma_scan<T, M>, 3 <= M <= 8): the rows set-up forms stay in registers up to the growth-rate
 // stage (WaveSolver<T, M, true>; 186 VGPRs at M = 8, two waves per SIMD) -- for launches of at most two waves per SIMD, whose
@@ -1111,26 +1120,25 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
                                                      T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
                                                      int* info_out, const T* __restrict__ lam_guess, T guess_width,
                                                      int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
-                                                     int t0_stride, T ih2, T ih) {
+                                                     int t0_stride, T ih2, T ih, int nparts_1d) {
   // t0_stride: 0 = the theta0 grid is shared by all lines; 1 (with n_theta0 = 1) = one theta0 per line (ibs_gamma_points_f64)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
   IBS_PROBE_AT(0);
-  // XCD-aware block -> (line, part) map.  Workgroups are dealt round-robin over the 8 XCDs, so blocks b
-  // and b+8 share an L2: the `nparts` blocks that scan different theta0 of ONE line are placed 8 apart
-  // and the line's geometry is fetched from HBM once per XCD instead of once per block (speed only).
-  const int nparts = (n_theta0 + wpb - 1) / wpb;
-  int line, part;
-  {
-    const int b = blockIdx.x;
-    const int chunk = b / (8 * nparts), r = b - chunk * 8 * nparts;
-    const int lines_here = min(8, n_lines - chunk * 8);
-    line = chunk * 8 + r % lines_here;
-    part = r / lines_here;
-    if (part >= nparts) return;   // cannot happen (r < lines_here*nparts is guaranteed by the grid size)
+  if constexpr (RES) {
+    // Every kernel argument the prologue reads, wanted HERE: the compiler fetches an argument in front of the block that first
+    // uses it, which made four dependent scalar-memory rounds between entry and the first staging load (map | theta0 | lam_guess |
+    // the array pointers).  One empty statement that names them all puts their fetches in one round at entry.
+    asm volatile("" :: "s"(bmag), "s"(gradpar), "s"(cvdrift), "s"(cvdrift0), "s"(gds2), "s"(gds21), "s"(gds22), "s"(ld), "s"(dPdrho),
+                 "s"(theta0), "s"(lam_guess), "s"(n_lines), "s"(n_theta0), "s"(N), "s"(t0_stride), "s"(nparts_1d), "s"(wpb));
   }
+  // XCD-aware block -> (line, part) map (ibs_scan_map.hpp): read from the block's indices; a column of the last chunk that has no
+  // line returns here, before it touches LDS, memory or the arrival counters
+  const ScanBlock blk = scan_block(n_lines, nparts_1d);
+  if (!blk.live) return;
+  const int line = blk.line, part = blk.part, nparts = blk.nparts;
   const int P = lds_pitch(N);
   T* A1 = smem; T* A3 = A1 + P; T* C0 = A3 + P; T* C1 = C0 + P; T* G0 = C1 + P; T* G1 = G0 + P; T* G2 = G1 + P;
   T* Xs = G2 + P + (size_t)wave * P;
@@ -1142,9 +1150,9 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
   const T th0 = theta0[(long)line * t0_stride + it0c];
   const long sys = (long)line * n_theta0 + it0c;
   const T guess = lam_guess ? lam_guess[sys] : T(0);
+  const T mdP = -dPdrho[line];
   {
     const long off = (long)line * ld;
-    const T mdP = -dPdrho[line];
     for (int j = threadIdx.x; j < N; j += blockDim.x) {
       const T B = bmag[off + j], gp = xabs(gradpar[off + j]);
       const T inv = T(1) / (gp * B);                    // 1/(|gradpar| B)   (IEEE divisions: the coefficients are
@@ -1267,10 +1275,10 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines,
                                                      T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
                                                      int* info_out, const T* __restrict__ lam_guess, T guess_width,
                                                      int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
-                                                     int t0_stride, T ih2, T ih) {
+                                                     int t0_stride, T ih2, T ih, int nparts_1d) {
   gamma_scan_body<T, M, scan_resident_built(M)>(n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld,
                                                 dPdrho, theta0, gam_out, lam_out, X_out, dX_out, dth0_out, info_out, lam_guess,
-                                                guess_width, lines_per_surf, surf_counter, pack, pack_mode, t0_stride, ih2, ih);
+                                                guess_width, lines_per_surf, surf_counter, pack, pack_mode, t0_stride, ih2, ih, nparts_1d);
 }
 // the lean form under a name of its own (3 <= M <= 8: launches above two waves per SIMD, option scan_resident = 0)
 template <typename T, int M>
@@ -1283,10 +1291,10 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan_lean(int n_l
                                                      T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
                                                      int* info_out, const T* __restrict__ lam_guess, T guess_width,
                                                      int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
-                                                     int t0_stride) {
+                                                     int t0_stride, int nparts_1d) {
   gamma_scan_body<T, M, false>(n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho, theta0,
                                gam_out, lam_out, X_out, dX_out, dth0_out, info_out, lam_guess, guess_width, lines_per_surf,
-                               surf_counter, pack, pack_mode, t0_stride, T(0), T(0));
+                               surf_counter, pack, pack_mode, t0_stride, T(0), T(0), nparts_1d);
 }
 
 
@@ -1302,22 +1310,14 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan_chain(
     const T* __restrict__ cvdrift, const T* __restrict__ cvdrift0, const T* __restrict__ gds2,
     const T* __restrict__ gds21, const T* __restrict__ gds22, long ld, const T* __restrict__ dPdrho,
     const T* __restrict__ theta0, T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out, int* info_out,
-    int chain, T w1, T w2) {
+    int chain, T w1, T w2, int nparts_1d) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   const int wave = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
-  const int waves_per_line = (n_theta0 + chain - 1) / chain;
-  const int nparts = (waves_per_line + wpb - 1) / wpb;
-  int line, part;
-  {   // XCD-aware block -> (line, part) map of k_gamma_scan
-    const int b = blockIdx.x;
-    const int chunk = b / (8 * nparts), r = b - chunk * 8 * nparts;
-    const int lines_here = min(8, n_lines - chunk * 8);
-    line = chunk * 8 + r % lines_here;
-    part = r / lines_here;
-    if (part >= nparts) return;
-  }
+  const ScanBlock blk = scan_block(n_lines, nparts_1d);     // XCD-aware block -> (line, part) map of k_gamma_scan
+  if (!blk.live) return;
+  const int line = blk.line, part = blk.part;
   const int P = lds_pitch(N);
   T* A1 = smem; T* A3 = A1 + P; T* C0 = A3 + P; T* C1 = C0 + P; T* G0 = C1 + P; T* G1 = G0 + P; T* G2 = G1 + P;
   T* Xs = (M < 3 || X_out || dX_out) ? G2 + P + (size_t)wave * P : nullptr;
@@ -1929,7 +1929,9 @@ template <typename T>
 static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb;
   const size_t lds = (size_t)(7 + wpb) * lds_pitch(a.N) * sizeof(T);
-  dim3 grid((unsigned)(((a.n_theta0 + wpb - 1) / wpb) * a.n_lines));
+  const ScanGrid sg = scan_grid(a.n_lines, (a.n_theta0 + wpb - 1) / wpb);
+  const dim3 grid(sg.x, sg.y, sg.z);
+  const int nparts_1d = sg.flat ? (a.n_theta0 + wpb - 1) / wpb : 0;
   if constexpr (scan_resident_built(IBS_M)) {
     if (!a.resident) {
       auto lean = k_gamma_scan_lean<T, IBS_M>;
@@ -1938,8 +1940,8 @@ static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
       hipLaunchKernelGGL(lean, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
                          a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
                          a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
-                         a.t0_stride);
-      note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan_lean<%s, %d>", type_name<T>(), IBS_M);
+                         a.t0_stride, nparts_1d);
+      note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan_lean<%s, %d>", type_name<T>(), IBS_M);
       return hipGetLastError();
     }
   }
@@ -1949,8 +1951,8 @@ static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
   hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
                      a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
                      a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
-                     a.t0_stride, a.ih2, a.ih);
-  note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan<%s, %d>", type_name<T>(), IBS_M);
+                     a.t0_stride, a.ih2, a.ih, nparts_1d);
+  note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan<%s, %d>", type_name<T>(), IBS_M);
   return hipGetLastError();
 }
 template <typename T>
@@ -1962,11 +1964,13 @@ static hipError_t launch_scan_chain(const ScanArgs<T>& a, hipStream_t st) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   const int waves_per_line = (a.n_theta0 + chain - 1) / chain;
-  dim3 grid((unsigned)(((waves_per_line + wpb - 1) / wpb) * a.n_lines));
+  const ScanGrid sg = scan_grid(a.n_lines, (waves_per_line + wpb - 1) / wpb);
+  const dim3 grid(sg.x, sg.y, sg.z);
+  const int nparts_1d = sg.flat ? (waves_per_line + wpb - 1) / wpb : 0;
   hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
                      a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
-                     a.dX, a.dth0, a.info, chain, a.chain_w1, a.chain_w2);
-  note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan_chain<%s, %d>", type_name<T>(), IBS_M);
+                     a.dX, a.dth0, a.info, chain, a.chain_w1, a.chain_w2, nparts_1d);
+  note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan_chain<%s, %d>", type_name<T>(), IBS_M);
   return hipGetLastError();
 }
 template <typename T>

@@ -42,11 +42,13 @@ __device__ double ibs_trace_all[404];
 // waves 0 .. 3 of a block stamp; a block's further waves do not (their rows would be the next block's, and past the end of the
 // table for the last block).
 __device__ long long ibs_probe_buf[(16 + 4) * 4096];
-#define IBS_PROBE_SLOT(k) ibs_probe_buf[(k) < 16 ? (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (k) \
-                                                 : 16 * 4096 + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + ((k) - 16)]
+// (the block's place in the linear order of the workgroups: blockIdx.x on the 1-D grids, and on the 3-D grids of the scan kernels)
+#define IBS_PROBE_BLOCK() (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z))
+#define IBS_PROBE_SLOT(k) ibs_probe_buf[(k) < 16 ? (IBS_PROBE_BLOCK() * 4 + (threadIdx.x >> 6)) * 16 + (k) \
+                                                 : 16 * 4096 + (IBS_PROBE_BLOCK() * 4 + (threadIdx.x >> 6)) * 4 + ((k) - 16)]
 // a stamp taken at one place (NOW) and written at a later one (PUT: where its store would sit in front of loads that are waited for)
 #define IBS_PROBE_NOW() wall_clock64()
-#define IBS_PROBE_PUT(k, t) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024 && threadIdx.x < 256) IBS_PROBE_SLOT(k) = (t); } while (0)
+#define IBS_PROBE_PUT(k, t) do { if ((threadIdx.x & 63) == 0 && IBS_PROBE_BLOCK() < 1024 && threadIdx.x < 256) IBS_PROBE_SLOT(k) = (t); } while (0)
 #define IBS_PROBE_AT(k) IBS_PROBE_PUT(k, wall_clock64())
 #else
 #define IBS_PROBE_AT(k) do {} while (0)
@@ -183,6 +185,13 @@ __device__ __forceinline__ double dppz_t(double src) {
 }
 template <int CTRL, int ROWMASK>
 __device__ __forceinline__ float dppz_t(float src) { return __int_as_float(dppz_i<CTRL, ROWMASK>(__float_as_int(src))); }
+
+// wave_shr:1 with the fill 1.0 in lane 0, = dpp_t<0x138, 0xF>(T(1), src): in double the low word of the fill is zero and comes from
+// the zero-fill form; only the high word names a previous value
+__device__ __forceinline__ double shr1_fill_one(double src) {
+  return __hiloint2double(dpp_i<0x138, 0xF>(0x3ff00000, __double2hiint(src)), dppz_i<0x138, 0xF>(__double2loint(src)));
+}
+__device__ __forceinline__ float shr1_fill_one(float src) { return dpp_t<0x138, 0xF>(1.0f, src); }
 
 // fetch into the rows of ROWMASK for a caller in which the lanes of the other rows never look at what they got: no previous value
 // is named, so none has to be set up in the destination (with `old = 0` and a partial row mask: one v_mov per dword and step)
@@ -818,9 +827,11 @@ struct WaveSolver {
     renorm(F);
     const M2<T> P = scan_fwd_rows(F, lane);
     shoot_m = readlane_t(P.a, kWave - 1); shoot_e = readlane_i(P.e, kWave - 1);
-    const T u0 = dpp_t<0x138, 0xF>(T(1), P.a);   // wave_shr:1  (lane 0 reads the fill: (1, 0), exponent 0)
-    const T um = dpp_t<0x138, 0xF>(T(0), P.c);
-    Eu = dpp_i<0x138, 0xF>(0, P.e);
+    // wave_shr:1  (lane 0 reads the fill: (1, 0), exponent 0.  Every word of that fill but the high word of 1.0 is zero, and a
+    // zero the fetch supplies itself (dppz_*: no register set up in front of it); sweep_fwd's values, bit for bit)
+    const T u0 = shr1_fill_one(P.a);
+    const T um = dppz_t<0x138, 0xF>(P.c);
+    Eu = dppz_i<0x138, 0xF>(P.e);
     zu_m1 = um; u0_in = u0;
     T zc = u0, zp = um;
     unsigned w = sign_word(um) >> 31;
@@ -901,6 +912,18 @@ struct WaveSolver {
   // of the prefix-product sweeps lost an eigenvalue (a shift that landed within their noise band of lam_2 read 0 instead of 1 and
   // became the bracket's upper end: one system of 10^6 at N_zeta = 1024 returned lam_2, 1.5e-10 ||A|| below lam_max: golden G10).
   int extra_above;
+  // RES: the entries around twist row I of lane Lk, read from that lane's registers (I a constant: no indexed register array):
+  // u_I and its predecessor, w_I and its successor, and the row's t = D_I - sig Ph_I as pass A forms it
+  template <int I>
+  __device__ __forceinline__ void twist_pick(T sig, int Lk, T& zu_k, T& um1, T& zw_k, T& wp1, T& t_k) const {
+    if constexpr (RES && I < M) {
+      zu_k = readlane_t(rr.zu[I], Lk);
+      if constexpr (I == 0) um1 = readlane_t(zu_m1, Lk); else um1 = readlane_t(rr.zu[I - 1], Lk);
+      zw_k = readlane_t(zw[I], Lk);
+      if constexpr (I == M - 1) wp1 = readlane_t(zw_p1, Lk); else wp1 = readlane_t(zw[I + 1], Lk);
+      t_k = readlane_t(xfma(-sig, Ph[I], D[I]), Lk);
+    }
+  }
   template <bool CNT = false>
   __device__ __forceinline__ T twisted(T sig) {
     // pass A: replay the forward solution; per-lane candidate for the twist row k = argmax f |u w| (any row with a large
@@ -908,7 +931,7 @@ struct WaveSolver {
     // dynamically indexed access is needed afterwards
     T best = T(0);
     int bi = 0;
-    T zu_b = T(1), zum_b = T(0), zw_b = T(1), zwp_b = T(0), t_b = T(0);
+    [[maybe_unused]] T zu_b = T(1), zum_b = T(0), zw_b = T(1), zwp_b = T(0), t_b = T(0);      // (lean form; RES: twist_pick)
     {
       T zc = u0_in, zp = zu_m1;
 #pragma unroll
@@ -918,9 +941,12 @@ struct WaveSolver {
         const T a = act ? xabs(Ph[i] * (zc * zw[i])) : T(0);
         const bool better = a > best;
         best = better ? a : best; bi = better ? i : bi;
-        zu_b = better ? zc : zu_b; zum_b = better ? zp : zum_b; t_b = better ? t : t_b;
-        zw_b = better ? zw[i] : zw_b; zwp_b = better ? (i == M - 1 ? zw_p1 : zw[i < M - 1 ? i + 1 : M - 1]) : zwp_b;
-        if constexpr (RES) rr.zu[i] = zc;
+        if constexpr (RES) {
+          rr.zu[i] = zc;                   // (the entries around the twist row are read from the winning lane's registers below)
+        } else {
+          zu_b = better ? zc : zu_b; zum_b = better ? zp : zum_b; t_b = better ? t : t_b;
+          zw_b = better ? zw[i] : zw_b; zwp_b = better ? (i == M - 1 ? zw_p1 : zw[i < M - 1 ? i + 1 : M - 1]) : zwp_b;
+        }
         const T zn = xfma(-t, zc, -zp);
         if (act) { zp = zc; zc = zn; }
       }
@@ -940,8 +966,29 @@ struct WaveSolver {
       Lk = __float_as_int(wave_max(key)) & 63;
     }
     const int ik = readlane_i(bi, Lk);
-    const T zu_k = readlane_t(zu_b, Lk), zw_k = readlane_t(zw_b, Lk), t_k = readlane_t(t_b, Lk);
-    const T um1 = readlane_t(zum_b, Lk), wp1 = readlane_t(zwp_b, Lk);
+    T zu_k, zw_k, t_k, um1, wp1;
+    if constexpr (RES) {
+      // Only lane Lk's candidate is ever read, and everything it names is still in that lane's registers: ik is wave-uniform, so
+      // one switch with constant register indices per case reads (u_k, u_{k-1}, w_k, w_{k+1}, t_k) there -- no select chain of five
+      // values per row in pass A.  A lane in which no row won (best = 0: pass A replaced nothing) holds the values the chain
+      // starts from.  best is never negative and never NaN, so "won" is "any bit set".
+      const int won = readlane_i(__double2hiint((double)best), Lk) | readlane_i(__double2loint((double)best), Lk);
+      zu_k = T(1); um1 = T(0); zw_k = T(1); wp1 = T(0); t_k = T(0);
+      switch (won != 0 ? ik : -1) {
+        case 0: twist_pick<0>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        case 1: twist_pick<1>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        case 2: twist_pick<2>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        case 3: twist_pick<3>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        case 4: twist_pick<4>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        case 5: twist_pick<5>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        case 6: twist_pick<6>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        case 7: twist_pick<7>(sig, Lk, zu_k, um1, zw_k, wp1, t_k); break;
+        default: break;
+      }
+    } else {
+      zu_k = readlane_t(zu_b, Lk); zw_k = readlane_t(zw_b, Lk); t_k = readlane_t(t_b, Lk);
+      um1 = readlane_t(zum_b, Lk); wp1 = readlane_t(zwp_b, Lk);
+    }
     const T uw = zu_k * zw_k;
     const T num = xfma(um1, zw_k, xfma(t_k, uw, wp1 * zu_k));   // row-k residual of the twisted vector (x u_k w_k)
     const int Euk = readlane_i(Eu, Lk), Ewk = readlane_i(Ew, Lk);
@@ -1325,7 +1372,7 @@ struct WaveSolver {
 #endif
     }
 #ifdef IBS_PROBE
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) { long long* q = &ibs_probe_buf[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 16]; q[5] = t_sweep; q[6] = t_full; q[7] = n_full; }
+    if ((threadIdx.x & 63) == 0 && IBS_PROBE_BLOCK() < 1024) { long long* q = &ibs_probe_buf[(IBS_PROBE_BLOCK() * 4 + (threadIdx.x >> 6)) * 16]; q[5] = t_sweep; q[6] = t_full; q[7] = n_full; }
 #endif
     inf.iters = it;
     inf.status = done ? 0 : 1;
