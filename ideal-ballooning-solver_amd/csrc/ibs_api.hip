@@ -59,17 +59,9 @@ static int fail(int code, const char* fmt, ...) {
 // Diagnostic overrides of the dispatch heuristics (0 = automatic).  Read ONCE from the environment when the context is
 // created (IBS_FORCE_P, IBS_SCAN_CHAIN, IBS_CHAIN_W1, IBS_CHAIN_W2, IBS_GEO_LPP), changed afterwards only through
 // ibs_set_option(): no getenv() on the call path, nothing process-global.
-struct ibs_options {
-  int force_p = 0;        // lanes per system: 64 | 32 | 16
-  int scan_chain = 0;     // theta0 values chained through one wave / group
+struct ibs_options : ibs::PlanOpts {     // (force_p, scan_chain, scan_resident, gcf_rows, gcf_direct, f32_lam, pack_mode, sturm_form: ibs_plan.hpp)
   int geo_lpp = 0;        // lanes per grid point of the geometry kernel: 1 | 2 | 4
-  int gcf_rows = -1;      // raw systems on long grids: -1 / 1 = row-streamed kernel, 0 = the 3-row staging of k_solve_gcf
-  int gcf_direct = -1;    // raw systems, one wave per system: rows read straight from global memory (k_solve_gcf_direct): -1 = by batch size, 0 = never, 1 = always
-  int scan_resident = -1; // k_gamma_scan, 3 <= rows per lane <= 8: -1 = the resident form up to two waves per SIMD and k_gamma_scan_lean above, 0 = lean everywhere, 1 = resident wherever built
-  int pack_mode = 0;      // hand-off of the fused scan + argmax: 1 = write-through + sc1 loads, 2 = release / acquire fences
-  int f32_lam = 0;        // FP32 eigenvalue-only requests: 0 = by grid size, 1 = all-FP32 iteration + FP64 certificate, 2 = FP32 in HBM + FP64 solver
   double sigma0 = std::numeric_limits<double>::quiet_NaN();   // not NaN: solves that return lam AND info flag lam_max >= sigma0 (informational status bit 4: utils.py:1597 would have taken the eigenpair nearest sigma0)
-  int sturm_form = 0;     // ibs_sturm_count_f64: 0 = by size (see there), 1 = prefix-product sweep (N <= 2050), 2 = division form, lanes as systems, 3 = division form, one wave per system
   int reclose = 1;        // FP64 raw systems: 1 = a solve whose closing bracket fails its consistency checks is re-closed in division form, 2 = only marked, 0 = off
   int refine_tangent = -1; // refinement: alpha-tangent of a point staged in LDS (1) or read from global memory in the sums (0); -1 = by batch size
   double chain_w1 = 0.25, chain_w2 = 1.0;   // relative widths of the chain's warm starts
@@ -93,8 +85,8 @@ struct ibs_ctx {
   // suspect list of the big-batch raw kernels (GcfArgs::fix_*): [count | system indices | polish values], grown on demand
   void* fix_buf = nullptr;
   long fix_cap = 0;
-  int lds_per_block = 160 * 1024;
-  int n_cu = 256;
+  ibs::Chip chip{256, 160 * 1024};   // CUs, LDS bytes a block may use
+  ibs::Built built{};                // the forms of this build (ibs_create: the non-null entries of launch_table())
   // native RCCL communicator of this rank (ibs_comm_init), null = none
   void* comm = nullptr;
   int comm_rank = 0, comm_n = 1;
@@ -193,7 +185,7 @@ int ensure_fix(ibs_ctx* c, long n_sys) {
   c->fix_cap = cap;
   return 0;
 }
-int long_waves(const ibs_ctx* c, long n_sys) { const long cap = 8L * c->n_cu; return (int)(n_sys < cap ? n_sys : cap); }   // (ibs_long.hip: kLongChunk)
+int long_waves(const ibs_ctx* c, long n_sys) { const long cap = 8L * c->chip.n_cu; return (int)(n_sys < cap ? n_sys : cap); }   // (ibs_long.hip: kLongChunk)
 // the persistent grid of long_waves(n) with doubles_per_wave of ctx->long_ws each, entered into the launch arguments a of a
 // one-wave-per-system kernel (a.work, a.work_doubles, a.n_waves: ibs_launch.hpp, persistent_grid)
 template <class A> int with_wave_ws(ibs_ctx* c, A& a, long n, size_t doubles_per_wave) {
@@ -276,41 +268,14 @@ struct HostStage {
   }
 };
 
+using ibs::is_long; using ibs::rows_per_lane;
 // long_ok: the entry point has the generic long-grid path behind it (ibs_long.hip)
-bool is_long(int N) { return N > 64 * ibs::kMaxM + 2; }
 int check_grid(int32_t N, double h, bool long_ok = false) {
-  const int n_max = long_ok ? ibs::kMaxLongN : 64 * ibs::kMaxM + 2;
-  if (N < 66 || N > n_max) return fail(IBS_ERR_UNSUPPORTED, "N=%d outside [66, %d]", N, n_max);
-  if ((N & 1) == 0) return fail(IBS_ERR_UNSUPPORTED, "N=%d is even: the reference's Simpson rule is restated for odd N only", N);
+  const ibs::GridCheck g = ibs::check_grid_length(N, long_ok);
+  if (g == ibs::GridCheck::Range) return fail(IBS_ERR_UNSUPPORTED, "N=%d outside [66, %d]", N, ibs::grid_n_max(long_ok));
+  if (g == ibs::GridCheck::Even) return fail(IBS_ERR_UNSUPPORTED, "N=%d is even: the reference's Simpson rule is restated for odd N only", N);
   if (!(h > 0)) return fail(IBS_ERR_ARG, "h must be > 0");
   return 0;
-}
-int rows_per_lane(int N) { return (N - 2 + 63) / 64; }
-
-// lanes per system.  64 = one wave per system (lowest latency, any N).  Large batches of short grids are
-// throughput (VALU-issue) bound: 32 / 16 lanes per system amortise the scan over 2 / 4 systems per wave.
-// option force_p = 64|32|16 overrides (tests).
-int pick_lanes(const ibs_ctx* ctx, int N, long n_sys) {
-  const int n = N - 2;
-  const bool can32 = n <= 32 * 20 && n >= 32 * 3 + 1, can16 = n <= 16 * 16 && n >= 16 * 3 + 1;
-  if (ctx->opt.force_p) {
-    const int f = ctx->opt.force_p;
-    if (f == 32 && can32) return 32;
-    if (f == 16 && can16) return 16;
-    return 64;
-  }
-  // Measured (tools/bench_lanes.py, r01_f): every iteration of the shift search is exactly one forward sweep, so
-  // the systems sharing a wave stay in step (15 +- 2 iterations) and the cheaper sweeps pay off as soon as the
-  // sub-wave launch still fills the chip: P = 32 from one wave per SIMD (N = 513: 2,048 systems 42 vs 50 us,
-  // 65,536 systems 0.77 vs 1.00 ms), P = 16 (whose 16-row chunks make a lone wave twice as slow) from two
-  // waves per SIMD (N = 257: 65,536 systems 0.38 vs 0.62 ms).  Smaller batches keep one wave per system.
-  const long simds = 4L * ctx->n_cu;
-  if (can16 && n_sys / 4 >= 2 * simds) return 16;
-  // (17..20 rows per lane, i.e. N up to the 641-point D3D grid: a lone wave is slower, pays off from 4 waves per SIMD:
-  //  N = 641: 65,536 systems 0.82 vs 1.05 ms, 8,192 systems 147 vs 150 us, 2,048 systems 72 vs 52 us)
-  const int m32 = (n + 31) / 32;
-  if (can32 && n_sys / 2 >= (m32 > 16 ? 4 : 1) * simds) return 32;
-  return 64;
 }
 
 __global__ void k_count_status(long n, const int* info, int* out) {
@@ -490,40 +455,49 @@ __global__ void k_scan_starts(int n_surf, int n_alpha, int n_theta0, const doubl
   if (sigma0) sigma0[s] = sg;
 }
 
-// One wave per system on a long grid: k_solve_gcf's three staged rows are 24.6 KB of LDS per wave at N = 1025 -- five waves
-// per CU where the registers admit eight.  A batch that fills the chip at more waves than the staging admits reads its rows
-// straight from global memory instead (k_solve_gcf_direct: no LDS).  Option gcf_direct: -1 = this rule, 0 = never, 1 = always.
-static bool use_direct(const ibs_ctx* ctx, int N, long n_sys) {
-  if (ctx->opt.gcf_direct == 0) return false;
-  if (ctx->opt.gcf_direct == 1) return true;
-  // (measured, tools/bench_direct.py, 2^19 systems: 1.45-1.65 x the staged / row-streamed kernels at N_zeta = 768 .. 1536, 1.2-1.3 x at 2048)
-  const long staged_waves_per_cu = (long)(ctx->lds_per_block / ((size_t)3 * ibs::lds_pitch(N) * sizeof(double)));
-  return staged_waves_per_cu < 8 && n_sys > (staged_waves_per_cu > 4 ? staged_waves_per_cu : 4) * ctx->n_cu;
+// the launcher of a planned raw solve (Long: none, launch_gcf_long) and of the second launch of the forms that list their suspects
+// (k_fix_gcf, by the rows per lane of one wave per system)
+template <typename T> using GcfLauncher = hipError_t (*)(const ibs::GcfArgs<T>&, hipStream_t);
+template <typename T>
+GcfLauncher<T> gcf_launcher(const ibs::GcfPlan& p) {
+  using F = ibs::GcfForm;
+  const ibs::LaunchTable& t = ibs::launch_table();
+  const int M = p.M, pi = p.P == 32 ? 0 : 1;
+  if constexpr (sizeof(T) == 8) {
+    switch (p.form) {
+      case F::Staged: return t.gcf_f64[M];      case F::Rows: return t.gcf_rows_f64[M];
+      case F::Direct: return t.gcf_direct_f64[M]; case F::Group: return t.gcf_f64_g[pi][M];
+      default: return nullptr;
+    }
+  } else {
+    switch (p.form) {
+      case F::F32: return t.gcf_f32[M];                     case F::F32Wide: return t.gcf_f32_wide[M];
+      case F::F32WideRows: return t.gcf_f32w_rows[M];       case F::F32WideDirect: return t.gcf_direct_f32w[M];
+      case F::F32LamDirect: return t.gcf_direct_f32lam[M];  case F::GroupWide: return t.gcf_f32w_g[pi][M];
+      default: return nullptr;
+    }
+  }
+}
+template <typename T>
+GcfLauncher<T> gcf_fix_launcher(int N) {
+  if constexpr (sizeof(T) == 8) return ibs::launch_table().gcf_fix_f64[rows_per_lane(N)];
+  else return ibs::launch_table().gcf_fix_f32w[rows_per_lane(N)];
 }
 
 template <typename T>
 int solve_gcf_impl(ibs_ctx* ctx, int64_t n_sys, int32_t N, T h, const T* g, const T* c, const T* f, int64_t ld,
-                   T* lam, T* gam, T* X, T* dX, int32_t* info, int32_t mem,
-                   hipError_t (*const* table)(const ibs::GcfArgs<T>&, hipStream_t), const T* gh = nullptr) {
+                   T* lam, T* gam, T* X, T* dX, int32_t* info, int32_t mem, const T* gh = nullptr) {
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
   if (n_sys < 0 || !g || !c || !f || ld < N) return fail(IBS_ERR_ARG, "bad arguments (n_sys=%lld ld=%lld N=%d)", (long long)n_sys, (long long)ld, N);
   if (int r = check_grid(N, (double)h, true)) return r;
   if (n_sys == 0) return 0;
-  // grids beyond 2050 points: the generic division-form path (ibs_long.hip), FP64 arithmetic on either element type
-  const bool lng = is_long(N);
-  int M = lng ? 1 : rows_per_lane(N);
-  if (!table[M]) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", M, N);
+  const ibs::GcfPlan plan = ibs::plan_gcf(ctx->chip, ctx->opt, ctx->built, (int)sizeof(T), (long)n_sys, N, gh != nullptr, gam != nullptr, X || dX);
+  if (plan.err == ibs::PlanError::NotBuilt) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", plan.M, N);
   ON_DEVICE(ctx);
-  auto launch = table[M];
-  size_t per_wave = (size_t)3 * ibs::lds_pitch(lng ? 66 : N) * sizeof(T);
+  if (plan.err == ibs::PlanError::NoLds) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, plan.per_wave);
   auto launch_it = [&](ibs::GcfArgs<T>& a) -> int {
-    if (!lng) {
-      // the big-batch forms (rows from global memory, sub-wave) only LIST their suspect systems; k_fix_gcf re-closes them afterwards
-      auto& t = ibs::launch_table();
-      bool lists;
-      if constexpr (sizeof(T) == 8) lists = launch == t.gcf_direct_f64[M] || launch == t.gcf_f64_g[0][M] || launch == t.gcf_f64_g[1][M];
-      else lists = launch == t.gcf_direct_f32w[M] || launch == t.gcf_f32w_g[0][M] || launch == t.gcf_f32w_g[1][M];
-      if (lists && (a.flags & 1)) {
+    if (plan.form != ibs::GcfForm::Long) {
+      if (plan.lists_suspects && (a.flags & 1)) {
         if (int r = ensure_fix(ctx, (long)a.n_sys)) return r;
         char* fb = static_cast<char*>(ctx->fix_buf);
         a.fix_count = reinterpret_cast<int*>(fb);
@@ -531,12 +505,12 @@ int solve_gcf_impl(ibs_ctx* ctx, int64_t n_sys, int32_t N, T h, const T* g, cons
         a.fix_center = reinterpret_cast<double*>(fb + 256 + (size_t)ctx->fix_cap * 8);
         HIPCHK(hipMemsetAsync(a.fix_count, 0, sizeof(int), ctx->stream));
       }
-      HIPCHK(launch(a, ctx->stream));
+      HIPCHK(gcf_launcher<T>(plan)(a, ctx->stream));
       if (a.fix_count) {
         ibs::LaunchNote keep = ibs::last_launch();         // (ibs_last_launch names the solver kernel, not its fix-up pass)
-        auto fix = (sizeof(T) == 8 ? (void*)t.gcf_fix_f64[rows_per_lane(N)] : (void*)t.gcf_fix_f32w[rows_per_lane(N)]);
+        const auto fix = gcf_fix_launcher<T>(N);
         if (!fix) return fail(IBS_ERR_UNSUPPORTED, "no fix-up kernel built for N=%d", N);
-        HIPCHK(reinterpret_cast<hipError_t (*)(const ibs::GcfArgs<T>&, hipStream_t)>(fix)(a, ctx->stream));
+        HIPCHK(fix(a, ctx->stream));
         ibs::last_launch() = keep;
       }
       return 0;
@@ -550,69 +524,8 @@ int solve_gcf_impl(ibs_ctx* ctx, int64_t n_sys, int32_t N, T h, const T* g, cons
     HIPCHK(ibs::launch_gcf_long(la, ctx->stream));
     return 0;
   };
-  if constexpr (sizeof(T) == 8) {
-    const int P = (gh || lng) ? 64 : pick_lanes(ctx, N, (long)n_sys);
-    if (P != 64) {
-      const int Mg = (N - 2 + P - 1) / P;
-      auto fn = ibs::launch_table().gcf_f64_g[P == 32 ? 0 : 1][Mg];
-      if (fn) { launch = fn; M = Mg; per_wave = (size_t)(64 / P) * ibs::lds_pitch(N) * sizeof(T); }
-    }
-  }
-  if constexpr (sizeof(T) == 4) if (!lng) {
-    // FP32 systems whose growth rate or eigenfunction is wanted: FP32 in HBM, widened to FP64 as they are read, solved by the
-    // FP64 solver -- in the same three forms as the FP64 entry point (sub-wave for large batches of short grids, row-streamed
-    // for long grids, else one wave per system with the three rows staged).  lam alone stays with the all-FP32 kernel, whose
-    // result is certified by an FP64 count pair (k_solve_gcf<float, M>).
-    // lam alone: the all-FP32 iteration with its FP64 certificate.  A batch that would get the 32-lane sub-wave form takes it with
-    // the rows read straight from global memory (k_solve_gcf_f32lam_direct: 1.12-1.15 x the FP64 sub-wave solver on FP32 bytes on
-    // smooth coefficients, 2.1 x on rough ones; 2,048 ... 10^6 systems, N_zeta = 256 ... 640, tools/bench_forms.py).  Where the
-    // 16-lane form runs (N <= 258, big batches) the FP64 sub-wave solver without its growth-rate stage stays: 1.5 x the all-FP32
-    // form on smooth coefficients, 0.83 x on rough ones.  Also where the direct form is not built or gcf_direct = 0; option
-    // f32_lam overrides.
-    const int P_lam = pick_lanes(ctx, N, (long)n_sys);
-    const auto fl = ibs::launch_table().gcf_direct_f32lam[M];
-    const bool fl_ok = fl && ctx->opt.gcf_direct != 0;
-    const bool wide_lam = ctx->opt.f32_lam == 2 || (ctx->opt.f32_lam == 0 && (P_lam == 16 || (P_lam == 32 && !fl_ok)));
-    if (gam || X || dX || wide_lam) {
-      auto fw = ibs::launch_table().gcf_f32_wide[M];
-      if (fw) { launch = fw; per_wave = (size_t)3 * ibs::lds_pitch(N) * sizeof(double); }
-      const int P = pick_lanes(ctx, N, (long)n_sys);
-      if (P != 64) {
-        const int Mg = (N - 2 + P - 1) / P;
-        auto fg = ibs::launch_table().gcf_f32w_g[P == 32 ? 0 : 1][Mg];
-        if (fg) { launch = fg; M = Mg; per_wave = (size_t)(64 / P) * ibs::lds_pitch(N) * sizeof(double); }
-      } else {
-        auto fr = ibs::launch_table().gcf_f32w_rows[M];
-        if (fr && ctx->opt.gcf_rows != 0) { launch = fr; per_wave = (size_t)ibs::lds_pitch(N) * sizeof(double); }
-        auto fd = ibs::launch_table().gcf_direct_f32w[M];
-        if (fd && use_direct(ctx, N, (long)n_sys)) { launch = fd; per_wave = (size_t)ibs::lds_pitch(N) * sizeof(double); }
-      }
-    } else {
-      // eigenvalues only, all-FP32 iteration + FP64 certificate: big batches read their rows from global memory
-      if (!gh && fl_ok && (P_lam != 64 || use_direct(ctx, N, (long)n_sys))) launch = fl;
-    }
-  }
-  if constexpr (sizeof(T) == 8) if (!lng) {
-    // long grids, one wave per system: stream the three rows through ONE LDS row per wave (k_solve_gcf_rows) -- the
-    // 3-row staging of k_solve_gcf leaves two waves per CU at N_zeta = 2048 and five at 1024
-    auto fr = ibs::launch_table().gcf_rows_f64[M];
-    if (!gh && launch == table[M] && fr && ctx->opt.gcf_rows != 0) { launch = fr; per_wave = (size_t)ibs::lds_pitch(N) * sizeof(T); }
-    auto fd = ibs::launch_table().gcf_direct_f64[M];
-    if (!gh && (launch == table[M] || launch == fr) && fd && use_direct(ctx, N, (long)n_sys)) { launch = fd; per_wave = (size_t)ibs::lds_pitch(N) * sizeof(T); }
-  }
-  // the direct forms stage nothing: four waves per block, LDS only for the row X / dX are written from (ibs_kernels.hip: launch_gcf_direct,
-  // launch_gcf_f32lam_direct take the block shape from a.wpb)
-  bool direct_form;
-  if constexpr (sizeof(T) == 8) direct_form = !lng && launch == ibs::launch_table().gcf_direct_f64[M];
-  else direct_form = !lng && (launch == ibs::launch_table().gcf_direct_f32w[M] || launch == ibs::launch_table().gcf_direct_f32lam[M]);
-  if (direct_form) per_wave = (X || dX) ? (size_t)ibs::lds_pitch(N) * sizeof(double) : 0;
-  int wpb = per_wave ? (int)((size_t)ctx->lds_per_block / per_wave) : 4;
-  if (wpb > 4) wpb = 4;
-  // keep >= 3 blocks per CU resident when LDS allows it
-  while (!direct_form && wpb > 1 && (size_t)wpb * per_wave * 3 > (size_t)ctx->lds_per_block) --wpb;
-  if (wpb < 1) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, per_wave);
   ibs::GcfArgs<T> a{};
-  a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.wpb = wpb;
+  a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.wpb = plan.wpb;
   a.flags = ctx->opt.reclose == 1 ? 1 : (ctx->opt.reclose == 2 ? 2 : 0);
   const size_t in_elems = (size_t)n_sys * ld, out_elems = (size_t)n_sys * N;
   // (host pointers: lam and info are always carved; gam not asked for stays null -- the kernels then take their eigenvalue-only
@@ -695,16 +608,30 @@ int ibs_create(ibs_ctx** out, int device_id) {
   HIPCHK(hipGetDeviceProperties(&prop, device_id));
   ibs_ctx* c = new ibs_ctx();
   c->device = device_id;
-  c->lds_per_block = (int)prop.sharedMemPerBlock > 64 * 1024 ? (int)prop.sharedMemPerBlock : 64 * 1024;
-  if (prop.maxSharedMemoryPerMultiProcessor > (size_t)c->lds_per_block) c->lds_per_block = (int)prop.maxSharedMemoryPerMultiProcessor;
-  if (c->lds_per_block > 160 * 1024) c->lds_per_block = 160 * 1024;
-  c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  c->chip.lds_per_block = (int)prop.sharedMemPerBlock > 64 * 1024 ? (int)prop.sharedMemPerBlock : 64 * 1024;
+  if (prop.maxSharedMemoryPerMultiProcessor > (size_t)c->chip.lds_per_block) c->chip.lds_per_block = (int)prop.maxSharedMemoryPerMultiProcessor;
+  if (c->chip.lds_per_block > 160 * 1024) c->chip.lds_per_block = 160 * 1024;
+  c->chip.n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   if (const char* e = getenv("IBS_FORCE_P")) c->opt.force_p = atoi(e);
   if (const char* e = getenv("IBS_SCAN_CHAIN")) c->opt.scan_chain = atoi(e);
   if (const char* e = getenv("IBS_GEO_LPP")) c->opt.geo_lpp = atoi(e);
   if (const char* e = getenv("IBS_CHAIN_W1")) c->opt.chain_w1 = atof(e);
   if (const char* e = getenv("IBS_CHAIN_W2")) c->opt.chain_w2 = atof(e);
   c->opt_created = c->opt;
+  // the forms of this build, for the planner: once per context (the registrars have run before main)
+  const ibs::LaunchTable& t = ibs::launch_table();
+  ibs::Built& b = c->built;
+  for (int M = 0; M <= ibs::kMaxM; ++M) {
+    auto mark = [M](uint64_t& mask, auto* entry) { if (entry) mask |= uint64_t(1) << M; };
+    mark(b.gcf_f64, t.gcf_f64[M]); mark(b.gcf_f32, t.gcf_f32[M]); mark(b.gcf_f32_wide, t.gcf_f32_wide[M]);
+    mark(b.scan, t.scan_f64[M]); mark(b.scan_chain, t.scan_chain_f64[M]);
+    mark(b.gcf_rows, t.gcf_rows_f64[M]); mark(b.gcf_f32w_rows, t.gcf_f32w_rows[M]);
+    mark(b.gcf_direct, t.gcf_direct_f64[M]); mark(b.gcf_f32w_direct, t.gcf_direct_f32w[M]); mark(b.gcf_f32lam_direct, t.gcf_direct_f32lam[M]);
+    for (int pi = 0; pi < 2; ++pi) {
+      mark(b.gcf_g[pi], t.gcf_f64_g[pi][M]); mark(b.gcf_f32w_g[pi], t.gcf_f32w_g[pi][M]);
+      mark(b.scan_g[pi], t.scan_f64_g[pi][M]); mark(b.scan_chain_g[pi], t.scan_chain_f64_g[pi][M]);
+    }
+  }
   *out = c;
   return 0;
 }
@@ -918,20 +845,20 @@ int ibs_synchronize(ibs_ctx* c) {
 int ibs_solve_gcf_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c,
                       const double* f, int64_t ld, double* lam, double* gam, double* X, double* dX,
                       int32_t* info, int32_t mem) {
-  return solve_gcf_impl<double>(ctx, n_sys, N, h, g, c, f, ld, lam, gam, X, dX, info, mem, ibs::launch_table().gcf_f64);
+  return solve_gcf_impl<double>(ctx, n_sys, N, h, g, c, f, ld, lam, gam, X, dX, info, mem);
 }
 
 int ibs_solve_gcfh_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
                        const double* c, const double* f, int64_t ld, double* lam, double* gam, double* X, double* dX,
                        int32_t* info, int32_t mem) {
   if (!gh) return fail(IBS_ERR_ARG, "gh is null");
-  return solve_gcf_impl<double>(ctx, n_sys, N, h, g, c, f, ld, lam, gam, X, dX, info, mem, ibs::launch_table().gcf_f64, gh);
+  return solve_gcf_impl<double>(ctx, n_sys, N, h, g, c, f, ld, lam, gam, X, dX, info, mem, gh);
 }
 
 int ibs_solve_gcf_f32(ibs_ctx* ctx, int64_t n_sys, int32_t N, float h, const float* g, const float* c,
                       const float* f, int64_t ld, float* lam, float* gam, float* X, float* dX,
                       int32_t* info, int32_t mem) {
-  return solve_gcf_impl<float>(ctx, n_sys, N, h, g, c, f, ld, lam, gam, X, dX, info, mem, ibs::launch_table().gcf_f32);
+  return solve_gcf_impl<float>(ctx, n_sys, N, h, g, c, f, ld, lam, gam, X, dX, info, mem);
 }
 
 // ---- the eigenpair nearest sigma (ibs_nearest.hip; utils.py:1597)
@@ -1333,125 +1260,26 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
     return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
   if (int r = check_grid(N, h, true)) return r;
   if (n_lines == 0 || n_theta0 == 0) return 0;
-  const bool lng = is_long(N);                 // grids beyond 2050 points: launch_scan_long
-  int M = lng ? 1 : rows_per_lane(N);
-  auto fn = ibs::launch_table().scan_f64[M];     // (on long grids only a check that the build is complete)
-  if (!fn) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", M, N);
+  const ibs::ScanPlan plan = ibs::plan_scan(ctx->chip, ctx->opt, ctx->built, n_lines, n_theta0, N, lam_guess != nullptr, X || dX, t0_per_line, pack != nullptr);
+  if (plan.err == ibs::PlanError::NotBuilt) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", plan.M, N);
   ON_DEVICE(ctx);
+  if (plan.err == ibs::PlanError::NoLds) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
+  const ibs::LaunchTable& t = ibs::launch_table();
+  const int pi = plan.P == 32 ? 0 : 1;
+  hipError_t (*fn)(const ibs::ScanArgs<double>&, hipStream_t) = nullptr;
+  switch (plan.form) {
+    case ibs::ScanForm::Wave: case ibs::ScanForm::WaveLean: fn = t.scan_f64[plan.M]; break;
+    case ibs::ScanForm::WaveChain: fn = t.scan_chain_f64[plan.M]; break;
+    case ibs::ScanForm::Group: fn = t.scan_f64_g[pi][plan.M]; break;
+    case ibs::ScanForm::GroupChain: fn = t.scan_chain_f64_g[pi][plan.M]; break;
+    case ibs::ScanForm::Long: break;                   // (launch_scan_long)
+  }
   ibs::ScanArgs<double> a{};
-  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = ld; a.wpb = 1;
+  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = ld;
   a.t0_stride = t0_per_line ? 1 : 0;
-  int G = 1;
-  if (!lng) {
-  const size_t per_arr = (size_t)ibs::lds_pitch(N) * sizeof(double);
-  if (8 * per_arr > (size_t)ctx->lds_per_block) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
-  int cap = ibs::scan_max_threads(M) / 64;
-  decltype(fn) fn_g_chain = nullptr;     // chained / warm-started sub-wave kernel of the same (P, M)
-  {
-    const int P = t0_per_line ? 64 : pick_lanes(ctx, N, (long)n_lines * n_theta0);
-    if (P != 64 && n_theta0 % (64 / P) == 0) {
-      const int Mg = (N - 2 + P - 1) / P;
-      auto fg = ibs::launch_table().scan_f64_g[P == 32 ? 0 : 1][Mg];
-      auto fgc = ibs::launch_table().scan_chain_f64_g[P == 32 ? 0 : 1][Mg];
-      if (fg && (fgc || !lam_guess)) { fn = fg; fn_g_chain = fgc; M = Mg; G = 64 / P; cap = ibs::scan_max_threads_g(Mg) / 64; }
-    }
-  }
-  // wpb = waves per block; each wave solves G theta0 values of the block's line
-  int wpb = (int)(((size_t)ctx->lds_per_block - 7 * per_arr) / (per_arr * G));
-  if (wpb > cap) wpb = cap;
-  const int waves_per_line = (n_theta0 + G - 1) / G;
-  if (wpb > waves_per_line) wpb = waves_per_line;
-  if (wpb < 1) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
-  // small batches: spread the waves over all CUs (the solver is issue-bound, one wave per SIMD is
-  // the fastest placement) instead of packing a line's theta0 values onto one CU
-  {
-    const long waves = (long)n_lines * waves_per_line;
-    long per_blk = waves / ctx->n_cu;
-    if (per_blk < 1) per_blk = 1;
-    if (per_blk < wpb) wpb = (int)per_blk;
-  }
-  // balance the waves over the blocks of a line
-  const int nblk = (waves_per_line + wpb - 1) / wpb;
-  wpb = (waves_per_line + nblk - 1) / nblk;
-  a.wpb = wpb;
-  // A chain shortens the blocks (a line's waves = theta0 slots / chain) while every block still stages the whole line:
-  // the LDS then limits the waves per CU.  Shorten the chain until the blocks that fit a CU hold as many waves as the
-  // registers allow (tools/batch_sweep.py, 8 theta0 per line, N = 513, 65,536 solves: chain 4 = one wave per block =
-  // 4 waves per CU: 6.5e7 solves/s; chain 2: 1.0e8).
-  auto fit_chain = [&](int chain, int slots, int rows, int cap_waves) {
-    const int occ = rows <= 4 ? 4 : (rows <= 8 ? 3 : (rows <= 16 ? 2 : 1));        // waves per SIMD the VGPRs allow
-    const long blocks_per_cu = (long)((size_t)ctx->lds_per_block / (7 * per_arr));
-    while (chain > 1) {
-      long w = (slots + chain - 1) / chain;
-      if (w > cap_waves) w = cap_waves;
-      if (blocks_per_cu * w >= 4L * occ) break;
-      chain >>= 1;
-    }
-    return chain;
-  };
-  // Batches much larger than the chip (one wave per system, no caller-supplied guesses): chain consecutive theta0
-  // values of a line through one wave, each solve warm-started from the previous eigenvalue (k_gamma_scan_chain).
-  // 4 per wave once that still leaves two waves per SIMD, 2 from there down to two waves of chained work per SIMD
-  // (tools/bench_chain_sizes.py).  option scan_chain = n overrides.
-  if (G > 1 && fn_g_chain) {
-    // sub-wave kernels: the same chain over the theta0 slots of a group; caller-supplied guesses go through the same
-    // kernel with a chain of one
-    const int slots = n_theta0 / G;                       // theta0 values per group position of a line
-    const long waves = (long)n_lines * slots, simds = 4L * ctx->n_cu;
-    int chain = 1;
-    if (!lam_guess) {
-      if (slots >= 4 && waves >= 8 * simds) chain = 4;
-      else if (slots >= 2 && waves >= 4 * simds) chain = 2;
-      chain = fit_chain(chain, slots, M, cap);
-      if (ctx->opt.scan_chain >= 1 && ctx->opt.scan_chain <= slots) chain = ctx->opt.scan_chain;
-    }
-    if (chain > 1 || lam_guess) {
-      const bool need_x = X || dX;
-      const int wpl = (slots + chain - 1) / chain;          // waves per line
-      long w = need_x ? (long)(((size_t)ctx->lds_per_block - 7 * per_arr) / (per_arr * G)) : cap;
-      if (w > cap) w = cap;
-      if (w > wpl) w = wpl;
-      if (w >= 1) {
-        const int nb = (wpl + (int)w - 1) / (int)w;
-        a.wpb = (wpl + nb - 1) / nb;
-        a.chain = chain;
-        a.chain_w1 = ctx->opt.chain_w1; a.chain_w2 = ctx->opt.chain_w2;
-        fn = fn_g_chain;
-      } else if (lam_guess) {
-        return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
-      }
-    }
-  }
-  if (G == 1 && !lam_guess && !t0_per_line) {
-    const long waves = (long)n_lines * n_theta0, simds = 4L * ctx->n_cu;
-    int chain = 1;
-    if (n_theta0 >= 8 && waves >= 8 * simds) chain = 4;
-    else if (n_theta0 >= 4 && waves >= 4 * simds) chain = 2;      // (N = 1025: 2,048 solves 70 vs 95 us, 4,096: 111 vs 105 us)
-    chain = fit_chain(chain, n_theta0, M, cap);
-    if (ctx->opt.scan_chain >= 1 && ctx->opt.scan_chain <= n_theta0) chain = ctx->opt.scan_chain;
-    auto fc = ibs::launch_table().scan_chain_f64[M];
-    if (chain > 1 && fc) {
-      const bool need_x = (M < 3) || X || dX;
-      const int wpl = (n_theta0 + chain - 1) / chain;
-      long w = need_x ? (long)(((size_t)ctx->lds_per_block - 7 * per_arr) / per_arr) : cap;
-      if (w > cap) w = cap;
-      if (w > wpl) w = wpl;
-      if (w >= 1) {
-        const int nb = (wpl + (int)w - 1) / (int)w;
-        a.wpb = (wpl + nb - 1) / nb;
-        a.chain = chain;
-        a.chain_w1 = ctx->opt.chain_w1; a.chain_w2 = ctx->opt.chain_w2;     // defaults 0.25 / 1.0 measured on the NCSX shapes (tools/bench_chain.py): 9.2 sweeps per solve instead of 15.7
-        fn = fc;
-      }
-    }
-  }
-  // One wave per system, unchained, 3 <= M <= 8: the resident form of k_gamma_scan (186 VGPRs at M = 8: two waves per SIMD) while the
-  // launch holds no more than that -- its time is then a lone wave's latency --, k_gamma_scan_lean (four at M = 8) above.
-  if (fn == ibs::launch_table().scan_f64[M] && G == 1) {
-    const long grid_waves = (long)((n_theta0 + a.wpb - 1) / a.wpb) * n_lines * a.wpb;
-    a.resident = ctx->opt.scan_resident == 0 ? 0 : (ctx->opt.scan_resident == 1 ? 1 : (grid_waves <= 2L * 4 * ctx->n_cu ? 1 : 0));
-  }
-  }   // (!lng)
+  a.wpb = plan.wpb; a.resident = plan.resident; a.chain = plan.chain;
+  // (widths of the chain's warm starts: defaults 0.25 / 1.0 measured on the NCSX shapes (tools/bench_chain.py): 9.2 sweeps per solve instead of 15.7)
+  if (plan.chain) { a.chain_w1 = ctx->opt.chain_w1; a.chain_w2 = ctx->opt.chain_w2; }
   // (the divisions of the kernel's set-up and growth-rate stage, done once here: correctly rounded on both sides)
   a.ih2 = 1.0 / (h * h); a.ih = 1.0 / h;
   const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
@@ -1466,8 +1294,7 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
     a.dth0 = s.out(dth0, n_sys); a.info = s.status(info, n_sys);
   };
   return staged(ctx, mem, decl, [&]() -> int {
-    const bool fused = !lng && pack && fn == ibs::launch_table().scan_f64[M] && G == 1;
-    if (fused) {
+    if (plan.fused_pack) {
       // one launch: the block that completes a surface reduces it (k_gamma_scan's epilogue)
       ibs_ctx::SurfCounters* sc = nullptr;
       for (auto& e : ctx->surf_counters) if (e.stream == ctx->stream) { sc = &e; break; }
@@ -1479,18 +1306,15 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
         HIPCHK(hipMemsetAsync(sc->buf, 0, (size_t)cap_n * sizeof(int), ctx->stream));
         sc->n = cap_n;
       }
-      a.lines_per_surf = n_lines / n_surf; a.surf_counter = sc->buf; a.pack = pack;
-      const long nblocks = (long)((n_theta0 + a.wpb - 1) / a.wpb) * n_lines;
-      a.pack_mode = (nblocks <= ctx->n_cu && ctx->opt.pack_mode != 2) ? 1 : 2;
-      if (ctx->opt.pack_mode == 1) a.pack_mode = 1;
+      a.lines_per_surf = n_lines / n_surf; a.surf_counter = sc->buf; a.pack = pack; a.pack_mode = plan.pack_mode;
     }
-    if (lng) {
+    if (!fn) {
       if (int r = launch_scan_long(ctx, a)) return r;
     } else {
       HIPCHK(fn(a, ctx->stream));
     }
     flag_sigma<double>(ctx, (long)n_sys, a.lam, a.info);
-    if (pack && !fused) {                          // chained / sub-wave / long-grid scans: the reduction is a second launch
+    if (pack && !plan.fused_pack) {                          // chained / sub-wave / long-grid scans: the reduction is a second launch
       const int n_per = (n_lines / n_surf) * n_theta0;
       hipLaunchKernelGGL(k_surface_argmax, dim3(n_surf), dim3(argmax_threads(n_per)), 0, ctx->stream, n_per, gam, (int*)nullptr, (double*)nullptr, pack);
       HIPCHK(hipGetLastError());
@@ -1628,15 +1452,8 @@ int ibs_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const d
   const auto fn = ibs::launch_table().grad_f64[M];
   if (!lng && !fn) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", M, N);
   ON_DEVICE(ctx);
-  const size_t per_wave = (size_t)8 * ibs::lds_pitch(lng ? 66 : N) * sizeof(double);
-  int wpb = (int)((size_t)ctx->lds_per_block / per_wave);
-  if (wpb > 4) wpb = 4;
+  const int wpb = ibs::plan_grad_wpb(ctx->chip, n_pts, N);
   if (wpb < 1) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
-  {
-    long per_blk = (long)n_pts / ctx->n_cu;
-    if (per_blk < 1) per_blk = 1;
-    if (per_blk < wpb) wpb = (int)per_blk;
-  }
   ibs::GradArgs<double> a{};
   a.n_pts = n_pts; a.N = N; a.h = h; a.ld = ld; a.del_alpha = del_alpha; a.wpb = wpb;
   const size_t n = (size_t)n_pts, geo_elems = n * 3 * 8 * ld;
@@ -1741,7 +1558,7 @@ int ibs_fieldline_geometry_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int3
     rows = fit == 1;
   }
   if (rows) { a.nrows_mn = nrows_mn; a.nrows_nyq = nrows_nyq; a.dn_mn = dn_mn; a.dn_nyq = dn_nyq; }
-  a.form = ibs::geo_pick_usable(a, n_lines, N, ctx->n_cu);
+  a.form = ibs::geo_pick_usable(a, n_lines, N, ctx->chip.n_cu);
   const size_t img_bytes = geo_img_bytes(a, a.form.lpp);
   const bool host = mem == IBS_MEM_HOST;
   if (host)
@@ -1763,7 +1580,7 @@ int ibs_fieldline_geometry_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int3
     a.surf_used = s.scratch<int>(n_surf, mark);
   };
   return staged(ctx, mem, decl, [&]() -> int {
-    HIPCHK(ibs::launch_geometry(a, ctx->stream, ctx->n_cu));
+    HIPCHK(ibs::launch_geometry(a, ctx->stream, ctx->chip.n_cu));
     return 0;
   });
 }
@@ -1873,29 +1690,13 @@ int ibs_sturm_count_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const 
   if (N < 66 || N > ibs::kMaxLongN) return fail(IBS_ERR_UNSUPPORTED, "N=%d outside [66, %d]", N, ibs::kMaxLongN);
   if (!(h > 0)) return fail(IBS_ERR_ARG, "h must be > 0");
   if (n_sys == 0) return 0;
-  // forms: the prefix-product sweep (one wave per system, N <= 2050: the bandwidth kernel of rounds 1-5), and two division-form
-  // kernels for any N (ibs_long.hip): lanes as systems (batches) and one wave per system (a handful of systems on a long grid)
-  // By size: the sweep up to 2,050 points -- except where its lanes sit 128 / 256 bytes apart (16 / 32 rows per lane: 4.2 / 2.8 TB/s
-  // against 6.3 at 8, 12, 24 rows) and the batch fills the chip with 64 systems per wave: there the division form is exact AND faster
-  // (4.9-5.1 TB/s; tools/experiments/sturm_crossover.py)
-  int form = ctx->opt.sturm_form;
-  if (form == 0) {
-    if (is_long(N)) form = n_sys >= 64 ? 2 : 3;
-    else {
-      const int Mr = rows_per_lane(N);
-      form = ((Mr == 16 && n_sys >= 65536) || (Mr == 32 && n_sys >= 32768)) ? 2 : 1;
-    }
-  }
-  if (form == 1 && is_long(N)) form = 2;
-  const bool lng = form != 1;
-  const int M = lng ? 1 : rows_per_lane(N);
-  auto fn = form == 2 ? &ibs::launch_sturm_div : (form == 3 ? &ibs::launch_sturm_long : ibs::launch_table().sturm_f64[M]);
+  const ibs::SturmPlan plan = ibs::plan_sturm(ctx->chip, ctx->opt, (long)n_sys, N);
+  const int M = plan.M;
+  auto fn = plan.form == 2 ? &ibs::launch_sturm_div : (plan.form == 3 ? &ibs::launch_sturm_long : ibs::launch_table().sturm_f64[M]);
   if (!fn) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", M, N);
   ON_DEVICE(ctx);
-  const size_t per_wave = (size_t)N * sizeof(double);
-  int wpb = lng ? 1 : (int)((size_t)ctx->lds_per_block / per_wave);
-  if (wpb > 4) wpb = 4;
-  if (wpb < 1) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, per_wave);
+  const int wpb = plan.wpb;
+  if (wpb < 1) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, plan.per_wave);
   ibs::SturmArgs<double> a{};
   a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.wpb = wpb;
   const size_t in_elems = (size_t)n_sys * ld;
@@ -2027,7 +1828,7 @@ static int geo_reclose_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int
     }
     // re-closing is rare: at most one wave per CU, and at most 256 MiB of row workspace
     const size_t per_wave = ibs::reclose_ws_doubles(N) * sizeof(double);
-    long nw = (long)n_sys < ctx->n_cu ? (long)n_sys : ctx->n_cu;
+    long nw = (long)n_sys < ctx->chip.n_cu ? (long)n_sys : ctx->chip.n_cu;
     const long fit = (long)((size_t(256) << 20) / per_wave);
     if (nw > fit) nw = fit;
     if (nw < 1) nw = 1;
@@ -2123,9 +1924,9 @@ int ibs_refine_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_ny
   // The alpha-tangent (4 more rows) in LDS saves the evaluation's sums a second trip to global memory but leaves room for ONE
   // block per CU at N = 969 (105 of 160 KB); without it two fit (70 KB each).  Batches with more points than CUs take the
   // second form: their first rounds would otherwise run in two waves of blocks.
-  int lds_tangent = (12 * row_b + lds_extra <= (size_t)ctx->lds_per_block) ? 1 : 0;
-  if (ctx->opt.refine_tangent == 0 || (ctx->opt.refine_tangent < 0 && n_pts > ctx->n_cu)) lds_tangent = 0;
-  if (8 * row_b + lds_extra > (size_t)ctx->lds_per_block) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
+  int lds_tangent = (12 * row_b + lds_extra <= (size_t)ctx->chip.lds_per_block) ? 1 : 0;
+  if (ctx->opt.refine_tangent == 0 || (ctx->opt.refine_tangent < 0 && n_pts > ctx->chip.n_cu)) lds_tangent = 0;
+  if (8 * row_b + lds_extra > (size_t)ctx->chip.lds_per_block) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
   // every round = one objective/gradient evaluation of every point still in the batch.  An iteration takes at most
   // maxls = 20 line-search evaluations, and once more after a memory restart
   const int max_rounds = 2 + 42 * (maxiter > 0 ? maxiter : 1);
@@ -2156,8 +1957,8 @@ int ibs_refine_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_ny
     if (fit == 1) { ga.nrows_mn = nrows_mn; ga.nrows_nyq = nrows_nyq; ga.dn_mn = dn_mn; ga.dn_nyq = dn_nyq; }
   }
   // the lanes-per-point forms the rounds can take as the batch shrinks (geo_pick_form is monotone in the batch size)
-  const int lpp_first = ibs::geo_pick_usable(ga, n_lines, N, ctx->n_cu).lpp;
-  const int lpp_last = ibs::geo_pick_usable(ga, 3, N, ctx->n_cu).lpp;
+  const int lpp_first = ibs::geo_pick_usable(ga, n_lines, N, ctx->chip.n_cu).lpp;
+  const int lpp_last = ibs::geo_pick_usable(ga, 3, N, ctx->chip.n_cu).lpp;
   ibs::RefineEvalArgs<double> ea{};
   const double *d_th, *d_start;
   RefineState* d_st;
@@ -2219,8 +2020,8 @@ int ibs_refine_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_ny
       const int nc = hist[need_r] - 1;
       if (nc <= 0) { rounds = need_r; break; }
       ga.n_lines = 3 * nc;
-      ga.form = ibs::geo_pick_usable(ga, ga.n_lines, N, ctx->n_cu);
-      HIPCHK(ibs::launch_geometry(ga, st, ctx->n_cu));
+      ga.form = ibs::geo_pick_usable(ga, ga.n_lines, N, ctx->chip.n_cu);
+      HIPCHK(ibs::launch_geometry(ga, st, ctx->chip.n_cu));
       ea.n_c_max = nc;
       HIPCHK(eval(ea, st));
       ++enq;

@@ -16,15 +16,6 @@
 #ifndef IBS_M
 #error "compile with -DIBS_M=<rows per lane>"
 #endif
-// fewest rows per lane for which the read-from-global-memory forms are built: k_solve_gcf_direct (FP64 solver) pays where the
-// staging limits the occupancy (N > 578; below, the sub-wave forms are faster: tools/bench_forms.py), the all-FP32 eigenvalue-only
-// form k_solve_gcf_f32lam_direct on every big batch
-#ifndef IBS_DIRECT_MIN_M
-#define IBS_DIRECT_MIN_M 9
-#endif
-#ifndef IBS_F32LAM_DIRECT_MIN_M
-#define IBS_F32LAM_DIRECT_MIN_M 3
-#endif
 
 namespace ibs {
 
@@ -1105,7 +1096,7 @@ __device__ __forceinline__ ScanBlock scan_block(int n_lines, int nparts_1d) {
 // ---------------------------------------------------------------- geometry-fed theta0 scan
 // grid = ceil(n_theta0 / wpb) blocks ("parts") per line, laid out by scan_grid (ibs_scan_map.hpp: 3-D, chunks of 8 lines); block =
 // wpb waves; wave w solves theta0 index part*wpb + w.
-// dynamic LDS = (7 + wpb) * lds_pitch(N) * sizeof(T).  Geometry arrays are [n_lines][ld].
+// dynamic LDS = scan_lds_rows(wpb) * lds_pitch(N) * sizeof(T) (ibs_plan.hpp).  Geometry arrays are [n_lines][ld].
 // Two forms of one body.  RES (k_gamma_scan<T, M>, 3 <= M <= 8): the rows set-up forms stay in registers up to the growth-rate
 // stage (WaveSolver<T, M, true>; 186 VGPRs at M = 8, two waves per SIMD) -- for launches of at most two waves per SIMD, whose
 // time is the latency of a lone wave.  Lean (k_gamma_scan_lean<T, M>, and k_gamma_scan at every other M): rebuilt and replayed
@@ -1262,8 +1253,6 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
     IBS_PROBE_AT(18);
   }
 }
-
-constexpr bool scan_resident_built(int M) { return M >= 3 && M <= 8; }
 
 template <typename T, int M>
 __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines, int n_theta0, int N, T h,
@@ -1928,7 +1917,7 @@ static hipError_t launch_gcf_rows_wide(const GcfArgs<float>& a, hipStream_t st) 
 template <typename T>
 static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb;
-  const size_t lds = (size_t)(7 + wpb) * lds_pitch(a.N) * sizeof(T);
+  const size_t lds = (size_t)scan_lds_rows(wpb) * lds_pitch(a.N) * sizeof(T);
   const ScanGrid sg = scan_grid(a.n_lines, (a.n_theta0 + wpb - 1) / wpb);
   const dim3 grid(sg.x, sg.y, sg.z);
   const int nparts_1d = sg.flat ? (a.n_theta0 + wpb - 1) / wpb : 0;
@@ -1958,8 +1947,7 @@ static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
 template <typename T>
 static hipError_t launch_scan_chain(const ScanArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb, chain = a.chain;
-  const bool need_x = (IBS_M < 3) || a.X || a.dX;          // (the LDS-round-trip finish of M < 3 always uses the row)
-  const size_t lds = (size_t)(7 + (need_x ? wpb : 0)) * lds_pitch(a.N) * sizeof(T);
+  const size_t lds = (size_t)scan_lds_rows(wpb, 1, scan_chain_need_x(IBS_M, a.X || a.dX)) * lds_pitch(a.N) * sizeof(T);
   auto kern = k_gamma_scan_chain<T, IBS_M>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
@@ -2017,7 +2005,7 @@ struct IBS_CAT(Registrar, IBS_M) {
   IBS_CAT(Registrar, IBS_M)() {
     LaunchTable& t = launch_table();
     t.gcf_f64[IBS_M] = &launch_gcf<double>;
-#if IBS_M >= 24
+#if IBS_M >= IBS_ROWS_MIN_M
     // long grids (N >= 1475, e.g. N_zeta = 2048): one LDS row per wave -> four waves per CU (registers: one per SIMD) where
     // the three-row staging admits three (M = 24..28) or two (M = 29..32).  Below, the three-row kernel holds as many or
     // more waves and is faster (N_zeta = 1024, M = 16: 198 VGPRs, two waves per SIMD, 3.7e7 against 3.0e7 solves/s)

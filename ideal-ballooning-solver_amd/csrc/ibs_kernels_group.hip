@@ -365,7 +365,7 @@ template <typename T>
 static hipError_t launch_scan_g(const ScanArgs<T>& a, hipStream_t st) {
   constexpr int G = 64 / IBS_P;
   const int wpb = a.wpb;
-  const size_t lds = (size_t)(7 + wpb * G) * lds_pitch(a.N) * sizeof(T);
+  const size_t lds = (size_t)scan_lds_rows(wpb, G) * lds_pitch(a.N) * sizeof(T);
   auto kern = k_gamma_scan_g<T, IBS_M, IBS_P>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
@@ -382,8 +382,7 @@ template <typename T>
 static hipError_t launch_scan_g_chain(const ScanArgs<T>& a, hipStream_t st) {
   constexpr int G = 64 / IBS_P;
   const int wpb = a.wpb, chain = a.chain < 1 ? 1 : a.chain;
-  const bool need_x = a.X || a.dX;
-  const size_t lds = (size_t)(7 + (need_x ? wpb * G : 0)) * lds_pitch(a.N) * sizeof(T);
+  const size_t lds = (size_t)scan_lds_rows(wpb, G, a.X || a.dX) * lds_pitch(a.N) * sizeof(T);
   auto kern = k_gamma_scan_g_chain<T, IBS_M, IBS_P>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;

@@ -5,10 +5,9 @@
 #include <cstdarg>
 #include <cstdio>
 
-namespace ibs {
+#include "ibs_plan.hpp"     // kMaxM, kMaxLongN, lds_pitch, scan_max_threads(_g): the launch shapes are planned there
 
-constexpr int kMaxM = 32;   // rows per lane: N - 2 <= 64 * kMaxM  (N <= 2050)
-constexpr int kMaxLongN = 65537;   // longer grids, up to this many points, run on the generic division-form path (ibs_long.hip)
+namespace ibs {
 
 template <typename T>
 struct GcfArgs {
@@ -288,14 +287,5 @@ struct LaunchNote { char name[96]; long blocks; int threads; };
 LaunchNote& last_launch();      // thread-local (ibs_api.hip)
 void note_launch(long blocks, int threads, const char* fmt, ...);
 template <typename T> constexpr const char* type_name() { return sizeof(T) == 8 ? "double" : "float"; }
-
-// threads per block the scan kernel is compiled for (register budget: 5M doubles per lane)
-// LDS rows of the wave kernels are padded by one element per 8 (element j lives at j + (j >> 3)): a lane reads a
-// contiguous chunk of ~M rows, i.e. lanes are M elements apart, and for even M (8 at N = 513) an unpadded row
-// puts 16 lanes on the same banks.  Row pitch in elements:
-constexpr int lds_pitch(int N) { return N + (N >> 3) + 1; }
-
-constexpr int scan_max_threads(int M) { return M <= 16 ? 512 : 256; }
-constexpr int scan_max_threads_g(int M) { return M <= 8 ? 512 : 256; }   // sub-wave kernels (ibs_group.hpp)
 
 }  // namespace ibs

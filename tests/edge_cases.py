@@ -70,7 +70,7 @@ def rows_per_lane(N):
 
 
 def lanes_allowed(N):
-    """the lanes-per-system forms pick_lanes (csrc/ibs_api.hip) admits at this length besides 64"""
+    """the lanes-per-system forms pick_lanes (csrc/ibs_plan.hpp) admits at this length besides 64"""
     n = N - 2
     return [P for P, lo, hi in ((32, 97, 640), (16, 49, 256)) if lo <= n <= hi]
 

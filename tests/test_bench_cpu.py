@@ -234,7 +234,7 @@ def test_docs_state_the_limits_the_code_has():
     rounds): slots of the overlapped gather, the grid limits of the register-resident and the long-grid paths"""
     import re
     api = open(os.path.join(ROOT, "ideal-ballooning-solver_amd", "csrc", "ibs_api.hip")).read()
-    launch = open(os.path.join(ROOT, "ideal-ballooning-solver_amd", "csrc", "ibs_launch.hpp")).read()
+    launch = open(os.path.join(ROOT, "ideal-ballooning-solver_amd", "csrc", "ibs_plan.hpp")).read()   # (kMaxM, kMaxLongN: where the grid checks are)
     hdr = open(os.path.join(ROOT, "include", "ibs.h")).read()
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     design = open(os.path.join(ROOT, "DESIGN.md")).read()

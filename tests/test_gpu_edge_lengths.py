@@ -118,7 +118,7 @@ def well_batch(N, targets):
 
 
 def raw_kernel(N, dtype="double", gh=False):
-    """the kernel a handful of systems takes in ibs_solve_gcf_f64 / _f32 (with gam) / ibs_solve_gcfh_f64 (csrc/ibs_api.hip: solve_gcf_impl)"""
+    """the kernel a handful of systems takes in ibs_solve_gcf_f64 / _f32 (with gam) / ibs_solve_gcfh_f64 (csrc/ibs_plan.hpp: plan_gcf)"""
     M = ec.rows_per_lane(N)
     if not is_short(N):
         return "ibs::k_solve_gcf_long<%s>" % dtype

@@ -131,7 +131,7 @@ def check_fp32(N, tag, targets, r):
 
 
 def staged_name(N, fp32=False):
-    """the small-batch kernel of ibs_solve_gcf_f64 / ibs_solve_gcf_f32 with a growth rate (csrc/ibs_api.hip: solve_gcf_impl)"""
+    """the small-batch kernel of ibs_solve_gcf_f64 / ibs_solve_gcf_f32 with a growth rate (csrc/ibs_plan.hpp: plan_gcf)"""
     M = ec.rows_per_lane(N)
     if fp32:
         return "ibs::k_solve_gcf_rows<double, %d, float>" % M if M >= 24 else "ibs::k_solve_gcf_wide<%d>" % M

@@ -227,7 +227,7 @@ def test_rows_straight_from_global_memory_agree_with_the_staged_kernels(ctx, N):
 
 
 def test_direct_form_is_what_big_batches_on_long_grids_get(ctx):
-    """the dispatch rule (ibs_api.hip use_direct): N = 1025, one wave per system -- a batch beyond what the three-row staging holds
+    """the dispatch rule (ibs_plan.hpp use_direct): N = 1025, one wave per system -- a batch beyond what the three-row staging holds
     in flight (5 waves per CU) runs k_solve_gcf_direct, a small one keeps the staged kernel (coalesced staging = lower latency)"""
     import torch
     dev = torch.device("cuda:0")
@@ -257,7 +257,7 @@ def test_direct_form_is_what_big_batches_on_long_grids_get(ctx):
 
 @pytest.mark.parametrize("N", [131, 321, 513, 641])
 def test_fp32_eigenvalues_alone_on_short_grids(ctx, N):
-    """FP32 eigenvalue-only requests where the sub-wave forms exist (ibs_api.hip, `wide_lam`): a batch that would get the 32-lane
+    """FP32 eigenvalue-only requests where the sub-wave forms exist (ibs_plan.hpp, `wide_lam`): a batch that would get the 32-lane
     form runs the all-FP32 iteration + FP64 certificate with its rows read from global memory (k_solve_gcf_f32lam_direct, built
     from 3 rows per lane), the 16-lane regime (N <= 258, big batches) keeps the FP64 sub-wave solver; both within
     (N_zeta + 4) eps32 ||A|| of the FP64 solve on EVERY system, the only status the informational bit 2; ragged batches included."""
