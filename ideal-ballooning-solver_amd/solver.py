@@ -33,47 +33,34 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
-class _Args:
-    """marshals a homogeneous set of arrays (all numpy or all torch-cuda) to raw pointers"""
 
-    def __init__(self, dtype=np.float64):
-        self.mem = None
-        self.keep = []
-        self.dtype = np.dtype(dtype)
 
-    def _torch_dtype(self):
+_F64, _F32, _I32 = np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.int32)
+_NULL = C.c_void_p(None)
+_NO_ROWS = np.zeros((0, 2), np.int32)
+_TORCH_DTYPES = {}
+
+
+def _torch_dtype(dtype):
+    if not _TORCH_DTYPES:
         import torch
-        return {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32,
-                np.dtype(np.int32): torch.int32}
+        _TORCH_DTYPES.update({_F64: torch.float64, _F32: torch.float32, _I32: torch.int32})
+    return _TORCH_DTYPES[dtype]
 
-    def inp(self, x, dtype=None):
-        dtype = np.dtype(dtype or self.dtype)
-        if _is_torch(x):
-            if not x.is_cuda:
-                raise IbsError("torch tensors must live on the GPU (got %s)" % x.device)
-            td = self._torch_dtype()[dtype]
-            if x.dtype != td or not x.is_contiguous():
-                x = x.to(td).contiguous()
-            self._set(MEM_DEVICE)
-            self.keep.append(x)
-            return C.c_void_p(x.data_ptr())
-        a = np.ascontiguousarray(x, dtype=dtype)
-        self._set(MEM_HOST)
-        self.keep.append(a)
-        return C.c_void_p(a.ctypes.data)
 
-    def out(self, shape, like_torch=None, dtype=None, want=True):
-        dtype = np.dtype(dtype or self.dtype)
-        if not want:
-            return None, C.c_void_p(None)
-        if self.mem == MEM_DEVICE:
-            import torch
-            t = torch.empty(shape, dtype=self._torch_dtype()[dtype], device=like_torch.device)
-            self.keep.append(t)
-            return t, C.c_void_p(t.data_ptr())
-        a = np.empty(shape, dtype=dtype)
-        self.keep.append(a)
-        return a, C.c_void_p(a.ctypes.data)
+class _Args:
+    """one library call of a Context: inputs and outputs are declared in the order of the C prototype (each declaration returns the
+    pointer to pass), call() makes the call, result() returns the outputs.  The memory kind of the call is that of its first array
+    (all numpy or all torch-cuda); device=...: a call on that device whatever comes first, host arrays go up with upload=True."""
+
+    def __init__(self, ctx, dtype=_F64, device=None, host=False):
+        self.ctx = ctx
+        self.dtype = np.dtype(dtype)
+        self.mem = MEM_HOST if host else None if device is None else MEM_DEVICE
+        self.ref = device       # the torch device of a device call: where outputs are allocated and whose current stream is used
+        self.keep = []          # converted copies, uploads and outputs: alive during the call
+        self.temps = []         # device temporaries the (asynchronous) call reads: alive until the context's next such call
+        self.outs = {}
 
     def _set(self, mem):
         if self.mem is None:
@@ -81,6 +68,126 @@ class _Args:
         elif self.mem != mem:
             raise IbsError("mixing host (numpy) and device (torch.cuda) arrays in one call is not supported")
 
+    def inp(self, x, dtype=None, upload=False):
+        """pointer to x as a contiguous array of dtype (default: the call's); None -> a null pointer"""
+        if x is None:
+            return _NULL
+        dtype = self.dtype if dtype is None else dtype
+        if _is_torch(x):
+            if not x.is_cuda:
+                raise IbsError("torch tensors must live on the GPU (got %s)" % x.device)
+            td = _torch_dtype(dtype)
+            if x.dtype != td or not x.is_contiguous():
+                x = x.to(td).contiguous()
+                self.temps.append(x)
+            self._set(MEM_DEVICE)
+            if self.ref is None:
+                self.ref = x.device
+            self.keep.append(x)
+            return C.c_void_p(x.data_ptr())
+        a = np.ascontiguousarray(x, dtype=dtype)
+        if upload and self.mem == MEM_DEVICE:
+            import torch
+            t = torch.from_numpy(a).to(self.ref)
+            self.temps.append(t)
+            return C.c_void_p(t.data_ptr())
+        self._set(MEM_HOST)
+        self.keep.append(a)
+        return C.c_void_p(a.ctypes.data)
+
+    def rows(self, x, shape):
+        """a scalar-or-array input (sigma, shift, gam_bar, lam_bar) as float64 of `shape` in the memory kind of the call"""
+        if x is None:
+            return _NULL
+        if self.mem == MEM_DEVICE:
+            import torch
+            t = torch.as_tensor(x, dtype=torch.float64, device=self.ref)
+            return self.inp(t.expand(shape).contiguous() if t.dim() == 0 else t.reshape(shape))
+        a = np.asarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float64)
+        return self.inp(np.broadcast_to(a, shape) if a.ndim == 0 else a.reshape(shape))
+
+    def geo(self, h, geo7, dPdrho, theta0, points=False):
+        """the leading arguments of a geometry-fed entry point: seven (n_lines, N) arrays, dPdrho (n_lines,) and theta0 --
+        (n_theta0,) of a scan, one per line of a points call -> (arguments up to theta0, shape of one output, N)"""
+        n_lines, N = geo7[0].shape
+        shape = (n_lines,) if points else (n_lines, int(theta0.shape[0]))
+        return [*shape, N, float(h), *[self.inp(a) for a in geo7], N, self.inp(dPdrho), self.inp(theta0)], shape, N
+
+    def lines(self, line_surf, line_alpha, theta, n_surf, what="line_surf"):
+        """(line_surf, line_alpha, theta) as int32 / float64 / float64 in the memory kind of the call: resident tensors pass through
+        (the geometry kernel clamps the surface index itself), host arrays are uploaded for a device call; a host line_surf is
+        range-checked against the n_surf the library is given"""
+        if not _is_torch(line_surf):
+            line_surf = np.ascontiguousarray(line_surf, dtype=np.int32)
+            if line_surf.size and (line_surf.min() < 0 or line_surf.max() >= n_surf):
+                raise IbsError("%s out of range" % what)
+        return self.inp(line_surf, _I32, True), self.inp(line_alpha, _F64, True), self.inp(theta, _F64, True)
+
+    def tables(self, tables, tabs=None, use_rows=True):
+        """the table arguments of a table-fed entry point -> (n_surf, [n_surf, mnmax, mnmax_nyq, seven table pointers], [n_rows,
+        rows, n_rows_nyq, rows_nyq, dn, dn_nyq]); a device call reads the copies resident on its device (uploaded once and kept ON
+        the tables object: a cache keyed by id(tables) would hand a later object that re-uses the id the previous object's tables),
+        with `tabs` = (tab_mn, tab_nyq, scal) in place of the last three"""
+        if self.mem == MEM_DEVICE:
+            dev = self.ctx._device_tables(tables, self.ref)
+            seven, rows = (dev[:7] if tabs is None else dev[:4] + list(tabs)), dev[7:]
+        else:
+            tabs = None         # (device calls only)
+            seven = (tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal)
+            rows = (tables.rows_mn, tables.rows_nyq) if use_rows else (_NO_ROWS, _NO_ROWS)
+        n_surf = len(tables.s) if tabs is None else int(tabs[2].shape[0])
+        nr = (len(tables.rows_mn), len(tables.rows_nyq)) if use_rows else (0, 0)
+        return (n_surf, [n_surf, len(tables.xm), len(tables.xm_nyq), *[self.inp(a) for a in seven]],
+                [nr[0], self.inp(rows[0], _I32), nr[1], self.inp(rows[1], _I32), float(tables.dn_mn), float(tables.dn_nyq)])
+
+    def out(self, name, shape, dtype=None, want=True):
+        """pointer to a new array the call fills, returned under `name`; want=False: a null pointer and no entry"""
+        if not want:
+            return _NULL
+        dtype = self.dtype if dtype is None else dtype
+        if self.mem == MEM_DEVICE:
+            import torch
+            t = self.outs[name] = torch.empty(shape, dtype=_torch_dtype(dtype), device=self.ref)
+            return C.c_void_p(t.data_ptr())
+        a = self.outs[name] = np.empty(shape, dtype=dtype)
+        return C.c_void_p(a.ctypes.data)
+
+    def inout(self, what, name, a, dtype, optional=False):
+        """pointer to the caller's own array, which the call updates in place: it must already be what the library reads"""
+        if a is None:
+            if optional:
+                return _NULL
+            raise IbsError("%s: %s is required" % (what, name))
+        if _is_torch(a):
+            ok = a.is_cuda and a.is_contiguous() and a.dtype == _torch_dtype(dtype)
+        else:
+            ok = isinstance(a, np.ndarray) and a.flags.c_contiguous and a.flags.writeable and a.dtype == dtype
+        if not ok:
+            raise IbsError("%s: %s is updated in place and must be a contiguous %s array" % (what, name, dtype.name))
+        return self.inp(a, dtype)
+
+    def call(self, name, *args, mem=True):
+        """ibs_<name>(handle, *args[, mem]) on the current torch stream of a device call -> its checked return value"""
+        ctx = self.ctx
+        if self.mem == MEM_DEVICE:
+            ctx._stream_from_torch(self.ref)
+            if self.temps:
+                ctx._keep = self.temps
+        fn = getattr(ctx._lib, name)
+        return check(fn(ctx._h, *args, self.mem) if mem else fn(ctx._h, *args), name)
+
+    def result(self, nbad=None):
+        """dict of the wanted outputs[, nbad]"""
+        if nbad is not None:
+            self.outs["nbad"] = nbad
+        return self.outs
+
+
+def _refine_views(buf, n):
+    """the packed result of ibs_refine_f64, 4 n float64 words = x_opt (n, 2) | f_opt (n,) | n_evals (n,) int32 in the rest: one
+    buffer, so that a device call's results come back in one copy"""
+    i32 = np.int32 if isinstance(buf, np.ndarray) else _torch_dtype(_I32)
+    return buf[:2 * n].reshape(n, 2), buf[2 * n:3 * n], buf[3 * n:].view(i32)[:n]
 
 
 def _device_key(device):
@@ -109,8 +216,9 @@ class Context:
     __del__ = close
 
     def _stream_from_torch(self, ref):
+        """the library works on the current torch stream of ref's device (ref: a tensor or a torch.device)"""
         import torch
-        self._lib.ibs_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream))
+        self._lib.ibs_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(getattr(ref, "device", ref)).cuda_stream))
 
     def synchronize(self):
         check(self._lib.ibs_synchronize(self._h), "ibs_synchronize")
@@ -209,73 +317,34 @@ class Context:
     def reset_options(self):
         self.set_option("all", None)
 
+
     # ---- raw (g, c, f) systems --------------------------------------------------------------
     def solve_gcf(self, h, g, c, f, want_X=False, want_info=False, dtype=np.float64, gh=None, want_gam=True):
         """g, c, f: (n_sys, N).  Returns dict(lam, gam[, X, dX][, info]).  gh (n_sys, N) optional half-grid g
         (first N-1 columns used): see ibs_solve_gcfh_f64.  float32: with want_gam / want_X the systems are widened to
         FP64 inside the solver (FP32 in HBM only); want_gam=False and no X = the all-FP32 kernel, eigenvalues only."""
-        ar = _Args(dtype)
+        ar = _Args(self, dtype)
         n_sys, N = g.shape
-        pg, pc, pf = ar.inp(g), ar.inp(c), ar.inp(f)
-        ref = g if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        lam, plam = ar.out((n_sys,), ref)
-        gam, pgam = ar.out((n_sys,), ref, want=want_gam)
-        X, pX = ar.out((n_sys, N), ref, want=want_X)
-        dX, pdX = ar.out((n_sys, N), ref, want=want_X)
-        info, pinfo = ar.out((n_sys,), ref, dtype=np.int32, want=want_info)
-        hh = float(h)
-        if gh is not None:
-            pgh = ar.inp(gh)
-            rc = check(self._lib.ibs_solve_gcfh_f64(self._h, n_sys, N, hh, pg, pgh, pc, pf, N, plam, pgam, pX, pdX, pinfo,
-                                                    ar.mem), "ibs_solve_gcfh_f64")
-        else:
-            fn = self._lib.ibs_solve_gcf_f64 if np.dtype(dtype) == np.float64 else self._lib.ibs_solve_gcf_f32
-            rc = check(fn(self._h, n_sys, N, hh, pg, pc, pf, N, plam, pgam, pX, pdX, pinfo, ar.mem), "ibs_solve_gcf")
-        out = dict(lam=lam, gam=gam, nbad=rc)
-        if want_X:
-            out.update(X=X, dX=dX)
-        if want_info:
-            out.update(info=info)
+        name = "ibs_solve_gcfh_f64" if gh is not None else "ibs_solve_gcf_f64" if ar.dtype == _F64 else "ibs_solve_gcf_f32"
+        half = () if gh is None else (ar.inp(gh),)
+        rc = ar.call(name, n_sys, N, float(h), ar.inp(g), *half, ar.inp(c), ar.inp(f), N, ar.out("lam", (n_sys,)),
+                     ar.out("gam", (n_sys,), want=want_gam), ar.out("X", (n_sys, N), want=want_X), ar.out("dX", (n_sys, N), want=want_X),
+                     ar.out("info", (n_sys,), _I32, want_info))
+        out = ar.result(rc)
+        out.setdefault("gam", None)
         return out
-
-    def _sigma_rows(self, ar, sigma, shape, ref):
-        """sigma as a float64 array of `shape` in the memory kind of the call (a scalar is broadcast)"""
-        if ref is not None:
-            import torch
-            t = torch.as_tensor(sigma, dtype=torch.float64, device=ref.device)
-            return ar.inp(t.expand(shape).contiguous() if t.dim() == 0 else t.reshape(shape))
-        a = np.asarray(sigma.detach().cpu().numpy() if _is_torch(sigma) else sigma, dtype=np.float64)
-        return ar.inp(np.broadcast_to(a, shape) if a.ndim == 0 else a.reshape(shape))
 
     def solve_gcf_nearest(self, h, g, c, f, sigma, gh=None, want_X=False, want_info=False):
         """the eigenpair NEAREST sigma (ibs_solve_gcf_nearest_f64: what utils.py:1597's eigs(A, 1, sigma=sigma0) returns).
         g, c, f (and gh, optional half-grid g as in solve_gcf): (n_sys, N); sigma: a scalar or (n_sys,).
         Returns dict(lam, idx, gam[, X, dX][, info], nbad): idx = the number of eigenvalues above lam (0 = lam_max, -1 = invalid
         data); info status bit 5 = the two eigenvalues about sigma are equally near within 4 N eps ||A|| (the larger is returned)."""
-        ar = _Args()
+        ar = _Args(self)
         n_sys, N = g.shape
-        pg, pc, pf = ar.inp(g), ar.inp(c), ar.inp(f)
-        pgh = ar.inp(gh) if gh is not None else C.c_void_p(None)
-        ref = g if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        psig = self._sigma_rows(ar, sigma, (n_sys,), ref)
-        lam, plam = ar.out((n_sys,), ref)
-        idx, pidx = ar.out((n_sys,), ref, dtype=np.int32)
-        gam, pgam = ar.out((n_sys,), ref)
-        X, pX = ar.out((n_sys, N), ref, want=want_X)
-        dX, pdX = ar.out((n_sys, N), ref, want=want_X)
-        info, pinfo = ar.out((n_sys,), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_solve_gcf_nearest_f64(self._h, n_sys, N, float(h), pg, pgh, pc, pf, N, psig, plam, pidx, pgam,
-                                                       pX, pdX, pinfo, ar.mem), "ibs_solve_gcf_nearest_f64")
-        out = dict(lam=lam, idx=idx, gam=gam, nbad=rc)
-        if want_X:
-            out.update(X=X, dX=dX)
-        if want_info:
-            out.update(info=info)
-        return out
+        rc = ar.call("ibs_solve_gcf_nearest_f64", n_sys, N, float(h), ar.inp(g), ar.inp(gh), ar.inp(c), ar.inp(f), N,
+                     ar.rows(sigma, (n_sys,)), ar.out("lam", (n_sys,)), ar.out("idx", (n_sys,), _I32), ar.out("gam", (n_sys,)),
+                     ar.out("X", (n_sys, N), want=want_X), ar.out("dX", (n_sys, N), want=want_X), ar.out("info", (n_sys,), _I32, want_info))
+        return ar.result(rc)
 
     def solve_gcf_vjp(self, h, g, c, f, lam, X, gam_bar=None, lam_bar=None, want_info=False):
         """exact vector-Jacobian product of gam and lam in the rows (ibs_solve_gcf_vjp_f64): g, c, f, X (n_sys, N), lam (n_sys,), the
@@ -284,24 +353,12 @@ class Context:
         an eigenpair of its rows (or whose data are invalid) gets status bit 1 and NaN rows."""
         if gam_bar is None and lam_bar is None:
             raise IbsError("solve_gcf_vjp: gam_bar and lam_bar are both None")
-        ar = _Args()
+        ar = _Args(self)
         n_sys, N = g.shape
-        pg, pc, pf, pX, plam = ar.inp(g), ar.inp(c), ar.inp(f), ar.inp(X), ar.inp(lam)
-        ref = g if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        pgb = self._sigma_rows(ar, gam_bar, (n_sys,), ref) if gam_bar is not None else C.c_void_p(None)
-        plb = self._sigma_rows(ar, lam_bar, (n_sys,), ref) if lam_bar is not None else C.c_void_p(None)
-        gb, pgb_out = ar.out((n_sys, N), ref)
-        cb, pcb_out = ar.out((n_sys, N), ref)
-        fb, pfb_out = ar.out((n_sys, N), ref)
-        info, pinfo = ar.out((n_sys,), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_solve_gcf_vjp_f64(self._h, n_sys, N, float(h), pg, pc, pf, N, plam, pX, pgb, plb, pgb_out, pcb_out,
-                                                   pfb_out, pinfo, ar.mem), "ibs_solve_gcf_vjp_f64")
-        out = dict(g_bar=gb, c_bar=cb, f_bar=fb, nbad=rc)
-        if want_info:
-            out.update(info=info)
-        return out
+        rc = ar.call("ibs_solve_gcf_vjp_f64", n_sys, N, float(h), ar.inp(g), ar.inp(c), ar.inp(f), N, ar.inp(lam), ar.inp(X),
+                     ar.rows(gam_bar, (n_sys,)), ar.rows(lam_bar, (n_sys,)), ar.out("g_bar", (n_sys, N)), ar.out("c_bar", (n_sys, N)),
+                     ar.out("f_bar", (n_sys, N)), ar.out("info", (n_sys,), _I32, want_info))
+        return ar.result(rc)
 
     # ---- marginal stability -----------------------------------------------------------------
     def marginal_gcf(self, h, g, c, want_X=False, want_grad=False, want_info=False):
@@ -310,55 +367,30 @@ class Context:
         Returns dict(scale, mu = 1 / s*[, X, gam0][, g_bar, c_bar][, info], nbad): X the marginal mode (zero ends, largest entry +1),
         gam0 its FD4 / Simpson quotient (O(h^2) from 0), g_bar / c_bar = d s* / d g, d s* / d c (n_sys, N).  info status bit 8: no
         c_j > 0, scale = inf and mu = 0 (not counted in nbad)."""
-        ar = _Args()
+        ar = _Args(self)
         n_sys, N = g.shape
-        pg, pc = ar.inp(g), ar.inp(c)
-        ref = g if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        scale, pscale = ar.out((n_sys,), ref)
-        mu, pmu = ar.out((n_sys,), ref)
-        X, pX = ar.out((n_sys, N), ref, want=want_X)
-        gam0, pgam0 = ar.out((n_sys,), ref, want=want_X)
-        gb, pgb = ar.out((n_sys, N), ref, want=want_grad)
-        cb, pcb = ar.out((n_sys, N), ref, want=want_grad)
-        info, pinfo = ar.out((n_sys,), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_marginal_gcf_f64(self._h, n_sys, N, float(h), pg, pc, N, pscale, pmu, pX, pgam0, pgb, pcb, pinfo,
-                                                  ar.mem), "ibs_marginal_gcf_f64")
-        out = dict(scale=scale, mu=mu, nbad=rc)
-        if want_X:
-            out.update(X=X, gam0=gam0)
-        if want_grad:
-            out.update(g_bar=gb, c_bar=cb)
-        if want_info:
-            out.update(info=info)
-        return out
+        rc = ar.call("ibs_marginal_gcf_f64", n_sys, N, float(h), ar.inp(g), ar.inp(c), N, ar.out("scale", (n_sys,)), ar.out("mu", (n_sys,)),
+                     ar.out("X", (n_sys, N), want=want_X), ar.out("gam0", (n_sys,), want=want_X), ar.out("g_bar", (n_sys, N), want=want_grad),
+                     ar.out("c_bar", (n_sys, N), want=want_grad), ar.out("info", (n_sys,), _I32, want_info))
+        return ar.result(rc)
 
     def marginal_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_grad=False, want_info=False):
         """the critical scale of dPdrho of every (line, theta0), at fixed geometry arrays (ibs_marginal_scan_f64): arrays as in
         gamma_scan.  Returns dict(scale, mu[, dscale_dtheta0, dscale_ddPdrho][, info], nbad) shaped (n_lines, n_theta0);
         dPdrho_crit = scale * dPdrho[:, None]."""
-        ar = _Args()
-        n_lines, N = bmag.shape
-        n_t0 = int(theta0.shape[0])
-        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
-        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
-        ref = bmag if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        scale, pscale = ar.out((n_lines, n_t0), ref)
-        mu, pmu = ar.out((n_lines, n_t0), ref)
-        dth, pdth = ar.out((n_lines, n_t0), ref, want=want_grad)
-        ddP, pddP = ar.out((n_lines, n_t0), ref, want=want_grad)
-        info, pinfo = ar.out((n_lines, n_t0), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_marginal_scan_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, pscale, pmu, pdth, pddP,
-                                                   pinfo, ar.mem), "ibs_marginal_scan_f64")
-        out = dict(scale=scale, mu=mu, nbad=rc)
-        if want_grad:
-            out.update(dscale_dtheta0=dth, dscale_ddPdrho=ddP)
-        if want_info:
-            out.update(info=info)
-        return out
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0)
+        rc = ar.call("ibs_marginal_scan_f64", *head, ar.out("scale", shape), ar.out("mu", shape),
+                     ar.out("dscale_dtheta0", shape, want=want_grad), ar.out("dscale_ddPdrho", shape, want=want_grad),
+                     ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
+
+    @staticmethod
+    def _three_lines(geo):
+        n_pts, three, eight, N = geo.shape
+        if three != 3 or eight != 8:
+            raise IbsError("geo must be (n_pts, 3, 8, N)")
+        return n_pts, N
 
     def marginal_obj_w_grad(self, h, geo, theta0, del_alpha=0.004, want_grad=True, want_info=False):
         """the objective of the margin's refinement in (alpha, theta0) (ibs_marginal_obj_w_grad_f64): geo (n_pts, 3, 8, N) -- the
@@ -366,28 +398,12 @@ class Context:
         dPdrho (the centre line's)[, jac = dscale / s*^2, dscale = (d s* / d alpha, d s* / d theta0): (n_pts, 2)][, info], nbad).
         want_grad=False: the side lines are not read and no mode is formed.  info status bit 8: scale = inf, val = 0, jac = dscale = 0
         (not counted in nbad); bits 0-1: NaN outputs -- or, where only a side line held invalid data, NaN jac and dscale alone."""
-        ar = _Args()
-        n_pts, three, eight, N = geo.shape
-        if three != 3 or eight != 8:
-            raise IbsError("geo must be (n_pts, 3, 8, N)")
-        pg, pt = ar.inp(geo), ar.inp(theta0)
-        ref = geo if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        val, pval = ar.out((n_pts,), ref)
-        jac, pjac = ar.out((n_pts, 2), ref, want=want_grad)
-        scale, pscale = ar.out((n_pts,), ref)
-        dscale, pdscale = ar.out((n_pts, 2), ref, want=want_grad)
-        dP, pdP = ar.out((n_pts,), ref)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_marginal_obj_w_grad_f64(self._h, n_pts, N, float(h), pg, N, pt, float(del_alpha), pval, pjac, pscale,
-                                                         pdscale, pdP, pinfo, ar.mem), "ibs_marginal_obj_w_grad_f64")
-        out = dict(val=val, scale=scale, dPdrho=dP, nbad=rc)
-        if want_grad:
-            out.update(jac=jac, dscale=dscale)
-        if want_info:
-            out.update(info=info)
-        return out
+        n_pts, N = self._three_lines(geo)
+        ar = _Args(self)
+        rc = ar.call("ibs_marginal_obj_w_grad_f64", n_pts, N, float(h), ar.inp(geo), N, ar.inp(theta0), float(del_alpha),
+                     ar.out("val", (n_pts,)), ar.out("jac", (n_pts, 2), want=want_grad), ar.out("scale", (n_pts,)),
+                     ar.out("dscale", (n_pts, 2), want=want_grad), ar.out("dPdrho", (n_pts,)), ar.out("info", (n_pts,), _I32, want_info))
+        return ar.result(rc)
 
     def marginal_obj_w_grad_tangent(self, h, geo, geo_da, theta0, want_grad=True, want_geo_bar=False, want_info=False):
         """marginal_obj_w_grad with the derivative in alpha exact as well, from ONE line per point (ibs_marginal_obj_w_grad_tangent_f64):
@@ -397,58 +413,27 @@ class Context:
         line's own dPdrho included: the cotangent to hand to fieldline_geometry_vjp][, info], nbad).  want_grad=False and
         want_geo_bar=False: no mode is formed.  Status bits as marginal_obj_w_grad; geo_bar is zero with bit 8 and NaN with a failed
         solve, and kept where only geo_da held invalid data (bit 1, NaN jac and dscale)."""
-        ar = _Args()
         eight, n_pts, N = geo.shape
         if eight != 8 or (geo_da is not None and tuple(geo_da.shape) != (8, n_pts, N)):
             raise IbsError("geo and geo_da must both be (8, n_pts, N)")
         if geo_da is None and want_grad:
             raise IbsError("geo_da is required with want_grad")
-        pg, pt = ar.inp(geo), ar.inp(theta0)
-        pd = ar.inp(geo_da) if geo_da is not None else C.c_void_p(None)
-        ref = geo if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        val, pval = ar.out((n_pts,), ref)
-        jac, pjac = ar.out((n_pts, 2), ref, want=want_grad)
-        scale, pscale = ar.out((n_pts,), ref)
-        dscale, pdscale = ar.out((n_pts, 2), ref, want=want_grad)
-        dP, pdP = ar.out((n_pts,), ref)
-        gbar, pgbar = ar.out((8, n_pts, N), ref, want=want_geo_bar)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_marginal_obj_w_grad_tangent_f64(self._h, n_pts, N, float(h), pg, pd, N, pt, pval, pjac, pscale, pdscale,
-                                                                 pdP, pgbar, pinfo, ar.mem), "ibs_marginal_obj_w_grad_tangent_f64")
-        out = dict(val=val, scale=scale, dPdrho=dP, nbad=rc)
-        if want_grad:
-            out.update(jac=jac, dscale=dscale)
-        if want_geo_bar:
-            out.update(geo_bar=gbar)
-        if want_info:
-            out.update(info=info)
-        return out
+        ar = _Args(self)
+        rc = ar.call("ibs_marginal_obj_w_grad_tangent_f64", n_pts, N, float(h), ar.inp(geo), ar.inp(geo_da), N, ar.inp(theta0),
+                     ar.out("val", (n_pts,)), ar.out("jac", (n_pts, 2), want=want_grad), ar.out("scale", (n_pts,)),
+                     ar.out("dscale", (n_pts, 2), want=want_grad), ar.out("dPdrho", (n_pts,)),
+                     ar.out("geo_bar", (8, n_pts, N), want=want_geo_bar), ar.out("info", (n_pts,), _I32, want_info))
+        return ar.result(rc)
 
     def gamma_scan_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma, want_info=False):
         """the coarse scan of ball_scan.py:248-273 with the eigenpair nearest sigma, as upstream (sigma = 1.0 there: ball_scan.py:230);
         ibs_gamma_scan_nearest_f64.  Geometry arrays (n_lines, N); dPdrho (n_lines,); theta0 (n_theta0,); sigma a scalar or
         (n_lines, n_theta0).  Returns dict(gam, lam, idx[, info], nbad) shaped (n_lines, n_theta0)."""
-        ar = _Args()
-        n_lines, N = bmag.shape
-        n_t0 = int(theta0.shape[0])
-        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
-        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
-        ref = bmag if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        psig = self._sigma_rows(ar, sigma, (n_lines, n_t0), ref)
-        gam, pgam = ar.out((n_lines, n_t0), ref)
-        lam, plam = ar.out((n_lines, n_t0), ref)
-        idx, pidx = ar.out((n_lines, n_t0), ref, dtype=np.int32)
-        info, pinfo = ar.out((n_lines, n_t0), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_gamma_scan_nearest_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, psig, pgam, plam,
-                                                        pidx, pinfo, ar.mem), "ibs_gamma_scan_nearest_f64")
-        out = dict(gam=gam, lam=lam, idx=idx, nbad=rc)
-        if want_info:
-            out.update(info=info)
-        return out
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0)
+        rc = ar.call("ibs_gamma_scan_nearest_f64", *head, ar.rows(sigma, shape), ar.out("gam", shape), ar.out("lam", shape),
+                     ar.out("idx", shape, _I32), ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
 
     # ---- geometry x theta0 scan ---------------------------------------------------------------
     def gamma_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0,
@@ -459,159 +444,92 @@ class Context:
         that fails is solved again in division form (reclose_scan: lam, gam, X, dX replaced; dgam_dtheta0 is not), and out["cert"]
         (int32: 0 = certified, 8 = re-closed and certified, bits 0-2 = open, see certify_scan) and out["ncert_failed"] (host arrays
         only) are added.  certify=False makes today's calls only."""
+        geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
         if certify:
-            out = self.gamma_scan(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_X=want_X,
-                                  want_dtheta0=want_dtheta0, want_info=want_info, lam_guess=lam_guess, guess_width=guess_width)
-            geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+            out = self.gamma_scan(h, *geo, dPdrho, theta0, want_X=want_X, want_dtheta0=want_dtheta0, want_info=want_info,
+                                  lam_guess=lam_guess, guess_width=guess_width)
             out["cert"] = self.certify_scan(h, *geo, dPdrho, theta0, out["lam"])
             out["ncert_failed"] = self.reclose_scan(h, *geo, dPdrho, theta0, out["cert"], out["lam"], out["gam"], out.get("X"),
                                                     out.get("dX"))
             return out
-        ar = _Args()
-        n_lines, N = bmag.shape
-        n_t0 = int(theta0.shape[0])
-        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
-        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
-        ref = bmag if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        gam, pgam = ar.out((n_lines, n_t0), ref)
-        lam, plam = ar.out((n_lines, n_t0), ref)
-        X, pX = ar.out((n_lines, n_t0, N), ref, want=want_X)
-        dX, pdX = ar.out((n_lines, n_t0, N), ref, want=want_X)
-        dth, pdth = ar.out((n_lines, n_t0), ref, want=want_dtheta0)
-        info, pinfo = ar.out((n_lines, n_t0), ref, dtype=np.int32, want=want_info)
-        if lam_guess is not None:
-            pg = ar.inp(lam_guess)
-            rc = check(self._lib.ibs_gamma_scan_warm_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, pg,
-                                                         float(guess_width), pgam, plam, pX, pdX, pdth, pinfo, ar.mem),
-                       "ibs_gamma_scan_warm_f64")
-        else:
-            rc = check(self._lib.ibs_gamma_scan_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0,
-                                                    pgam, plam, pX, pdX, pdth, pinfo, ar.mem), "ibs_gamma_scan_f64")
-        out = dict(gam=gam, lam=lam, nbad=rc)
-        if want_X:
-            out.update(X=X, dX=dX)
-        if want_dtheta0:
-            out.update(dgam_dtheta0=dth)
-        if want_info:
-            out.update(info=info)
-        return out
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, geo, dPdrho, theta0)
+        warm = () if lam_guess is None else (ar.inp(lam_guess), float(guess_width))
+        rc = ar.call("ibs_gamma_scan_f64" if lam_guess is None else "ibs_gamma_scan_warm_f64", *head, *warm, ar.out("gam", shape),
+                     ar.out("lam", shape), ar.out("X", shape + (N,), want=want_X), ar.out("dX", shape + (N,), want=want_X),
+                     ar.out("dgam_dtheta0", shape, want=want_dtheta0), ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
 
     def gamma_scan_argmax(self, h, geo7, dPdrho, theta0, n_surf):
         """coarse scan + per-surface first maximum in ONE C call on device tensors (ibs_gamma_scan_argmax_f64; replaces
         ball_scan.py:248-295 for all surfaces at once).  geo7: seven (n_lines, N) tensors, lines surface-major.
         Returns dict(gam, lam (n_lines, n_theta0), pack (n_surf, 2) = (max, first row-major index), info)."""
-        import torch
-        ar = _Args()
-        n_lines, N = geo7[0].shape
-        n_t0 = int(theta0.shape[0])
-        ptrs = [ar.inp(a) for a in geo7]
-        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, geo7, dPdrho, theta0)
         if ar.mem != MEM_DEVICE:
             raise IbsError("gamma_scan_argmax takes device tensors")
-        ref = geo7[0]
-        self._stream_from_torch(ref)
-        gam, pgam = ar.out((n_lines, n_t0), ref)
-        lam, plam = ar.out((n_lines, n_t0), ref)
-        pack, ppack = ar.out((n_surf, 2), ref)
-        info, pinfo = ar.out((n_lines, n_t0), ref, dtype=np.int32)
-        check(self._lib.ibs_gamma_scan_argmax_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, int(n_surf),
-                                                  pgam, plam, ppack, pinfo), "ibs_gamma_scan_argmax_f64")
-        return dict(gam=gam, lam=lam, pack=pack, info=info)
+        ar.call("ibs_gamma_scan_argmax_f64", *head, int(n_surf), ar.out("gam", shape), ar.out("lam", shape), ar.out("pack", (n_surf, 2)),
+                ar.out("info", shape, _I32), mem=False)
+        return ar.result()
 
     def gamma_points(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0,
                      want_X=False, want_dtheta0=False, want_info=False, certify=False):
         """one (line, theta0) pair per point (ibs_gamma_points_f64: the final solve of ball_scan.py:322-339 for many
         surfaces at once).  geometry arrays (n_pts, N); dPdrho, theta0 (n_pts,).  Returns dict(gam, lam[, X, dX][, ...]).
         certify=True: as in gamma_scan (certify_points, reclose_points; out["cert"], out["ncert_failed"])."""
+        geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
         if certify:
-            out = self.gamma_points(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_X=want_X,
-                                    want_dtheta0=want_dtheta0, want_info=want_info)
-            geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+            out = self.gamma_points(h, *geo, dPdrho, theta0, want_X=want_X, want_dtheta0=want_dtheta0, want_info=want_info)
             out["cert"] = self.certify_points(h, *geo, dPdrho, theta0, out["lam"])
             out["ncert_failed"] = self.reclose_points(h, *geo, dPdrho, theta0, out["cert"], out["lam"], out["gam"], out.get("X"),
                                                       out.get("dX"))
             return out
-        ar = _Args()
-        n_pts, N = bmag.shape
-        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
-        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
-        ref = bmag if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        gam, pgam = ar.out((n_pts,), ref)
-        lam, plam = ar.out((n_pts,), ref)
-        X, pX = ar.out((n_pts, N), ref, want=want_X)
-        dX, pdX = ar.out((n_pts, N), ref, want=want_X)
-        dth, pdth = ar.out((n_pts,), ref, want=want_dtheta0)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_gamma_points_f64(self._h, n_pts, N, float(h), *ptrs, N, pdP, pt0, pgam, plam, pX, pdX,
-                                                  pdth, pinfo, ar.mem), "ibs_gamma_points_f64")
-        out = dict(gam=gam, lam=lam, nbad=rc)
-        if want_X:
-            out.update(X=X, dX=dX)
-        if want_dtheta0:
-            out.update(dgam_dtheta0=dth)
-        if want_info:
-            out.update(info=info)
-        return out
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, geo, dPdrho, theta0, points=True)
+        rc = ar.call("ibs_gamma_points_f64", *head, ar.out("gam", shape), ar.out("lam", shape), ar.out("X", shape + (N,), want=want_X),
+                     ar.out("dX", shape + (N,), want=want_X), ar.out("dgam_dtheta0", shape, want=want_dtheta0),
+                     ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
 
     def scan_starts(self, alpha_scan, theta0_scan, pack, n_bad, want_sigma0=False):
         """start points (n_surf, 2) = (alpha, theta0) of the refinement from the per-surface maxima `pack`, on the device
         (ibs_scan_starts_f64; ball_scan.py:279-295).  All arguments device tensors; n_bad: int32 tensor of one element that
         accumulates the number of surfaces whose maximum is not finite.  want_sigma0: returns (start, sigma0 (n_surf,)) with
         the refinement's shift of every surface, 1.3 |max| + 0.05 (0.05 for an all-zero table: ball_scan.py:282, 289)."""
-        import torch
+        ar = _Args(self, device=pack.device)
         n_surf = pack.shape[0]
-        start = torch.empty((n_surf, 2), dtype=torch.float64, device=pack.device)
-        sigma0 = torch.empty((n_surf,), dtype=torch.float64, device=pack.device) if want_sigma0 else None
-        self._stream_from_torch(pack)
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-        check(self._lib.ibs_scan_starts_f64(self._h, n_surf, alpha_scan.shape[0], theta0_scan.shape[0], p(alpha_scan),
-                                            p(theta0_scan), p(pack), p(start), p(sigma0), p(n_bad)), "ibs_scan_starts_f64")
-        return (start, sigma0) if want_sigma0 else start
+        ar.call("ibs_scan_starts_f64", n_surf, alpha_scan.shape[0], theta0_scan.shape[0], ar.inp(alpha_scan), ar.inp(theta0_scan),
+                ar.inp(pack), ar.out("start", (n_surf, 2)), ar.out("sigma0", (n_surf,), want=want_sigma0),
+                ar.inout("scan_starts", "n_bad", n_bad, _I32), mem=False)
+        return (ar.outs["start"], ar.outs["sigma0"]) if want_sigma0 else ar.outs["start"]
 
     def obj_w_grad(self, h, geo, theta0, del_alpha=0.004, want_info=False):
         """geo: (n_pts, 3, 8, N) -- lines (alpha-d/2, alpha, alpha+d/2) x (bmag, gradpar, cvdrift, cvdrift0,
         gds2, gds21, gds22, gbdrift); theta0: (n_pts,).  Returns (val (n_pts,), jac (n_pts, 2)) with the
         sign convention of utils.py:1728: val = -gam, jac = (-dgam/dalpha, -dgam/dtheta0)."""
-        ar = _Args()
-        n_pts, three, eight, N = geo.shape
-        if three != 3 or eight != 8:
-            raise IbsError("geo must be (n_pts, 3, 8, N)")
-        pg, pt = ar.inp(geo), ar.inp(theta0)
-        ref = geo if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        val, pval = ar.out((n_pts,), ref)
-        jac, pjac = ar.out((n_pts, 2), ref)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        check(self._lib.ibs_obj_w_grad_f64(self._h, n_pts, N, float(h), pg, N, pt, float(del_alpha), pval, pjac,
-                                           pinfo, ar.mem), "ibs_obj_w_grad_f64")
-        return (val, jac, info) if want_info else (val, jac)
+        n_pts, N = self._three_lines(geo)
+        ar = _Args(self)
+        ar.call("ibs_obj_w_grad_f64", n_pts, N, float(h), ar.inp(geo), N, ar.inp(theta0), float(del_alpha), ar.out("val", (n_pts,)),
+                ar.out("jac", (n_pts, 2)), ar.out("info", (n_pts,), _I32, want_info))
+        return tuple(ar.outs.values())
+
+    @staticmethod
+    def _val_jac(ar, want_info):
+        """(val, jac) or, with want_info, (val, jac, dict of the other outputs)"""
+        out = ar.outs
+        val, jac = out.pop("val"), out.pop("jac")
+        return (val, jac, out) if want_info else (val, jac)
 
     def obj_w_grad_nearest(self, h, geo, theta0, sigma, del_alpha=0.004, want_info=False):
         """obj_w_grad with the eigenpair NEAREST sigma (ibs_obj_w_grad_nearest_f64: utils.py:1632-1728 as the refinement of
         ball_scan.py:305-314 runs it, sigma = 1.3 |gam| + 0.05).  geo (n_pts, 3, 8, N), theta0 (n_pts,), sigma a scalar or (n_pts,).
         Returns (val, jac) or, with want_info, (val, jac, dict(lam, idx, info)); a failed solve gives NaN val and jac."""
-        ar = _Args()
-        n_pts, three, eight, N = geo.shape
-        if three != 3 or eight != 8:
-            raise IbsError("geo must be (n_pts, 3, 8, N)")
-        pg, pt = ar.inp(geo), ar.inp(theta0)
-        ref = geo if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        psig = self._sigma_rows(ar, sigma, (n_pts,), ref)
-        val, pval = ar.out((n_pts,), ref)
-        jac, pjac = ar.out((n_pts, 2), ref)
-        lam, plam = ar.out((n_pts,), ref, want=want_info)
-        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        check(self._lib.ibs_obj_w_grad_nearest_f64(self._h, n_pts, N, float(h), pg, N, pt, psig, float(del_alpha), pval, pjac,
-                                                   plam, pidx, pinfo, ar.mem), "ibs_obj_w_grad_nearest_f64")
-        return (val, jac, dict(lam=lam, idx=idx, info=info)) if want_info else (val, jac)
+        n_pts, N = self._three_lines(geo)
+        ar = _Args(self)
+        ar.call("ibs_obj_w_grad_nearest_f64", n_pts, N, float(h), ar.inp(geo), N, ar.inp(theta0), ar.rows(sigma, (n_pts,)),
+                float(del_alpha), ar.out("val", (n_pts,)), ar.out("jac", (n_pts, 2)), ar.out("lam", (n_pts,), want=want_info),
+                ar.out("idx", (n_pts,), _I32, want_info), ar.out("info", (n_pts,), _I32, want_info))
+        return self._val_jac(ar, want_info)
 
     def obj_w_grad_exact(self, h, geo, theta0, del_alpha=0.004, sigma=None, want_info=False):
         """obj_w_grad with the EXACT gradient of the gam it returns (ibs_obj_w_grad_exact_f64: utils.py:1632-1728 with the exact
@@ -620,125 +538,53 @@ class Context:
         Returns (val, jac) or, with want_info, (val, jac, dict(gam, lam, idx, info)).  A failed solve (status bits 0-1) gives NaN
         val and jac; an adjoint that refuses the pair (status bit 7) NaN jac alone; bit 6 (a replaced pivot of the adjoint solve) is
         informational.  EXACT_VJP_SHIFT moves info's status to solve_gcf_vjp's two bits."""
-        ar = _Args()
-        n_pts, three, eight, N = geo.shape
-        if three != 3 or eight != 8:
-            raise IbsError("geo must be (n_pts, 3, 8, N)")
-        pg, pt = ar.inp(geo), ar.inp(theta0)
-        ref = geo if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        psig = self._sigma_rows(ar, sigma, (n_pts,), ref) if sigma is not None else C.c_void_p(None)
-        val, pval = ar.out((n_pts,), ref)
-        jac, pjac = ar.out((n_pts, 2), ref)
-        gam, pgam = ar.out((n_pts,), ref, want=want_info)
-        lam, plam = ar.out((n_pts,), ref, want=want_info)
-        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        check(self._lib.ibs_obj_w_grad_exact_f64(self._h, n_pts, N, float(h), pg, N, pt, psig, float(del_alpha), pval, pjac, pgam,
-                                                 plam, pidx, pinfo, ar.mem), "ibs_obj_w_grad_exact_f64")
-        return (val, jac, dict(gam=gam, lam=lam, idx=idx, info=info)) if want_info else (val, jac)
+        n_pts, N = self._three_lines(geo)
+        ar = _Args(self)
+        ar.call("ibs_obj_w_grad_exact_f64", n_pts, N, float(h), ar.inp(geo), N, ar.inp(theta0), ar.rows(sigma, (n_pts,)),
+                float(del_alpha), ar.out("val", (n_pts,)), ar.out("jac", (n_pts, 2)), ar.out("gam", (n_pts,), want=want_info),
+                ar.out("lam", (n_pts,), want=want_info), ar.out("idx", (n_pts,), _I32, want_info), ar.out("info", (n_pts,), _I32, want_info))
+        return self._val_jac(ar, want_info)
 
     def obj_w_grad_exact_tangent(self, h, geo, geo_da, theta0, sigma=None, want_info=False):
         """obj_w_grad_exact with the derivative in alpha exact as well, from ONE line per point (ibs_obj_w_grad_exact_tangent_f64):
         geo, geo_da (8, n_pts, N) as fieldline_geometry and fieldline_geometry_dalpha return them for the same lines, theta0 (n_pts,);
         no del_alpha.  sigma, the return values and the status bits are obj_w_grad_exact's; val, jac[:, 1] and the info dict are the
         bits obj_w_grad_exact gives on the same centre line."""
-        ar = _Args()
         eight, n_pts, N = geo.shape
         if eight != 8 or tuple(geo_da.shape) != (8, n_pts, N):
             raise IbsError("geo and geo_da must both be (8, n_pts, N)")
-        pg, pd, pt = ar.inp(geo), ar.inp(geo_da), ar.inp(theta0)
-        ref = geo if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        psig = self._sigma_rows(ar, sigma, (n_pts,), ref) if sigma is not None else C.c_void_p(None)
-        val, pval = ar.out((n_pts,), ref)
-        jac, pjac = ar.out((n_pts, 2), ref)
-        gam, pgam = ar.out((n_pts,), ref, want=want_info)
-        lam, plam = ar.out((n_pts,), ref, want=want_info)
-        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        check(self._lib.ibs_obj_w_grad_exact_tangent_f64(self._h, n_pts, N, float(h), pg, pd, N, pt, psig, pval, pjac, pgam, plam, pidx,
-                                                         pinfo, ar.mem), "ibs_obj_w_grad_exact_tangent_f64")
-        return (val, jac, dict(gam=gam, lam=lam, idx=idx, info=info)) if want_info else (val, jac)
+        ar = _Args(self)
+        ar.call("ibs_obj_w_grad_exact_tangent_f64", n_pts, N, float(h), ar.inp(geo), ar.inp(geo_da), N, ar.inp(theta0),
+                ar.rows(sigma, (n_pts,)), ar.out("val", (n_pts,)), ar.out("jac", (n_pts, 2)), ar.out("gam", (n_pts,), want=want_info),
+                ar.out("lam", (n_pts,), want=want_info), ar.out("idx", (n_pts,), _I32, want_info), ar.out("info", (n_pts,), _I32, want_info))
+        return self._val_jac(ar, want_info)
 
     def gamma_points_nearest(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, sigma,
                              want_X=False, want_info=False):
         """gamma_points with the eigenpair NEAREST sigma (ibs_gamma_points_nearest_f64: the final solve of ball_scan.py:322-339,
         sigma = 0.42 there).  Geometry arrays (n_pts, N); dPdrho, theta0 (n_pts,); sigma a scalar or (n_pts,).
         Returns dict(gam, lam, idx[, X, dX][, info], nbad)."""
-        ar = _Args()
-        n_pts, N = bmag.shape
-        ptrs = [ar.inp(a) for a in (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)]
-        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
-        ref = bmag if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        psig = self._sigma_rows(ar, sigma, (n_pts,), ref)
-        gam, pgam = ar.out((n_pts,), ref)
-        lam, plam = ar.out((n_pts,), ref)
-        idx, pidx = ar.out((n_pts,), ref, dtype=np.int32)
-        X, pX = ar.out((n_pts, N), ref, want=want_X)
-        dX, pdX = ar.out((n_pts, N), ref, want=want_X)
-        info, pinfo = ar.out((n_pts,), ref, dtype=np.int32, want=want_info)
-        rc = check(self._lib.ibs_gamma_points_nearest_f64(self._h, n_pts, N, float(h), *ptrs, N, pdP, pt0, psig, pgam, plam, pidx,
-                                                          pX, pdX, pinfo, ar.mem), "ibs_gamma_points_nearest_f64")
-        out = dict(gam=gam, lam=lam, idx=idx, nbad=rc)
-        if want_X:
-            out.update(X=X, dX=dX)
-        if want_info:
-            out.update(info=info)
-        return out
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0, points=True)
+        rc = ar.call("ibs_gamma_points_nearest_f64", *head, ar.rows(sigma, shape), ar.out("gam", shape), ar.out("lam", shape),
+                     ar.out("idx", shape, _I32), ar.out("X", shape + (N,), want=want_X), ar.out("dX", shape + (N,), want=want_X),
+                     ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
 
+    # ---- table-fed: field-line geometry, its derivatives, the refinement --------------------------
     def fieldline_geometry(self, tables, line_surf, line_alpha, theta, device=None, use_rows=True, tabs=None):
         """geometry of the field lines (tables.s[line_surf[i]], line_alpha[i]) on the grid theta (row F1).
         Returns dict(geo=(8, n_lines, N), dPdrho=(n_lines,)); geo[0..6] + dPdrho feed gamma_scan directly.
         device=None: numpy in / numpy out (staged);  device=torch.device(...): results stay in HBM.
         tabs (device calls): (tab_mn, tab_nyq, scal) device tensors to use in place of the tables' resident copies, for any
         number of surfaces (ibs_amd.autograd.fieldline_geometry); the mode tables stay those of `tables`."""
-        n_lines = len(line_surf)
-        N = len(theta)
-        resident = device is not None and all(_is_torch(a) for a in (line_surf, line_alpha, theta))
-        if not resident:
-            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
-            la = np.ascontiguousarray(line_alpha, dtype=np.float64)
-            th = np.ascontiguousarray(theta, dtype=np.float64)
-            if ls.size and (ls.min() < 0 or ls.max() >= len(tables.s)):
-                raise IbsError("line_surf out of range")
-        host = [tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal]
-        rows = [tables.rows_mn, tables.rows_nyq] if use_rows else [np.zeros((0, 2), np.int32)] * 2
-        if device is None:
-            geo = np.empty((8, n_lines, N)); dP = np.empty(n_lines)
-            p = lambda a: C.c_void_p(a.ctypes.data)
-            check(self._lib.ibs_fieldline_geometry_f64(self._h, len(tables.s), len(tables.xm), len(tables.xm_nyq),
-                                                       *[p(a) for a in host], n_lines, p(ls), p(la), N, p(th), N, p(geo),
-                                                       p(dP), len(rows[0]), p(rows[0]), len(rows[1]), p(rows[1]),
-                                                       float(tables.dn_mn), float(tables.dn_nyq), MEM_HOST), "ibs_fieldline_geometry_f64")
-            return dict(geo=geo, dPdrho=dP)
-        import torch
-        # tables are uploaded once and stay resident; the device copies live ON the tables object (a cache keyed by
-        # id(tables) would hand a later object that re-uses the id the previous object's tables)
-        allc = self._device_tables(tables, device)
-        dev = allc[:7] if tabs is None else allc[:4] + [t.contiguous() for t in tabs]
-        d_rows = allc[7:]
-        if resident:      # index / angle / grid tensors already in HBM (int32, float64, float64): no upload, no host check
-            #               (the geometry kernel clamps the surface index itself)
-            d_ls, d_la, d_th = line_surf.to(torch.int32).contiguous(), line_alpha.to(torch.float64).contiguous(), theta.to(torch.float64).contiguous()
-        else:
-            d_ls, d_la, d_th = (torch.from_numpy(a).to(device) for a in (ls, la, th))
-        geo = torch.empty((8, n_lines, N), dtype=torch.float64, device=device)
-        dP = torch.empty((n_lines,), dtype=torch.float64, device=device)
-        self._stream_from_torch(geo)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        nr = (len(tables.rows_mn), len(tables.rows_nyq)) if use_rows else (0, 0)
-        check(self._lib.ibs_fieldline_geometry_f64(self._h, len(tables.s) if tabs is None else int(tabs[2].shape[0]), len(tables.xm), len(tables.xm_nyq),
-                                                   *[p(t) for t in dev], n_lines, p(d_ls), p(d_la), N, p(d_th), N, p(geo),
-                                                   p(dP), nr[0], p(d_rows[0]), nr[1], p(d_rows[1]), float(tables.dn_mn), float(tables.dn_nyq),
-                                                   MEM_DEVICE),
-              "ibs_fieldline_geometry_f64")
-        self._keep = (d_ls, d_la, d_th)
-        return dict(geo=geo, dPdrho=dP)
+        n_lines, N = len(line_surf), len(theta)
+        ar = _Args(self, device=device, host=device is None)
+        n_surf, head, rows = ar.tables(tables, tabs, use_rows)
+        pls, pla, pth = ar.lines(line_surf, line_alpha, theta, n_surf)
+        ar.call("ibs_fieldline_geometry_f64", *head, n_lines, pls, pla, N, pth, N, ar.out("geo", (8, n_lines, N)),
+                ar.out("dPdrho", (n_lines,)), *rows)
+        return ar.result()
 
     def fieldline_geometry_vjp(self, tables, line_surf, line_alpha, theta, geo_bar, dPdrho_bar=None, device=None,
                                want=("tab_mn", "tab_nyq", "scal", "alpha"), tabs=None):
@@ -752,47 +598,15 @@ class Context:
         if not want or not want <= {"tab_mn", "tab_nyq", "scal", "alpha"}:
             raise IbsError("want must name at least one of tab_mn, tab_nyq, scal, alpha")
         n_lines, N = len(line_surf), len(theta)
-        n_surf, mnmax, mnq = len(tables.s) if tabs is None else int(tabs[2].shape[0]), len(tables.xm), len(tables.xm_nyq)
         if tuple(geo_bar.shape) != (8, n_lines, N):
             raise IbsError("geo_bar must be (8, n_lines, N)")
-        shapes = dict(tab_mn=(n_surf, 6, mnmax), tab_nyq=(n_surf, 7, mnq), scal=(n_surf, 6), alpha=(n_lines,))
-        names = ("tab_mn", "tab_nyq", "scal", "alpha")
-        head = (self._h, n_surf, mnmax, mnq)
-        if device is None:
-            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
-            la = np.ascontiguousarray(line_alpha, dtype=np.float64)
-            th = np.ascontiguousarray(theta, dtype=np.float64)
-            gb = np.ascontiguousarray(geo_bar, dtype=np.float64)
-            db = None if dPdrho_bar is None else np.ascontiguousarray(dPdrho_bar, dtype=np.float64)
-            host = [tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal]
-            outs = {k: (np.empty(shapes[k]) if k in want else None) for k in names}
-            p = lambda a: C.c_void_p(None if a is None else a.ctypes.data)
-            check(self._lib.ibs_fieldline_geometry_vjp_f64(*head, *[p(a) for a in host], n_lines, p(ls), p(la), N, p(th), N,
-                                                           p(gb), p(db), *[p(outs[k]) for k in names], MEM_HOST),
-                  "ibs_fieldline_geometry_vjp_f64")
-            return {k + "_bar": outs[k] for k in names}
-        import torch
-        allc = self._device_tables(tables, device)
-        dev = allc[:7] if tabs is None else allc[:4] + [t.contiguous() for t in tabs]
-        if all(_is_torch(a) for a in (line_surf, line_alpha, theta)):
-            d_ls, d_la, d_th = line_surf.to(torch.int32).contiguous(), line_alpha.to(torch.float64).contiguous(), theta.to(torch.float64).contiguous()
-        else:
-            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
-            if ls.size and (ls.min() < 0 or ls.max() >= n_surf):
-                raise IbsError("line_surf out of range")
-            d_ls = torch.from_numpy(ls).to(device)
-            d_la = torch.from_numpy(np.ascontiguousarray(line_alpha, dtype=np.float64)).to(device)
-            d_th = torch.from_numpy(np.ascontiguousarray(theta, dtype=np.float64)).to(device)
-        gb = geo_bar.to(torch.float64).contiguous()
-        db = None if dPdrho_bar is None else dPdrho_bar.to(torch.float64).contiguous()
-        outs = {k: (torch.empty(shapes[k], dtype=torch.float64, device=device) if k in want else None) for k in names}
-        self._stream_from_torch(gb)
-        p = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-        check(self._lib.ibs_fieldline_geometry_vjp_f64(*head, *[p(t) for t in dev], n_lines, p(d_ls), p(d_la), N, p(d_th), N,
-                                                       p(gb), p(db), *[p(outs[k]) for k in names], MEM_DEVICE),
-              "ibs_fieldline_geometry_vjp_f64")
-        self._keep = (d_ls, d_la, d_th, gb, db, dev)
-        return {k + "_bar": outs[k] for k in names}
+        ar = _Args(self, device=device, host=device is None)
+        n_surf, head, _ = ar.tables(tables, tabs)
+        pls, pla, pth = ar.lines(line_surf, line_alpha, theta, n_surf)
+        shapes = dict(tab_mn=(n_surf, 6, head[1]), tab_nyq=(n_surf, 7, head[2]), scal=(n_surf, 6), alpha=(n_lines,))
+        ar.call("ibs_fieldline_geometry_vjp_f64", *head, n_lines, pls, pla, N, pth, N, ar.inp(geo_bar), ar.inp(dPdrho_bar),
+                *[ar.out(k + "_bar", shape, want=k in want) for k, shape in shapes.items()])
+        return {k + "_bar": ar.outs.get(k + "_bar") for k in shapes}
 
     def fieldline_geometry_dalpha(self, tables, line_surf, line_alpha, theta, device=None):
         """alpha-tangent of fieldline_geometry (ibs_fieldline_geometry_dalpha_f64): dict(geo_da=(8, n_lines, N)), the derivative of the
@@ -800,44 +614,23 @@ class Context:
         1683-1718.  dPdrho does not depend on alpha and has no tangent.  One lane per grid point: a line alone gives its batch bits.
         device=None: numpy in / numpy out (staged);  device=torch.device(...): numpy or device tensors in, a device tensor out."""
         n_lines, N = len(line_surf), len(theta)
-        head = (self._h, len(tables.s), len(tables.xm), len(tables.xm_nyq))
-        if device is None:
-            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
-            la = np.ascontiguousarray(line_alpha, dtype=np.float64)
-            th = np.ascontiguousarray(theta, dtype=np.float64)
-            host = [tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal]
-            out = np.empty((8, n_lines, N))
-            p = lambda a: C.c_void_p(a.ctypes.data)
-            check(self._lib.ibs_fieldline_geometry_dalpha_f64(*head, *[p(a) for a in host], n_lines, p(ls), p(la), N, p(th), N, p(out),
-                                                              MEM_HOST), "ibs_fieldline_geometry_dalpha_f64")
-            return dict(geo_da=out)
-        import torch
-        dev = self._device_tables(tables, device)[:7]
-        if all(_is_torch(a) for a in (line_surf, line_alpha, theta)):
-            d_ls, d_la, d_th = line_surf.to(torch.int32).contiguous(), line_alpha.to(torch.float64).contiguous(), theta.to(torch.float64).contiguous()
-        else:
-            ls = np.ascontiguousarray(line_surf, dtype=np.int32)
-            if ls.size and (ls.min() < 0 or ls.max() >= len(tables.s)):
-                raise IbsError("line_surf out of range")
-            d_ls = torch.from_numpy(ls).to(device)
-            d_la = torch.from_numpy(np.ascontiguousarray(line_alpha, dtype=np.float64)).to(device)
-            d_th = torch.from_numpy(np.ascontiguousarray(theta, dtype=np.float64)).to(device)
-        out = torch.empty((8, n_lines, N), dtype=torch.float64, device=device)
-        self._stream_from_torch(out)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        check(self._lib.ibs_fieldline_geometry_dalpha_f64(*head, *[p(t) for t in dev], n_lines, p(d_ls), p(d_la), N, p(d_th), N, p(out),
-                                                          MEM_DEVICE), "ibs_fieldline_geometry_dalpha_f64")
-        self._keep = (d_ls, d_la, d_th, dev)
-        return dict(geo_da=out)
+        ar = _Args(self, device=device, host=device is None)
+        n_surf, head, _ = ar.tables(tables)
+        pls, pla, pth = ar.lines(line_surf, line_alpha, theta, n_surf)
+        ar.call("ibs_fieldline_geometry_dalpha_f64", *head, n_lines, pls, pla, N, pth, N, ar.out("geo_da", (8, n_lines, N)))
+        return ar.result()
 
-    def _device_tables(self, tables, device):
-        """the surface/mode/row tables of `tables` resident on `device` (uploaded once, cached on the object)"""
+    def _device_tables(self, tables, device, filled=True):
+        """the surface/mode/row tables of `tables` resident on `device` (uploaded once, cached on the object); filled=False leaves
+        tab_mn, tab_nyq and scal empty on creation, for a row-wise upload"""
         import torch
         cache = tables.__dict__.setdefault("_device_copies", {})
         key = _device_key(device)
         if key not in cache:
-            host = [tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal]
-            cache[key] = [torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in host + [tables.rows_mn, tables.rows_nyq]]
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            big = up if filled else (lambda a: torch.empty(a.shape, dtype=torch.float64, device=device))
+            cache[key] = [up(tables.xm), up(tables.xn), up(tables.xm_nyq), up(tables.xn_nyq), big(tables.tab_mn), big(tables.tab_nyq),
+                          big(tables.scal), up(tables.rows_mn), up(tables.rows_nyq)]
             # (a caching allocator may hand these rows the addresses of a freed table set: the library's verdict on device-resident
             #  rows is keyed by address and size)
             self.set_option("forget_rows", 1)
@@ -848,19 +641,20 @@ class Context:
         asynchronous on the current torch stream when the host arrays are page-locked (SurfaceTables.frame(pinned=True)).
         For callers that fill a frame piece by piece while earlier pieces are already being worked on."""
         import torch
-        cache = tables.__dict__.setdefault("_device_copies", {})
-        key = _device_key(device)
-        if key not in cache:
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            e = lambda a: torch.empty(a.shape, dtype=torch.float64, device=device)
-            cache[key] = [t(tables.xm), t(tables.xn), t(tables.xm_nyq), t(tables.xn_nyq), e(tables.tab_mn), e(tables.tab_nyq),
-                          e(tables.scal), t(tables.rows_mn), t(tables.rows_nyq)]
-            self.set_option("forget_rows", 1)
-        dev = cache[key]
+        dev = self._device_tables(tables, device, filled=False)
         pinned = getattr(tables, "_pinned", {})
         for k, name in ((4, "tab_mn"), (5, "tab_nyq"), (6, "scal")):
             src = pinned[name] if name in pinned else torch.from_numpy(getattr(tables, name))
             dev[k][r0:r1].copy_(src[r0:r1], non_blocking=True)
+
+    def _refine(self, ar, tables, n, pt_surf, starts, n_theta, theta, del_alpha, maxiter, ftol, gtol):
+        """the one call of ibs_refine_f64 -> (packed result buffer, rounds)"""
+        _, head, rows = ar.tables(tables)
+        pout = ar.out("packed", (4 * n,)).value or 0
+        rounds = ar.call("ibs_refine_f64", *head, *rows, n, ar.inp(pt_surf, _I32, True), ar.inp(starts, _F64, True), n_theta,
+                         ar.inp(theta, _F64, True), float(del_alpha), int(maxiter), float(ftol), float(gtol), C.c_void_p(pout),
+                         C.c_void_p(pout + 16 * n), C.c_void_p(pout + 24 * n))
+        return ar.outs["packed"], rounds
 
     def refine(self, tables, pt_surf, starts, theta, del_alpha=0.004, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, device=None):
         """maximise gam over (alpha, theta0) from starts (n, 2) on surfaces tables.s[pt_surf] -- the whole
@@ -874,61 +668,29 @@ class Context:
             raise IbsError("starts must be (len(pt_surf), 2)")
         if ps.size and (ps.min() < 0 or ps.max() >= len(tables.s)):
             raise IbsError("pt_surf out of range")
-        nr = (len(tables.rows_mn), len(tables.rows_nyq))
-        head = (self._h, len(tables.s), len(tables.xm), len(tables.xm_nyq))
-        tail = (float(del_alpha), int(maxiter), float(ftol), float(gtol))
-        if device is None:
-            xo = np.empty((n, 2)); fo = np.empty(n); ne = np.zeros(n, dtype=np.int32)
-            p = lambda a: C.c_void_p(a.ctypes.data)
-            host = [tables.xm, tables.xn, tables.xm_nyq, tables.xn_nyq, tables.tab_mn, tables.tab_nyq, tables.scal]
-            rounds = check(self._lib.ibs_refine_f64(*head, *[p(a) for a in host], nr[0], p(tables.rows_mn), nr[1],
-                                                    p(tables.rows_nyq), float(tables.dn_mn), float(tables.dn_nyq), n, p(ps),
-                                                    p(st), len(th), p(th), *tail, p(xo), p(fo), p(ne), MEM_HOST),
-                           "ibs_refine_f64")
-            return xo, fo, ne, rounds
-        import torch
-        dev = self._device_tables(tables, device)
-        # the grid and the point -> surface map rarely change between calls: their device copies are kept on the tables
-        # object, keyed by content; the start points go up in one copy, the results come back in one
-        cache = tables.__dict__.setdefault("_refine_inputs", {})
-        key = (_device_key(device), th.tobytes(), ps.tobytes())
-        if key not in cache:
-            cache.clear()
-            cache[key] = (torch.from_numpy(ps).to(device), torch.from_numpy(th).to(device))
-        d_ps, d_th = cache[key]
-        d_st = torch.from_numpy(st).to(device)
-        out = torch.empty((4 * n,), dtype=torch.float64, device=device)     # x_opt (2n) | f_opt (n) | n_evals (n int32 in n/2.. words)
-        xo, fo = out[:2 * n].view(n, 2), out[2 * n:3 * n]
-        ne = out[3 * n:].view(torch.int32)[:n]
-        self._stream_from_torch(out)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rounds = check(self._lib.ibs_refine_f64(*head, *[p(t) for t in dev[:7]], nr[0], p(dev[7]), nr[1], p(dev[8]),
-                                                float(tables.dn_mn), float(tables.dn_nyq), n, p(d_ps), p(d_st), len(th),
-                                                p(d_th), *tail, p(xo), p(fo), p(ne), MEM_DEVICE), "ibs_refine_f64")
-        h = out.cpu()
-        return (h[:2 * n].view(n, 2).numpy(), h[2 * n:3 * n].numpy(), h[3 * n:].view(torch.int32)[:n].numpy().copy(), rounds)
+        ar = _Args(self, device=device, host=device is None)
+        if device is not None:
+            # the grid and the point -> surface map rarely change between calls: their device copies are kept on the tables
+            # object, keyed by content; the start points go up in one copy, the results come back in one
+            import torch
+            cache = tables.__dict__.setdefault("_refine_inputs", {})
+            key = (_device_key(device), th.tobytes(), ps.tobytes())
+            if key not in cache:
+                cache.clear()
+                cache[key] = (torch.from_numpy(ps).to(device), torch.from_numpy(th).to(device))
+            ps, th = cache[key]
+        out, rounds = self._refine(ar, tables, n, ps, st, len(th), th, del_alpha, maxiter, ftol, gtol)
+        xo, fo, ne = _refine_views(out if device is None else out.cpu(), n)
+        return (xo, fo, ne, rounds) if device is None else (xo.numpy(), fo.numpy(), ne.numpy().copy(), rounds)
 
     def refine_device(self, tables, d_pt_surf, d_start, d_theta, del_alpha=0.004, maxiter=30, ftol=5.0e-11, gtol=2.0e-8):
         """refine() on device tensors, results left in HBM: d_pt_surf (n,) int32, d_start (n, 2), d_theta (N,) float64.
         Returns (x_opt (n, 2), f_opt (n,) = -gam, n_evals (n,) int32, rounds); the tensors are stream-ordered on the
         current torch stream (include/ibs.h: ibs_refine_f64 with device pointers)."""
-        import torch
-        device = d_start.device
         n = int(d_pt_surf.shape[0])
-        dev = self._device_tables(tables, device)
-        nr = (len(tables.rows_mn), len(tables.rows_nyq))
-        out = torch.empty((4 * n,), dtype=torch.float64, device=device)     # x_opt (2n) | f_opt (n) | n_evals (n int32 in n/2.. words)
-        xo, fo = out[:2 * n].view(n, 2), out[2 * n:3 * n]
-        ne = out[3 * n:].view(torch.int32)[:n]
-        self._stream_from_torch(out)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rounds = check(self._lib.ibs_refine_f64(self._h, len(tables.s), len(tables.xm), len(tables.xm_nyq),
-                                                *[p(t) for t in dev[:7]], nr[0], p(dev[7]), nr[1], p(dev[8]),
-                                                float(tables.dn_mn), float(tables.dn_nyq), n, p(d_pt_surf), p(d_start),
-                                                int(d_theta.shape[0]), p(d_theta), float(del_alpha), int(maxiter), float(ftol),
-                                                float(gtol), p(xo), p(fo), p(ne), MEM_DEVICE), "ibs_refine_f64")
-        self._keep_refine = (d_pt_surf, d_start, d_theta, out)
-        return xo, fo, ne, rounds
+        out, rounds = self._refine(_Args(self, device=d_start.device), tables, n, d_pt_surf, d_start, int(d_theta.shape[0]), d_theta,
+                                   del_alpha, maxiter, ftol, gtol)
+        return (*_refine_views(out, n), rounds)
 
     def refine_stats(self):
         """(evaluations, forward sweeps, rounds needed, rounds enqueued) of the last refine() call of this context"""
@@ -939,16 +701,10 @@ class Context:
     def hf_grad(self, X, dX, f, g_p, c_p, f_p, gam):
         """Hellmann-Feynman d(gam)/dp for caller-built tangents (utils.py:1676-1680, 1721-1725).
         X, dX, f, g_p, c_p, f_p: (n_sys, N); gam: (n_sys,) -> jac (n_sys,)"""
-        ar = _Args()
+        ar = _Args(self)
         n_sys, N = X.shape
-        ptrs = [ar.inp(a) for a in (X, dX, f, g_p, c_p, f_p)]
-        pgam = ar.inp(gam)
-        ref = X if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        jac, pjac = ar.out((n_sys,), ref)
-        check(self._lib.ibs_hf_grad_f64(self._h, n_sys, N, *ptrs, N, pgam, pjac, ar.mem), "ibs_hf_grad_f64")
-        return jac
+        ar.call("ibs_hf_grad_f64", n_sys, N, *[ar.inp(a) for a in (X, dX, f, g_p, c_p, f_p)], N, ar.inp(gam), ar.out("jac", (n_sys,)))
+        return ar.outs["jac"]
 
     def sturm_count(self, h, g, c, f, shift, exact=False):
         """eigenvalues of (T, F) above shift[i] per system (ibs_sturm_count_f64).  exact=True: the division-form kernel (lanes as
@@ -961,55 +717,33 @@ class Context:
                 return self.sturm_count(h, g, c, f, shift)
             finally:
                 self.set_option("sturm_form", None)
-        ar = _Args()
+        ar = _Args(self)
         n_sys, N = g.shape
-        pg, pc, pf, ps = ar.inp(g), ar.inp(c), ar.inp(f), ar.inp(shift)
-        ref = g if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        cnt, pcnt = ar.out((n_sys,), ref, dtype=np.int32)
-        check(self._lib.ibs_sturm_count_f64(self._h, n_sys, N, float(h), pg, pc, pf, N, ps, pcnt, ar.mem),
-              "ibs_sturm_count_f64")
-        return cnt
+        ar.call("ibs_sturm_count_f64", n_sys, N, float(h), ar.inp(g), ar.inp(c), ar.inp(f), N, ar.inp(shift), ar.out("count", (n_sys,), _I32))
+        return ar.outs["count"]
 
     # ---- geometry-fed Sturm count, count-pair certificate and re-close (ibs_certify.hip) ------
-    def _geo_inputs(self, ar, geo7, dPdrho, theta0, points):
-        n_lines, N = geo7[0].shape
-        n_t0 = 1 if points else int(theta0.shape[0])
-        if points and int(theta0.shape[0]) != n_lines:
-            raise IbsError("theta0 must hold one value per point (%d), got %d" % (n_lines, int(theta0.shape[0])))
-        ptrs = [ar.inp(a) for a in geo7]
-        pdP, pt0 = ar.inp(dPdrho), ar.inp(theta0)
-        ref = geo7[0] if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        return n_lines, n_t0, N, ptrs, pdP, pt0, ref
-
     def geo_sturm_count(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, shift=0.0):
         """eigenvalues above shift for every (line, theta0) of a geometry-fed scan (ibs_geo_sturm_count_f64: the number of unstable
         modes at shift 0, bishop_ball_s-alpha.py:110-115 for real field lines).  Arrays as in gamma_scan; shift a scalar or
         (n_lines, n_theta0).  Returns int32 (n_lines, n_theta0).  Even N is accepted."""
-        ar = _Args()
-        n_lines, n_t0, N, ptrs, pdP, pt0, ref = self._geo_inputs(ar, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho,
-                                                                 theta0, False)
-        ps = self._sigma_rows(ar, shift, (n_lines, n_t0), ref)
-        cnt, pcnt = ar.out((n_lines, n_t0), ref, dtype=np.int32)
-        check(self._lib.ibs_geo_sturm_count_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, ps, pcnt, ar.mem),
-              "ibs_geo_sturm_count_f64")
-        return cnt
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0)
+        ar.call("ibs_geo_sturm_count_f64", *head, ar.rows(shift, shape), ar.out("count", shape, _I32))
+        return ar.outs["count"]
+
+    @staticmethod
+    def _one_theta0_per_point(points, geo7, theta0):
+        if points and int(theta0.shape[0]) != geo7[0].shape[0]:
+            raise IbsError("theta0 must hold one value per point (%d), got %d" % (geo7[0].shape[0], int(theta0.shape[0])))
 
     def _certify(self, points, h, geo7, dPdrho, theta0, lam, tol_factor):
-        ar = _Args()
-        n_lines, n_t0, N, ptrs, pdP, pt0, ref = self._geo_inputs(ar, geo7, dPdrho, theta0, points)
-        plam = ar.inp(lam)
-        cert, pcert = ar.out((n_lines,) if points else (n_lines, n_t0), ref, dtype=np.int32)
-        if points:
-            check(self._lib.ibs_gamma_points_certify_f64(self._h, n_lines, N, float(h), *ptrs, N, pdP, pt0, plam, float(tol_factor),
-                                                         pcert, ar.mem), "ibs_gamma_points_certify_f64")
-        else:
-            check(self._lib.ibs_gamma_scan_certify_f64(self._h, n_lines, n_t0, N, float(h), *ptrs, N, pdP, pt0, plam,
-                                                       float(tol_factor), pcert, ar.mem), "ibs_gamma_scan_certify_f64")
-        return cert
+        self._one_theta0_per_point(points, geo7, theta0)
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, geo7, dPdrho, theta0, points)
+        ar.call("ibs_gamma_points_certify_f64" if points else "ibs_gamma_scan_certify_f64", *head, ar.inp(lam), float(tol_factor),
+                ar.out("cert", shape, _I32))
+        return ar.outs["cert"]
 
     def certify_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, lam, tol_factor=0.0):
         """count-pair certificate of the eigenvalues lam (n_lines, n_theta0) of a geometry-fed scan (ibs_gamma_scan_certify_f64): with
@@ -1023,28 +757,12 @@ class Context:
         return self._certify(True, h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0, lam, tol_factor)
 
     def _reclose(self, points, h, geo7, dPdrho, theta0, cert, lam, gam, X, dX, tol_factor):
-        ar = _Args()
-        n_lines, n_t0, N, ptrs, pdP, pt0, ref = self._geo_inputs(ar, geo7, dPdrho, theta0, points)
-        # in-out arrays: updated in place, so they must already be what the library reads
-        io = []
-        for name, a, dt in (("cert", cert, np.int32), ("lam", lam, np.float64), ("gam", gam, np.float64), ("X", X, np.float64),
-                            ("dX", dX, np.float64)):
-            if a is None:
-                if name in ("X", "dX"):
-                    io.append(C.c_void_p(None))
-                    continue
-                raise IbsError("reclose: %s is required" % name)
-            if _is_torch(a):
-                ok = a.is_cuda and a.is_contiguous() and a.dtype == ar._torch_dtype()[np.dtype(dt)]
-            else:
-                ok = isinstance(a, np.ndarray) and a.flags.c_contiguous and a.flags.writeable and a.dtype == np.dtype(dt)
-            if not ok:
-                raise IbsError("reclose: %s is updated in place and must be a contiguous %s array" % (name, np.dtype(dt).name))
-            io.append(ar.inp(a, dtype=dt))
-        fn = self._lib.ibs_gamma_points_reclose_f64 if points else self._lib.ibs_gamma_scan_reclose_f64
-        dims = (n_lines,) if points else (n_lines, n_t0)
-        return check(fn(self._h, *dims, N, float(h), *ptrs, N, pdP, pt0, float(tol_factor), *io, ar.mem),
-                     "ibs_gamma_points_reclose_f64" if points else "ibs_gamma_scan_reclose_f64")
+        self._one_theta0_per_point(points, geo7, theta0)
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, geo7, dPdrho, theta0, points)
+        return ar.call("ibs_gamma_points_reclose_f64" if points else "ibs_gamma_scan_reclose_f64", *head, float(tol_factor),
+                       ar.inout("reclose", "cert", cert, _I32), ar.inout("reclose", "lam", lam, _F64), ar.inout("reclose", "gam", gam, _F64),
+                       ar.inout("reclose", "X", X, _F64, optional=True), ar.inout("reclose", "dX", dX, _F64, optional=True))
 
     def reclose_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, cert, lam, gam, X=None, dX=None,
                      tol_factor=0.0):
@@ -1065,29 +783,20 @@ class Context:
     def surface_argmax_pack(self, gam):
         """gam: device tensor (n_surf, n_per_surf) -> pack (n_surf, 2) = (max, first row-major index) on the device
         (ibs_surface_argmax_pack_f64; ball_scan.py:283-288), the input of scan_starts."""
-        import torch
+        ar = _Args(self)
         n_surf, n_per = gam.shape
-        if not (_is_torch(gam) and gam.is_cuda):
+        pgam = ar.inp(gam)
+        if ar.mem != MEM_DEVICE:
             raise IbsError("surface_argmax_pack takes a device tensor")
-        gam = gam.to(torch.float64).contiguous()
-        self._stream_from_torch(gam)
-        pack = torch.empty((n_surf, 2), dtype=torch.float64, device=gam.device)
-        check(self._lib.ibs_surface_argmax_pack_f64(self._h, n_surf, n_per, C.c_void_p(gam.data_ptr()), C.c_void_p(pack.data_ptr())),
-              "ibs_surface_argmax_pack_f64")
-        return pack
+        ar.call("ibs_surface_argmax_pack_f64", n_surf, n_per, pgam, ar.out("pack", (n_surf, 2)), mem=False)
+        return ar.outs["pack"]
 
     def surface_argmax(self, gam):
         """gam: (n_surf, n_per_surf) -> (idx int32 (n_surf,), val (n_surf,)); first index on ties (ball_scan.py:283-288)."""
-        ar = _Args()
+        ar = _Args(self)
         n_surf, n_per = gam.shape
-        pg = ar.inp(gam)
-        ref = gam if ar.mem == MEM_DEVICE else None
-        if ref is not None:
-            self._stream_from_torch(ref)
-        idx, pidx = ar.out((n_surf,), ref, dtype=np.int32)
-        val, pval = ar.out((n_surf,), ref)
-        check(self._lib.ibs_surface_argmax_f64(self._h, n_surf, n_per, pg, pidx, pval, ar.mem), "ibs_surface_argmax_f64")
-        return idx, val
+        ar.call("ibs_surface_argmax_f64", n_surf, n_per, ar.inp(gam), ar.out("idx", (n_surf,), _I32), ar.out("val", (n_surf,)))
+        return ar.outs["idx"], ar.outs["val"]
 
 
 _DEFAULT = {}

@@ -29,6 +29,50 @@ def test_library_exports_every_declared_symbol():
     assert set(names) == set(_lib.SYMBOLS), set(names) ^ set(_lib.SYMBOLS)
 
 
+def header_prototypes():
+    """{symbol: (return type, [argument type, ...])} of every prototype of include/ibs.h, the types as written less the name"""
+    txt = open(os.path.join(ROOT, "include", "ibs.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s]*?[\w*])\s*\b(ibs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        args = " ".join(args.split())
+        types = []
+        for a in ([] if args in ("", "void") else args.split(",")):
+            a = a.strip()
+            if not a.endswith("*"):
+                a = re.sub(r"\b\w+$", "", a).strip()            # drop the parameter's name
+            types.append(a.replace(" *", "*"))
+        protos[name] = (" ".join(ret.split()).replace(" *", "*"), types)
+    return protos
+
+
+SCALARS = {"int": (ctypes.c_int, ctypes.c_int32), "int32_t": (ctypes.c_int32, ctypes.c_int), "int64_t": (ctypes.c_int64,),
+           "double": (ctypes.c_double,), "float": (ctypes.c_float,)}
+
+
+def test_signature_table_matches_the_header():
+    """_lib.SYMBOLS, kept by hand, against the prototypes: argument count, kind and width of every argument, return type"""
+    protos = header_prototypes()
+    assert set(protos) == set(_lib.SYMBOLS) == set(header_symbols())
+    assert len(protos) >= 55
+    for name, (ret, types) in sorted(protos.items()):
+        res, argtypes = _lib.SYMBOLS[name]
+        assert (ret, res) == (("const char*", ctypes.c_char_p) if name == "ibs_last_error" else ("int", ctypes.c_int)), name
+        assert len(types) == len(argtypes), (name, types, argtypes)
+        for k, (t, a) in enumerate(zip(types, argtypes)):
+            if t == "const char*":
+                assert a is ctypes.c_char_p, (name, k, t, a)
+                continue
+            t = re.sub(r"^const\s+", "", t)
+            if t in SCALARS:
+                assert a in SCALARS[t], (name, k, t, a)
+            else:               # any other pointer (a writable char* may be a c_char_p as well: ibs_last_launch's name buffer)
+                assert t.endswith("*"), (name, k, t)
+                assert a is ctypes.c_void_p or issubclass(a, ctypes._Pointer) or (t == "char*" and a is ctypes.c_char_p), (name, k, t, a)
+    assert ctypes.sizeof(ctypes.c_int) == 4
+
+
 def test_version_and_error_string():
     lib = _lib.lib()
     assert lib.ibs_version() >= 100
