@@ -17,7 +17,7 @@ import warnings
 
 import torch
 
-from .solver import IbsError, VjpStatusWarning, default_context, vjp_status_message
+from .solver import CLUSTER_BIT, IbsError, VjpStatusWarning, default_context, vjp_status_message
 
 _MODES = ("max", "nearest")
 
@@ -59,6 +59,53 @@ def solve_gcf(h, g, c, f, eigenpair="max", sigma=None, ctx=None):
     the eigenpair is locally constant in sigma (no gradient)."""
     _check_mode(eigenpair, sigma)
     return _SolveGcf.apply(float(h), g, c, f, eigenpair, sigma, ctx or default_context(g.device.index or 0))
+
+
+class _SolveGcfModes(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, h, g, c, f, n_modes, ictx):
+        r = ictx.solve_gcf_modes(h, g, c, f, n_modes, want_X=True, want_info=True)
+        fctx.save_for_backward(g, c, f, r["lam"], r["X"], ((r["info"] >> 16) & CLUSTER_BIT).ne(0))
+        fctx.h, fctx.ictx = h, ictx
+        return r["gam"], r["lam"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gam_bar, lam_bar):
+        g, c, f, lam, X, cluster = fctx.saved_tensors
+        active = gam_bar.ne(0) | lam_bar.ne(0)                    # (n_sys, n_modes): the pairs the cotangent reaches
+        rows = [torch.zeros_like(g), torch.zeros_like(c), torch.zeros_like(f)]
+        flags = [(active & cluster).any(1).sum()]
+        # (the VJP of an active mode runs on all systems, those with a clustered or untouched pair included: their rows and status
+        # words are masked out below, which is cheaper than gathering the systems of every mode)
+        for m in [m for m, on in enumerate(active.any(0).tolist()) if on]:
+            r = fctx.ictx.solve_gcf_vjp(fctx.h, g, c, f, lam[:, m].contiguous(), X[:, m].contiguous(), gam_bar=gam_bar[:, m].contiguous(),
+                                        lam_bar=lam_bar[:, m].contiguous(), want_info=True)
+            use = (active[:, m] & ~cluster[:, m])[:, None]        # (a clustered pair with a zero cotangent contributes nothing)
+            for acc, k in zip(rows, ("g_bar", "c_bar", "f_bar")):
+                acc += torch.where(use, r[k], torch.zeros_like(acc))
+            st = ((r["info"] >> 16) & 3) * use[:, 0]
+            flags += [(st & 1).ne(0).sum(), (st & 2).ne(0).sum()]
+        refused = (active & cluster).any(1)[:, None]              # the derivative of one member of a cluster does not exist
+        rows = [torch.where(refused, torch.full_like(a, float("nan")), a) for a in rows]
+        n = torch.stack(flags).tolist()                           # (one host synchronisation)
+        n_cluster, n_pivot, n_bad = n[0], sum(n[1::2]), sum(n[2::2])
+        parts = [vjp_status_message(n_pivot, n_bad)] if n_pivot or n_bad else []
+        if n_cluster:
+            parts.append("solve_gcf_modes: %d system(s) with a cotangent on a clustered mode (status bit 9: one member of a cluster has "
+                         "no derivative of its own, NaN rows)" % n_cluster)
+        if parts:
+            warnings.warn("; ".join(parts), VjpStatusWarning, stacklevel=2)
+        return None, rows[0], rows[1], rows[2], None, None
+
+
+def solve_gcf_modes(h, g, c, f, n_modes, ctx=None):
+    """(gam, lam), each (n_sys, n_modes), of the n_modes largest eigenpairs of the raw systems g, c, f (n_sys, N), mode 0 = lam_max's
+    (Context.solve_gcf_modes).  Differentiable in g, c and f: the backward is one Context.solve_gcf_vjp per mode the cotangent
+    reaches, on that mode's (lam, X) and cotangent columns, summed.  A clustered mode (status bit 9: a neighbouring eigenvalue within
+    4 N eps ||A||) has no derivative of its own: with a non-zero cotangent the system's rows are NaN and a VjpStatusWarning is issued;
+    with a zero cotangent it contributes nothing."""
+    return _SolveGcfModes.apply(float(h), g, c, f, int(n_modes), ctx or default_context(g.device.index or 0))
 
 
 class _MarginalScale(torch.autograd.Function):

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <string>
 #include <vector>
@@ -887,6 +888,38 @@ int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, 
   });
 }
 
+// ---- spectrum mode: the n_modes largest eigenpairs of every system (ibs_modes.hip)
+// the persistent grid of long_waves() with its workspace in ctx->long_ws (modes_ws_doubles(N) per wave)
+static int check_n_modes(int32_t n_modes) {
+  if (n_modes < 1 || n_modes > ibs::kMaxModes) return fail(IBS_ERR_ARG, "n_modes=%d outside [1, %d]", n_modes, ibs::kMaxModes);
+  return 0;
+}
+int ibs_solve_gcf_modes_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh, const double* c,
+                            const double* f, int64_t ld, int32_t n_modes, double* lam, double* gam, double* X, double* dX,
+                            int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_sys < 0 || !g || !c || !f || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_sys=%lld ld=%lld N=%d)", (long long)n_sys, (long long)ld, N);
+  if (int r = check_n_modes(n_modes)) return r;
+  if (!lam && !gam && !X && !dX && !info) return fail(IBS_ERR_ARG, "no output requested (lam, gam, X, dX and info are all null)");
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_sys == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t in_elems = (size_t)n_sys * ld, n_out = (size_t)n_sys * n_modes, out_elems = n_out * N;
+  ibs::ModesArgs a{};
+  a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.n_modes = n_modes;
+  auto decl = [&](Stage& s) {
+    a.g = s.in(g, in_elems); a.c = s.in(c, in_elems); a.f = s.in(f, in_elems); a.gh = s.in(gh, in_elems);
+    a.lam = s.out(lam, n_out); a.gam = s.out(gam, n_out); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
+    a.info = s.status(info, n_out);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, a.n_sys, ibs::modes_ws_doubles(N))) return r;
+    HIPCHK(ibs::launch_gcf_modes(a, ctx->stream));
+    return 0;
+  });
+}
+
 // ---- exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip)
 // the persistent grid of long_waves() with its workspace in ctx->long_ws (vjp_ws_doubles(N) per wave)
 int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c, const double* f,
@@ -1030,19 +1063,21 @@ int ibs_marginal_obj_w_grad_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, 
   });
 }
 
-// Coarse scan with the nearest eigenpair: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
-// arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and solved by k_solve_gcf_nearest; chunks are
-// bounded by kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".
+// Scans that solve the assembled rows: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
+// arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and handed to solve(first system, systems, G, C, F,
+// work, work_doubles, waves) -- a one-wave-per-system kernel with ws_per_wave doubles of workspace per wave; chunks are bounded by
+// kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".
 static constexpr size_t kNearestScanBytes = size_t(1) << 30;
-static int scan_nearest_device(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const geo7[7],
-                               int64_t ld, const double* dPdrho, const double* theta0, const double* sigma, double* gam,
-                               double* lam, int32_t* idx, int32_t* info) {
+using ScanChunkSolve = std::function<int(long, long, double*, double*, double*, double*, size_t, long)>;
+static int scan_rows_chunked(ibs_ctx* ctx, const char* what, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
+                             const double* const geo7[7], int64_t ld, const double* dPdrho, const double* theta0, size_t ws_per_wave,
+                             const ScanChunkSolve& solve) {
   int nw = 0;
   double *work, *G, *C, *F;
   auto carve = [&](Carve& cv, long L) {          // ctx->long_ws of a chunk of L lines
     const long S = L * n_theta0;
     nw = long_waves(ctx, S);
-    work = cv.take<double>((size_t)nw * ibs::nearest_ws_doubles(N));
+    work = cv.take<double>((size_t)nw * ws_per_wave);
     G = cv.take<double>((size_t)S * N); C = cv.take<double>((size_t)S * N); F = cv.take<double>((size_t)S * N);
   };
   auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
@@ -1054,28 +1089,38 @@ static int scan_nearest_device(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
   const size_t bytes = bytes_of(L);
   if (ensure_long_ws(ctx, bytes) != 0) {
     (void)hipGetLastError();
-    return fail(IBS_ERR_HIP, "gamma_scan_nearest: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
-                "which could not be allocated", L, n_theta0, N, bytes);
+    return fail(IBS_ERR_HIP, "%s: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
+                "which could not be allocated", what, L, n_theta0, N, bytes);
   }
   Carve cv{static_cast<char*>(ctx->long_ws)};
   carve(cv, L);
   for (long l0 = 0; l0 < n_lines; l0 += L) {
     const int Lc = (int)(n_lines - l0 < L ? n_lines - l0 : L);
-    const long s0 = l0 * n_theta0, S = (long)Lc * n_theta0;
     ibs::ScanArgs<double> sa{};
     sa.n_lines = Lc; sa.n_theta0 = n_theta0; sa.N = N; sa.h = h; sa.ld = ld; sa.t0_stride = 0;
     sa.bmag = geo7[0] + l0 * ld; sa.gradpar = geo7[1] + l0 * ld; sa.cvdrift = geo7[2] + l0 * ld; sa.cvdrift0 = geo7[3] + l0 * ld;
     sa.gds2 = geo7[4] + l0 * ld; sa.gds21 = geo7[5] + l0 * ld; sa.gds22 = geo7[6] + l0 * ld;
     sa.dPdrho = dPdrho + l0; sa.theta0 = theta0;
     HIPCHK(ibs::launch_assemble_long(sa, G, C, F, nullptr, nullptr, nullptr, ctx->stream));
+    if (int r = solve(l0 * n_theta0, (long)Lc * n_theta0, G, C, F, work, (size_t)nw * ws_per_wave, (long)nw)) return r;
+  }
+  return 0;
+}
+
+// coarse scan with the nearest eigenpair: the chunks are solved by k_solve_gcf_nearest
+static int scan_nearest_device(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const geo7[7],
+                               int64_t ld, const double* dPdrho, const double* theta0, const double* sigma, double* gam,
+                               double* lam, int32_t* idx, int32_t* info) {
+  return scan_rows_chunked(ctx, "gamma_scan_nearest", n_lines, n_theta0, N, h, geo7, ld, dPdrho, theta0, ibs::nearest_ws_doubles(N),
+                           [&](long s0, long S, double* G, double* C, double* F, double* work, size_t work_doubles, long nw) -> int {
     ibs::NearestArgs a{};
     a.n_sys = S; a.N = N; a.h = h; a.g = G; a.c = C; a.f = F; a.gh = nullptr; a.ld = N; a.sigma = sigma + s0;
     a.lam = lam ? lam + s0 : nullptr; a.idx = idx ? idx + s0 : nullptr; a.gam = gam ? gam + s0 : nullptr; a.X = nullptr; a.dX = nullptr;
     a.info = info ? info + s0 : nullptr;
-    a.work = work; a.work_doubles = (size_t)nw * ibs::nearest_ws_doubles(N); a.n_waves = nw;
+    a.work = work; a.work_doubles = work_doubles; a.n_waves = nw;
     HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
-  }
-  return 0;
+    return 0;
+  });
 }
 
 int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
@@ -1102,6 +1147,45 @@ int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
   };
   return staged(ctx, mem, decl,
                 [&] { return scan_nearest_device(ctx, n_lines, n_theta0, N, h, geo7, ld, dP, t0, sig, dgam, dlam, didx, dinfo); });
+}
+
+// the n_modes largest eigenvalues and growth rates of every (line, theta0): the chunks of scan_rows_chunked solved by k_solve_gcf_modes
+int ibs_gamma_scan_modes_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
+                             const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
+                             const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                             const double* dPdrho, const double* theta0, int32_t n_modes, double* gam, double* lam,
+                             int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_lines < 0 || n_theta0 < 0 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho ||
+      !theta0 || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  if (int r = check_n_modes(n_modes)) return r;
+  if (!gam && !lam && !info) return fail(IBS_ERR_ARG, "no output requested (gam, lam and info are all null)");
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  const size_t n_out = (size_t)n_lines * n_theta0 * n_modes, in_elems = (size_t)n_lines * ld;
+  const double *geo7[7], *dP, *t0;
+  double *dgam, *dlam;
+  int* dinfo;
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) geo7[k] = s.in(src[k], in_elems);
+    dP = s.in(dPdrho, n_lines); t0 = s.in(theta0, n_theta0);
+    dgam = s.out(gam, n_out); dlam = s.out(lam, n_out); dinfo = s.status(info, n_out);
+  };
+  return staged(ctx, mem, decl, [&] {
+    return scan_rows_chunked(ctx, "gamma_scan_modes", n_lines, n_theta0, N, h, geo7, ld, dP, t0, ibs::modes_ws_doubles(N),
+                             [&](long s0, long S, double* G, double* C, double* F, double* work, size_t work_doubles, long nw) -> int {
+      const long o = s0 * n_modes;
+      ibs::ModesArgs a{};
+      a.n_sys = S; a.N = N; a.h = h; a.g = G; a.c = C; a.f = F; a.gh = nullptr; a.ld = N; a.n_modes = n_modes;
+      a.lam = dlam ? dlam + o : nullptr; a.gam = dgam ? dgam + o : nullptr; a.info = dinfo ? dinfo + o : nullptr;
+      a.work = work; a.work_doubles = work_doubles; a.n_waves = nw;
+      HIPCHK(ibs::launch_gcf_modes(a, ctx->stream));
+      return 0;
+    });
+  });
 }
 
 // ---- geometry-fed points with the eigenpair nearest sigma[p] (ibs_nearest_grad.hip): the refinement's objective + gradient and

@@ -75,6 +75,17 @@ struct NearestArgs {
   double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
 };
 hipError_t launch_gcf_nearest(const NearestArgs& a, hipStream_t st);
+// the n_modes largest eigenpairs (ibs_modes.hip), FP64, any N in [66, kMaxLongN], 1 <= n_modes <= kMaxModes: one wave per system on the
+// same persistent grid.  Per-wave workspace, in this order: the eigenvector stage's nearest_ws_doubles(N), kMaxModes closed
+// eigenvalues, kMaxModes status words (ints, in kMaxModes doubles of room).  Outputs [n_sys][n_modes] (X, dX: [n_sys][n_modes][N])
+constexpr size_t modes_ws_doubles(int N) { return nearest_ws_doubles(N) + 2 * (size_t)kMaxModes; }
+struct ModesArgs {
+  long n_sys; int N; double h;
+  const double *g, *c, *f, *gh; long ld; int n_modes;            // gh: null = mean of neighbouring g
+  double *lam, *gam, *X, *dX; int* info;                          // each optional
+  double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
+};
+hipError_t launch_gcf_modes(const ModesArgs& a, hipStream_t st);
 // exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip), FP64, any N in [66, kMaxLongN]: one wave per
 // system, persistent grid of min(n_sys, n_waves) waves, each with vjp_ws_doubles(N) doubles of workspace at work + wave * vjp_ws_doubles(N)
 constexpr size_t vjp_ws_doubles(int N) { return 3 * (size_t)N; }

@@ -25,6 +25,7 @@ namespace ibs {
 
 constexpr int kMaxM = 32;   // rows per lane: N - 2 <= 64 * kMaxM  (N <= 2050)
 constexpr int kMaxLongN = 65537;   // longer grids, up to this many points, run on the generic division-form path (ibs_long.hip)
+constexpr int kMaxModes = 16;      // eigenpairs per system of the spectrum mode (ibs_modes.hpp, ibs_modes.hip)
 
 // LDS rows of the wave kernels are padded by one element per 8 (element j lives at j + (j >> 3)): a lane reads a
 // contiguous chunk of ~M rows, i.e. lanes are M elements apart, and for even M (8 at N = 513) an unpadded row

@@ -14,6 +14,7 @@ around the reference's own utils.vmec_fieldlines (ball_scan.py:251-261).
 import numpy as np
 
 from ._lib import IbsError
+from .solver import CLUSTER_BIT
 
 GEO_ORDER = ("bmag", "gradpar_theta_pest", "cvdrift", "cvdrift0", "gds2", "gds21", "gds22", "gbdrift")
 
@@ -251,6 +252,37 @@ class BallooningScan:
         dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
         cnt = self.ctx.geo_sturm_count(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan, shift)
         return np.asarray(cnt).reshape(len(self.own), na, nt)
+
+    # -- the top of the spectrum on the coarse grid of the surfaces this rank owns, one launch
+    def modes(self, n_modes):
+        """the n_modes largest eigenvalues and their growth rates of every (alpha, theta0) of the coarse grid (Context.gamma_scan_modes,
+        1 <= n_modes <= 16): dict(lam, gam, cluster), each (n_own, nalpha, ntheta0, n_modes), mode 0 = lam_max's; cluster (bool): a
+        neighbouring eigenvalue lies within 4 N eps ||A|| -- lam holds, gam is the quotient of some vector of the cluster.  The modes
+        mode_count() counts: (lam > 0).sum(-1) == min(n_modes, mode_count()).  Flagged solves (status bits 0-1) raise IbsError."""
+        na, nt = len(self.alpha_scan), len(self.theta0_scan)
+        if not self.own:
+            z = np.zeros((0, na, nt, int(n_modes)))
+            return dict(lam=z, gam=z.copy(), cluster=z.astype(bool))
+        if self.tables is not None and self.device is not None:
+            import torch
+            r = self.ctx.fieldline_geometry(self.tables, np.repeat(self._own_surf(), na), np.tile(self.alpha_scan, len(self.own)),
+                                            self.theta, device=self.device)
+            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
+            out = self.ctx.gamma_scan_modes(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, n_modes, want_info=True)
+            out = {k: out[k].cpu().numpy() for k in ("lam", "gam", "info")}
+        else:
+            geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
+            dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
+            out = self.ctx.gamma_scan_modes(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan, n_modes,
+                                            want_info=True)
+        status = np.asarray(out["info"]) >> 16
+        nbad = int(((status & 3) != 0).sum())
+        if nbad:
+            raise IbsError("%d of %d modes of the coarse grid were flagged (status bits 0-1: iteration cap or invalid data)"
+                           % (nbad, status.size))
+        shape = (len(self.own), na, nt, -1)
+        return dict(lam=np.asarray(out["lam"]).reshape(shape), gam=np.asarray(out["gam"]).reshape(shape),
+                    cluster=((status & CLUSTER_BIT) != 0).reshape(shape))
 
     # -- marginal stability on the coarse grid of the surfaces this rank owns, one launch
     def marginal(self, refine=False, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, jac="reference"):

@@ -28,6 +28,10 @@ def vjp_status_message(n_pivot, n_bad):
 # pivot, bit 1 refused), i.e. status bits 6 and 7 of the info word
 EXACT_VJP_SHIFT = 16 + 6
 
+# spectrum mode (ibs_*_modes_f64): modes per system at most, and the informational status bit of a clustered mode (info >> 16)
+MAX_MODES = 16
+CLUSTER_BIT = 1 << 9
+
 
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
@@ -346,6 +350,32 @@ class Context:
                      ar.out("X", (n_sys, N), want=want_X), ar.out("dX", (n_sys, N), want=want_X), ar.out("info", (n_sys,), _I32, want_info))
         return ar.result(rc)
 
+    @staticmethod
+    def _n_modes(n_modes):
+        ok = isinstance(n_modes, (int, float, np.integer, np.floating)) and not isinstance(n_modes, bool)
+        if not ok or int(n_modes) != n_modes or not 1 <= n_modes <= MAX_MODES:
+            raise IbsError("n_modes must be an integer in [1, %d], not %r" % (MAX_MODES, n_modes))
+        return int(n_modes)
+
+    def solve_gcf_modes(self, h, g, c, f, n_modes, gh=None, want_X=False, want_info=False):
+        """the n_modes LARGEST eigenpairs of every system (ibs_solve_gcf_modes_f64), 1 <= n_modes <= 16: g, c, f (and gh, optional
+        half-grid g as in solve_gcf): (n_sys, N).  Returns dict(lam, gam[, X, dX][, info], nbad): lam, gam, info (n_sys, n_modes),
+        mode 0 = lam_max and the eigenvalues descending; X, dX (n_sys, n_modes, N), the entry of largest magnitude +1.  info
+        status bit 9 (CLUSTER_BIT, per mode, informational): a neighbouring eigenvalue lies within 4 N eps ||A|| -- lam holds, the
+        vector is some vector of the cluster's invariant subspace and gam its quotient."""
+        K = self._n_modes(n_modes)
+        if len(g.shape) != 2:
+            raise IbsError("solve_gcf_modes: g must be (n_sys, N), not %s" % (tuple(g.shape),))
+        n_sys, N = g.shape
+        for name, a in (("c", c), ("f", f), ("gh", gh)):
+            if a is not None and tuple(a.shape) != (n_sys, N):
+                raise IbsError("solve_gcf_modes: %s must be (%d, %d) like g, not %s" % (name, n_sys, N, tuple(a.shape)))
+        ar = _Args(self)
+        rc = ar.call("ibs_solve_gcf_modes_f64", n_sys, N, float(h), ar.inp(g), ar.inp(gh), ar.inp(c), ar.inp(f), N, K,
+                     ar.out("lam", (n_sys, K)), ar.out("gam", (n_sys, K)), ar.out("X", (n_sys, K, N), want=want_X),
+                     ar.out("dX", (n_sys, K, N), want=want_X), ar.out("info", (n_sys, K), _I32, want_info))
+        return ar.result(rc)
+
     def solve_gcf_vjp(self, h, g, c, f, lam, X, gam_bar=None, lam_bar=None, want_info=False):
         """exact vector-Jacobian product of gam and lam in the rows (ibs_solve_gcf_vjp_f64): g, c, f, X (n_sys, N), lam (n_sys,), the
         eigenpair any simple one of the rows (solve_gcf's or solve_gcf_nearest's); gam_bar, lam_bar (n_sys,) or scalars, either may be
@@ -433,6 +463,26 @@ class Context:
         head, shape, N = ar.geo(h, (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22), dPdrho, theta0)
         rc = ar.call("ibs_gamma_scan_nearest_f64", *head, ar.rows(sigma, shape), ar.out("gam", shape), ar.out("lam", shape),
                      ar.out("idx", shape, _I32), ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
+
+    def gamma_scan_modes(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, n_modes, want_info=False):
+        """the n_modes largest eigenvalues and growth rates of every (line, theta0) of a coarse scan (ibs_gamma_scan_modes_f64), arrays
+        as in gamma_scan, 1 <= n_modes <= 16.  Returns dict(gam, lam[, info], nbad) shaped (n_lines, n_theta0, n_modes), mode 0 =
+        lam_max; status bit 9 (CLUSTER_BIT) as in solve_gcf_modes.  No eigenfunctions."""
+        K = self._n_modes(n_modes)
+        geo7 = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        if len(bmag.shape) != 2:
+            raise IbsError("gamma_scan_modes: the seven geometry arrays must be (n_lines, N), not %s" % (tuple(bmag.shape),))
+        n_lines, N = bmag.shape
+        for a in geo7[1:]:
+            if tuple(a.shape) != (n_lines, N):
+                raise IbsError("gamma_scan_modes: the seven geometry arrays must all be (%d, %d), not %s" % (n_lines, N, tuple(a.shape)))
+        if tuple(dPdrho.shape) != (n_lines,) or len(theta0.shape) != 1:
+            raise IbsError("gamma_scan_modes: dPdrho must be (%d,) and theta0 (n_theta0,)" % n_lines)
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, geo7, dPdrho, theta0)
+        rc = ar.call("ibs_gamma_scan_modes_f64", *head, K, ar.out("gam", shape + (K,)), ar.out("lam", shape + (K,)),
+                     ar.out("info", shape + (K,), _I32, want_info))
         return ar.result(rc)
 
     # ---- geometry x theta0 scan ---------------------------------------------------------------

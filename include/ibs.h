@@ -44,6 +44,11 @@
  *            the line unstable -- scale = +inf, mu = 0, the derivatives are 0 and X, gam0 are NaN (informational: not counted by
  *            return values > 0).  ibs_marginal_obj_w_grad_f64 writes val = 0 and jac = dscale = 0 with it, and sets bit 1 with val
  *            and scale kept (jac = dscale = NaN) where the centre line solved but a side line of the alpha tangent held invalid data.
+ *     bit 9, spectrum-mode entry points (ibs_*_modes_f64) only, per mode: "clustered" -- a neighbouring eigenvalue (the mode before
+ *            or after it, or the first one not asked for) lies within tau = 4 N eps ||A||.  lam still holds to tau; the vector is
+ *            SOME vector of the cluster's invariant subspace (it satisfies the pencil to the residual bound of ibs_solve_gcf_vjp_f64
+ *            and is otherwise unspecified) and gam is that vector's quotient.  Informational: not counted by return values > 0.
+ *            The derivative of one member of a cluster does not exist: do not hand such a pair to ibs_solve_gcf_vjp_f64.
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
  *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
  *     for every sigma, lam_max's among them; they never set bit 4.
@@ -182,6 +187,18 @@ int ibs_solve_gcf_f32(ibs_ctx* ctx, int64_t n_sys, int32_t N, float h, const flo
 int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
                               const double* c, const double* f, int64_t ld, const double* sigma, double* lam,
                               int32_t* idx, double* gam, double* X, double* dX, int32_t* info, int32_t mem);
+/* Spectrum mode: the n_modes LARGEST eigenpairs of every system, 1 <= n_modes <= 16 (else IBS_ERR_ARG).  Nothing upstream corresponds
+ * (utils.py:1597 asks ARPACK for one pair); ibs_sturm_count_f64 says how many modes lie above a shift, this returns them.
+ * Arrays as in ibs_solve_gcf_nearest_f64 (gh may be NULL).  lam, gam, info [n_sys][n_modes]: mode 0 is lam_max's, the eigenvalues
+ * descend; X, dX [n_sys][n_modes][N], scaled so that the entry of largest magnitude is +1.  Every output is optional, at least one
+ * must be given.  FP64, any odd N in [66, 65537], one wavefront per system in division form (csrc/ibs_modes.hip): all n_modes
+ * brackets are closed by the SAME passes of 64 shifts (simultaneous multisection, csrc/ibs_modes.hpp: 10 passes for one mode, 15-17
+ * for eight, against 9-12 each one by one), |lam_m - lam_m(exact)| <= 4 N eps ||A||.  info: bits 0-15 = the passes of the system's
+ * multisection (the same in all its modes); status per mode: bit 0 (32 passes did not close the mode's bracket), bit 1 (invalid
+ * data: set on all modes of the system, every floating-point output NaN) and the informational bit 9 (clustered: conventions above). */
+int ibs_solve_gcf_modes_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
+                            const double* c, const double* f, int64_t ld, int32_t n_modes, double* lam, double* gam,
+                            double* X, double* dX, int32_t* info, int32_t mem);
 /* Exact vector-Jacobian product of gam (the FD4 / Simpson quotient of utils.py:1601-1621) and of lam with respect to the rows
  * (g, c, f) of raw systems on a uniform grid, the half-grid g the mean of neighbouring g (the systems of ibs_solve_gcf_f64).  Nothing
  * upstream corresponds: its only derivatives are the Hellmann-Feynman formulas of obj_w_grad (utils.py:1666-1725), which put gam in
@@ -210,6 +227,15 @@ int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
                                const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                                const double* dPdrho, const double* theta0, const double* sigma, double* gam, double* lam,
                                int32_t* idx, int32_t* info, int32_t mem);
+/* The n_modes largest eigenvalues and growth rates of every (line, theta0) of a coarse scan (ibs_solve_gcf_modes_f64 on the rows of
+ * ibs_gamma_scan_f64's arrays).  gam, lam, info [n_lines][n_theta0][n_modes], all optional, at least one given; no eigenfunctions.
+ * Rows of whole lines are assembled and solved chunk after chunk exactly as in ibs_gamma_scan_nearest_f64 (the same workspace bound
+ * of about 1 GiB, the same option "nearest_chunk_systems"); the chunking changes no bit of the results. */
+int ibs_gamma_scan_modes_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
+                             const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
+                             const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                             const double* dPdrho, const double* theta0, int32_t n_modes, double* gam, double* lam,
+                             int32_t* info, int32_t mem);
 /* ibs_obj_w_grad_f64 with the eigenpair nearest sigma[n_pts] (utils.py:1632-1728 as the refinement of ball_scan.py:305-314 runs it,
  * sigma = 1.3 |gam| + 0.05 of the surface's coarse maximum): geo, theta0, del_alpha, val and jac as in ibs_obj_w_grad_f64; lam,
  * idx and info [n_pts] optional (conventions above: status bits 1 (also: sigma not finite) and 5, idx).  FP64, any odd N in
