@@ -281,7 +281,7 @@ __device__ __forceinline__ void finish_chunk(WaveSolver<T, M, RES>& ws, Src& src
   T m = T(0);
 #pragma unroll
   for (int i = 0; i < M; ++i) m = xmax(m, xabs(x[i]));
-  m = uniform(wave_max(m));
+  if constexpr (RES) m = wave_max_l63(m); else m = uniform(wave_max(m));
   const T rm = T(1) / m;
 #pragma unroll
   for (int i = 0; i < M; ++i) x[i] *= rm;                                   // utils.py:1605 (v / max|v|)
@@ -342,11 +342,22 @@ __device__ __forceinline__ void finish_chunk(WaveSolver<T, M, RES>& ws, Src& src
     }
   }
   IBS_PROBE_AT(14);
-  y0 = wave_sum(y0); y1 = wave_sum(y1);
+  if constexpr (RES) {
+    // the sums of the stage in lock-step (wave_reduce_lockstep): each is the sum the lean form takes, bit for bit
+    if (HF && do_hf) {                                               // (wave-uniform)
+      T r[5] = {y0, y1, hc, hg, hf};
+      wave_reduce_lockstep<T, false, false, false, false, false>(r);
+      y0 = r[0]; y1 = r[1]; hc = r[2]; hg = r[3]; hf = r[4];
+    } else {
+      T r[2] = {y0, y1};
+      wave_reduce_lockstep<T, false, false>(r);
+      y0 = r[0]; y1 = r[1];
+    }
+  } else { y0 = wave_sum(y0); y1 = wave_sum(y1); }
   const T gam = y0 / y1;                                             // utils.py:1621 (the 1/3 of Simpson cancels)
   if constexpr (HF) {
     if (do_hf) {
-      hc = wave_sum(hc); hg = wave_sum(hg); hf = wave_sum(hf);
+      if constexpr (!RES) { hc = wave_sum(hc); hg = wave_sum(hg); hf = wave_sum(hf); }
       const T jac = hc / y1 - hg / y1 - gam * hf / y1;               // utils.py:1676-1680
       if (lane == 0) dth0_out[sys] = (TO)jac;
     }
@@ -1243,7 +1254,7 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
         best = take ? v[k] : best; bi = take ? i : bi;
       }
     }
-    wave_argmax_first(best, bi);
+    if constexpr (RES) wave_argmax_first_l63(best, bi); else wave_argmax_first(best, bi);
     if (lane == 0) {
       pack[2 * surf] = best; pack[2 * surf + 1] = (T)bi;
       // the counter's reset, for the next launch on this stream: behind the loads, whose waits would otherwise wait for it too

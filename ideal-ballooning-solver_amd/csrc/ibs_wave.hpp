@@ -257,6 +257,91 @@ __device__ __forceinline__ T uniform(T v) {  // value is already identical in al
   return readlane_t(v, 0);
 }
 
+// ---------------------------------------------------------------- reductions of the resident form (WaveSolver<T, M, true>)
+// The ladders above, for the kernel whose step time is the path of ONE wave: K reductions whose inputs are all ready advance
+// one ladder level at a time, so that within a level the K fetch-and-combine triples are independent and a triple never waits
+// (s_nop) for the step before it; and every step is the fetch plus one combine, nothing else.  Only lane 63 is read, and that
+// decides what a step may leave out.  Lane 63's tree: row_shr:1 reads lane 62; row_shr:2 lane 61; row_shr:4 lane 59; row_shr:8
+// lane 55 -- lane 16 r + i of row r then holds the partial of lanes 16 r .. 16 r + i for i = 1, 3, 7 after 1, 2, 3 steps, all of
+// them lanes with a source in every step they took -- then row_bcast:15 gives it lane 47 (the total of row 2) and row_bcast:31
+// lane 31 (by then the total of rows 0 and 1).  So
+//  * the value a lane WITHOUT a source receives is never part of lane 63's result: a max step fetches with the zero fill of
+//    bound_ctrl (dppz_t: no copy of v into the destination first) although 0 is no identity of max;
+//  * the two row_bcast steps write the rows that consume them and nothing else (dppu_t, as in scan_fwd_rows): no zero pair is
+//    set up for rows 0 / 2 and 0 / 1, which lane 63 never reads after that step;
+//  * a sum is wave_sum's sum bit for bit (same controls, same operand order, lane 63 adds the same partials), max is exact.
+// max_plain: ONE v_max.  The compiler's fmax first canonicalises an operand whose origin it cannot see (a DPP fetch is a move of
+// two integers) with a v_max x, x, x of its own, to quiet a signalling NaN.  No operand here can be one: every reduced value is
+// the result of arithmetic on this wave (fma, mul, max, |x|), which delivers quiet NaNs only, or a copy of such a result, or the
+// zero fill.  With quiet operands v_max is the fmax of above: the other operand if one is NaN.
+__device__ __forceinline__ double max_plain(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float max_plain(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
+template <bool... MAX>
+constexpr bool maxes_first() {
+  constexpr bool mx[sizeof...(MAX)] = {MAX...};
+  for (int k = 1; k < (int)sizeof...(MAX); ++k) if (mx[k] && !mx[k - 1]) return false;
+  return true;
+}
+// one ladder level of K reductions.  MAX...: the operation of each (true = max, false = sum), the maxes first.  The fetches of all
+// K stand in front of the combines of all K, and scheduling barriers keep the levels apart.
+// (A VGPR written by a VALU instruction may be read by a DPP fetch two wait states later at the earliest, by a v_readlane one.  The
+// compiler counts an asm statement's outputs among such writes: behind max_plain it places the s_nop itself where a lone ladder
+// needs one, and none where the other ladders' instructions fill the slots.)
+template <typename T, int CTRL, int ROWMASK, bool ROWS, bool... MAX>
+__device__ __forceinline__ void reduce_level(T (&v)[sizeof...(MAX)]) {
+  constexpr int K = sizeof...(MAX);
+  constexpr int n_max = (0 + ... + (MAX ? 1 : 0));
+  T f[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if constexpr (ROWS) f[k] = dppu_t<CTRL, ROWMASK>(v[k]); else f[k] = dppz_t<CTRL, ROWMASK>(v[k]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < n_max; ++k) v[k] = max_plain(v[k], f[k]);
+#pragma unroll
+  for (int k = n_max; k < K; ++k) v[k] += f[k];
+  __builtin_amdgcn_sched_barrier(0);
+}
+// K wave-wide reductions in lock-step: v[k] <- the sum or the maximum of v[k] over the wave, wave-uniform
+template <typename T, bool... MAX>
+__device__ __forceinline__ void wave_reduce_lockstep(T (&v)[sizeof...(MAX)]) {
+  constexpr int K = sizeof...(MAX);
+  static_assert(maxes_first<MAX...>(), "the maxes first");
+  __builtin_amdgcn_sched_barrier(0);
+  reduce_level<T, 0x111, 0xF, false, MAX...>(v);      // row_shr:1
+  reduce_level<T, 0x112, 0xF, false, MAX...>(v);      // row_shr:2
+  reduce_level<T, 0x114, 0xF, false, MAX...>(v);      // row_shr:4
+  reduce_level<T, 0x118, 0xF, false, MAX...>(v);      // row_shr:8
+  reduce_level<T, 0x142, 0xA, true, MAX...>(v);       // row_bcast:15 -> rows 1, 3
+  reduce_level<T, 0x143, 0xC, true, MAX...>(v);       // row_bcast:31 -> rows 2, 3
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = readlane_t(v[k], 63);
+}
+// the single ladders of the resident form
+template <typename T>
+__device__ __forceinline__ T wave_sum_l63(T v) { T r[1] = {v}; wave_reduce_lockstep<T, false>(r); return r[0]; }
+template <typename T>
+__device__ __forceinline__ T wave_max_l63(T v) { T r[1] = {v}; wave_reduce_lockstep<T, true>(r); return r[0]; }
+// wave_argmax_first for a caller that reads lane 63 only (the hand-off of the resident scan kernel): fetches that name no previous
+// value, so v and idx are not copied in front of every step.  A lane without a source meets the pair (0, 0) instead of its own;
+// no such lane is in lane 63's tree (above), and the winning pair keeps its bits as before.
+template <typename T>
+__device__ __forceinline__ void wave_argmax_first_l63(T& v, int& idx) {
+  auto meet = [&](T v2, int i2) {
+    const bool take = (v2 > v) | ((v2 == v) & (i2 < idx));      // (no short circuit: selects, not branches)
+    v = take ? v2 : v; idx = take ? i2 : idx;
+  };
+  meet(dppz_t<0x111, 0xF>(v), dppz_i<0x111, 0xF>(idx));
+  meet(dppz_t<0x112, 0xF>(v), dppz_i<0x112, 0xF>(idx));
+  meet(dppz_t<0x114, 0xF>(v), dppz_i<0x114, 0xF>(idx));
+  meet(dppz_t<0x118, 0xF>(v), dppz_i<0x118, 0xF>(idx));
+  meet(dppu_t<0x142, 0xA>(v), dppu_i<0x142, 0xA>(idx));
+  meet(dppu_t<0x143, 0xC>(v), dppu_i<0x143, 0xC>(idx));
+  v = readlane_t(v, 63); idx = readlane_i(idx, 63);
+}
+
 // ---------------------------------------------------------------- 2x2 transfer matrices with exponent
 template <typename T>
 struct M2 {
@@ -725,14 +810,31 @@ struct WaveSolver {
     // wave-level bounds:  lam_max <= max c/f (Gershgorin);  lam_max >= any Rayleigh quotient
     const T e0 = readlane_t(e_first, 0);
     const T en = readlane_t(e_lo, kWave - 1);
-    const T sc_all = wave_sum(sum_c), sf_all = wave_sum(sum_f);
-    normA = uniform(wave_max(vna));
-    hi = uniform(wave_max(vhi));
-    lo = uniform(xmax(wave_max(vlo), (sc_all - e0 - en) / sf_all));
+    T sc_all, sf_all, vlo_all;
+    [[maybe_unused]] T A, B, C;
+    if constexpr (RES) {
+      // every reduction of set-up has its input by now: one lock-step group (the values and their order of use are the lean form's)
+      if constexpr (TRIAL) {
+        T r[8] = {vna, vhi, vlo, sum_c, sum_f, tA, tB, tC};
+        wave_reduce_lockstep<T, true, true, true, false, false, false, false, false>(r);
+        normA = r[0]; hi = r[1]; vlo_all = r[2]; sc_all = r[3]; sf_all = r[4]; A = r[5]; B = r[6]; C = r[7];
+      } else {
+        T r[5] = {vna, vhi, vlo, sum_c, sum_f};
+        wave_reduce_lockstep<T, true, true, true, false, false>(r);
+        normA = r[0]; hi = r[1]; vlo_all = r[2]; sc_all = r[3]; sf_all = r[4];
+      }
+    } else {
+      sc_all = wave_sum(sum_c); sf_all = wave_sum(sum_f);
+      normA = uniform(wave_max(vna));
+      hi = uniform(wave_max(vhi));
+      vlo_all = wave_max(vlo);
+    }
+    const T rq_all = (sc_all - e0 - en) / sf_all;
+    if constexpr (RES) lo = uniform(max_plain(vlo_all, rq_all)); else lo = uniform(xmax(vlo_all, rq_all));
     hi += T(8) * Eps<T>::v * normA;
     lo -= T(8) * Eps<T>::v * normA;
     if constexpr (TRIAL) {
-      const T A = wave_sum(tA), B = wave_sum(tB), C = wave_sum(tC);
+      if constexpr (!RES) { A = wave_sum(tA); B = wave_sum(tB); C = wave_sum(tC); }
       const T rho = A / B;
       trial_rho = rho;
       trial_del = approx_sqrt(xmax(xfma(-rho, A, C), T(0)) / B);       // |r|^2 = x'T F^-1 T x - rho x'Tx  (rho = x'Tx / x'Fx)
@@ -960,10 +1062,10 @@ struct WaveSolver {
     int Lk;
     if constexpr (sizeof(T) == 8) {
       key = __hiloint2double(__double2hiint(key), (__double2loint(key) & ~63) | lane);
-      Lk = __double2loint(wave_max(key)) & 63;
+      if constexpr (RES) Lk = __double2loint(wave_max_l63(key)) & 63; else Lk = __double2loint(wave_max(key)) & 63;
     } else {
       key = __int_as_float((__float_as_int(key) & ~63) | lane);
-      Lk = __float_as_int(wave_max(key)) & 63;
+      if constexpr (RES) Lk = __float_as_int(wave_max_l63(key)) & 63; else Lk = __float_as_int(wave_max(key)) & 63;
     }
     const int ik = readlane_i(bi, Lk);
     T zu_k, zw_k, t_k, um1, wp1;
@@ -1053,7 +1155,10 @@ struct WaveSolver {
       extra_above = wave_sum_i(c);
     }
     sig_vec = sig;
-    const T tot = wave_sum(acc);
+    // (RES: a ladder of its own -- the key's maximum above decides fu and fw, which acc is made of, so the two cannot share
+    //  their levels; the resident kernel solves without CNT, so there is no extra_above to go with acc either)
+    T tot;
+    if constexpr (RES) tot = wave_sum_l63(acc); else tot = wave_sum(acc);
     return sig + num * fast_rcp(uw * tot);
   }
 
