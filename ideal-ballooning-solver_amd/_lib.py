@@ -51,6 +51,8 @@ SYMBOLS = {
     "ibs_marginal_obj_w_grad_tangent_f64": (C.c_int, [_P, _I32, _I32, _D, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_gamma_scan_nearest_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P,
                                              _P, _P, _P, _P, _I32]),
+    "ibs_gamma_scan_vjp_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P,
+                                         _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_obj_w_grad_nearest_f64": (C.c_int, [_P, _I32, _I32, _D, _P, _I64, _P, _P, _D, _P, _P, _P, _P, _P, _I32]),
     "ibs_obj_w_grad_exact_f64": (C.c_int, [_P, _I32, _I32, _D, _P, _I64, _P, _P, _D, _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_gamma_points_nearest_f64": (C.c_int, [_P, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P,

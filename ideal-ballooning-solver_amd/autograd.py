@@ -10,6 +10,9 @@ Simpson quotient of utils.py:1601-1621), not the Hellmann-Feynman formulas of ut
     gam = iag.growth_rate(h, *geo[:7], dP, theta0)
     gam.sum().backward()            # gradients in the surface tables tm, tq, the scalars sc and line_alpha
 
+    gam = iag.gamma_scan(h, *geo[:7], dP, theta0)       # theta0 (n_theta0,): the scan kernel forward, ONE ibs_gamma_scan_vjp_f64 backward
+    objective.smooth_max(gam.reshape(n_surf, n_alpha, -1), 20.0).sum().backward()
+
 Float64 CUDA tensors throughout; uniform grids, odd N in [66, 65537] (the limits of the kernels).  A backward whose VJP flags a system
 (status bits 0-1 of ibs_solve_gcf_vjp_f64) issues a VjpStatusWarning.  `import ibs_amd` does not import
 this module, nor torch."""
@@ -187,6 +190,76 @@ def growth_rate(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho,
         sigma = sigma.expand(n_lines, n_t0).reshape(-1) if sigma.dim() == 0 else sigma.reshape(-1)
     gam, _ = solve_gcf(h, g.reshape(-1, N), c.reshape(-1, N), f.reshape(-1, N), eigenpair, sigma, ctx)
     return gam.reshape(n_lines, n_t0)
+
+
+GAM_RESOLVE_TOL = 1e-8     # the library's stated FP64 tolerance on gam: how far the backward's own solve may be from the forward's
+
+
+class _GammaScan(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, eigenpair, sigma, ictx):
+        geo7 = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        if eigenpair == "max":
+            gam = ictx.gamma_scan(h, *geo7, dPdrho, theta0)["gam"]
+        else:
+            gam = ictx.gamma_scan_nearest(h, *geo7, dPdrho, theta0, sigma)["gam"]
+        fctx.save_for_backward(*geo7, dPdrho, theta0, gam, *([sigma] if eigenpair == "nearest" else []))
+        fctx.h, fctx.ictx = h, ictx
+        return gam
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gam_bar):
+        *geo7, dPdrho, theta0, gam = fctx.saved_tensors[:10]
+        sigma = fctx.saved_tensors[10] if len(fctx.saved_tensors) > 10 else None
+        need = fctx.needs_input_grad
+        want = [k for k, on in (("geo", any(need[1:8])), ("dPdrho", need[8]), ("theta0", need[9])) if on]
+        if not want:
+            return (None,) * 13
+        r = fctx.ictx.gamma_scan_vjp(fctx.h, *geo7, dPdrho, theta0, gam_bar.contiguous(), sigma=sigma, want=want, want_info=True)
+        # the backward re-solved in division form: a line on which its gam is not the forward's (another eigenpair: clustered modes, a
+        # nearest pair that changed hands) has no gradient here
+        active = gam_bar.ne(0)
+        moved = (active & ~((r["gam"] - gam).abs() <= GAM_RESOLVE_TOL)).any(1)
+        st = ((r["info"] >> 16) & 3) | (((r["info"] >> (16 + 6)) & 2))           # solve failed | adjoint refused
+        n_moved, n_pivot, n_bad = torch.stack([moved.sum(), (active & ((r["info"] >> (16 + 6)) & 1).ne(0)).sum(),
+                                               (active & st.ne(0)).sum()]).tolist()     # (one host synchronisation)
+        parts = [vjp_status_message(n_pivot, n_bad)] if n_pivot or n_bad else []
+        if n_moved:
+            parts.append("gamma_scan: %d line(s) on which the backward's division-form solve gave a gam more than %g from the forward's "
+                         "(another eigenpair: NaN gradients)" % (n_moved, GAM_RESOLVE_TOL))
+        if parts:
+            warnings.warn("; ".join(parts), VjpStatusWarning, stacklevel=2)
+        nan = float("nan")
+        geo_bar = r["geo_bar"]
+        if geo_bar is not None:
+            geo_bar = torch.where(moved[None, :, None], torch.full_like(geo_bar, nan), geo_bar)
+        dP_bar = r["dPdrho_bar"]
+        if dP_bar is not None:
+            dP_bar = torch.where(moved, torch.full_like(dP_bar, nan), dP_bar)
+        t0_bar = r["theta0_bar"]
+        if t0_bar is not None:
+            t0_bar = torch.where(moved[:, None], torch.full_like(t0_bar, nan), t0_bar).sum(0)      # theta0 is shared by the lines
+        planes = [geo_bar[k] if geo_bar is not None and need[1 + k] else None for k in range(7)]
+        return (None, *planes, dP_bar, t0_bar, None, None, None)
+
+
+def gamma_scan(h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, eigenpair="max", sigma=None, ctx=None):
+    """gam (n_lines, n_theta0) of the lines (geometry arrays (n_lines, N), dPdrho (n_lines,)) at theta0 (n_theta0,), shared by all lines:
+    the forward is the scan kernel itself (Context.gamma_scan, or gamma_scan_nearest with eigenpair="nearest" and sigma a scalar or
+    (n_lines, n_theta0)), the backward ONE Context.gamma_scan_vjp call (ibs_gamma_scan_vjp_f64): the (g, c, f) rows of the systems
+    never become torch tensors.  Differentiable in the seven arrays, dPdrho and theta0 (its gradient is the sum over the lines).
+    Composes with fieldline_geometry: gamma_scan(h, *geo[:7], dP, theta0).  The backward solves again, in division form; a line
+    on which that gam is more than 1e-8 from the forward's gets NaN gradients and a VjpStatusWarning, as do status bits 0-1 and 7 of
+    the VJP.  growth_rate is the same function through torch expressions (and takes per-line theta0)."""
+    _check_mode(eigenpair, sigma)
+    if theta0.dim() != 1:
+        raise ValueError("gamma_scan takes theta0 (n_theta0,), shared by the lines; growth_rate takes (n_lines, n_theta0)")
+    if eigenpair == "nearest":
+        sigma = torch.as_tensor(sigma, dtype=torch.float64, device=bmag.device)
+        sigma = sigma.expand(bmag.shape[0], theta0.shape[0]).contiguous() if sigma.dim() == 0 else sigma
+    return _GammaScan.apply(float(h), bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, eigenpair, sigma,
+                            ctx or default_context(bmag.device.index or 0))
 
 
 class _FieldlineGeometry(torch.autograd.Function):

@@ -1188,6 +1188,85 @@ int ibs_gamma_scan_modes_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, in
   });
 }
 
+// ---- vector-Jacobian product of a whole (line, theta0) table of growth rates (ibs_scan_vjp.hip; nothing upstream corresponds): whole
+// lines chunk after chunk under the budget of scan_rows_chunked (kNearestScanBytes, or option "nearest_chunk_systems"); a chunk's
+// workspace in ctx->long_ws = the persistent grid's per-wave workspace (ibs::exact_points_ws), three cotangent rows and a verdict per system
+int ibs_gamma_scan_vjp_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
+                           const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
+                           const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                           const double* dPdrho, const double* theta0, const double* sigma, const double* gam_bar,
+                           double* geo_bar, double* dPdrho_bar, double* theta0_bar, double* gam, double* lam, int32_t* info,
+                           int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho || !theta0 || !gam_bar)
+    return fail(IBS_ERR_ARG, "null argument (the geometry arrays, dPdrho, theta0 and gam_bar are required)");
+  if (!geo_bar && !dPdrho_bar && !theta0_bar) return fail(IBS_ERR_ARG, "geo_bar, dPdrho_bar and theta0_bar are all null");
+  if (n_lines < 0 || n_theta0 < 0 || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  const size_t n_sys = (size_t)n_lines * n_theta0, plane = (size_t)n_lines * ld;
+  const bool need_rows = geo_bar || dPdrho_bar;
+  ibs::ScanVjpArgs a{};                                    // the whole call; each chunk launches a copy with its lines
+  a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld; a.ld_bar = (long)ld;
+  double* d_geo_bar = nullptr;
+  auto decl = [&](Stage& s) {
+    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], plane);
+    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_theta0); a.sigma = s.in(sigma, n_sys); a.gam_bar = s.in(gam_bar, n_sys);
+    d_geo_bar = s.out(geo_bar, 7 * plane); a.dPdrho_bar = s.out(dPdrho_bar, n_lines); a.theta0_bar = s.out(theta0_bar, n_sys);
+    a.gam = s.out(gam, n_sys); a.lam = s.out(lam, n_sys);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (mem == IBS_MEM_HOST && d_geo_bar && ld > N)      // (host pointers: the padding columns come back as zero)
+      HIPCHK(hipMemsetAsync(d_geo_bar, 0, 7 * plane * sizeof(double), ctx->stream));
+    const size_t per_wave = ibs::exact_points_ws(N).total;
+    int nw = 0;
+    double *work = nullptr, *rows = nullptr;
+    int* flag = nullptr;
+    auto carve = [&](Carve& cv, long L) {                  // ctx->long_ws of a chunk of L lines
+      const long S = L * n_theta0;
+      nw = long_waves(ctx, S);
+      work = cv.take<double>((size_t)nw * per_wave);
+      rows = need_rows ? cv.take<double>((size_t)S * 3 * N) : nullptr;
+      flag = cv.take<int>((size_t)S);
+    };
+    auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
+    long L = n_lines;
+    if (ctx->opt.nearest_chunk_systems > 0) L = ctx->opt.nearest_chunk_systems / n_theta0;
+    else while (L > 1 && bytes_of(L) > kNearestScanBytes) L = (L + 1) / 2;
+    if (L < 1) L = 1;
+    if (L > n_lines) L = n_lines;
+    const size_t bytes = bytes_of(L);
+    if (ensure_long_ws(ctx, bytes) != 0) {
+      (void)hipGetLastError();
+      return fail(IBS_ERR_HIP, "gamma_scan_vjp: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
+                  "which could not be allocated", L, n_theta0, N, bytes);
+    }
+    Carve cv{static_cast<char*>(ctx->long_ws)};
+    carve(cv, L);
+    for (long l0 = 0; l0 < n_lines; l0 += L) {
+      const long s0 = l0 * n_theta0;
+      ibs::ScanVjpArgs c = a;
+      c.n_lines = (int)(n_lines - l0 < L ? n_lines - l0 : L);
+      for (int k = 0; k < 7; ++k) {
+        c.geo7[k] = a.geo7[k] + l0 * ld;
+        c.geo_bar[k] = d_geo_bar ? d_geo_bar + k * plane + l0 * ld : nullptr;
+      }
+      c.dPdrho = a.dPdrho + l0; c.gam_bar = a.gam_bar + s0;
+      c.sigma = a.sigma ? a.sigma + s0 : nullptr;
+      c.dPdrho_bar = a.dPdrho_bar ? a.dPdrho_bar + l0 : nullptr; c.theta0_bar = a.theta0_bar ? a.theta0_bar + s0 : nullptr;
+      c.gam = a.gam ? a.gam + s0 : nullptr; c.lam = a.lam ? a.lam + s0 : nullptr; c.info = a.info ? a.info + s0 : nullptr;
+      c.rows = rows; c.flag = flag;
+      c.work = work; c.work_doubles = (size_t)nw * per_wave; c.n_waves = nw;
+      HIPCHK(ibs::launch_scan_vjp(c, ctx->stream));
+    }
+    return 0;
+  });
+}
+
 // ---- geometry-fed points with the eigenpair nearest sigma[p] (ibs_nearest_grad.hip): the refinement's objective + gradient and
 // the final solve of ball_scan.py:305-339 in upstream's mode, one wave per point on the persistent grid of long_waves()
 // the per-wave workspace (ibs::nearest_points_ws) in ctx->long_ws

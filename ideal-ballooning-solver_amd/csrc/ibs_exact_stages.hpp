@@ -44,13 +44,13 @@ __device__ __forceinline__ ExactPair exact_eigenpair(const SrcLong<double, false
   return e;
 }
 
-// vjp_one with gam_bar = 1, lam_bar = 0 on the rows and the pair: g_bar, c_bar, f_bar in the workspace (g_bar and c_bar in the adjoint's
+// vjp_one with gam_bar = gbar (1 unless given), lam_bar = 0 on the rows and the pair: g_bar, c_bar, f_bar in the workspace (g_bar and c_bar in the adjoint's
 // own first two work rows, dead by then), fenced on return.  Returns the adjoint's status (bit 0 a replaced pivot: informational,
 // bit 1 refused: no gradient) and merges it into e.word at status bits 6-7
 __device__ __forceinline__ int exact_adjoint(const SrcLong<double, false>& src, const ExactPointsArgs& a, ExactPair& e, double* my,
-                                             const ExactPointsWs& L, double* lds, int lane) {
+                                             const ExactPointsWs& L, double* lds, int lane, double gbar = 1.0) {
   int* s_info = reinterpret_cast<int*>(my + L.scal + 1);
-  vjp_one(src, a.N, a.h, e.lam, my + L.X, 1.0, 0.0, my + L.gb, my + L.cb, my + L.fb, s_info + 1, 0, my + L.work, lds, lane);
+  vjp_one(src, a.N, a.h, e.lam, my + L.X, gbar, 0.0, my + L.gb, my + L.cb, my + L.fb, s_info + 1, 0, my + L.work, lds, lane);
   long_fence();                                             // (the cotangent rows of every lane, the adjoint's word of lane 0)
   const int vw = __builtin_amdgcn_readfirstlane(s_info[1]) >> 16;
   e.word |= (vw & 3) << (16 + 6);

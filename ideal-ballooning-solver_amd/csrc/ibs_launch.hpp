@@ -143,6 +143,24 @@ struct ExactPointsArgs {
 };
 hipError_t launch_obj_w_grad_exact(const ExactPointsArgs& a, hipStream_t st);
 hipError_t launch_obj_w_grad_exact_tangent(const ExactPointsArgs& a, hipStream_t st);
+// vector-Jacobian product of a whole (line, theta0) table of growth rates (ibs_scan_vjp.hip), one chunk of whole lines.  Two launches:
+// k_scan_vjp_points, one wave per system on the persistent grid of min(n_lines * n_theta0, n_waves) waves with the per-wave workspace
+// of k_exact_points (exact_points_ws), leaves each system's cotangent rows in rows [sys][3][N] and its verdict in flag [sys];
+// k_scan_vjp_reduce, one block per line, sums them through the fold over theta0, ascending.
+enum : int { kScanVjpSkip = 0, kScanVjpUse = 1, kScanVjpPoison = 2 };   // flag: gam_bar = 0 | rows valid | failed under a non-zero cotangent
+struct ScanVjpArgs {
+  int n_lines, n_theta0, N; double h;
+  const double* geo7[7]; long ld;                                   // the seven arrays of ibs_gamma_scan_f64, [n_lines][ld]
+  const double *dPdrho, *theta0;                                    // [n_lines], [n_theta0]
+  const double* sigma;                                              // [n_lines][n_theta0] or null = lam_max's eigenpair
+  const double* gam_bar;                                            // [n_lines][n_theta0]
+  double* geo_bar[7]; long ld_bar;                                  // optional (all seven or none), [n_lines][ld_bar]
+  double *dPdrho_bar, *theta0_bar;                                  // optional [n_lines], [n_lines][n_theta0]
+  double *gam, *lam; int* info;                                     // optional [n_lines][n_theta0]
+  double* rows; int* flag;                                          // chunk workspace: [n_sys][3][N] (null: theta0_bar alone is wanted), [n_sys]
+  double* work; size_t work_doubles; long n_waves;                  // the launch refuses less than min(n_sys, n_waves) waves' worth
+};
+hipError_t launch_scan_vjp(const ScanVjpArgs& a, hipStream_t st);
 // marginal stability (ibs_marginal.hip): the critical scale s* of the pressure gradient at fixed rows, FP64, any odd N in
 // [66, kMaxLongN]: one wave per system on the persistent grid of min(n_sys, n_waves) waves.  Per-wave workspace, in this order
 // (MarginalWs: the kernels carve it, the host sizes it): the eigenvector stage's nearest_ws_doubles(N), the marginal mode X, and in

@@ -19,6 +19,24 @@ def ballooning_objective(f_other, gam, gamma_thresh=-2.0e-4, prefac=50.0):
     return np.asarray(f_other, dtype=np.float64) + prefac * np.sum(np.maximum(gam - gamma_thresh, 0.0), axis=-1)
 
 
+def smooth_max(gam, beta):
+    """a smooth stand-in for the maximum of a (..., n_alpha, n_theta0) table of growth rates over its last two axes:
+    (logsumexp(beta gam) - log n) / beta, n = n_alpha n_theta0, beta > 0.  max - log(n) / beta <= value <= max, and the value is
+    differentiable where the maximum jumps between grid points.  gam: a torch tensor (differentiable) or anything numpy takes;
+    the result is of the same kind, shaped gam.shape[:-2]."""
+    beta = float(beta)
+    if not beta > 0.0:
+        raise IbsError("smooth_max: beta must be > 0")
+    if type(gam).__module__.startswith("torch"):
+        import torch
+        flat = gam.reshape(*gam.shape[:-2], -1)
+        return (torch.logsumexp(beta * flat, dim=-1) - float(np.log(flat.shape[-1]))) / beta
+    gam = np.asarray(gam, dtype=np.float64)
+    flat = beta * gam.reshape(*gam.shape[:-2], -1)
+    top = flat.max(axis=-1)
+    return (top + np.log(np.exp(flat - top[..., None]).sum(axis=-1)) - np.log(flat.shape[-1])) / beta
+
+
 def dof_fd_gradient(f0_arr, step_arr):
     """forward-difference gradient of sqrt(f0) over the DOFs (sims_runner_NCSX.py:258-261):
     df[i-1] = (f0_arr[i] - f0_arr[0]) / step_arr[i] * 0.5 / sqrt(f0_arr[0]),  i = 1..n_dof."""

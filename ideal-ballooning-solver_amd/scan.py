@@ -758,6 +758,36 @@ class BallooningScan:
         return dict(gam=gam.detach().reshape(n), dgam_dalpha=al.grad, dgam_dtheta0=t0.grad, tab_mn_bar=tm.grad, tab_nyq_bar=tq.grad,
                     scal_bar=sc.grad)
 
+    def smooth_max(self, beta):
+        """objective.smooth_max of every owned surface's WHOLE coarse (alpha, theta0) table and its exact gradient with respect to
+        the surface's own tables: an aggregate that sees a maximum that jumps, where sensitivity() is a statement at one frozen
+        point.  tables= + device= scans only; the eigenpair is this scan's (eigenpair="nearest": the one nearest SIGMA_COARSE, as in
+        the coarse scan).  Each owned surface gets its own differentiable copies of tab_mn, tab_nyq, scal and all nalpha coarse
+        lines of the surface index that copy: one geometry launch, one autograd.gamma_scan (the scan kernel forward,
+        ibs_gamma_scan_vjp_f64 backward), smooth_max, one backward through ibs_fieldline_geometry_vjp_f64.  Returns device tensors
+        dict(value, max: (n_own,); tab_mn_bar (n_own, 6, mnmax), tab_nyq_bar (n_own, 7, mnmax_nyq), scal_bar (n_own, 6)) =
+        d value / d tables; SurfaceTables.pullback carries them to the wout arrays, as after sensitivity()."""
+        import torch
+        from . import autograd as iag
+        from .objective import smooth_max
+        if self.tables is None or self.device is None:
+            raise IbsError("smooth_max() needs a scan built with tables= and device=")
+        dev, own = self.device, self._own_surf()
+        n, na = len(own), len(self.alpha_scan)
+        res = self._resident_inputs()
+        d = self.ctx._device_tables(self.tables, dev)
+        idx = torch.from_numpy(own.astype(np.int64)).to(dev)
+        tm, tq, sc = (d[k][idx].clone().requires_grad_(True) for k in (4, 5, 6))
+        line_surf = torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(na)
+        geo, dP = iag.fieldline_geometry(self.tables, line_surf, res["al"], res["th"], tab_mn=tm, tab_nyq=tq, scal=sc, ctx=self.ctx)
+        gam = iag.gamma_scan(self.h, *geo[:7], dP, res["t0"], eigenpair=self.eigenpair, sigma=SIGMA_COARSE if self.nearest else None,
+                             ctx=self.ctx)
+        tab = gam.reshape(n, na, -1)
+        value = smooth_max(tab, beta)
+        value.sum().backward()
+        return dict(value=value.detach(), max=tab.detach().reshape(n, -1).max(dim=1).values if n else value.detach(),
+                    tab_mn_bar=tm.grad, tab_nyq_bar=tq.grad, scal_bar=sc.grad)
+
     def marginal_sensitivity(self, points=None):
         """exact derivatives of every owned surface's critical scale s* at ONE point (alpha, theta0) of that surface, with respect to
         the point and to the surface's own tables.  tables= + device= scans only.  points (n_own, 2) = (alpha, theta0); None: the

@@ -485,6 +485,41 @@ class Context:
                      ar.out("info", shape + (K,), _I32, want_info))
         return ar.result(rc)
 
+    def gamma_scan_vjp(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, gam_bar, sigma=None,
+                       want=("geo", "dPdrho", "theta0"), want_info=False):
+        """exact vector-Jacobian product of the whole growth-rate table of a coarse scan (ibs_gamma_scan_vjp_f64): arrays as in
+        gamma_scan, gam_bar (n_lines, n_theta0) the cotangent of gam; sigma None: lam_max's eigenpair, else a scalar or
+        (n_lines, n_theta0): the eigenpair nearest it.  want: which of "geo", "dPdrho", "theta0" to return, at least one.
+        Returns dict(geo_bar (7, n_lines, N) in the order of the arguments, dPdrho_bar (n_lines,), theta0_bar (n_lines, n_theta0):
+        per system -- a caller whose lines share theta0 sums over the lines --, gam, lam[, info], nbad); entries not wanted are
+        None.  gam and lam are the division-form solve's own.  A system with gam_bar == 0 contributes exactly 0; a non-zero
+        cotangent on a failed solve (status bits 0-1), a refused adjoint (status bit 7) or a non-finite gam_bar (sets bit 1) makes
+        the rows and dPdrho_bar of its line and its own theta0_bar NaN.  EXACT_VJP_SHIFT moves info's status to solve_gcf_vjp's
+        two bits."""
+        geo7 = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        if len(bmag.shape) != 2:
+            raise IbsError("gamma_scan_vjp: the seven geometry arrays must be (n_lines, N), not %s" % (tuple(bmag.shape),))
+        n_lines, N = bmag.shape
+        for a in geo7[1:]:
+            if tuple(a.shape) != (n_lines, N):
+                raise IbsError("gamma_scan_vjp: the seven geometry arrays must all be (%d, %d), not %s" % (n_lines, N, tuple(a.shape)))
+        if tuple(dPdrho.shape) != (n_lines,) or len(theta0.shape) != 1:
+            raise IbsError("gamma_scan_vjp: dPdrho must be (%d,) and theta0 (n_theta0,)" % n_lines)
+        if tuple(gam_bar.shape) != (n_lines, int(theta0.shape[0])):
+            raise IbsError("gamma_scan_vjp: gam_bar must be (%d, %d), not %s" % (n_lines, theta0.shape[0], tuple(gam_bar.shape)))
+        want = tuple(want)
+        if not want or any(w not in ("geo", "dPdrho", "theta0") for w in want):
+            raise IbsError("gamma_scan_vjp: want must name at least one of 'geo', 'dPdrho', 'theta0', not %r" % (want,))
+        ar = _Args(self)
+        head, shape, N = ar.geo(h, geo7, dPdrho, theta0)
+        rc = ar.call("ibs_gamma_scan_vjp_f64", *head, ar.rows(sigma, shape), ar.inp(gam_bar),
+                     ar.out("geo_bar", (7, n_lines, N), want="geo" in want), ar.out("dPdrho_bar", (n_lines,), want="dPdrho" in want),
+                     ar.out("theta0_bar", shape, want="theta0" in want), ar.out("gam", shape), ar.out("lam", shape),
+                     ar.out("info", shape, _I32, want_info))
+        for k in ("geo_bar", "dPdrho_bar", "theta0_bar"):
+            ar.outs.setdefault(k, None)
+        return ar.result(rc)
+
     # ---- geometry x theta0 scan ---------------------------------------------------------------
     def gamma_scan(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0,
                    want_X=False, want_dtheta0=False, want_info=False, lam_guess=None, guess_width=None, certify=False):

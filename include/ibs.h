@@ -37,9 +37,10 @@
  *     bit 5, nearest-sigma entry points (ibs_*_nearest_f64): "nearest not determined" -- the eigenvalues on either side of
  *            sigma lie at distances that differ by less than 4 N eps ||A||; the larger one is returned
  *            (these entry points never set bit 3, whose re-close diagnostic occupies bits 5 and up on the lam_max entry points).
- *     bits 6-7, ibs_obj_w_grad_exact_f64 only: the two status bits of its adjoint solve (ibs_solve_gcf_vjp_f64's bits 0 and 1), moved
- *            clear of bits 0-5 -- bit 6: a pivot of the adjoint solve fell below pivmin and was replaced (informational: jac may be
- *            inaccurate); bit 7: the adjoint refused the pair (jac = NaN, val is good).  Neither is counted by return values > 0.
+ *     bits 6-7, ibs_obj_w_grad_exact*_f64 and ibs_gamma_scan_vjp_f64 only: the two status bits of the adjoint solve
+ *            (ibs_solve_gcf_vjp_f64's bits 0 and 1), moved clear of bits 0-5 -- bit 6: a pivot of the adjoint solve fell below pivmin
+ *            and was replaced (informational: jac may be inaccurate); bit 7: the adjoint refused the pair (jac = NaN, val is good;
+ *            ibs_gamma_scan_vjp_f64: that line's bars NaN).  Neither is counted by return values > 0.
  *     bit 8, marginal-stability entry points (ibs_marginal_*_f64) only: no row has c_j > 0, so no scale of the pressure gradient makes
  *            the line unstable -- scale = +inf, mu = 0, the derivatives are 0 and X, gam0 are NaN (informational: not counted by
  *            return values > 0).  ibs_marginal_obj_w_grad_f64 writes val = 0 and jac = dscale = 0 with it, and sets bit 1 with val
@@ -236,6 +237,34 @@ int ibs_gamma_scan_modes_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, in
                              const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                              const double* dPdrho, const double* theta0, int32_t n_modes, double* gam, double* lam,
                              int32_t* info, int32_t mem);
+/* Exact vector-Jacobian product of the whole table of growth rates of a coarse scan: the cotangent gam_bar[n_lines][n_theta0] of
+ * gam(line, theta0) carried back to the seven geometry arrays, dPdrho and theta0 of ibs_gamma_scan_f64.  Nothing upstream corresponds
+ * (its only derivatives are the Hellmann-Feynman formulas of obj_w_grad at one point per surface, utils.py:1666-1725).
+ *   arrays, ld, dPdrho [n_lines], theta0 [n_theta0] (shared by the lines): as in ibs_gamma_scan_f64;
+ *   sigma: NULL = lam_max's eigenpair, else [n_lines][n_theta0]: the eigenpair nearest sigma (as ibs_gamma_scan_nearest_f64);
+ *   gam_bar [n_lines][n_theta0]: required;
+ *   geo_bar [7][n_lines][ld] (out): geo_bar[k][l][j] = sum over theta0 of gam_bar[l][theta0] d gam(l, theta0) / d (array k of line l
+ *   at point j), k in the order bmag gradpar cvdrift cvdrift0 gds2 gds21 gds22, entries 0 .. N-1 of each row (a host call returns the
+ *   padding entries N .. ld-1 as 0, a device call leaves them alone); dPdrho_bar [n_lines] (out): the same sum for dPdrho (through c);
+ *   theta0_bar [n_lines][n_theta0] (out): gam_bar d gam / d theta0 PER SYSTEM (a caller whose lines share theta0 sums over the lines);
+ *   each of the three optional, at least one given; gam, lam, info [n_lines][n_theta0] optional.
+ * gam is the FD4 / Simpson quotient this call returns (utils.py:1601-1621), the half-grid g the mean of neighbouring g, and the
+ * derivative is exact for it; it passes through |gradpar| as d|x| = sgn(x) dx.  The eigenpair is solved here in division form at every
+ * N (as ibs_obj_w_grad_exact_f64), so gam may differ from ibs_gamma_scan_f64's in its last digits.  Status (conventions above): the
+ * solve's word with the adjoint's two flags at status bits 6 and 7, as ibs_obj_w_grad_exact_f64.  A system with gam_bar exactly 0
+ * contributes exactly 0 whatever its status.  A system with a non-zero cotangent whose solve failed (bits 0-1), whose adjoint was
+ * refused (bit 7) or whose gam_bar is not finite (sets bit 1) makes the seven rows and dPdrho_bar of ITS line and its own theta0_bar
+ * NaN; no other line changes by a bit.  FP64, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED).  One wavefront per
+ * system (solve, adjoint, theta0 contraction), then one block per line that sums the systems' cotangent rows through the theta0 fold,
+ * theta0 ascending (csrc/ibs_scan_vjp.hip); whole lines chunk after chunk under the workspace bound of ibs_gamma_scan_nearest_f64 (the
+ * same option "nearest_chunk_systems").  No floating-point atomics: results are bitwise repeatable and independent of the batch, of
+ * the order of the lines and of the chunking. */
+int ibs_gamma_scan_vjp_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
+                           const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
+                           const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                           const double* dPdrho, const double* theta0, const double* sigma, const double* gam_bar,
+                           double* geo_bar, double* dPdrho_bar, double* theta0_bar, double* gam, double* lam, int32_t* info,
+                           int32_t mem);
 /* ibs_obj_w_grad_f64 with the eigenpair nearest sigma[n_pts] (utils.py:1632-1728 as the refinement of ball_scan.py:305-314 runs it,
  * sigma = 1.3 |gam| + 0.05 of the surface's coarse maximum): geo, theta0, del_alpha, val and jac as in ibs_obj_w_grad_f64; lam,
  * idx and info [n_pts] optional (conventions above: status bits 1 (also: sigma not finite) and 5, idx).  FP64, any odd N in
