@@ -19,6 +19,7 @@
 #include "ibs_lbfgsb2.hpp"
 #include "ibs_refine.hpp"
 #include "ibs_certify.hpp"
+#include "ibs_regrid.hpp"
 #include <chrono>
 #include <thread>
 
@@ -485,6 +486,44 @@ GcfLauncher<T> gcf_fix_launcher(int N) {
   else return ibs::launch_table().gcf_fix_f32w[rows_per_lane(N)];
 }
 
+// a planned raw solve on device rows: the solver kernel of the plan, the fix-up launch of the forms that list their suspects, or the
+// long-grid kernel.  long_work: the long-grid kernel's workspace (long_waves(n_sys) * 3 N doubles) where the caller has carved it
+// out of ctx->long_ws together with the rows (the geometry-fed theta scans); null = ctx->long_ws is sized here and used whole
+template <typename T>
+int launch_planned_gcf(ibs_ctx* ctx, const ibs::GcfPlan& plan, ibs::GcfArgs<T>& a, double* long_work = nullptr) {
+  const int N = a.N;
+  if (plan.form != ibs::GcfForm::Long) {
+    if (plan.lists_suspects && (a.flags & 1)) {
+      if (int r = ensure_fix(ctx, (long)a.n_sys)) return r;
+      char* fb = static_cast<char*>(ctx->fix_buf);
+      a.fix_count = reinterpret_cast<int*>(fb);
+      a.fix_sys = reinterpret_cast<long*>(fb + 256);
+      a.fix_center = reinterpret_cast<double*>(fb + 256 + (size_t)ctx->fix_cap * 8);
+      HIPCHK(hipMemsetAsync(a.fix_count, 0, sizeof(int), ctx->stream));
+    }
+    HIPCHK(gcf_launcher<T>(plan)(a, ctx->stream));
+    if (a.fix_count) {
+      ibs::LaunchNote keep = ibs::last_launch();         // (ibs_last_launch names the solver kernel, not its fix-up pass)
+      const auto fix = gcf_fix_launcher<T>(N);
+      if (!fix) return fail(IBS_ERR_UNSUPPORTED, "no fix-up kernel built for N=%d", N);
+      HIPCHK(fix(a, ctx->stream));
+      ibs::last_launch() = keep;
+    }
+    return 0;
+  }
+  const int nw = long_waves(ctx, (long)a.n_sys);
+  if (!long_work) {
+    if (int r = ensure_long_ws(ctx, (size_t)nw * 3 * (size_t)N * sizeof(double))) return r;
+    long_work = static_cast<double*>(ctx->long_ws);
+  }
+  ibs::LongGcfArgs la{};
+  la.n_sys = a.n_sys; la.N = N; la.h = (double)a.h; la.g = a.g; la.c = a.c; la.f = a.f; la.gh = a.gh; la.f32 = sizeof(T) == 4;
+  la.ld = a.ld; la.lam = a.lam; la.gam = a.gam; la.X = a.X; la.dX = a.dX; la.info = a.info;
+  la.work = long_work; la.n_waves = nw;
+  HIPCHK(ibs::launch_gcf_long(la, ctx->stream));
+  return 0;
+}
+
 template <typename T>
 int solve_gcf_impl(ibs_ctx* ctx, int64_t n_sys, int32_t N, T h, const T* g, const T* c, const T* f, int64_t ld,
                    T* lam, T* gam, T* X, T* dX, int32_t* info, int32_t mem, const T* gh = nullptr) {
@@ -496,35 +535,7 @@ int solve_gcf_impl(ibs_ctx* ctx, int64_t n_sys, int32_t N, T h, const T* g, cons
   if (plan.err == ibs::PlanError::NotBuilt) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", plan.M, N);
   ON_DEVICE(ctx);
   if (plan.err == ibs::PlanError::NoLds) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, plan.per_wave);
-  auto launch_it = [&](ibs::GcfArgs<T>& a) -> int {
-    if (plan.form != ibs::GcfForm::Long) {
-      if (plan.lists_suspects && (a.flags & 1)) {
-        if (int r = ensure_fix(ctx, (long)a.n_sys)) return r;
-        char* fb = static_cast<char*>(ctx->fix_buf);
-        a.fix_count = reinterpret_cast<int*>(fb);
-        a.fix_sys = reinterpret_cast<long*>(fb + 256);
-        a.fix_center = reinterpret_cast<double*>(fb + 256 + (size_t)ctx->fix_cap * 8);
-        HIPCHK(hipMemsetAsync(a.fix_count, 0, sizeof(int), ctx->stream));
-      }
-      HIPCHK(gcf_launcher<T>(plan)(a, ctx->stream));
-      if (a.fix_count) {
-        ibs::LaunchNote keep = ibs::last_launch();         // (ibs_last_launch names the solver kernel, not its fix-up pass)
-        const auto fix = gcf_fix_launcher<T>(N);
-        if (!fix) return fail(IBS_ERR_UNSUPPORTED, "no fix-up kernel built for N=%d", N);
-        HIPCHK(fix(a, ctx->stream));
-        ibs::last_launch() = keep;
-      }
-      return 0;
-    }
-    const int nw = long_waves(ctx, (long)a.n_sys);
-    if (int r = ensure_long_ws(ctx, (size_t)nw * 3 * (size_t)N * sizeof(double))) return r;
-    ibs::LongGcfArgs la{};
-    la.n_sys = a.n_sys; la.N = N; la.h = (double)a.h; la.g = a.g; la.c = a.c; la.f = a.f; la.gh = a.gh; la.f32 = sizeof(T) == 4;
-    la.ld = a.ld; la.lam = a.lam; la.gam = a.gam; la.X = a.X; la.dX = a.dX; la.info = a.info;
-    la.work = static_cast<double*>(ctx->long_ws); la.n_waves = nw;
-    HIPCHK(ibs::launch_gcf_long(la, ctx->stream));
-    return 0;
-  };
+  auto launch_it = [&](ibs::GcfArgs<T>& a) -> int { return launch_planned_gcf<T>(ctx, plan, a); };
   ibs::GcfArgs<T> a{};
   a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.wpb = plan.wpb;
   a.flags = ctx->opt.reclose == 1 ? 1 : (ctx->opt.reclose == 2 ? 2 : 0);
@@ -1521,6 +1532,173 @@ int ibs_gamma_points_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const
                          double* lam, double* X, double* dX, double* dgam_dtheta0, int32_t* info, int32_t mem) {
   return gamma_scan_impl(ctx, n_pts, 1, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho, theta0, gam,
                          lam, X, dX, dgam_dtheta0, info, mem, nullptr, 0.0, 0, nullptr, true);
+}
+
+// ---- lines on a non-uniform theta grid (ibs_regrid.hip; utils.py:1565-1576): regrid onto the uniform grid of the window, then the raw
+// solvers with the half-grid row gh.  The checks of the theta arguments every such entry point shares; *h = the spacing of the solve
+static int check_theta_args(int32_t N, const double* theta, int64_t theta_ld, double lo, double hi, double* h) {
+  if (!theta) return fail(IBS_ERR_ARG, "theta is null");
+  if (theta_ld != 0 && theta_ld < N) return fail(IBS_ERR_ARG, "theta_ld=%lld is neither 0 (one shared grid) nor >= N=%d", (long long)theta_ld, N);
+  if (!ibs::regrid_window_ok(lo, hi)) return fail(IBS_ERR_ARG, "theta window [%g, %g]: theta_lo and theta_hi must be finite with theta_hi > theta_lo", lo, hi);
+  const ibs::GridCheck gc = ibs::check_grid_length(N, true);
+  *h = gc == ibs::GridCheck::Range ? 1.0 : ibs::regrid_spacing(N, lo, hi);
+  return check_grid(N, *h, true);
+}
+
+int ibs_regrid_rows_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, const double* theta, int64_t theta_ld, double theta_lo, double theta_hi,
+                        const double* g, const double* c, const double* f, int64_t ld, double* g_u, double* gh, double* c_u,
+                        double* f_u, int64_t ld_out, double* h_out, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_sys < 0 || !g || !g_u || !gh || ld < N || ld_out < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_sys=%lld ld=%lld ld_out=%lld N=%d)", (long long)n_sys, (long long)ld, (long long)ld_out, N);
+  if ((c != nullptr) != (c_u != nullptr) || (f != nullptr) != (f_u != nullptr))
+    return fail(IBS_ERR_ARG, "c / c_u and f / f_u are optional as pairs");
+  double h = 0.0;
+  if (int r = check_theta_args(N, theta, theta_ld, theta_lo, theta_hi, &h)) return r;
+  if (h_out) *h_out = h;
+  if (n_sys == 0) return 0;
+  ON_DEVICE(ctx);
+  ibs::RegridArgs a{};
+  a.n_lines = theta_ld ? n_sys : 1; a.per_line = theta_ld ? 1 : n_sys; a.N = N; a.theta_ld = theta_ld; a.lo = theta_lo; a.hi = theta_hi;
+  a.ld = ld; a.n_cu = ctx->chip.n_cu;
+  const size_t in_elems = (size_t)n_sys * ld;
+  auto decl = [&](Stage& s) {
+    a.theta = s.in(theta, theta_ld ? (size_t)n_sys * theta_ld : (size_t)N);
+    a.g = s.in(g, in_elems); a.c = s.in(c, in_elems); a.f = s.in(f, in_elems);
+    a.g_u = s.out_rows(g_u, n_sys, N, ld_out); a.gh = s.out_rows(gh, n_sys, N, ld_out);
+    a.c_u = s.out_rows(c_u, n_sys, N, ld_out); a.f_u = s.out_rows(f_u, n_sys, N, ld_out);
+    a.ld_out = (long)s.rows_ld(N, ld_out);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int { HIPCHK(ibs::launch_regrid_rows(a, ctx->stream)); return 0; });
+}
+
+// the arguments the three geometry-fed theta entry points share, checked before the context is touched
+static int check_theta_geo(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld, double lo,
+                           double hi, const double* const src[7], int64_t ld, const double* dPdrho, const double* theta0, double* h) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  bool geo_ok = true;
+  for (int k = 0; k < 7; ++k) geo_ok = geo_ok && src[k];
+  if (n_lines < 0 || n_theta0 < 0 || !geo_ok || !dPdrho || !theta0 || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  return check_theta_args(N, theta, theta_ld, lo, hi, h);
+}
+
+int ibs_assemble_gcf_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld,
+                               double theta_lo, double theta_hi, const double* bmag, const double* gradpar, const double* cvdrift,
+                               const double* cvdrift0, const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                               const double* dPdrho, const double* theta0, int32_t theta0_per_line, double* g_u, double* gh,
+                               double* c_u, double* f_u, double* h_out, int32_t* info, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  double h = 0.0;
+  if (int r = check_theta_geo(ctx, n_lines, n_theta0, N, theta, theta_ld, theta_lo, theta_hi, src, ld, dPdrho, theta0, &h)) return r;
+  if (!g_u || !gh || !c_u || !f_u) return fail(IBS_ERR_ARG, "g_u, gh, c_u and f_u are required");
+  if (theta0_per_line && n_theta0 != 1) return fail(IBS_ERR_ARG, "theta0_per_line needs n_theta0 = 1 (one theta0 per line), not %d", n_theta0);
+  if (h_out) *h_out = h;
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  ON_DEVICE(ctx);
+  ibs::RegridArgs a{};
+  a.n_lines = n_lines; a.per_line = n_theta0; a.N = N; a.theta_ld = theta_ld; a.lo = theta_lo; a.hi = theta_hi; a.ld = ld;
+  a.t0_per_line = theta0_per_line ? 1 : 0; a.ld_out = N; a.n_cu = ctx->chip.n_cu;
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
+  auto decl = [&](Stage& s) {
+    a.theta = s.in(theta, theta_ld ? (size_t)n_lines * theta_ld : (size_t)N);
+    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
+    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, theta0_per_line ? (size_t)n_lines : (size_t)n_theta0);
+    a.g_u = s.out(g_u, out_elems); a.gh = s.out(gh, out_elems); a.c_u = s.out(c_u, out_elems); a.f_u = s.out(f_u, out_elems);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int { HIPCHK(ibs::launch_assemble_regrid(a, ctx->stream)); return 0; });
+}
+
+// Geometry-fed scan on a non-uniform grid, on the pattern of scan_rows_chunked / launch_scan_long: the four regridded rows of a chunk of
+// whole lines are written to ctx->long_ws by k_assemble_regrid (the same budget kNearestScanBytes, the same option
+// "nearest_chunk_systems") and solved by the raw solver WITH gh, in the form plan_gcf picks for a caller-supplied half grid -- the
+// long-grid kernel beyond 2050 points, its workspace carved out of the same allocation.  A line that is not a grid reaches the solver
+// as NaN rows and comes back with status bit 1; k_regrid_poison then makes its floating-point outputs NaN.  Every system is a function of its own line: chunking changes no bit.
+static int scan_theta_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld, double lo,
+                           double hi, const double* const src[7], int64_t ld, const double* dPdrho, const double* theta0,
+                           bool t0_per_line, double* gam, double* lam, double* X, double* dX, int32_t* info, int32_t mem) {
+  double h = 0.0;
+  if (int r = check_theta_geo(ctx, n_lines, n_theta0, N, theta, theta_ld, lo, hi, src, ld, dPdrho, theta0, &h)) return r;
+  if (n_lines == 0 || n_theta0 == 0) return 0;
+  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
+  const ibs::GcfPlan plan = ibs::plan_gcf(ctx->chip, ctx->opt, ctx->built, 8, (long)n_sys, N, true, mem == IBS_MEM_HOST || gam, X || dX);
+  if (plan.err == ibs::PlanError::NotBuilt) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", plan.M, N);
+  ON_DEVICE(ctx);
+  if (plan.err == ibs::PlanError::NoLds) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, plan.per_wave);
+  const bool lng = plan.form == ibs::GcfForm::Long;
+  const double *dth, *geo7[7], *dP, *t0;
+  double *dgam, *dlam, *dXo, *ddX;
+  int* dinfo;
+  auto decl = [&](Stage& s) {
+    dth = s.in(theta, theta_ld ? (size_t)n_lines * theta_ld : (size_t)N);
+    for (int k = 0; k < 7; ++k) geo7[k] = s.in(src[k], in_elems);
+    dP = s.in(dPdrho, n_lines); t0 = s.in(theta0, t0_per_line ? (size_t)n_lines : (size_t)n_theta0);
+    dgam = s.out(gam, n_sys, true); dlam = s.out(lam, n_sys, true); dXo = s.out(X, out_elems); ddX = s.out(dX, out_elems);
+    dinfo = s.status(info, n_sys);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    double *work = nullptr, *G, *GH, *C, *F;
+    int* flag;                                     // the regrid's verdict on every system of the chunk
+    auto carve = [&](Carve& cv, long L) {          // ctx->long_ws of a chunk of L lines
+      const size_t S = (size_t)L * n_theta0;
+      if (lng) work = cv.take<double>((size_t)long_waves(ctx, (long)S) * 3 * (size_t)N);
+      G = cv.take<double>(S * N); GH = cv.take<double>(S * N); C = cv.take<double>(S * N); F = cv.take<double>(S * N);
+      flag = cv.take<int>(S);
+    };
+    auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
+    long L = n_lines;
+    if (ctx->opt.nearest_chunk_systems > 0) L = ctx->opt.nearest_chunk_systems / n_theta0;
+    else while (L > 1 && bytes_of(L) > kNearestScanBytes) L = (L + 1) / 2;
+    if (L < 1) L = 1;
+    if (L > n_lines) L = n_lines;
+    const size_t bytes = bytes_of(L);
+    if (ensure_long_ws(ctx, bytes) != 0) {
+      (void)hipGetLastError();
+      return fail(IBS_ERR_HIP, "%s: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
+                  "which could not be allocated", t0_per_line ? "gamma_points_theta" : "gamma_scan_theta", L, n_theta0, N, bytes);
+    }
+    Carve cv{static_cast<char*>(ctx->long_ws)};
+    carve(cv, L);
+    for (long l0 = 0; l0 < n_lines; l0 += L) {
+      const long Lc = n_lines - l0 < L ? n_lines - l0 : L, s0 = l0 * n_theta0, S = Lc * n_theta0;
+      ibs::RegridArgs ra{};
+      ra.n_lines = Lc; ra.per_line = n_theta0; ra.N = N; ra.theta = dth + (theta_ld ? l0 * theta_ld : 0); ra.theta_ld = theta_ld;
+      ra.lo = lo; ra.hi = hi; ra.ld = ld; ra.t0_per_line = t0_per_line ? 1 : 0; ra.n_cu = ctx->chip.n_cu;
+      for (int k = 0; k < 7; ++k) ra.geo7[k] = geo7[k] + l0 * ld;
+      ra.dPdrho = dP + l0; ra.theta0 = t0 + (t0_per_line ? l0 : 0);
+      ra.g_u = G; ra.gh = GH; ra.c_u = C; ra.f_u = F; ra.ld_out = N; ra.info = flag;
+      HIPCHK(ibs::launch_assemble_regrid(ra, ctx->stream));
+      ibs::GcfArgs<double> ga{};
+      ga.n_sys = S; ga.N = N; ga.h = h; ga.g = G; ga.gh = GH; ga.c = C; ga.f = F; ga.ld = N; ga.wpb = plan.wpb;
+      ga.flags = ctx->opt.reclose == 1 ? 1 : (ctx->opt.reclose == 2 ? 2 : 0);
+      ga.lam = dlam ? dlam + s0 : nullptr; ga.gam = dgam ? dgam + s0 : nullptr; ga.info = dinfo ? dinfo + s0 : nullptr;
+      ga.X = dXo ? dXo + (size_t)s0 * N : nullptr; ga.dX = ddX ? ddX + (size_t)s0 * N : nullptr;
+      if (int r = launch_planned_gcf<double>(ctx, plan, ga, work)) return r;
+      HIPCHK(ibs::launch_regrid_poison(S, N, flag, ga.lam, ga.gam, ga.X, ga.dX, ctx->stream));
+    }
+    flag_sigma<double>(ctx, (long)n_sys, dlam, dinfo);
+    return 0;
+  });
+}
+
+int ibs_gamma_scan_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld,
+                             double theta_lo, double theta_hi, const double* bmag, const double* gradpar, const double* cvdrift,
+                             const double* cvdrift0, const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                             const double* dPdrho, const double* theta0, double* gam, double* lam, double* X, double* dX,
+                             int32_t* info, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  return scan_theta_impl(ctx, n_lines, n_theta0, N, theta, theta_ld, theta_lo, theta_hi, src, ld, dPdrho, theta0, false, gam, lam, X, dX,
+                         info, mem);
+}
+
+int ibs_gamma_points_theta_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, const double* theta, int64_t theta_ld, double theta_lo,
+                               double theta_hi, const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
+                               const double* gds2, const double* gds21, const double* gds22, int64_t ld, const double* dPdrho,
+                               const double* theta0, double* gam, double* lam, double* X, double* dX, int32_t* info, int32_t mem) {
+  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  return scan_theta_impl(ctx, n_pts, 1, N, theta, theta_ld, theta_lo, theta_hi, src, ld, dPdrho, theta0, true, gam, lam, X, dX, info, mem);
 }
 
 int ibs_scan_starts_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_alpha, int32_t n_theta0, const double* alpha,

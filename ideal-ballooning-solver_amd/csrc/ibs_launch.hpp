@@ -212,6 +212,23 @@ hipError_t launch_sturm_long(const SturmArgs<double>& a, hipStream_t st);
 hipError_t launch_sturm_div(const SturmArgs<double>& a, hipStream_t st);     // lanes as systems, division form, any N
 template <typename T> struct ScanArgs;
 hipError_t launch_assemble_long(const ScanArgs<double>& a, double* g, double* c, double* f, double* gt, double* ct, double* ft, hipStream_t st);
+// lines on a non-uniform theta grid (ibs_regrid.hip): the regrid of utils.py:1565-1576 onto the uniform grid of the window [lo, hi].
+// n_lines grids (theta + line * theta_ld; theta_ld = 0: one shared row), each shared by per_line consecutive systems; outputs
+// g_u, gh, c_u, f_u [n_lines * per_line][ld_out], gh[N - 1] = 0; info [n_lines * per_line] optional (status bit 1: not a grid, NaN rows).
+// launch_regrid_rows: raw rows g, c, f [n_lines * per_line][ld] (c / c_u and f / f_u optional as pairs).  launch_assemble_regrid: the
+// seven arrays geo7 [n_lines][ld], dPdrho [n_lines] and theta0 [per_line] -- or, t0_per_line, per_line = 1 and theta0 [n_lines].
+struct RegridArgs {
+  long n_lines, per_line; int N;
+  const double* theta; long theta_ld; double lo, hi;
+  const double *g, *c, *f; long ld;
+  const double* geo7[7]; const double *dPdrho, *theta0; int t0_per_line;
+  double *g_u, *gh, *c_u, *f_u; long ld_out; int* info;
+  int n_cu;
+};
+hipError_t launch_regrid_rows(const RegridArgs& a, hipStream_t st);
+hipError_t launch_assemble_regrid(const RegridArgs& a, hipStream_t st);
+// NaN into lam, gam [n_sys] and X, dX [n_sys][N] (each optional) of the systems whose flag word (RegridArgs::info) carries status bit 1
+hipError_t launch_regrid_poison(long n_sys, int N, const int* flag, double* lam, double* gam, double* X, double* dX, hipStream_t st);
 
 // field-line geometry kernel (ibs_geometry.hip)
 // dPdrho[line] = -0.5 mean((cvdrift - gbdrift) bmag^2) of lines laid out geo[k * plane + line * ld + j], k = 0 .. 7 (ball_scan.py:262)

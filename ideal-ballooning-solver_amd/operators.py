@@ -137,6 +137,34 @@ def _gamma_ball_nearest(ctx, dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, sigm
     return float(r["gam"][0]), r["X"][0], r["dX"][0], g, c, f
 
 
+def gamma_ball_full_many(dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, ctx=None, eigenpair="max", sigma0=0.42):
+    """gamma_ball_full for n lines in one call, on ANY increasing grids: dPdrho (n,), theta_PEST (N,) shared or (n, N), the four arrays
+    (n, N).  Returns (gam (n,), X, dX, g, c, f), each array (n, N), with the meaning of utils.py:1624: every line is regridded as
+    upstream does (utils.py:1565-1576) and solved on the device (Context.gamma_points_theta with zero theta0 planes); a uniform grid
+    goes the same way and agrees with gamma_ball_full to rounding.  All lines share the window theta_PEST[..., 0], theta_PEST[..., -1].
+    eigenpair="max": lam_max's eigenpair; "nearest": the one nearest sigma0, as upstream (utils.py:1597).  A line whose grid is not
+    increasing on the window comes back NaN.  numpy arrays or torch CUDA tensors."""
+    if eigenpair not in ("max", "nearest"):
+        raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
+    ctx = ctx or default_context()
+    if len(B.shape) != 2:
+        raise IbsError("gamma_ball_full_many: B, gradpar, cvdrift and gds2 must be (n, N), not %s" % (tuple(B.shape),))
+    if type(B).__module__.startswith("torch"):
+        import torch
+        z, zn = torch.zeros_like(B), torch.zeros(B.shape[0], dtype=B.dtype, device=B.device)
+        dPdrho = torch.as_tensor(dPdrho, dtype=B.dtype, device=B.device)
+    else:
+        B, gradpar, cvdrift, gds2 = (np.asarray(a, dtype=np.float64) for a in (B, gradpar, cvdrift, gds2))
+        theta_PEST = np.asarray(theta_PEST, dtype=np.float64)
+        z, zn = np.zeros_like(B), np.zeros(B.shape[0])
+        dPdrho = np.asarray(dPdrho, dtype=np.float64)
+    geo = (theta_PEST, B, gradpar, cvdrift, z, gds2, z, z, dPdrho, zn)
+    rows = ctx.assemble_gcf_theta(*geo, points=True)
+    kw = dict(sigma=float(sigma0)) if eigenpair == "nearest" else {}
+    r = ctx.gamma_points_theta(*geo, want_X=True, eigenpair=eigenpair, **kw)
+    return r["gam"], r["X"], r["dX"], rows["g"], rows["c"], rows["f"]
+
+
 def marginal_dPdrho(dPdrho, theta_PEST, B, gradpar, cvdrift, gds2, ctx=None):
     """The pressure gradient at which the line of gamma_ball_full's arguments is marginally stable, at FIXED geometry arrays:
     returns (dPdrho_crit, s*, X) with dPdrho_crit = s* dPdrho, s* the critical scale of Context.marginal_gcf (s* < 1: the line is

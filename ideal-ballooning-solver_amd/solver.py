@@ -576,6 +576,132 @@ class Context:
                      ar.out("info", shape, _I32, want_info))
         return ar.result(rc)
 
+    # ---- lines on a non-uniform theta grid (include/ibs.h: ibs_regrid_rows_f64 and the *_theta_f64 entry points) -------------
+    @staticmethod
+    def _theta_window(theta, window):
+        """(theta_lo, theta_hi) as host floats: `window`, or the two end values of theta (of its first row: all lines share the window).
+        The library takes them as host scalars, so for a device tensor this is one small copy to the host."""
+        if window is not None:
+            lo, hi = window
+            return float(lo), float(hi)
+        first = theta if len(theta.shape) == 1 else theta[0]
+        return float(first[0]), float(first[-1])
+
+    @staticmethod
+    def _theta_rows(what, theta, n_rows, N):
+        """theta_ld of a grid argument: (N,) = one shared grid (0), (n_rows, N) = one row each (N)"""
+        shape = tuple(theta.shape)
+        if shape == (N,):
+            return 0
+        if shape == (n_rows, N):
+            return N
+        raise IbsError("%s: theta must be (%d,) or (%d, %d), not %s" % (what, N, n_rows, N, shape))
+
+    def _theta_call(self, first):
+        """the call object of a theta entry point: its memory kind is that of the data arrays; a host theta goes up with them"""
+        return _Args(self, device=first.device, host=False) if _is_torch(first) else _Args(self, host=True)
+
+    def regrid_rows(self, theta, g, c=None, f=None, window=None, want_info=False):
+        """raw rows on a non-uniform grid -> the uniform grid of the same window, as utils.py:1565-1576 (ibs_regrid_rows_f64): g (and c,
+        f, each optional) (n_sys, N) on theta, (N,) shared or (n_sys, N).  Returns dict(h, g, gh, c, f[, info], nbad): h the spacing
+        and (g, gh, c, f) the rows to hand to solve_gcf(h, g, c, f, gh=gh) / solve_gcf_nearest / solve_gcf_modes; c / f None where not
+        given.  window=None reads the two end values of theta (a small copy to the host for a device tensor); a row that is not an
+        increasing grid on the window gives NaN rows and status bit 1 (counted in nbad)."""
+        n_sys, N = g.shape
+        ld_t = self._theta_rows("regrid_rows", theta, n_sys, N)
+        lo, hi = self._theta_window(theta, window)
+        ar = self._theta_call(g)
+        h = C.c_double(0.0)
+        rc = ar.call("ibs_regrid_rows_f64", n_sys, N, ar.inp(theta, upload=True), ld_t, lo, hi, ar.inp(g), ar.inp(c), ar.inp(f), N,
+                     ar.out("g", (n_sys, N)), ar.out("gh", (n_sys, N)), ar.out("c", (n_sys, N), want=c is not None),
+                     ar.out("f", (n_sys, N), want=f is not None), N, C.byref(h), ar.out("info", (n_sys,), _I32, want_info))
+        out = ar.result(rc)
+        out.setdefault("c", None)
+        out.setdefault("f", None)
+        out["h"] = h.value
+        return out
+
+    def assemble_gcf_theta(self, theta, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, points=False,
+                           window=None, want_info=False):
+        """the regridded rows of every (line, theta0) system of geometry on a non-uniform grid (ibs_assemble_gcf_theta_f64): g, c, f are
+        formed at the samples and interpolated, as upstream.  Arrays (n_lines, N), dPdrho (n_lines,), theta (N,) or (n_lines, N);
+        theta0 (n_theta0,), or with points=True (n_lines,): one per line.  Returns dict(h, g, gh, c, f[, info], nbad), the rows shaped
+        (n_lines, n_theta0, N) -- (n_lines, N) with points=True.  window as in regrid_rows."""
+        geo7 = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        n_lines, N = bmag.shape
+        ld_t = self._theta_rows("assemble_gcf_theta", theta, n_lines, N)
+        lo, hi = self._theta_window(theta, window)
+        shape = (n_lines,) if points else (n_lines, int(theta0.shape[0]))
+        ar = self._theta_call(bmag)
+        h = C.c_double(0.0)
+        rc = ar.call("ibs_assemble_gcf_theta_f64", n_lines, 1 if points else shape[1], N, ar.inp(theta, upload=True), ld_t, lo, hi,
+                     *[ar.inp(a) for a in geo7], N, ar.inp(dPdrho), ar.inp(theta0), 1 if points else 0,
+                     ar.out("g", shape + (N,)), ar.out("gh", shape + (N,)), ar.out("c", shape + (N,)), ar.out("f", shape + (N,)),
+                     C.byref(h), ar.out("info", shape, _I32, want_info))
+        out = ar.result(rc)
+        out["h"] = h.value
+        return out
+
+    def _theta_composed(self, what, points, theta, geo7, dPdrho, theta0, want_X, want_info, window, eigenpair, sigma, n_modes):
+        """eigenpair="nearest" / n_modes=K of the theta scans: assemble_gcf_theta, then the raw solver with gh, reshaped"""
+        if eigenpair not in ("max", "nearest"):
+            raise IbsError("%s: eigenpair must be 'max' or 'nearest', not %r" % (what, eigenpair))
+        if n_modes is not None and eigenpair == "nearest":
+            raise IbsError("%s: n_modes and eigenpair='nearest' exclude each other" % what)
+        if eigenpair == "nearest" and sigma is None:
+            raise IbsError("%s: eigenpair='nearest' needs sigma" % what)
+        rows = self.assemble_gcf_theta(theta, *geo7, dPdrho, theta0, points=points, window=window, want_info=True)
+        shape, N = tuple(rows["g"].shape[:-1]), rows["g"].shape[-1]
+        n_sys = int(np.prod(shape))
+        g, gh, c, f = (rows[k].reshape(n_sys, N) for k in ("g", "gh", "c", "f"))
+        if n_modes is not None:
+            K = self._n_modes(n_modes)
+            r = self.solve_gcf_modes(rows["h"], g, c, f, K, gh=gh, want_X=want_X, want_info=want_info)
+            tail = (K,)
+        else:
+            r = self.solve_gcf_nearest(rows["h"], g, c, f, sigma, gh=gh, want_X=want_X, want_info=want_info)
+            tail = ()
+        out = {k: (v.reshape(shape + tail + ((N,) if k in ("X", "dX") else ())) if k != "nbad" else v) for k, v in r.items()}
+        out["h"] = rows["h"]
+        return out
+
+    def gamma_scan_theta(self, theta, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_X=False,
+                         want_info=False, window=None, eigenpair="max", sigma=None, n_modes=None):
+        """gamma_scan for geometry on a NON-UNIFORM theta grid (ibs_gamma_scan_theta_f64): every line is regridded as upstream does
+        (utils.py:1565-1576) and solved with the half-grid row, on the device.  theta (N,) shared or (n_lines, N); arrays (n_lines, N);
+        dPdrho (n_lines,); theta0 (n_theta0,).  Returns dict(gam, lam[, X, dX][, info], nbad) shaped (n_lines, n_theta0[, N]).
+        window=None reads the two end values of theta -- for a device tensor a small copy to the host; pass window=(lo, hi) to avoid
+        it.  A line whose row is not an increasing grid on the window gives NaN and status bit 1.
+        eigenpair="nearest" (with sigma, a scalar or (n_lines, n_theta0)) and n_modes=K are compositions: assemble_gcf_theta, then
+        solve_gcf_nearest / solve_gcf_modes with gh; their dicts, reshaped to (n_lines, n_theta0[, K][, N])."""
+        geo7 = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        if eigenpair != "max" or n_modes is not None:
+            return self._theta_composed("gamma_scan_theta", False, theta, geo7, dPdrho, theta0, want_X, want_info, window, eigenpair,
+                                        sigma, n_modes)
+        return self._theta_scan("ibs_gamma_scan_theta_f64", False, theta, geo7, dPdrho, theta0, want_X, want_info, window)
+
+    def gamma_points_theta(self, theta, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, want_X=False,
+                           want_info=False, window=None, eigenpair="max", sigma=None, n_modes=None):
+        """gamma_points on a non-uniform grid (ibs_gamma_points_theta_f64: the final solve of ball_scan.py:322-339 for many lines at
+        once): line i at its own theta0[i]; theta (N,) or (n_pts, N).  Returns dict(gam, lam[, X, dX][, info], nbad) shaped (n_pts[, N]):
+        the bits gamma_scan_theta gives at the same (line, theta0).  window, eigenpair, sigma and n_modes as in gamma_scan_theta."""
+        geo7 = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        if eigenpair != "max" or n_modes is not None:
+            return self._theta_composed("gamma_points_theta", True, theta, geo7, dPdrho, theta0, want_X, want_info, window, eigenpair,
+                                        sigma, n_modes)
+        return self._theta_scan("ibs_gamma_points_theta_f64", True, theta, geo7, dPdrho, theta0, want_X, want_info, window)
+
+    def _theta_scan(self, name, points, theta, geo7, dPdrho, theta0, want_X, want_info, window):
+        n_lines, N = geo7[0].shape
+        ld_t = self._theta_rows(name, theta, n_lines, N)
+        lo, hi = self._theta_window(theta, window)
+        shape = (n_lines,) if points else (n_lines, int(theta0.shape[0]))
+        ar = self._theta_call(geo7[0])
+        rc = ar.call(name, *shape, N, ar.inp(theta, upload=True), ld_t, lo, hi, *[ar.inp(a) for a in geo7], N, ar.inp(dPdrho),
+                     ar.inp(theta0), ar.out("gam", shape), ar.out("lam", shape), ar.out("X", shape + (N,), want=want_X),
+                     ar.out("dX", shape + (N,), want=want_X), ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
+
     def scan_starts(self, alpha_scan, theta0_scan, pack, n_bad, want_sigma0=False):
         """start points (n_surf, 2) = (alpha, theta0) of the refinement from the per-surface maxima `pack`, on the device
         (ibs_scan_starts_f64; ball_scan.py:279-295).  All arguments device tensors; n_bad: int32 tensor of one element that

@@ -12,7 +12,9 @@
  *   - `mem`: IBS_MEM_DEVICE = all data pointers are device (HBM) pointers, the call is
  *     asynchronous on the context's stream; IBS_MEM_HOST = host pointers, the library stages
  *     through its own device workspace and the call returns after the results are back.
- *   - grids are uniform in theta with N points (N odd, N >= 66) and spacing h; arrays of one system/line are contiguous,
+ *   - grids are uniform in theta with N points (N odd, N >= 66) and spacing h -- except in the four *_theta_f64 / ibs_regrid_rows_f64
+ *     entry points, which take any increasing grid and regrid it as the reference does (utils.py:1565-1576); every entry point that
+ *     takes h alone assumes a uniform grid and does not look at theta.  Arrays of one system/line are contiguous,
  *     consecutive systems are `ld` elements apart.  Up to N = 2050 the register-resident kernels run (one wavefront or a part of
  *     one per system).  The reference takes any length (utils.py:1556-1624; its own rule N = 2 mpol ntor 4 + 1, ball_scan.py:201-208,
  *     passes 2050 from mpol ntor > 256 on): for 2050 < N <= 65537 ibs_solve_gcf_f64 / _f32, ibs_solve_gcfh_f64, ibs_gamma_scan_f64 /
@@ -431,6 +433,56 @@ int ibs_gamma_points_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const
                          const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
                          const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, double* gam,
                          double* lam, double* X, double* dX, double* dgam_dtheta0, int32_t* info, int32_t mem);
+
+/* Lines on a NON-UNIFORM theta grid.
+ * Replaces: utils.py:1565-1576 -- gamma_ball_full takes any increasing theta_PEST and regrids before it solves: g, c, f by np.interp
+ * onto np.linspace(theta[0], theta[-1], N), g once more at the uniform half points, h = np.diff(th_half)[2] -- batched on the device
+ * (csrc/ibs_regrid.hpp states the arithmetic with its rounding, csrc/ibs_regrid.hip runs it).  The four entry points share
+ *   theta, theta_ld: the grids; theta_ld = 0: theta[N], one grid shared by all lines, theta_ld >= N: one row per line (per system of
+ *     ibs_regrid_rows_f64), theta_ld apart (anything else: IBS_ERR_ARG);
+ *   theta_lo, theta_hi: HOST scalars, the window every line shares (finite, theta_hi > theta_lo, else IBS_ERR_ARG): every grid must have
+ *     theta[0] == theta_lo and theta[N-1] == theta_hi.  h is a host scalar everywhere in this library, so it is not read from device memory;
+ *   h_out: host pointer, optional: the spacing to hand to the raw solvers with the rows.
+ * A row is a grid when it is finite, strictly increasing and has its ends on the window.  A line whose row is not gets NaN rows and
+ * status bit 1 in its info word (growth rates: NaN and the solver's status bit 1), counted by return values > 0; no other line changes
+ * by a bit.  One thread per uniform node finds the node's interval of the line's grid once, by bisection (the row staged in LDS up to
+ * 2050 points, read from global memory beyond) and serves every system of the line with it.  No sums and no atomics: the results are
+ * bitwise repeatable and independent of the batch, of the order of the lines and of the chunking.  Any odd N in [66, 65537] (even N
+ * and N outside: IBS_ERR_UNSUPPORTED); all argument checks run before the context is touched.
+ *
+ * ibs_regrid_rows_f64: raw rows g, c, f [n_sys][ld] on theta -> g_u, c_u, f_u on the uniform nodes and gh at the half nodes (gh[k]
+ * between nodes k and k+1, gh[N-1] = 0), [n_sys][ld_out]: the arguments of ibs_solve_gcfh_f64 / _nearest_f64 / _modes_f64.  c / c_u and
+ * f / f_u are optional as pairs; info [n_sys] optional. */
+int ibs_regrid_rows_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, const double* theta, int64_t theta_ld, double theta_lo,
+                        double theta_hi, const double* g, const double* c, const double* f, int64_t ld, double* g_u, double* gh,
+                        double* c_u, double* f_u, int64_t ld_out, double* h_out, int32_t* info, int32_t mem);
+/* The same from the geometry: for every (line, theta0) system g, c, f are formed AT THE SAMPLES (ball_scan.py:267-268,
+ * utils.py:1560-1562: the expressions of ibs_gamma_scan_f64) and then interpolated -- upstream's order: the formed rows are
+ * interpolated, not the geometry arrays.  Arrays, dPdrho and theta0 as in ibs_gamma_scan_f64; theta0_per_line != 0: n_theta0 = 1 and
+ * theta0 [n_lines], one value per line (as ibs_gamma_points_f64).  g_u, gh, c_u, f_u [n_lines * n_theta0][N], all required;
+ * info [n_lines * n_theta0] optional. */
+int ibs_assemble_gcf_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld,
+                               double theta_lo, double theta_hi, const double* bmag, const double* gradpar, const double* cvdrift,
+                               const double* cvdrift0, const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                               const double* dPdrho, const double* theta0, int32_t theta0_per_line, double* g_u, double* gh,
+                               double* c_u, double* f_u, double* h_out, int32_t* info, int32_t mem);
+/* ibs_gamma_scan_f64 on a non-uniform grid: the regridded rows of whole lines are written to a workspace of about 1 GiB at most,
+ * chunk after chunk (option "nearest_chunk_systems" sets the chunk instead, as in ibs_gamma_scan_nearest_f64; a chunk of one line that
+ * cannot be allocated fails with the bytes it needs), and solved by the kernel of ibs_solve_gcfh_f64 -- one wave per system up to 2050
+ * points, the long-grid path beyond.  Outputs [n_lines][n_theta0] (X, dX: [n_lines][n_theta0][N]), all optional.  On a uniform grid
+ * the result differs from ibs_gamma_scan_f64's by rounding only (gh is the interpolant at the midpoint there, not the mean). */
+int ibs_gamma_scan_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld,
+                             double theta_lo, double theta_hi, const double* bmag, const double* gradpar, const double* cvdrift,
+                             const double* cvdrift0, const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                             const double* dPdrho, const double* theta0, double* gam, double* lam, double* X, double* dX,
+                             int32_t* info, int32_t mem);
+/* ibs_gamma_points_f64 on a non-uniform grid (the final solve of ball_scan.py:322-339): line i at its own theta0[i]; the bits of
+ * ibs_gamma_scan_theta_f64 at the same (line, theta0). */
+int ibs_gamma_points_theta_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, const double* theta, int64_t theta_ld, double theta_lo,
+                               double theta_hi, const double* bmag, const double* gradpar, const double* cvdrift,
+                               const double* cvdrift0, const double* gds2, const double* gds21, const double* gds22, int64_t ld,
+                               const double* dPdrho, const double* theta0, double* gam, double* lam, double* X, double* dX,
+                               int32_t* info, int32_t mem);
 
 /* Start points of the refinement from the coarse scan's per-surface maxima, on the device (device pointers only).
  * Replaces: ball_scan.py:279-295 -- the first maximum of the surface's (alpha, theta0) table gives x0 = (alpha_scan[i],
