@@ -94,6 +94,7 @@ SYMBOLS = {
     "ibs_gamma_points_reclose_f64": (C.c_int, [_P, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _D, _P, _P, _P, _P, _P, _I32]),
     "ibs_surface_argmax_f64": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _I32]),
     "ibs_surface_argmax_pack_f64": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "ibs_scan_peaks_f64": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32]),
 }
 
 

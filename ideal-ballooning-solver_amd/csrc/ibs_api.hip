@@ -20,6 +20,7 @@
 #include "ibs_refine.hpp"
 #include "ibs_certify.hpp"
 #include "ibs_regrid.hpp"
+#include "ibs_scan_peaks.hpp"
 #include <chrono>
 #include <thread>
 
@@ -451,7 +452,8 @@ __global__ void k_scan_starts(int n_surf, int n_alpha, int n_theta0, const doubl
   if (!ok) atomicAdd(n_bad, 1);                                           // a NaN / flagged table: reported, start (0, 0)
   else if (m != 0.0) {
     const int idx = (int)fi, i = idx / n_theta0, j = idx - i * n_theta0;   // first maximum, row-major (ball_scan.py:283-288)
-    a = alpha[i]; t = theta0[j]; sg = 1.3 * fabs(m) + 0.05;               // ball_scan.py:289, 295
+    // ball_scan.py:289, 295, rounded as Python rounds it (the product, then the sum: pick_start's bits, not a fused multiply-add's)
+    a = alpha[i]; t = theta0[j]; sg = ibs::peaks_sigma0(m);
   }
   start[2 * s] = a; start[2 * s + 1] = t;
   if (sigma0) sigma0[s] = sg;
@@ -2228,6 +2230,35 @@ int ibs_surface_argmax_pack_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per, con
   hipLaunchKernelGGL(k_surface_argmax, dim3(n_surf), dim3(argmax_threads(n_per)), 0, ctx->stream, n_per, gam, (int*)nullptr, (double*)nullptr, pack);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+int ibs_scan_peaks_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_alpha, int32_t n_theta0, int32_t n_starts, const double* alpha,
+                       const double* theta0, const double* gam, double* start, double* peak, int32_t* index, double* sigma0,
+                       int32_t* n_found, int32_t* n_bad, int32_t mem) {
+  if (n_surf < 0 || n_alpha < 1 || n_theta0 < 1 || n_starts < 1 || n_starts > ibs::kMaxStarts || !alpha || !theta0 || !gam || !start ||
+      !peak || !n_bad)
+    return fail(IBS_ERR_ARG, "bad arguments (n_starts in [1, %d], every dimension >= 1, gam, start, peak and n_bad required)", ibs::kMaxStarts);
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if ((int64_t)n_alpha * n_theta0 > 0x7fffffff / 2) return fail(IBS_ERR_ARG, "n_alpha * n_theta0 too large");
+  if (n_surf == 0) return 0;
+  ON_DEVICE(ctx);
+  const int n_per = n_alpha * n_theta0;
+  const size_t ns = (size_t)n_surf, K = (size_t)n_starts;
+  const bool host = mem == IBS_MEM_HOST;
+  int added = 0;                     // host pointers: the call's own count, added to *n_bad once the outputs are back
+  ibs::ScanPeaksArgs a{n_surf, n_alpha, n_theta0, n_starts};
+  auto decl = [&](Stage& s) {
+    a.alpha = s.in(alpha, (size_t)n_alpha); a.theta0 = s.in(theta0, (size_t)n_theta0); a.gam = s.in(gam, ns * n_per);
+    a.start = s.out(start, 2 * ns * K); a.peak = s.out(peak, ns * K); a.index = s.out(index, ns * K); a.sigma0 = s.out(sigma0, ns * K);
+    a.n_found = s.out(n_found, ns); a.n_bad = host ? s.out(&added, 1) : n_bad;
+  };
+  const int rc = staged(ctx, mem, decl, [&]() -> int {
+    if (host) HIPCHK(hipMemsetAsync(a.n_bad, 0, sizeof(int), ctx->stream));
+    HIPCHK(ibs::launch_scan_peaks(a, argmax_threads(n_per), ctx->stream));
+    return 0;
+  });
+  if (rc == 0 && host) *n_bad += added;
+  return rc;
 }
 
 int ibs_refine_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_nyq, const double* xm, const double* xn,

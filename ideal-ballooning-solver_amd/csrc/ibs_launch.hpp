@@ -230,6 +230,16 @@ hipError_t launch_assemble_regrid(const RegridArgs& a, hipStream_t st);
 // NaN into lam, gam [n_sys] and X, dX [n_sys][N] (each optional) of the systems whose flag word (RegridArgs::info) carries status bit 1
 hipError_t launch_regrid_poison(long n_sys, int N, const int* flag, double* lam, double* gam, double* X, double* dX, hipStream_t st);
 
+// the n_starts best peaks of every surface's coarse table and the refinement's starts from them (ibs_scan_peaks.hip; the rule:
+// ibs_scan_peaks.hpp).  gam [n_surf][n_alpha][n_theta0]; start [n_surf][n_starts][2], peak [n_surf][n_starts]; index, sigma0
+// [n_surf][n_starts] and n_found [n_surf] optional; *n_bad is added to.  One block of `threads` (a multiple of 64, at most 256) per surface
+struct ScanPeaksArgs {
+  int n_surf, n_alpha, n_theta0, n_starts;
+  const double *alpha, *theta0, *gam;
+  double *start, *peak; int* index; double* sigma0; int* n_found; int* n_bad;
+};
+hipError_t launch_scan_peaks(const ScanPeaksArgs& a, int threads, hipStream_t st);
+
 // field-line geometry kernel (ibs_geometry.hip)
 // dPdrho[line] = -0.5 mean((cvdrift - gbdrift) bmag^2) of lines laid out geo[k * plane + line * ld + j], k = 0 .. 7 (ball_scan.py:262)
 hipError_t launch_line_dPdrho(int n_lines, int N, long ld, size_t plane, const double* geo, double* dPdrho, hipStream_t st);

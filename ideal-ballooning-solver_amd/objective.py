@@ -152,6 +152,9 @@ class AdjointStep:
     certify=True (eigenpair="max" only, else ValueError) certifies and re-closes the coarse tables and the final solves of every
     equilibrium (BallooningScan's certify=True; the refinement's own evaluations are not certified): the counts travel with the rows'
     one copy into .last_certificate = dict(checked, reclosed, failed), summed over the ranks; failed > 0 raises IbsError.
+    n_starts=K > 1 (an integer in [1, 16], else ValueError) refines every surface of every equilibrium from the K best peaks of its
+    coarse table and reports the best candidate (BallooningScan's n_starts); run()'s result keeps its keys.  n_starts=1, the default,
+    builds the scan exactly as before.
 
     Upstream this is ball_submit.py:64-95 (one `srun ball_scan.py iter dof ngroups` per DOF-perturbed equilibrium, each
     running vmec_splines -> coarse scan -> argmax -> L-BFGS-B -> final solve, ball_scan.py:190-347) followed by
@@ -167,8 +170,9 @@ class AdjointStep:
 
     def __init__(self, ctx, theta, svals, device, nalpha=24, ntheta0=15, del_alpha=0.004, gamma_thresh=-2.0e-4, prefac=50.0,
                  rank=0, world=1, dist=None, n_threads=0, n_chunks=4, gather_device=None, chunk_growth=1.0, eigenpair="max",
-                 jac="reference", certify=False):
-        from .scan import check_eigenpair, check_jac
+                 jac="reference", certify=False, n_starts=1):
+        from .scan import check_eigenpair, check_jac, check_n_starts
+        self.n_starts = check_n_starts(n_starts)
         self.eigenpair = check_eigenpair(eigenpair)
         self.jac = check_jac(jac)
         self.certify = bool(certify)
@@ -199,7 +203,8 @@ class AdjointStep:
             self._scan = BallooningScan(self.ctx, None, self.theta, np.tile(self.svals, n_eq_local), nalpha=self.nalpha,
                                         ntheta0=self.ntheta0, del_alpha=self.del_alpha, tables=tables, device=self.device,
                                         surf_index=np.arange(n), eigenpair=self.eigenpair, jac=self.jac,
-                                        **(dict(certify=True) if self.certify else {}))
+                                        **(dict(certify=True) if self.certify else {}),
+                                        **(dict(n_starts=self.n_starts) if self.n_starts > 1 else {}))
         self._scan.tables = tables
         return self._scan
 

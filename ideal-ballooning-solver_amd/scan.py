@@ -38,6 +38,60 @@ def pick_start(gam_table, alpha_scan, theta0_scan):
     return float(alpha_scan[i]), float(theta0_scan[j]), 1.3 * abs(float(gam_table[i, j])) + 0.05, (i, j)
 
 
+MAX_STARTS = 16
+
+
+def check_n_starts(n_starts):
+    ok = isinstance(n_starts, (int, np.integer)) and not isinstance(n_starts, bool)
+    if not ok or not 1 <= n_starts <= MAX_STARTS:
+        raise ValueError("n_starts must be an integer in [1, %d], not %r" % (MAX_STARTS, n_starts))
+    return int(n_starts)
+
+
+def pick_starts(gam_table, alpha_scan, theta0_scan, n_starts):
+    """the n_starts best local maxima ("peaks") of a coarse table (n_alpha, n_theta0) as the starts of a multi-start refinement:
+    the rule of ibs_scan_peaks_f64 (csrc/ibs_scan_peaks.hpp) in numpy, and that kernel's oracle.
+    A neighbour w of entry v beats it if w > v, or w == v and w has the smaller row-major index; a NaN never beats anything.  An
+    entry is a peak if it is not NaN and none of its up to eight neighbours (i +- 1, j +- 1) inside the table beats it -- no
+    wrap-around: alpha in [0, pi] and theta0 in [0, pi / 2] are a box, as in the refinement's bounds.  Peaks rank by value
+    descending, ties by index ascending, so the first maximum of the table is peak 0.
+    Slot 0 is pick_start's: start (alpha[i], theta0[j]), sigma0 = 1.3 |gam| + 0.05; a maximum of exactly 0 starts at (0, 0) with
+    sigma0 = 0.05 (ball_scan.py:279-282); one that is not finite (or a table of NaN) is counted in n_bad -- where pick_start
+    raises -- and starts at (0, 0).  In the last two cases n_found = 0 and every slot repeats slot 0.  Slots 1 .. n_starts - 1 are
+    the next peaks in rank, each with its own start, value, index and sigma0 = 1.3 |peak| + 0.05; with fewer peaks than slots
+    n_found is the number found and the remaining slots repeat slot 0.
+    Returns dict(start (n_starts, 2), peak (n_starts,), index int32 (n_starts,): row-major, -1 where the start is no node,
+    sigma0 (n_starts,), n_found, n_bad)."""
+    K = check_n_starts(n_starts)
+    tab = np.asarray(gam_table, dtype=np.float64)
+    na, nt = tab.shape
+    idx = np.arange(na * nt, dtype=np.int64).reshape(na, nt)
+    pv = np.full((na + 2, nt + 2), np.nan); pv[1:-1, 1:-1] = tab
+    pi = np.full((na + 2, nt + 2), -1, dtype=np.int64); pi[1:-1, 1:-1] = idx
+    beaten = np.isnan(tab)
+    with np.errstate(invalid="ignore"):
+        for di in (0, 1, 2):
+            for dj in (0, 1, 2):
+                if (di, dj) != (1, 1):
+                    w, iw = pv[di:di + na, dj:dj + nt], pi[di:di + na, dj:dj + nt]
+                    beaten |= (w > tab) | ((w == tab) & (iw < idx))          # (the NaN frame never beats: both comparisons are false)
+    flat = tab.reshape(-1)
+    peaks = np.nonzero(~beaten.reshape(-1))[0]
+    picks = peaks[np.lexsort((peaks, -flat[peaks]))][:K]
+    m = float(flat[picks[0]]) if len(picks) else float("nan")
+    ok = bool(np.isfinite(m))
+    node = ok and m != 0.0
+    nf = len(picks) if node else 0
+    out = dict(start=np.zeros((K, 2)), peak=np.full(K, m), index=np.full(K, -1, dtype=np.int32), sigma0=np.full(K, 0.05),
+               n_found=nf, n_bad=0 if ok else 1)
+    for k in range(K if node else 0):
+        e = int(picks[k if k < nf else 0])
+        v = float(flat[e])
+        out["start"][k] = alpha_scan[e // nt], theta0_scan[e % nt]
+        out["peak"][k], out["index"][k], out["sigma0"][k] = v, e, 1.3 * abs(v) + 0.05       # ball_scan.py:289, 295
+    return out
+
+
 def gather_rows_tensor(local, n_surf, rank, world, dist, ctx=None):
     """ONE all-gather of per-surface rows held as a torch tensor (device tensor: RCCL, in-stream; CPU tensor: gloo).
     ctx: a Context that holds a native communicator (Context.comm_init): the collective is then issued by the library
@@ -131,11 +185,19 @@ class BallooningScan:
     (surface_argmax_pack), and the final solves are certified and re-closed the same way.  The solves inside the refinement's objective
     are NOT certified: they only steer the optimizer, and the final solve at its end point is what is reported.  The counts of the
     last run are in .last_certificate = dict(checked, reclosed, failed); failed > 0 raises IbsError.  certify=False (the default)
-    takes exactly the code path it took before the option existed."""
+    takes exactly the code path it took before the option existed.
+    n_starts=K > 1: every surface is refined from the K best peaks of its coarse table (pick_starts / ibs_scan_peaks_f64: local
+    maxima over the eight neighbours, ranked by value; slot 0 is the first maximum, upstream's one start) and the best refined
+    candidate is reported, slot 0 winning ties -- a narrow basin whose crest lies between nodes can rank below the first maximum in
+    the table and still hold the surface's maximum.  All n K points run through the refinement and the final solve in one batch; a
+    surface with fewer than K peaks repeats slot 0 in the remaining slots (duplicated work, never preferred by the first-maximum
+    rule).  .last_candidates (n_own, K, 3) = (theta0, alpha, gam) of every slot and .last_peaks = dict(index, value (n_own, K),
+    n_found (n_own,)) describe the last run (device tensors on the device path, not synchronised).  n_starts=1 (the default) takes
+    exactly the code path and the calls it took before the option existed."""
 
     def __init__(self, ctx, fieldlines, theta, rho_arr, nalpha=24, ntheta0=15, del_alpha=0.004,
                  rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None, eigenpair="max",
-                 jac="reference", certify=False):
+                 jac="reference", certify=False, n_starts=1):
         """fieldlines: host geometry callable (see module docstring), or None together with
         tables=SurfaceTables (row F1): then the geometry is produced on `device` by the HIP geometry kernel and consumed
         there -- coarse scan, per-surface maximum, start points, refinement and final solve all stay in HBM and ONE small
@@ -143,7 +205,9 @@ class BallooningScan:
         tables.s nearest to rho_arr[k].  Table sets that hold several equilibria (SurfaceTables.from_wouts: s repeats
         per equilibrium) need the explicit index.
         eigenpair: "max" or "nearest" (anything else raises ValueError); jac: "reference", "exact" or "exact_tangent" (see the class
-        docstring; anything else raises IbsError, which is a ValueError too)."""
+        docstring; anything else raises IbsError, which is a ValueError too); n_starts: an integer in [1, 16] (else ValueError)."""
+        self.n_starts = check_n_starts(n_starts)
+        self.last_candidates = self.last_peaks = None
         self.eigenpair = check_eigenpair(eigenpair)
         self.nearest = eigenpair == "nearest"
         self.jac = check_jac(jac)
@@ -522,17 +586,19 @@ class BallooningScan:
             val, jac = self.ctx.obj_w_grad(self.h, geo, t0, d)
         return val.cpu().numpy(), jac.cpu().numpy()
 
-    def refine_batched(self, starts, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, sigma0=None):
+    def refine_batched(self, starts, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, sigma0=None, surf_idx=None):
         """the per-surface L-BFGS-B of ball_scan.py:307-314 (same bounds, tolerances and iteration cap) for every owned
         surface at once, driven from the host: one optimizer state per surface (csrc/ibs_lbfgsb2.hpp through the C ABI
         ibs_lbfgsb2_*), and every round ONE batched geometry + objective launch for the surfaces still running.
         The host-driven form of refine_device(), which it is tested against.
-        starts: (n, 2); sigma0 (n,): the shifts of eigenpair="nearest".  Returns (x_opt (n, 2), f_opt (n,) = -gam, rounds)."""
+        starts: (n, 2); sigma0 (n,): the shifts of eigenpair="nearest"; surf_idx (n,): the table index of every point's surface
+        (None: point k lies on owned surface k -- with it n points need not be n surfaces: the multi-start refinement).
+        Returns (x_opt (n, 2), f_opt (n,) = -gam, rounds)."""
         import ctypes as C
         from . import _lib
         lib = _lib.lib()
         lo = np.array([0.0, 0.0]); hi = np.array([np.pi, 0.5 * np.pi])
-        surf = self._own_surf()
+        surf = self._own_surf() if surf_idx is None else np.ascontiguousarray(surf_idx, dtype=np.int32)
         n = len(surf)
         p = lambda a: C.c_void_p(a.ctypes.data)
         x = np.clip(np.asarray(starts, dtype=np.float64).reshape(n, 2), lo, hi)
@@ -596,7 +662,8 @@ class BallooningScan:
         """device copies of what does not change between optimizer iterations: line -> (surface, alpha) tables of the coarse
         scan, the grids, the point -> surface map of the refinement"""
         import torch
-        key = (tuple(self.own), str(self.device))
+        K = self.n_starts
+        key = (tuple(self.own), str(self.device)) + ((K,) if K > 1 else ())
         if self._resident.get("key") != key:
             dev, na = self.device, len(self.alpha_scan)
             own = self._own_surf()
@@ -604,6 +671,8 @@ class BallooningScan:
             self._resident = dict(key=key, surf=t(np.repeat(own, na).astype(np.int32)), al=t(np.tile(self.alpha_scan, len(own))),
                                   th=t(self.theta), t0=t(self.theta0_scan), alpha=t(self.alpha_scan), pt_surf=t(own.astype(np.int32)),
                                   n_bad=torch.zeros(1, dtype=torch.int32, device=dev))
+            if K > 1:          # (the point -> surface map of the multi-start refinement: K consecutive points per surface)
+                self._resident["pt_surf_k"] = self._resident["pt_surf"].repeat_interleave(K)
         return self._resident
 
     def device_rows(self, refine=True, phases=None, chunks=None, fill=None):
@@ -629,6 +698,8 @@ class BallooningScan:
         n = len(self.own)
         if n == 0:
             return torch.empty((0, 3), dtype=torch.float64, device=dev), torch.zeros((), dtype=torch.float64, device=dev)
+        if self.n_starts > 1:
+            return self._device_rows_multi(refine, phases, chunks, fill)
         res = self._resident_inputs()
         na = len(self.alpha_scan)
         ev = {}
@@ -712,6 +783,108 @@ class BallooningScan:
         bad = bad + res["n_bad"][0]
         self._last_rows = rows           # (sensitivity()'s default points)
         self._cert_dev = ccount          # (checked, reclosed, failed) of this call, on the device: read with the rows' one copy
+        mark("f1")
+        if phases is not None:
+            torch.cuda.synchronize()
+            span = lambda a, b: sum(x.elapsed_time(y) for x, y in zip(ev[a], ev[b]))
+            phases["geometry_ms"] = span("g0", "g1"); phases["scan_argmax_ms"] = span("g1", "s1")
+            phases["refine_ms"] = span("r0", "r1"); phases["final_solve_ms"] = span("r1", "f1")
+            if fill is not None:
+                phases["host_tables_ms"] = t_fill * 1e3
+                phases["coarse_chunks"] = len(chunks)
+        return rows, bad.to(torch.float64)
+
+    def _device_rows_multi(self, refine, phases, chunks, fill):
+        """device_rows() for n_starts = K > 1: per chunk the coarse table goes through ibs_scan_peaks_f64 (K starts per surface, and
+        their shifts in nearest mode); all n K points are refined in the form the mode uses for one start (ibs_refine_f64 on device
+        pointers, or refine_batched with the point -> surface map), ONE final geometry and ONE final solve run for all of them (all
+        certified and counted with certify=True), ibs_surface_argmax_pack_f64 over [n][K] picks every surface's best candidate (slot
+        0 wins ties) and a device gather forms the rows.  bad counts the flagged solves of ALL candidates, n_bad once per surface.
+        Nothing returns to the host in between beyond what the refinement form already does.  refine=False: slot 0, the rows of
+        n_starts = 1."""
+        import time
+        import torch
+        ctx, dev, K = self.ctx, self.device, self.n_starts
+        n = len(self.own)
+        res = self._resident_inputs()
+        na, nt = len(self.alpha_scan), len(self.theta0_scan)
+        ev = {}
+
+        def mark(name):
+            if phases is not None:
+                e = torch.cuda.Event(enable_timing=True); e.record(); ev.setdefault(name, []).append(e)
+        res["n_bad"].zero_()
+        chunks = chunks or [(0, n)]
+        f64 = dict(dtype=torch.float64, device=dev)
+        start, peak = torch.empty((n, K, 2), **f64), torch.empty((n, K), **f64)
+        index = torch.empty((n, K), dtype=torch.int32, device=dev)
+        found = torch.empty((n,), dtype=torch.int32, device=dev)
+        sig0 = torch.empty((n, K), **f64) if self.nearest else None
+        bad = res["n_bad"][0] * 0
+        ccount = torch.zeros(3, **f64) if self.certify else None
+        t_fill = 0.0
+        for c0, c1 in chunks:
+            if fill is not None:
+                t0 = time.perf_counter(); fill(c0, c1); t_fill += time.perf_counter() - t0
+            mark("g0")
+            geo = ctx.fieldline_geometry(self.tables, res["surf"][c0 * na:c1 * na], res["al"][c0 * na:c1 * na], res["th"], device=dev)
+            mark("g1")
+            g7 = [geo["geo"][k] for k in range(7)]
+            if self.nearest:
+                sc = ctx.gamma_scan_nearest(self.h, *g7, geo["dPdrho"], res["t0"], SIGMA_COARSE, want_info=True)
+                flagged = ((sc["info"] >> 16) & 3) != 0
+            else:
+                # (the scan kernel of n_starts = 1, so that the table -- and slot 0 -- has that run's bits; its fused maximum is not used)
+                sc = ctx.gamma_scan_argmax(self.h, g7, geo["dPdrho"], res["t0"], c1 - c0)
+                if self.certify:
+                    cert = ctx.certify_scan(self.h, *g7, geo["dPdrho"], res["t0"], sc["lam"])
+                    ctx.reclose_scan(self.h, *g7, geo["dPdrho"], res["t0"], cert, sc["lam"], sc["gam"])
+                    ccount = ccount + self._cert_counts(cert)
+                flagged = (sc["info"] >> 16) != 0
+            pk = ctx.scan_peaks(res["alpha"], res["t0"], sc["gam"].view(c1 - c0, na, nt), K, n_bad=res["n_bad"],
+                                want_sigma0=self.nearest, want_index=True, want_found=True)
+            mark("s1")
+            start[c0:c1] = pk["start"]; peak[c0:c1] = pk["peak"]; index[c0:c1] = pk["index"]; found[c0:c1] = pk["n_found"]
+            if self.nearest:
+                sig0[c0:c1] = pk["sigma0"]
+            bad = bad + flagged.sum()
+        self.last_peaks = dict(index=index, value=peak, n_found=found)
+        mark("r0")
+        pts = start.view(n * K, 2)
+        if refine:
+            if self.nearest or self.exact or len(self.theta) > 2050:
+                # (the host-driven state machines, as for one start: ibs_refine_f64 has no nearest-sigma and no exact form, and holds
+                # the register-resident evaluation kernel, N <= 2050)
+                xh, fh, rounds = self.refine_batched(pts.cpu().numpy(), sigma0=sig0.view(-1).cpu().numpy() if self.nearest else None,
+                                                     surf_idx=np.repeat(self._own_surf(), K))
+                xo = torch.from_numpy(xh).to(dev); ne = self._batched_evals if self.exact else None
+            else:
+                xo, fo, ne, rounds = ctx.refine_device(self.tables, res["pt_surf_k"], pts, res["th"], self.del_alpha)
+            mark("r1")
+            xa, xt = xo[:, 0].contiguous(), xo[:, 1].contiguous()
+            gf = ctx.fieldline_geometry(self.tables, res["pt_surf_k"], xa, res["th"], device=dev)
+            g7 = [gf["geo"][k] for k in range(7)]
+            if self.nearest:
+                fin = ctx.gamma_points_nearest(self.h, *g7, gf["dPdrho"], xt, SIGMA_FINAL, want_info=True)
+                bad = bad + (((fin["info"] >> 16) & 3) != 0).sum()
+            else:
+                fin = ctx.gamma_points(self.h, *g7, gf["dPdrho"], xt, want_info=True, **self._certify_kw())
+                if self.certify:
+                    ccount = ccount + self._cert_counts(fin["cert"])
+                bad = bad + ((fin["info"] >> 16) != 0).sum()
+            cand = torch.stack([xt, xa, fin["gam"]], dim=1).view(n, K, 3)
+            best = ctx.surface_argmax_pack(fin["gam"].view(n, K))[:, 1]
+            best = torch.where(best < K, best, torch.zeros_like(best)).to(torch.int64)      # (no finite candidate: slot 0, and bad > 0)
+            rows = torch.gather(cand, 1, best.view(n, 1, 1).expand(n, 1, 3)).reshape(n, 3)
+            self.last_refine = dict(n_evals=ne, rounds=rounds)
+        else:
+            mark("r1")
+            cand = torch.stack([start[:, :, 1], start[:, :, 0], peak], dim=2)
+            rows = cand[:, 0].contiguous()
+        self.last_candidates = cand
+        bad = bad + res["n_bad"][0]
+        self._last_rows = rows           # (sensitivity()'s default points)
+        self._cert_dev = ccount
         mark("f1")
         if phases is not None:
             torch.cuda.synchronize()
@@ -846,6 +1019,31 @@ class BallooningScan:
             raise IbsError("%d of %d eigenvalues could not be certified (cert bits 0-2 after the re-close)"
                            % (self.last_certificate["failed"], self.last_certificate["checked"]))
 
+    def _multi_start_rows(self, tabs, refine):
+        """the callback path for n_starts = K > 1: pick_starts on every coarse table, self.refine from each of the n_found distinct
+        starts (at least one), the best refined candidate by the first-maximum rule (slot 0 wins ties); the slots beyond n_found
+        repeat slot 0's candidate without running it again.  refine=False: slot 0, the rows of n_starts = 1.  Fills
+        .last_candidates and .last_peaks (numpy)."""
+        K = self.n_starts
+        rows, cands = [], np.zeros((len(self.own), K, 3))
+        peaks = dict(index=np.zeros((len(self.own), K), dtype=np.int32), value=np.zeros((len(self.own), K)),
+                     n_found=np.zeros(len(self.own), dtype=np.int32))
+        for q, (k, tab) in enumerate(zip(self.own, tabs)):
+            pick_start(tab, self.alpha_scan, self.theta0_scan)           # (raises on a table with non-finite growth rates)
+            ps = pick_starts(tab, self.alpha_scan, self.theta0_scan, K)
+            peaks["index"][q], peaks["value"][q], peaks["n_found"][q] = ps["index"], ps["peak"], ps["n_found"]
+            for j in range(max(1, ps["n_found"])):
+                (a0, t0), sigma0 = ps["start"][j], ps["sigma0"][j]
+                if refine:
+                    t, a, gam, _ = self.refine(self.rho_arr[k], float(a0), float(t0), float(sigma0) if self.nearest else None)
+                else:
+                    t, a, gam = float(t0), float(a0), float(ps["peak"][j])
+                cands[q, j] = t, a, gam
+            cands[q, max(1, ps["n_found"]):] = cands[q, 0]
+            rows.append(tuple(cands[q, int(np.argmax(cands[q, :, 2])) if refine else 0]))
+        self.last_candidates, self.last_peaks = cands, peaks
+        return rows
+
     def local_rows(self, refine=True):
         """(theta0*, alpha*, gam) of the surfaces this rank owns, (n_own, 3): coarse scan -> argmax -> refinement -> final
         solve (ball_scan.py:248-339), no collective"""
@@ -876,13 +1074,15 @@ class BallooningScan:
         rows = []
         if self.certify:
             self._count_certificate(self._coarse_cert)
-        for k, tab in zip(self.own, tabs):
+        for k, tab in zip(self.own, tabs if self.n_starts == 1 else ()):
             a0, t0, sigma0, ij = pick_start(tab, self.alpha_scan, self.theta0_scan)
             if refine:
                 t, a, gam, _ = self.refine(self.rho_arr[k], a0, t0, sigma0 if self.nearest else None)
             else:
                 t, a, gam = t0, a0, float(np.max(tab))
             rows.append((t, a, gam))
+        if self.n_starts > 1:
+            rows = self._multi_start_rows(tabs, refine)
         if self.certify:
             self._raise_uncertified()
         return np.array(rows, dtype=np.float64).reshape(len(self.own), 3)

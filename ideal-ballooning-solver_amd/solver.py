@@ -31,6 +31,8 @@ EXACT_VJP_SHIFT = 16 + 6
 # spectrum mode (ibs_*_modes_f64): modes per system at most, and the informational status bit of a clustered mode (info >> 16)
 MAX_MODES = 16
 CLUSTER_BIT = 1 << 9
+# multi-start refinement (ibs_scan_peaks_f64): starts per surface at most
+MAX_STARTS = 16
 
 
 def _is_torch(x):
@@ -713,6 +715,40 @@ class Context:
                 ar.inp(pack), ar.out("start", (n_surf, 2)), ar.out("sigma0", (n_surf,), want=want_sigma0),
                 ar.inout("scan_starts", "n_bad", n_bad, _I32), mem=False)
         return (ar.outs["start"], ar.outs["sigma0"]) if want_sigma0 else ar.outs["start"]
+
+    @staticmethod
+    def _n_starts(n_starts):
+        ok = isinstance(n_starts, (int, float, np.integer, np.floating)) and not isinstance(n_starts, bool)
+        if not ok or int(n_starts) != n_starts or not 1 <= n_starts <= MAX_STARTS:
+            raise IbsError("n_starts must be an integer in [1, %d], not %r" % (MAX_STARTS, n_starts))
+        return int(n_starts)
+
+    def scan_peaks(self, alpha_scan, theta0_scan, gam, n_starts, n_bad=None, want_sigma0=False, want_index=False, want_found=False):
+        """the n_starts best peaks of every surface's coarse table and the starts of a multi-start refinement from them
+        (ibs_scan_peaks_f64; the rule: scan.pick_starts), 1 <= n_starts <= 16.  gam: (n_surf, n_alpha, n_theta0) -- numpy arrays or
+        device tensors, like the grids.  Returns dict(start (n_surf, n_starts, 2) = (alpha, theta0), peak (n_surf, n_starts)[, sigma0
+        (n_surf, n_starts) = 1.3 |peak| + 0.05][, index int32 (n_surf, n_starts): row-major, -1 where the start is (0, 0)][, n_found
+        int32 (n_surf,)], n_bad): slot 0 is the first maximum with the start of scan_starts, slots beyond n_found repeat it.
+        n_bad: int32 array of one element in the call's memory kind, which accumulates the number of surfaces whose maximum is not
+        finite (None: a zeroed one is made); it is returned under "n_bad"."""
+        K = self._n_starts(n_starts)
+        na, nt = int(alpha_scan.shape[0]), int(theta0_scan.shape[0])
+        if len(gam.shape) != 3 or tuple(gam.shape[1:]) != (na, nt):
+            raise IbsError("scan_peaks: gam must be (n_surf, %d, %d), not %s" % (na, nt, tuple(gam.shape)))
+        n_surf = int(gam.shape[0])
+        ar = _Args(self)
+        head = [ar.inp(alpha_scan), ar.inp(theta0_scan), ar.inp(gam)]
+        if n_bad is None:
+            if ar.mem == MEM_DEVICE:
+                import torch
+                n_bad = torch.zeros(1, dtype=torch.int32, device=ar.ref)
+            else:
+                n_bad = np.zeros(1, dtype=np.int32)
+        ar.call("ibs_scan_peaks_f64", n_surf, na, nt, K, *head, ar.out("start", (n_surf, K, 2)), ar.out("peak", (n_surf, K)),
+                ar.out("index", (n_surf, K), _I32, want_index), ar.out("sigma0", (n_surf, K), want=want_sigma0),
+                ar.out("n_found", (n_surf,), _I32, want_found), ar.inout("scan_peaks", "n_bad", n_bad, _I32))
+        ar.outs["n_bad"] = n_bad
+        return ar.outs
 
     def obj_w_grad(self, h, geo, theta0, del_alpha=0.004, want_info=False):
         """geo: (n_pts, 3, 8, N) -- lines (alpha-d/2, alpha, alpha+d/2) x (bmag, gradpar, cvdrift, cvdrift0,

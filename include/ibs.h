@@ -721,6 +721,27 @@ int ibs_surface_argmax_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per_surf, con
  * per-surface all-gather sends (replaces the three comm_lead.Gather of ball_scan.py:345-347). */
 int ibs_surface_argmax_pack_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per_surf, const double* gam, double* pack);
 
+/* The n_starts best local maxima ("peaks") of every surface's coarse table and the starts of a multi-start refinement from them.
+ * Replaces, in slot 0: ball_scan.py:279-295 -- the first maximum of the table, x0 = (alpha_scan[i], theta0_scan[j]) and sigma0 =
+ * 1.3 |gam| + 0.05; a maximum of exactly 0 starts from (0, 0) with sigma0 = 0.05 (:279-282); the start and sigma0 of
+ * ibs_surface_argmax_pack_f64 + ibs_scan_starts_f64, bit for bit.  Slots >= 1 have no upstream counterpart (upstream refines from the
+ * first maximum alone).
+ *   The rule (csrc/ibs_scan_peaks.hpp; ibs_amd.scan.pick_starts in numpy): a neighbour w of entry v beats it if w > v, or w == v and w
+ *   has the smaller row-major index; a NaN never beats anything.  A peak is an entry that is not NaN and that none of its up to
+ *   eight neighbours (i +- 1, j +- 1) inside the table beats -- no wrap-around: (alpha, theta0) is a box.  Peaks rank by value
+ *   descending, ties by index ascending; slot k holds peak k: its node, its value, its row-major index and its own sigma0 =
+ *   1.3 |peak| + 0.05.  n_found = the number of peaks found (<= n_starts); the slots from n_found on repeat slot 0.  A first maximum
+ *   of exactly 0, or one that is not finite (counted once in *n_bad; a table of NaN counts too), starts from (0, 0) with n_found = 0
+ *   and index -1 in every slot.
+ *   gam [n_surf][n_alpha][n_theta0]; alpha [n_alpha], theta0 [n_theta0]: the scan grids;  start [n_surf][n_starts][2] = (alpha,
+ *   theta0), peak [n_surf][n_starts];  index (int32), sigma0 [n_surf][n_starts] and n_found [n_surf] are optional (NULL);
+ *   *n_bad (NOT cleared here) += the number of surfaces whose maximum is not finite.  1 <= n_starts <= 16.
+ * Host or device pointers (mem).  n_starts outside [1, 16], a dimension < 1 or a required pointer NULL: IBS_ERR_ARG before the
+ * context is touched; n_surf = 0: nothing happens.  Results are bitwise repeatable and independent of n_surf. */
+int ibs_scan_peaks_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_alpha, int32_t n_theta0, int32_t n_starts, const double* alpha,
+                       const double* theta0, const double* gam, double* start, double* peak, int32_t* index, double* sigma0,
+                       int32_t* n_found, int32_t* n_bad, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif
