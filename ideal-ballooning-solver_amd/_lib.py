@@ -95,6 +95,13 @@ SYMBOLS = {
     "ibs_surface_argmax_f64": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _I32]),
     "ibs_surface_argmax_pack_f64": (C.c_int, [_P, _I32, _I32, _P, _P]),
     "ibs_scan_peaks_f64": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32]),
+    "ibs_theta0_polish_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I32, _D, _I32,
+                                        _P, _P, _P, _P, _P, _P, _P, _I32]),
+    "ibs_theta0_polish_state_bytes": (C.c_int, []),
+    "ibs_theta0_polish_init": (C.c_int, [_P, _I32, _P, _P, _I32, _D, _I32, _P]),
+    "ibs_theta0_polish_step": (C.c_int, [_P, _D, _I32, _P]),
+    "ibs_theta0_polish_result": (C.c_int, [_P, _P, _P, _P, _P]),
+    "ibs_row_peaks_f64": (C.c_int, [_I32, _I32, _I32, _P, _P, _P]),
 }
 
 

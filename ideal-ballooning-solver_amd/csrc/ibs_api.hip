@@ -21,6 +21,7 @@
 #include "ibs_certify.hpp"
 #include "ibs_regrid.hpp"
 #include "ibs_scan_peaks.hpp"
+#include "ibs_theta0_polish.hpp"
 #include <chrono>
 #include <thread>
 
@@ -720,6 +721,53 @@ int ibs_lbfgsb2_result(const void* state, double* x, double* f, int32_t* counter
   if (x) { x[0] = s.x[0]; x[1] = s.x[1]; }
   if (f) *f = s.f;
   if (counters) { counters[0] = s.n_iterations; counters[1] = s.nfgv; counters[2] = s.task; counters[3] = s.n_restarts; counters[4] = s.nskip; }
+  return 0;
+}
+
+// ---- host side of the theta0 search and the row peaks (ibs_theta0_polish.hpp): no GPU involved
+int ibs_theta0_polish_state_bytes(void) { return (int)sizeof(ibs::t0p::State); }
+
+int ibs_theta0_polish_init(void* state, int32_t n_theta0, const double* theta0, const double* row, int32_t node, double xtol,
+                           int32_t max_eval, double* x_next) {
+  if (!state || !theta0 || !row || !x_next) return fail(IBS_ERR_ARG, "null pointer");
+  if (n_theta0 < 1 || node < 0 || node >= n_theta0 || !(xtol > 0) || !std::isfinite(xtol) || max_eval < 1 || max_eval > ibs::t0p::kMaxEval)
+    return fail(IBS_ERR_ARG, "node in [0, n_theta0), xtol > 0 and finite, max_eval in [1, %d] required", ibs::t0p::kMaxEval);
+  if (!ibs::t0p::grid_ok(theta0, n_theta0)) return fail(IBS_ERR_ARG, "theta0 must be finite and strictly increasing");
+  if (!(row[node] == row[node])) return fail(IBS_ERR_ARG, "the node's gam is NaN");
+  auto& s = *static_cast<ibs::t0p::State*>(state);
+  const bool more = ibs::t0p::init_row(s, theta0, row, n_theta0, node, 0.0, xtol, max_eval);
+  *x_next = s.u;
+  return more ? 1 : 0;
+}
+
+int ibs_theta0_polish_step(void* state, double gam, int32_t eval_status, double* x_next) {
+  if (!state || !x_next) return fail(IBS_ERR_ARG, "null pointer");
+  auto& s = *static_cast<ibs::t0p::State*>(state);
+  const bool more = ibs::t0p::step(s, gam, 0.0, eval_status);
+  *x_next = s.u;
+  return more ? 1 : 0;
+}
+
+int ibs_theta0_polish_result(const void* state, double* theta0_star, double* gam_star, int32_t* n_eval, int32_t* status) {
+  if (!state) return fail(IBS_ERR_ARG, "null pointer");
+  const auto& s = *static_cast<const ibs::t0p::State*>(state);
+  double x, f, tag;
+  int st;
+  ibs::t0p::result(s, x, f, tag, st);
+  if (theta0_star) *theta0_star = x;
+  if (gam_star) *gam_star = f;
+  if (n_eval) *n_eval = s.n_eval;
+  if (status) *status = st;
+  return 0;
+}
+
+int ibs_row_peaks_f64(int32_t n_rows, int32_t n_theta0, int32_t K, const double* gam, int32_t* node, int32_t* n_found) {
+  if (n_rows < 0 || n_theta0 < 1 || K < 1 || K > ibs::t0p::kMaxSlots || !gam || !node)
+    return fail(IBS_ERR_ARG, "K in [1, %d], n_theta0 >= 1, gam and node required", ibs::t0p::kMaxSlots);
+  for (int32_t r = 0; r < n_rows; ++r) {
+    const int nf = ibs::t0p::row_peaks(gam + (size_t)r * n_theta0, n_theta0, K, node + (size_t)r * K);
+    if (n_found) n_found[r] = nf;
+  }
   return 0;
 }
 
@@ -2259,6 +2307,50 @@ int ibs_scan_peaks_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_alpha, int32_t n_
   });
   if (rc == 0 && host) *n_bad += added;
   return rc;
+}
+
+// ---- gam maximised over theta0 on every line (k_theta0_polish; the rule: ibs_theta0_polish.hpp)
+int ibs_theta0_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                          const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                          const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                          const double* gam, const double* lam, const int32_t* node_in, int32_t n_starts, double xtol,
+                          int32_t max_eval, double* theta0_star, double* gam_star, double* lam_star, int32_t* node,
+                          int32_t* n_eval, int32_t* info, int32_t* n_found, int32_t mem) {
+  if (n_starts < 1 || n_starts > ibs::t0p::kMaxSlots || !(xtol > 0) || !std::isfinite(xtol) || max_eval < 1 ||
+      max_eval > ibs::t0p::kMaxEval)
+    return fail(IBS_ERR_ARG, "n_starts in [1, %d], xtol > 0 and finite, max_eval in [1, %d] required (n_starts=%d xtol=%g max_eval=%d)",
+                ibs::t0p::kMaxSlots, ibs::t0p::kMaxEval, n_starts, xtol, max_eval);
+  if (n_lines < 0 || n_theta0 < 1 || N < 1 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho ||
+      !theta0 || !gam || !theta0_star || !gam_star || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d; the arrays, theta0, gam, theta0_star and gam_star are required)",
+                n_lines, n_theta0, (long long)ld, N);
+  if (int r = check_grid(N, h)) return r;
+  const bool host = mem == IBS_MEM_HOST;
+  if (host && !ibs::t0p::grid_ok(theta0, n_theta0)) return fail(IBS_ERR_ARG, "theta0 must be finite and strictly increasing");
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_lines == 0) return 0;
+  const ibs::Theta0PolishPlan plan = ibs::plan_theta0_polish(ctx->chip, ctx->built, N, n_starts);
+  auto fn = ibs::launch_table().theta0_polish_f64[plan.M];
+  if (plan.err == ibs::PlanError::NotBuilt || !fn) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", plan.M, N);
+  if (plan.err == ibs::PlanError::NoLds) return fail(IBS_ERR_UNSUPPORTED, "N=%d does not fit the LDS staging", N);
+  ON_DEVICE(ctx);
+  ibs::Theta0PolishArgs<double> a{};
+  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = ld;
+  a.n_starts = n_starts; a.xtol = xtol; a.max_eval = max_eval; a.w1 = ctx->opt.chain_w1; a.w2 = ctx->opt.chain_w2;
+  const size_t in_elems = (size_t)n_lines * ld, n_sys = (size_t)n_lines * n_theta0, n_slots = (size_t)n_lines * n_starts;
+  auto decl = [&](Stage& s) {
+    a.bmag = s.in(bmag, in_elems); a.gradpar = s.in(gradpar, in_elems); a.cvdrift = s.in(cvdrift, in_elems);
+    a.cvdrift0 = s.in(cvdrift0, in_elems); a.gds2 = s.in(gds2, in_elems); a.gds21 = s.in(gds21, in_elems); a.gds22 = s.in(gds22, in_elems);
+    a.dPdrho = s.in(dPdrho, (size_t)n_lines); a.theta0 = s.in(theta0, (size_t)n_theta0); a.gam = s.in(gam, n_sys); a.lam = s.in(lam, n_sys);
+    a.node_in = s.in(node_in, n_slots);
+    a.theta0_star = s.out(theta0_star, n_slots); a.gam_star = s.out(gam_star, n_slots); a.lam_star = s.out(lam_star, n_slots);
+    a.node = s.out(node, n_slots); a.n_eval = s.out(n_eval, n_slots); a.n_found = s.out(n_found, (size_t)n_lines);
+    a.info = s.status(info, n_slots);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    HIPCHK(fn(a, ctx->stream));
+    return 0;
+  });
 }
 
 int ibs_refine_f64(ibs_ctx* ctx, int32_t n_surf, int32_t mnmax, int32_t mnmax_nyq, const double* xm, const double* xn,

@@ -11,6 +11,7 @@
 #include "ibs_launch.hpp"
 #include "ibs_scan_map.hpp"
 #include "ibs_refine.hpp"
+#include "ibs_theta0_polish.hpp"
 #include <type_traits>
 
 #ifndef IBS_M
@@ -1370,6 +1371,134 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan_chain(
   }
 }
 
+// ---------------------------------------------------------------- gam maximised over theta0 on every line
+// One block per line (plain 1-D grid), one wave per start slot (block = n_starts <= 4 waves).  The line is staged once, as above; every
+// wave then runs the bounded Brent search of ibs_theta0_polish.hpp between the coarse nodes about its peak of the row gam[line][:],
+// each requested theta0 one lean solve through the fold (SrcGeo) warm-started from the eigenvalues before it.  ball_scan.py:248-295
+// has no such step.  A slot's arithmetic depends on nothing but its line, its node and the row: the other waves of the block, the
+// number of lines and their order do not enter.
+// The search state of a wave lives in LDS (all 64 lanes execute the same scalar statements on it and store the same values); the
+// growth-rate stage hands gam back through one LDS word per wave: it is given that word as its gam output, so finish() and
+// finish_chunk() are the code the scan runs, untouched.
+// dynamic LDS = theta0_polish_lds_rows(M, n_starts) * lds_pitch(N) * sizeof(T) (ibs_plan.hpp).
+static_assert(kTheta0PolishMaxStarts == t0p::kMaxSlots, "the plan's slots per line are the rule's");
+template <typename T, int M>
+__global__ void __launch_bounds__(64 * t0p::kMaxSlots) k_theta0_polish(Theta0PolishArgs<T> p) {
+  static_assert(std::is_same<T, double>::value, "the search state is FP64");
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  __shared__ t0p::State states[t0p::kMaxSlots];
+  __shared__ T gam_word[t0p::kMaxSlots];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int K = blockDim.x >> 6;
+  const int line = blockIdx.x;
+  const int N = p.N, n_theta0 = p.n_theta0;
+  const int P = lds_pitch(N);
+  T* A1 = smem; T* A3 = A1 + P; T* C0 = A3 + P; T* C1 = C0 + P; T* G0 = C1 + P; T* G1 = G0 + P; T* G2 = G1 + P;
+  T* Xs = M < 3 ? G2 + P + (size_t)wave * P : nullptr;
+  {
+    const long off = (long)line * p.ld;
+    const T mdP = -p.dPdrho[line];
+    for (int j = threadIdx.x; j < N; j += blockDim.x) {
+      const T B = p.bmag[off + j], gp = xabs(p.gradpar[off + j]);
+      const T inv = T(1) / (gp * B);
+      const int q = lpos(j);
+      A1[q] = gp / B; A3[q] = inv / (B * B);
+      C0[q] = mdP * p.cvdrift[off + j] * inv; C1[q] = mdP * p.cvdrift0[off + j] * inv;
+      G0[q] = p.gds2[off + j]; G1[q] = p.gds21[off + j]; G2[q] = p.gds22[off + j];
+    }
+  }
+  __syncthreads();
+  // ---- the slot's node: the row's own peak of this rank, or the caller's
+  const T* row = p.gam + (size_t)line * n_theta0;
+  const size_t slot = (size_t)line * K + wave;
+  const T nan = T(__builtin_nan(""));
+  const bool grid_ok = t0p::grid_ok(p.theta0, n_theta0);
+  int node = -1, n_found = 0;
+  if (p.node_in) {
+    node = p.node_in[slot];
+    if (node >= n_theta0) node = -1;
+  } else {
+    int nodes[t0p::kMaxSlots];
+    n_found = t0p::row_peaks(row, n_theta0, K, nodes);
+    node = nodes[0];
+#pragma unroll
+    for (int k = 1; k < t0p::kMaxSlots; ++k) node = (k == wave) ? nodes[k] : node;
+  }
+  node = __builtin_amdgcn_readfirstlane(node);
+  if (p.n_found && wave == 0 && lane == 0) p.n_found[line] = n_found;
+  if (node >= 0 && !(row[node] == row[node])) node = -1;                 // (a caller's node without a value)
+  if (node < 0 || !grid_ok) {                                             // (wave-uniform)
+    if (lane == 0) {
+      p.theta0_star[slot] = nan; p.gam_star[slot] = nan;
+      if (p.lam_star) p.lam_star[slot] = nan;
+      if (p.node) p.node[slot] = grid_ok ? -1 : node;
+      if (p.n_eval) p.n_eval[slot] = 0;
+      if (p.info) p.info[slot] = grid_ok ? 0 : (2 << 16);
+    }
+    return;
+  }
+  t0p::State& st = states[wave];
+  const T lam_node = p.lam ? p.lam[(size_t)line * n_theta0 + node] : nan;
+  bool more = t0p::init_row(st, p.theta0, row, n_theta0, node, lam_node, p.xtol, p.max_eval);
+  wave_lds_sync();
+  // eigenvalues of this wave's last two solves and where they were taken; the coarse lam of the node counts as one
+  T lam_p1 = lam_node, lam_p2 = T(0), th_p1 = p.theta0[node], th_p2 = T(0);
+  int have = finite_of(lam_node) ? 1 : 0;
+  int sweeps = 0;
+  for (int it = 0; it < t0p::kMaxEval; ++it) {
+    if (!__builtin_amdgcn_readfirstlane((int)more)) break;
+    // (N opaque once per evaluation, for the reason k_gamma_scan_chain gives)
+    int Nq = N;
+    asm volatile("" : "+s"(Nq));
+    const T th0 = uniform(st.u);
+    SrcGeo<T> src{A1, A3, C0, C1, G0, G1, G2, th0, T(2) * th0, th0 * th0};
+    WaveSolver<T, M> ws;
+    SolveInfo inf{0, 0};
+    const bool bad = ws.template setup<SrcGeo<T>, true>(src, Nq, p.h);
+    T lam = T(0);
+    if (!bad) {
+      const T floor_w = T(4096) * T(64) * Eps<T>::v * ws.normA;
+      T guess = lam_p1, width = xmax(p.w1 * xabs(lam_p1), floor_w);
+      if (have == 2) {
+        // linear extrapolation in theta0 from the last two eigenvalues; a wrong guess costs sweeps, never correctness
+        guess = lam_p1 + (lam_p1 - lam_p2) * ((th0 - th_p1) / (th_p1 - th_p2));
+        width = xmax(p.w2 * xmax(xabs(guess - lam_p1), xabs(lam_p1 - lam_p2)), floor_w);
+      }
+      if (have == 0 || !finite_of(guess) || !finite_of(width)) ws.trial_guess(guess, width);
+      lam = ws.solve(inf, true, guess, width);
+      lam_p2 = lam_p1; th_p2 = th_p1; lam_p1 = lam; th_p1 = th0; have = have < 2 ? have + 1 : 2;
+    } else {
+      inf.status = 2; ws.sweep(ws.hi); ws.twisted(ws.hi); have = 0;
+    }
+    T* gw = &gam_word[wave];
+    if constexpr (M >= 3)
+      finish_chunk<T, M, SrcGeo<T>, true>(ws, src, Nq, p.h, Xs, lam, inf, 0L, nullptr, gw, nullptr, nullptr, nullptr, nullptr);
+    else
+      finish<T, M, SrcGeo<T>, true>(ws, src, Nq, p.h, Xs, lam, inf, 0L, nullptr, gw, nullptr, nullptr, nullptr, nullptr);
+    // The stage stores gam from lane 0 with a relaxed agent-scope atomic store through a generic pointer (for the scan's cross-CU
+    // hand-off).  Here that pointer is an LDS word: the store is a flat store that the address routes to LDS, where the scope
+    // bits mean nothing (LDS is coherent within the block and only this wave touches the word), and a relaxed store orders
+    // nothing by itself.  A flat store counts on both vmcnt and lgkmcnt, so both are drained before the word is read back.
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wave_lds_sync();
+    const T gam = uniform(*const_cast<volatile T*>(gw));
+    sweeps += inf.iters;
+    more = t0p::step(st, (double)gam, (double)lam, inf.status);
+    wave_lds_sync();
+  }
+  if (lane == 0) {
+    double x, f, tag;
+    int status;
+    t0p::result(st, x, f, tag, status);
+    p.theta0_star[slot] = x; p.gam_star[slot] = f;
+    if (p.lam_star) p.lam_star[slot] = tag;
+    if (p.node) p.node[slot] = node;
+    if (p.n_eval) p.n_eval[slot] = st.n_eval;
+    if (p.info) p.info[slot] = (sweeps > 0xffff ? 0xffff : sweeps) | (status << 16);
+  }
+}
+
 // ---------------------------------------------------------------- objective + Hellmann-Feynman gradient
 // One wave per (alpha, theta0) evaluation point (utils.py:1632-1728 obj_w_grad given the three field
 // lines alpha-d/2, alpha, alpha+d/2).  geo: [n_pts][3][8][ld] in the order bmag, gradpar, cvdrift,
@@ -1973,6 +2102,16 @@ static hipError_t launch_scan_chain(const ScanArgs<T>& a, hipStream_t st) {
   return hipGetLastError();
 }
 template <typename T>
+static hipError_t launch_theta0_polish(const Theta0PolishArgs<T>& a, hipStream_t st) {
+  const size_t lds = (size_t)theta0_polish_lds_rows(IBS_M, a.n_starts) * lds_pitch(a.N) * sizeof(T);
+  auto kern = k_theta0_polish<T, IBS_M>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)a.n_lines), dim3(a.n_starts * 64), lds, st, a);
+  note_launch(a.n_lines, a.n_starts * 64, "ibs::k_theta0_polish<%s, %d>", type_name<T>(), IBS_M);
+  return hipGetLastError();
+}
+template <typename T>
 static hipError_t launch_sturm(const SturmArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb;
   const size_t lds = (size_t)wpb * a.N * sizeof(T);
@@ -2041,6 +2180,7 @@ struct IBS_CAT(Registrar, IBS_M) {
 #endif
     t.scan_f64[IBS_M] = &launch_scan<double>;
     t.scan_chain_f64[IBS_M] = &launch_scan_chain<double>;
+    t.theta0_polish_f64[IBS_M] = &launch_theta0_polish<double>;
     t.sturm_f64[IBS_M] = &launch_sturm<double>;
     t.grad_f64[IBS_M] = &launch_grad<double>;
     t.refine_f64[IBS_M] = &launch_refine_eval<double>;

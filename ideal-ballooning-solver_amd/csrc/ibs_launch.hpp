@@ -39,6 +39,18 @@ struct ScanArgs {
   // per SIMD), 0 = the lean form k_gamma_scan_lean (126 VGPRs at M = 8).  ih2 = 1 / (h * h), ih = 1 / h: divided once, on the host
   int resident; T ih2, ih;
 };
+// gam maximised over theta0 about the peaks of every line's coarse row (k_theta0_polish; the rule: ibs_theta0_polish.hpp).  One block
+// per line, n_starts <= 4 waves.  gam (required), lam (optional warm starts) [n_lines][n_theta0]; node_in (optional) and every output
+// but n_found [n_lines] are [n_lines][n_starts]; theta0_star and gam_star are required.  w1, w2: the widths of the warm starts, as
+// ScanArgs::chain_w1 / chain_w2
+template <typename T>
+struct Theta0PolishArgs {
+  int n_lines, n_theta0, N; T h;
+  const T *bmag, *gradpar, *cvdrift, *cvdrift0, *gds2, *gds21, *gds22; long ld;
+  const T *dPdrho, *theta0, *gam, *lam; const int* node_in;
+  int n_starts; T xtol; int max_eval; T w1, w2;
+  T *theta0_star, *gam_star, *lam_star; int *node, *n_eval, *info, *n_found;
+};
 template <typename T>
 struct SturmArgs {
   long n_sys; int N; T h; const T* g; const T* c; const T* f; long ld; const T* shift; int* count; int wpb;
@@ -326,6 +338,7 @@ struct LaunchTable {
   hipError_t (*gcf_f32w_g[2][kMaxM + 1])(const GcfArgs<float>&, hipStream_t);  // the same, 32 / 16 lanes per system
   hipError_t (*scan_f64[kMaxM + 1])(const ScanArgs<double>&, hipStream_t);
   hipError_t (*scan_chain_f64[kMaxM + 1])(const ScanArgs<double>&, hipStream_t);
+  hipError_t (*theta0_polish_f64[kMaxM + 1])(const Theta0PolishArgs<double>&, hipStream_t);
   hipError_t (*sturm_f64[kMaxM + 1])(const SturmArgs<double>&, hipStream_t);
   hipError_t (*grad_f64[kMaxM + 1])(const GradArgs<double>&, hipStream_t);
   hipError_t (*refine_f64[kMaxM + 1])(const RefineEvalArgs<double>&, hipStream_t);   // one round of ibs_refine_f64 (ibs_refine.hpp)

@@ -235,6 +235,20 @@ inline ScanPlan plan_scan(const Chip& chip, const PlanOpts& opts, const Built& b
   return p;
 }
 
+// ---------------------------------------------------------------- gam maximised over theta0 (k_theta0_polish)
+// One block per line on a plain 1-D grid, one wave per start slot.  LDS rows: the staged line's seven arrays, and a row per wave only
+// where the growth-rate stage goes through LDS (M < 3: finish()); the search states and the gam words are static (< 1 KB).
+constexpr int kTheta0PolishMaxStarts = 4;
+constexpr int theta0_polish_lds_rows(int M, int n_starts) { return kScanLineRows + (M < 3 ? n_starts : 0); }
+struct Theta0PolishPlan { PlanError err; int M, threads, lds_rows; };
+inline Theta0PolishPlan plan_theta0_polish(const Chip& chip, const Built& built, int N, int n_starts) {
+  Theta0PolishPlan p{PlanError::None, rows_per_lane(N), 64 * n_starts, 0};
+  p.lds_rows = theta0_polish_lds_rows(p.M, n_starts);
+  if (!has(built.scan_chain, p.M)) p.err = PlanError::NotBuilt;      // (registered beside k_gamma_scan_chain, for every M)
+  else if ((size_t)p.lds_rows * lds_pitch(N) * sizeof(double) + 1024 > (size_t)chip.lds_per_block) p.err = PlanError::NoLds;
+  return p;
+}
+
 // ---------------------------------------------------------------- raw (g, c, f) solves
 enum class GcfForm {
   Staged,          // k_solve_gcf<double, M>: one wave per system, the three rows staged in LDS

@@ -14,7 +14,7 @@ around the reference's own utils.vmec_fieldlines (ball_scan.py:251-261).
 import numpy as np
 
 from ._lib import IbsError
-from .solver import CLUSTER_BIT
+from .solver import CLUSTER_BIT, MAX_ROW_STARTS
 
 GEO_ORDER = ("bmag", "gradpar_theta_pest", "cvdrift", "cvdrift0", "gds2", "gds21", "gds22", "gbdrift")
 
@@ -90,6 +90,149 @@ def pick_starts(gam_table, alpha_scan, theta0_scan, n_starts):
         out["start"][k] = alpha_scan[e // nt], theta0_scan[e % nt]
         out["peak"][k], out["index"][k], out["sigma0"][k] = v, e, 1.3 * abs(v) + 0.05       # ball_scan.py:289, 295
     return out
+
+
+POLISH_MAX_EVAL = 64
+NODE_RETURNED_BIT, MAX_EVAL_BIT, ONE_SIDED_BIT = 1 << 10, 1 << 11, 1 << 12
+_GOLD = 0.3819660112501051          # (3 - sqrt 5) / 2
+
+
+def row_peaks(gam, K):
+    """the K best peaks of every row of gam (n_rows, n_theta0) (or of one row): the rule of ibs_row_peaks_f64 and of the kernel behind
+    ibs_theta0_polish_f64 (csrc/ibs_theta0_polish.hpp) in numpy -- pick_starts' rule in one dimension.  Entry j is a peak if it is
+    not NaN and neither neighbour inside the row beats it (w beats v if w > v, or w == v and w has the smaller index; a NaN never
+    beats anything); peaks rank by value descending, ties by index ascending.  Returns (node int32 (n_rows, K), n_found int32
+    (n_rows,)): slot k holds peak k, slots from n_found on repeat slot 0, a row without a finite entry has n_found = 0 and node -1."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_ROW_STARTS:
+        raise ValueError("K must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, K))
+    tab = np.atleast_2d(np.asarray(gam, dtype=np.float64))
+    n_rows, nt = tab.shape
+    idx = np.arange(nt)
+    node = np.full((n_rows, K), -1, dtype=np.int32)
+    n_found = np.zeros(n_rows, dtype=np.int32)
+    pad = np.full((n_rows, nt + 2), np.nan); pad[:, 1:-1] = tab
+    with np.errstate(invalid="ignore"):
+        left, right = pad[:, :-2], pad[:, 2:]
+        beaten = np.isnan(tab) | (left >= tab) | (right > tab)        # (the left neighbour has the smaller index: it wins ties)
+    for r in range(n_rows):
+        peaks = idx[~beaten[r]]
+        picks = peaks[np.lexsort((peaks, -tab[r, peaks]))][:K]
+        n_found[r] = len(picks)
+        if len(picks):
+            node[r] = picks[0]
+            node[r, :len(picks)] = picks
+    return node, n_found
+
+
+def polish_theta0(f, theta0, row, node, xtol=1e-5, max_eval=32):
+    """gam maximised over theta0 about node `node` of the coarse row `row` (values of f at the nodes theta0): the state machine of
+    csrc/ibs_theta0_polish.hpp (ibs_theta0_polish_init / _step / _result, and every wave of ibs_theta0_polish_f64) restated in
+    pure Python, statement by statement, so that it asks f for the same points bit for bit.  f(theta0) -> gam, or (gam, status).
+    Bracket [theta0[node - 1], theta0[node + 1]], cut to the node where the row ends or the neighbour is NaN (exactly one side cut:
+    status bit 12; zero length: the node, no evaluation).  Brent's bounded search on the absolute tolerance xtol, seeded with the
+    three known values (one-sided: first the golden point next to the node); it stops on |x - m| <= 2 xtol - (b - a) / 2 or after
+    max_eval evaluations (bit 11).  A value that is not finite, or that comes with status bit 0 or 1 (a failed evaluation), counts as -inf.  The result is the best evaluated point only if its
+    value is strictly greater than the node's, else the node with the row's value (bit 10).
+    Returns dict(theta0, gam, n_eval, status, points: the requested theta0 in order)."""
+    theta0 = np.asarray(theta0, dtype=np.float64)
+    row = np.asarray(row, dtype=np.float64)
+    n, j = len(theta0), int(node)
+    if not (0 <= j < n) or not (xtol > 0 and np.isfinite(xtol)) or not 1 <= max_eval <= POLISH_MAX_EVAL or np.isnan(row[j]):
+        raise ValueError("polish_theta0: node in [0, n), a gam at the node, xtol > 0 and max_eval in [1, %d] required" % POLISH_MAX_EVAL)
+    if not (np.all(np.isfinite(theta0)) and np.all(np.diff(theta0) > 0)):
+        raise ValueError("polish_theta0: theta0 must be finite and strictly increasing")
+    has_lo = j > 0 and not np.isnan(row[j - 1])
+    has_hi = j + 1 < n and not np.isnan(row[j + 1])
+    xn, fn = float(theta0[j]), float(row[j])
+    a = float(theta0[j - 1]) if has_lo else xn
+    b = float(theta0[j + 1]) if has_hi else xn
+    s = dict(a=a, b=b, x=xn, fx=fn, w=xn, fw=fn, v=xn, fv=fn, d=0.0, e=0.0, n_eval=0, status=0)
+    points = []
+    tol1, tol2 = float(xtol), 2.0 * float(xtol)
+
+    def propose():
+        """Brent's next point, or None when the search is over"""
+        if s["n_eval"] >= max_eval:
+            s["status"] |= MAX_EVAL_BIT
+            return None
+        a, b, x, w, v = s["a"], s["b"], s["x"], s["w"], s["v"]
+        fx, fw, fv = s["fx"], s["fw"], s["fv"]
+        xm = 0.5 * (a + b)
+        if abs(x - xm) <= tol2 - 0.5 * (b - a):
+            return None
+        parab, d = False, 0.0
+        with np.errstate(all="ignore"):
+            if abs(s["e"]) > tol1:
+                r = np.float64(x - w) * np.float64(fx - fv)
+                q = np.float64(x - v) * np.float64(fx - fw)
+                p = np.float64(x - v) * q - np.float64(x - w) * r
+                q = 2.0 * (q - r)
+                if q > 0.0:
+                    p = -p
+                q = abs(q)
+                etemp = s["e"]
+                if abs(p) < abs(0.5 * q * etemp) and p > q * (a - x) and p < q * (b - x):
+                    d = float(p / q)
+                    u = x + d
+                    if u - a < tol2 or b - u < tol2:
+                        d = tol1 if xm >= x else -tol1
+                    parab = True
+                    s["e"] = s["d"]
+        if not parab:
+            s["e"] = a - x if x >= xm else b - x
+            d = _GOLD * s["e"]
+        s["d"] = d
+        s["n_eval"] += 1
+        return x + d if abs(d) >= tol1 else (x + tol1 if d > 0.0 else x - tol1)
+
+    def value(u):
+        points.append(u)
+        r = f(u)
+        g, st = r if isinstance(r, tuple) else (r, 0)
+        s["status"] |= int(st) & 3
+        g = float(g)
+        return g if np.isfinite(g) and not int(st) & 3 else -np.inf
+
+    u = None
+    if b > a:
+        if has_lo and has_hi:
+            flo, fhi = float(row[j - 1]), float(row[j + 1])
+            lo_better = flo >= fhi
+            s["w"], s["fw"] = (a, flo) if lo_better else (b, fhi)
+            s["v"], s["fv"] = (b, fhi) if lo_better else (a, flo)
+            s["d"] = s["e"] = b - a
+            u = propose()
+        else:
+            s["status"] |= ONE_SIDED_BIT
+            s["v"], s["fv"] = (b, float(row[j + 1])) if has_hi else (a, float(row[j - 1]))
+            u = a + _GOLD * (b - a) if has_hi else b - _GOLD * (b - a)
+            s["n_eval"] = 1
+            fu = value(u)
+            s["x"], s["fx"] = u, fu
+            s["d"] = s["e"] = b - a
+            u = propose()
+    while u is not None:
+        fu = value(u)
+        x = s["x"]
+        if fu >= s["fx"]:
+            if u >= x:
+                s["a"] = x
+            else:
+                s["b"] = x
+            s["v"], s["fv"], s["w"], s["fw"], s["x"], s["fx"] = s["w"], s["fw"], x, s["fx"], u, fu
+        else:
+            if u < x:
+                s["a"] = u
+            else:
+                s["b"] = u
+            if fu >= s["fw"] or s["w"] == x:
+                s["v"], s["fv"], s["w"], s["fw"] = s["w"], s["fw"], u, fu
+            elif fu >= s["fv"] or s["v"] == x or s["v"] == s["w"]:
+                s["v"], s["fv"] = u, fu
+        u = propose()
+    better = s["fx"] > fn
+    return dict(theta0=s["x"] if better else xn, gam=s["fx"] if better else fn, n_eval=s["n_eval"],
+                status=s["status"] | (0 if better else NODE_RETURNED_BIT), points=points)
 
 
 def gather_rows_tensor(local, n_surf, rank, world, dist, ctx=None):
@@ -193,11 +336,16 @@ class BallooningScan:
     surface with fewer than K peaks repeats slot 0 in the remaining slots (duplicated work, never preferred by the first-maximum
     rule).  .last_candidates (n_own, K, 3) = (theta0, alpha, gam) of every slot and .last_peaks = dict(index, value (n_own, K),
     n_found (n_own,)) describe the last run (device tensors on the device path, not synchronised).  n_starts=1 (the default) takes
-    exactly the code path and the calls it took before the option existed."""
+    exactly the code path and the calls it took before the option existed.
+    theta0_polish=True (tables= and device= only, n_starts=1, eigenpair="max"; else ValueError): after the coarse scan every line's
+    growth rate is maximised over theta0 between the nodes (Context.theta0_polish, one call with one slot per line, on the lines
+    the scan staged: no geometry launch), and every surface's refinement starts from its best polished (alpha_i, theta0*) in place of
+    the best node; refine=False rows report that point and its value.  .last_envelope holds that call's outputs (device tensors).
+    theta0_polish=False (the default) makes exactly the calls it made before the option existed."""
 
     def __init__(self, ctx, fieldlines, theta, rho_arr, nalpha=24, ntheta0=15, del_alpha=0.004,
                  rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None, eigenpair="max",
-                 jac="reference", certify=False, n_starts=1):
+                 jac="reference", certify=False, n_starts=1, theta0_polish=False):
         """fieldlines: host geometry callable (see module docstring), or None together with
         tables=SurfaceTables (row F1): then the geometry is produced on `device` by the HIP geometry kernel and consumed
         there -- coarse scan, per-surface maximum, start points, refinement and final solve all stay in HBM and ONE small
@@ -208,6 +356,15 @@ class BallooningScan:
         docstring; anything else raises IbsError, which is a ValueError too); n_starts: an integer in [1, 16] (else ValueError)."""
         self.n_starts = check_n_starts(n_starts)
         self.last_candidates = self.last_peaks = None
+        self.theta0_polish = bool(theta0_polish)
+        self.last_envelope = None
+        if self.theta0_polish:
+            if tables is None or device is None:
+                raise ValueError("theta0_polish=True runs on the resident path: tables= and device= are required")
+            if self.n_starts != 1:
+                raise ValueError("theta0_polish=True takes n_starts=1")
+            if eigenpair == "nearest":
+                raise ValueError("theta0_polish=True maximises lam_max's growth rate: eigenpair='nearest' is not supported")
         self.eigenpair = check_eigenpair(eigenpair)
         self.nearest = eigenpair == "nearest"
         self.jac = check_jac(jac)
@@ -316,6 +473,49 @@ class BallooningScan:
         dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
         cnt = self.ctx.geo_sturm_count(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan, shift)
         return np.asarray(cnt).reshape(len(self.own), na, nt)
+
+    # -- every line's growth rate maximised over theta0 between the nodes of the coarse grid, two launches
+    def envelope(self, n_starts=1, xtol=1e-5, max_eval=32):
+        """gam_env(alpha) = max over theta0 of gam(alpha, theta0) of every line of the coarse grid: the coarse scan, then
+        Context.theta0_polish about the n_starts <= 4 best peaks of every line's row (Brent between the nodes on the staged line:
+        no geometry launch beyond the coarse scan's).  Returns numpy dict(theta0, gam, node, n_eval (n_own, nalpha, n_starts),
+        n_found (n_own, nalpha), surface (n_own, 3) = (theta0*, alpha, gam) of the best slot of every surface, first maximum in
+        (alpha, slot) order).  gam is never below the coarse row, so surface[:, 2] bounds the coarse maximum from above.
+        eigenpair="nearest" is refused (ValueError): that mode's gam is not lam_max's.  Flagged solves (status bits 0-1) raise."""
+        if self.nearest:
+            raise ValueError("envelope() maximises lam_max's growth rate: eigenpair='nearest' is not supported")
+        if isinstance(n_starts, bool) or not isinstance(n_starts, (int, np.integer)) or not 1 <= n_starts <= MAX_ROW_STARTS:
+            raise ValueError("n_starts must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, n_starts))
+        na, K = len(self.alpha_scan), int(n_starts)
+        if not self.own:
+            z = np.zeros((0, na, K))
+            return dict(theta0=z, gam=z.copy(), node=z.astype(np.int32), n_eval=z.astype(np.int32), n_found=np.zeros((0, na), np.int32),
+                        surface=np.zeros((0, 3)))
+        if self.tables is not None and self.device is not None:
+            import torch
+            r = self.ctx.fieldline_geometry(self.tables, np.repeat(self._own_surf(), na), np.tile(self.alpha_scan, len(self.own)),
+                                            self.theta, device=self.device)
+            geo7, dP, t0 = [r["geo"][k] for k in range(7)], r["dPdrho"], torch.from_numpy(self.theta0_scan).to(self.device)
+        else:
+            geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
+            dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
+            geo7, t0 = [np.ascontiguousarray(geo[:, k]) for k in range(7)], self.theta0_scan
+        sc = self.ctx.gamma_scan(self.h, *geo7, dP, t0, want_info=True)
+        out = self.ctx.theta0_polish(self.h, *geo7, dP, t0, sc["gam"], n_starts=K, xtol=xtol, max_eval=max_eval, lam=sc["lam"],
+                                     want_info=True)
+        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        nbad = int(((host(sc["info"]) >> 16) != 0).sum()) + int((((host(out["info"]) >> 16) & 3) != 0).sum())
+        if nbad:
+            raise IbsError("%d solves of the envelope were flagged (status bits 0-1: iteration cap or invalid data)" % nbad)
+        n = len(self.own)
+        res = {k: host(out[k]).reshape(n, na, K) for k in ("theta0", "gam", "node", "n_eval")}
+        res["n_found"] = host(out["n_found"]).reshape(n, na)
+        flat = np.where(np.isnan(res["gam"]), -np.inf, res["gam"]).reshape(n, na * K)
+        best = np.argmax(flat, axis=1)                                           # (first maximum)
+        rows = np.arange(n)
+        res["surface"] = np.stack([res["theta0"].reshape(n, -1)[rows, best], self.alpha_scan[best // K],
+                                   res["gam"].reshape(n, -1)[rows, best]], axis=1)
+        return res
 
     # -- the top of the spectrum on the coarse grid of the surfaces this rank owns, one launch
     def modes(self, n_modes):
@@ -715,6 +915,7 @@ class BallooningScan:
         bad = res["n_bad"][0] * 0
         ccount = torch.zeros(3, dtype=torch.float64, device=dev) if self.certify else None
         t_fill = 0.0
+        envs = []
         for c0, c1 in chunks:
             if fill is not None:
                 t0 = time.perf_counter(); fill(c0, c1); t_fill += time.perf_counter() - t0
@@ -739,12 +940,29 @@ class BallooningScan:
                     ccount = ccount + self._cert_counts(cert)
                 st = ctx.scan_starts(res["alpha"], res["t0"], sc["pack"], res["n_bad"])
                 flagged = (sc["info"] >> 16) != 0
+            gm = sc["pack"][:, 0]
+            if self.theta0_polish:
+                # every line's crest between the nodes; the surface's start is the first maximum of gam_env over its lines
+                env = ctx.theta0_polish(self.h, *[geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], sc["gam"], lam=sc["lam"],
+                                        want_info=True)
+                envs.append(env)
+                ge = torch.nan_to_num(env["gam"].view(c1 - c0, na), nan=-float("inf"))
+                gm = ge.max(dim=1).values
+                col = torch.arange(na, device=dev).expand_as(ge)
+                first = torch.where(ge == gm[:, None], col, na).min(dim=1).values.clamp(max=na - 1)
+                ok = torch.isfinite(gm) & (gm != 0.0)                              # (else the start scan_starts gave: (0, 0))
+                t_star = env["theta0"].view(c1 - c0, na).gather(1, first[:, None])[:, 0]
+                st = torch.where(ok[:, None], torch.stack([res["alpha"][first], t_star], dim=1), st)
+                gm = torch.where(ok, gm, sc["pack"][:, 0])
+                flagged = torch.cat([flagged.view(-1), (((env["info"] >> 16) & 3) != 0).view(-1)])
             mark("s1")
             if len(chunks) == 1:
-                start, gmax = st, sc["pack"][:, 0]
+                start, gmax = st, gm
             else:
-                start[c0:c1] = st; gmax[c0:c1] = sc["pack"][:, 0]
+                start[c0:c1] = st; gmax[c0:c1] = gm
             bad = bad + flagged.sum()
+        if envs:
+            self.last_envelope = {k: torch.cat([e[k] for e in envs]) for k in envs[0] if k != "nbad"}
         mark("r0")
         if refine and self.nearest:
             # ibs_refine_f64 has no nearest-sigma form: the host-driven state machines, one geometry + ibs_obj_w_grad_nearest_f64

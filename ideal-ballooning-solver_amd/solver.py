@@ -33,6 +33,7 @@ MAX_MODES = 16
 CLUSTER_BIT = 1 << 9
 # multi-start refinement (ibs_scan_peaks_f64): starts per surface at most
 MAX_STARTS = 16
+MAX_ROW_STARTS = 4      # ibs_theta0_polish_f64: start slots per line
 
 
 def _is_torch(x):
@@ -749,6 +750,34 @@ class Context:
                 ar.out("n_found", (n_surf,), _I32, want_found), ar.inout("scan_peaks", "n_bad", n_bad, _I32))
         ar.outs["n_bad"] = n_bad
         return ar.outs
+
+    def theta0_polish(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, gam, n_starts=1, xtol=1e-5,
+                      max_eval=32, lam=None, node=None, want_lam=False, want_info=False, want_found=True):
+        """gam of every line maximised over theta0 between the nodes of its coarse row (ibs_theta0_polish_f64; the rule:
+        scan.row_peaks and scan.polish_theta0): about the n_starts <= 4 best peaks of gam[line], or about the nodes the caller names.
+        geometry arrays (n_lines, N), odd N <= 2050; dPdrho (n_lines,); theta0 (n_theta0,): finite and strictly increasing; gam
+        (n_lines, n_theta0): the coarse table of gamma_scan on these lines; lam, same shape, optional: warm starts; node int32
+        (n_lines, n_starts), optional: the nodes to polish about (-1 = skip the slot) instead of the row's own peaks.
+        Returns dict(theta0, gam (n_lines, n_starts), node, n_eval int32 (n_lines, n_starts)[, lam][, info int32: sweeps | status << 16]
+        [, n_found int32 (n_lines,)], nbad): gam is never below the coarse row; status bit 10 = the node itself was returned, bit 11 =
+        max_eval reached, bit 12 = one-sided bracket.  Slots from n_found on repeat slot 0; a row without a finite entry gives NaN."""
+        K = int(n_starts)
+        if K != n_starts or not 1 <= K <= MAX_ROW_STARTS:
+            raise IbsError("n_starts must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, n_starts))
+        geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        shape = (int(geo[0].shape[0]), int(theta0.shape[0]))
+        for name, t in (("gam", gam), ("lam", lam)):
+            if t is not None and tuple(t.shape) != shape:
+                raise IbsError("theta0_polish: %s must be %s, not %s" % (name, shape, tuple(t.shape)))
+        slots = (shape[0], K)
+        if node is not None and tuple(node.shape) != slots:
+            raise IbsError("theta0_polish: node must be %s, not %s" % (slots, tuple(node.shape)))
+        ar = _Args(self)
+        head, _, N = ar.geo(h, geo, dPdrho, theta0)
+        rc = ar.call("ibs_theta0_polish_f64", *head, ar.inp(gam), ar.inp(lam), ar.inp(node, _I32), K, float(xtol), int(max_eval),
+                     ar.out("theta0", slots), ar.out("gam", slots), ar.out("lam", slots, want=want_lam), ar.out("node", slots, _I32),
+                     ar.out("n_eval", slots, _I32), ar.out("info", slots, _I32, want_info), ar.out("n_found", (shape[0],), _I32, want_found))
+        return ar.result(rc)
 
     def obj_w_grad(self, h, geo, theta0, del_alpha=0.004, want_info=False):
         """geo: (n_pts, 3, 8, N) -- lines (alpha-d/2, alpha, alpha+d/2) x (bmag, gradpar, cvdrift, cvdrift0,

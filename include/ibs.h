@@ -52,6 +52,9 @@
  *            SOME vector of the cluster's invariant subspace (it satisfies the pencil to the residual bound of ibs_solve_gcf_vjp_f64
  *            and is otherwise unspecified) and gam is that vector's quotient.  Informational: not counted by return values > 0.
  *            The derivative of one member of a cluster does not exist: do not hand such a pair to ibs_solve_gcf_vjp_f64.
+ *     bits 10-12, ibs_theta0_polish_f64 only, per start slot, all informational (not counted by return values > 0): bit 10 = the
+ *            coarse node itself was returned (no evaluated point beat it strictly); bit 11 = the search stopped at max_eval;
+ *            bit 12 = one-sided bracket (the row ends at the node, or the neighbour on that side is NaN).
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
  *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
  *     for every sigma, lam_max's among them; they never set bit 4.
@@ -741,6 +744,58 @@ int ibs_surface_argmax_pack_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per_surf
 int ibs_scan_peaks_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_alpha, int32_t n_theta0, int32_t n_starts, const double* alpha,
                        const double* theta0, const double* gam, double* start, double* peak, int32_t* index, double* sigma0,
                        int32_t* n_found, int32_t* n_bad, int32_t mem);
+
+/* The growth rate of every line maximised over theta0 BETWEEN the nodes of the coarse scan: gam_env = max over theta0 of gam(line,
+ * theta0), about the n_starts best peaks of the line's coarse row.  Stands beside ball_scan.py:248-295, where upstream has no such
+ * step: it reads every maximum off the nodes and refines only the surface's first maximum, in (alpha, theta0), at three new field
+ * lines per evaluation.  The theta0 direction needs no new geometry: the fold (ball_scan.py:267-268) turns the staged line into the
+ * system of any theta0.
+ *   The rule (csrc/ibs_theta0_polish.hpp; ibs_amd.scan.row_peaks and polish_theta0 in Python).  Row peaks: entry j of gam[line][:] is
+ *   a peak if it is not NaN and neither neighbour inside the row beats it (w beats v if w > v, or w == v and w has the smaller index; a
+ *   NaN never beats anything); peaks rank by value descending, ties by index ascending; slot k holds peak k, slots from n_found on
+ *   repeat slot 0, a row without a finite entry has n_found = 0, node -1 and NaN outputs.  Bracket of node j: [theta0[j-1],
+ *   theta0[j+1]], cut to the node on a side where the row ends or the neighbour is NaN; zero length: the node, 0 evaluations; exactly
+ *   one side cut: status bit 12.  Search: Brent's bounded maximiser (parabolic step, golden-section fallback; derivative-free: the
+ *   Hellmann-Feynman dgam_dtheta0 is not the derivative of the gam that is returned), seeded with the three known node values so that
+ *   nothing known is solved again (one-sided: first the golden point next to the node); it stops on |x - m| <= 2 xtol - (b - a) / 2
+ *   or after max_eval evaluations (bit 11); an evaluation that fails or is not finite counts as -inf and its status bits 0-1 are
+ *   OR-ed into the slot's word.  Incumbent: the result is the polished point only if its gam is STRICTLY greater than the node's,
+ *   else the node itself with the table's gam (bit 10): gam_star is never below the coarse row.
+ *   The seven arrays [n_lines][ld], dPdrho [n_lines]: as ibs_gamma_scan_f64;  theta0 [n_theta0]: finite and strictly increasing;
+ *   gam [n_lines][n_theta0]: the coarse table (required);  lam, same shape, optional: warm starts of the first solve of a slot;
+ *   node_in [n_lines][n_starts], optional: polish about THESE nodes (-1, a node outside the row or one whose gam is NaN = skip the
+ *   slot: NaN outputs, node -1) instead of the row's own peaks; n_found is then written as 0;
+ *   theta0_star, gam_star [n_lines][n_starts] (required);  lam_star (the eigenvalue at theta0_star; NaN where the node is returned and
+ *   lam is NULL), node, n_eval, info (int32) [n_lines][n_starts] and n_found [n_lines] optional.
+ *   info: bits 0..15 = forward sweeps of all evaluations of the slot, saturated; bits 16.. = the status (conventions above).
+ * FP64, odd N in [66, 2050]; beyond, and even N: IBS_ERR_UNSUPPORTED (the staged-line kernel has no long-grid form).  n_starts outside
+ * [1, 4], xtol <= 0 or not finite, max_eval outside [1, 64], a dimension < 1 or a required pointer NULL: IBS_ERR_ARG before the context
+ * is touched; n_lines = 0: nothing happens.  A theta0 grid that is not finite and strictly increasing: IBS_ERR_ARG on host pointers;
+ * on device pointers every slot gets status bit 1 and NaN.  Host or device pointers (mem); host pointers: returns the number of slots
+ * with status bit 0 or 1.  One block per line, one wavefront per slot; results are bitwise repeatable and independent of n_lines, of
+ * the order of the lines and, for slot 0, of n_starts. */
+int ibs_theta0_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                          const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                          const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                          const double* gam, const double* lam, const int32_t* node_in, int32_t n_starts, double xtol,
+                          int32_t max_eval, double* theta0_star, double* gam_star, double* lam_star, int32_t* node,
+                          int32_t* n_eval, int32_t* info, int32_t* n_found, int32_t mem);
+
+/* HOST side of the same rule (no GPU involved; the pattern of ibs_lbfgsb2_*): the search of one node as a reverse-communication
+ * state machine, and the row peaks.
+ *   state: caller-owned buffer of ibs_theta0_polish_state_bytes() bytes.
+ *   init:  theta0 [n_theta0], row [n_theta0] = the coarse gam of the line, node = the entry to polish about; returns 1 = evaluate gam
+ *          at *x_next, 0 = finished at once (zero-length bracket).  A bad grid, node, xtol or max_eval: IBS_ERR_ARG.
+ *   step:  hand over gam at the point last requested and the status bits 0-1 of that evaluation; returns 1 = evaluate at *x_next,
+ *          0 = finished.
+ *   result: theta0_star, gam_star, n_eval, status (bits 0-1, 10, 11, 12), each optional.
+ *   ibs_row_peaks_f64: gam [n_rows][n_theta0] -> node [n_rows][K] (int32), n_found [n_rows] (optional), 1 <= K <= 4. */
+int ibs_theta0_polish_state_bytes(void);
+int ibs_theta0_polish_init(void* state, int32_t n_theta0, const double* theta0, const double* row, int32_t node, double xtol,
+                           int32_t max_eval, double* x_next);
+int ibs_theta0_polish_step(void* state, double gam, int32_t eval_status, double* x_next);
+int ibs_theta0_polish_result(const void* state, double* theta0_star, double* gam_star, int32_t* n_eval, int32_t* status);
+int ibs_row_peaks_f64(int32_t n_rows, int32_t n_theta0, int32_t K, const double* gam, int32_t* node, int32_t* n_found);
 
 #ifdef __cplusplus
 }
