@@ -66,6 +66,7 @@ static int fail(int code, const char* fmt, ...) {
 struct ibs_options : ibs::PlanOpts {     // (force_p, scan_chain, scan_resident, gcf_rows, gcf_direct, f32_lam, pack_mode, sturm_form: ibs_plan.hpp)
   int geo_lpp = 0;        // lanes per grid point of the geometry kernel: 1 | 2 | 4
   double sigma0 = std::numeric_limits<double>::quiet_NaN();   // not NaN: solves that return lam AND info flag lam_max >= sigma0 (informational status bit 4: utils.py:1597 would have taken the eigenpair nearest sigma0)
+  int scan_trial_table = 1; // resident theta0 scan: 1 = the trial vector's start comes from the context's per-grid table, 0 = every wave computes it
   int reclose = 1;        // FP64 raw systems: 1 = a solve whose closing bracket fails its consistency checks is re-closed in division form, 2 = only marked, 0 = off
   int refine_tangent = -1; // refinement: alpha-tangent of a point staged in LDS (1) or read from global memory in the sums (0); -1 = by batch size
   double chain_w1 = 0.25, chain_w2 = 1.0;   // relative widths of the chain's warm starts
@@ -106,6 +107,14 @@ struct ibs_ctx {
   // have their fused kernels in flight at the same time, and shared counters would mix their arrivals.
   struct SurfCounters { hipStream_t stream; int* buf; int n; };
   std::vector<SurfCounters> surf_counters;
+  // trial tables of the resident scan kernel (k_trial_table: the start of every lane's trial vector, a function of the grid length and
+  // the rows per lane alone), built on first use and kept until ibs_destroy.  An entry belongs to the STREAM it was built on as well:
+  // build and use are then ordered by the stream itself, with no synchronisation, whichever streams the context is moved between.
+  // A full cache replaces the entry used longest ago, behind a device synchronisation (a launch on another stream may still read it)
+  struct TrialTable { int N = 0, M = 0; hipStream_t stream = nullptr; double* buf = nullptr; unsigned long long used = 0; };
+  static constexpr int kTrialTables = 16;
+  TrialTable trial_tables[kTrialTables];
+  unsigned long long trial_clock = 0;
   // ibs_refine_f64: per-round counts posted by the device (pinned host memory), statistics of the last call
   int* refine_hist = nullptr;
   int refine_hist_len = 0;
@@ -659,6 +668,7 @@ int ibs_destroy(ibs_ctx* c) {
   if (c->long_ws) hipFree(c->long_ws);
   if (c->fix_buf) hipFree(c->fix_buf);
   for (auto& sc : c->surf_counters) if (sc.buf) hipFree(sc.buf);
+  for (auto& tt : c->trial_tables) if (tt.buf) hipFree(tt.buf);
   if (c->refine_hist) hipHostFree(c->refine_hist);
   if (c->hs) hipHostFree(c->hs);
   delete c;
@@ -681,6 +691,7 @@ int ibs_set_option(ibs_ctx* c, const char* name, double value) {
   else if (n == "gcf_rows") c->opt.gcf_rows = reset ? c->opt_created.gcf_rows : (int)value;
   else if (n == "gcf_direct") c->opt.gcf_direct = reset ? c->opt_created.gcf_direct : (int)value;
   else if (n == "scan_resident") c->opt.scan_resident = reset ? c->opt_created.scan_resident : (int)value;
+  else if (n == "scan_trial_table") c->opt.scan_trial_table = reset ? c->opt_created.scan_trial_table : (int)value;
   else if (n == "pack_mode") c->opt.pack_mode = reset ? c->opt_created.pack_mode : (int)value;
   else if (n == "f32_lam") c->opt.f32_lam = reset ? c->opt_created.f32_lam : (int)value;
   else if (n == "reclose") c->opt.reclose = reset ? c->opt_created.reclose : (int)value;
@@ -1468,6 +1479,34 @@ static int launch_scan_long(ibs_ctx* ctx, const ibs::ScanArgs<double>& a) {
   return 0;
 }
 
+// The trial table of the resident scan kernel for (N, M) on the context's current stream (ibs_ctx::trial_tables): the cached one, or
+// a new one whose build is enqueued on that stream in front of the launch that reads it.  *out = null where there is none to give (the
+// option is off, no builder for this M, or the stream is being captured: a captured build would run at replay, not now, and the
+// entry would be taken for built) -- the kernel then computes the values itself, to the same bits.
+static int trial_table_for(ibs_ctx* ctx, int N, int M, const double** out) {
+  *out = nullptr;
+  const ibs::LaunchTable& t = ibs::launch_table();
+  if (!ctx->opt.scan_trial_table || M < 0 || M > ibs::kMaxM || !t.trial_table_f64[M]) return 0;
+  ibs_ctx::TrialTable* slot = nullptr;
+  for (auto& e : ctx->trial_tables) {
+    if (e.buf && e.N == N && e.M == M && e.stream == ctx->stream) { e.used = ++ctx->trial_clock; *out = e.buf; return 0; }
+    if (!slot || (slot->buf && (!e.buf || e.used < slot->used))) slot = &e;      // a free entry, else the one used longest ago
+  }
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(ctx->stream, &cap) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (cap != hipStreamCaptureStatusNone) return 0;
+  if (slot->buf) {
+    HIPCHK(hipDeviceSynchronize());
+    slot->N = 0;                                   // (not (N, M)'s until its build is enqueued: a failure below leaves no false entry)
+  } else {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&slot->buf), (size_t)ibs::kTrialTableLen * sizeof(double)));
+  }
+  HIPCHK(t.trial_table_f64[M](N, slot->buf, ctx->stream));
+  slot->N = N; slot->M = M; slot->stream = ctx->stream; slot->used = ++ctx->trial_clock;
+  *out = slot->buf;
+  return 0;
+}
+
 static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
                            const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
                            const double* gds2, const double* gds21, const double* gds22, int64_t ld,
@@ -1531,6 +1570,9 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
         sc->n = cap_n;
       }
       a.lines_per_surf = n_lines / n_surf; a.surf_counter = sc->buf; a.pack = pack; a.pack_mode = plan.pack_mode;
+    }
+    if (plan.form == ibs::ScanForm::Wave && plan.resident) {
+      if (int r = trial_table_for(ctx, N, plan.M, &a.trial_tab)) return r;
     }
     if (!fn) {
       if (int r = launch_scan_long(ctx, a)) return r;

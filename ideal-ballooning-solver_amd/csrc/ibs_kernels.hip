@@ -1123,8 +1123,9 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
                                                      T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
                                                      int* info_out, const T* __restrict__ lam_guess, T guess_width,
                                                      int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
-                                                     int t0_stride, T ih2, T ih, int nparts_1d) {
+                                                     int t0_stride, T ih2, T ih, int nparts_1d, const T* __restrict__ trial_tab) {
   // t0_stride: 0 = the theta0 grid is shared by all lines; 1 (with n_theta0 = 1) = one theta0 per line (ibs_gamma_points_f64)
+  // trial_tab (RES only): the table k_trial_table<T, M> filled for this N, or null = set-up computes the trial vector's start itself
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1135,7 +1136,8 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
     // uses it, which made four dependent scalar-memory rounds between entry and the first staging load (map | theta0 | lam_guess |
     // the array pointers).  One empty statement that names them all puts their fetches in one round at entry.
     asm volatile("" :: "s"(bmag), "s"(gradpar), "s"(cvdrift), "s"(cvdrift0), "s"(gds2), "s"(gds21), "s"(gds22), "s"(ld), "s"(dPdrho),
-                 "s"(theta0), "s"(lam_guess), "s"(n_lines), "s"(n_theta0), "s"(N), "s"(t0_stride), "s"(nparts_1d), "s"(wpb));
+                 "s"(theta0), "s"(lam_guess), "s"(n_lines), "s"(n_theta0), "s"(N), "s"(t0_stride), "s"(nparts_1d), "s"(wpb),
+                 "s"(trial_tab));
   }
   // XCD-aware block -> (line, part) map (ibs_scan_map.hpp): read from the block's indices; a column of the last chunk that has no
   // line returns here, before it touches LDS, memory or the arrival counters
@@ -1154,6 +1156,11 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
   const long sys = (long)line * n_theta0 + it0c;
   const T guess = lam_guess ? lam_guess[sys] : T(0);
   const T mdP = -dPdrho[line];
+  // (RES) the lane's start of the trial vector from the per-grid table, requested here for the same reason
+  [[maybe_unused]] T tab_prev = T(0), tab_cur = T(0), tab_two_cd = T(0);
+  if constexpr (RES) {
+    if (trial_tab) { tab_prev = trial_tab[2 * lane]; tab_cur = trial_tab[2 * lane + 1]; tab_two_cd = trial_tab[2 * kWave]; }
+  }
   {
     const long off = (long)line * ld;
     for (int j = threadIdx.x; j < N; j += blockDim.x) {
@@ -1171,7 +1178,10 @@ __device__ __forceinline__ void gamma_scan_body(int n_lines, int n_theta0, int N
   IBS_PROBE_AT(1);
   SrcGeo<T> src{A1, A3, C0, C1, G0, G1, G2, th0, T(2) * th0, th0 * th0};
   WaveSolver<T, M, RES> ws;
-  if constexpr (RES) { ws.rr.ih2 = ih2; ws.rr.ih = ih; }
+  if constexpr (RES) {
+    ws.rr.ih2 = ih2; ws.rr.ih = ih;
+    ws.rr.has_tab = trial_tab != nullptr; ws.rr.tab_prev = tab_prev; ws.rr.tab_cur = tab_cur; ws.rr.tab_two_cd = tab_two_cd;
+  }
   SolveInfo inf{0, 0};
 #ifdef IBS_PROBE_TWICE
   // experiment (round 5, tools/scan_probe.py): the set-up executed twice, the first result discarded -- is its time the code's
@@ -1276,10 +1286,11 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan(int n_lines,
                                                      T* gam_out, T* lam_out, T* X_out, T* dX_out, T* dth0_out,
                                                      int* info_out, const T* __restrict__ lam_guess, T guess_width,
                                                      int lines_per_surf, int* surf_counter, T* pack, int pack_mode,
-                                                     int t0_stride, T ih2, T ih, int nparts_1d) {
+                                                     int t0_stride, T ih2, T ih, int nparts_1d, const T* __restrict__ trial_tab) {
   gamma_scan_body<T, M, scan_resident_built(M)>(n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld,
                                                 dPdrho, theta0, gam_out, lam_out, X_out, dX_out, dth0_out, info_out, lam_guess,
-                                                guess_width, lines_per_surf, surf_counter, pack, pack_mode, t0_stride, ih2, ih, nparts_1d);
+                                                guess_width, lines_per_surf, surf_counter, pack, pack_mode, t0_stride, ih2, ih, nparts_1d,
+                                                trial_tab);
 }
 // the lean form under a name of its own (3 <= M <= 8: launches above two waves per SIMD, option scan_resident = 0)
 template <typename T, int M>
@@ -1295,7 +1306,20 @@ __global__ void __launch_bounds__(scan_max_threads(M)) k_gamma_scan_lean(int n_l
                                                      int t0_stride, int nparts_1d) {
   gamma_scan_body<T, M, false>(n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho, theta0,
                                gam_out, lam_out, X_out, dX_out, dth0_out, info_out, lam_guess, guess_width, lines_per_surf,
-                               surf_counter, pack, pack_mode, t0_stride, T(0), T(0), nparts_1d);
+                               surf_counter, pack, pack_mode, t0_stride, T(0), T(0), nparts_1d, nullptr);
+}
+
+// The per-grid trial table of the resident k_gamma_scan<T, M> (kTrialTableLen values): one wave, lane L stores trial_start's x_a and
+// x_{a+1} of its chunk, lane 0 the recurrence factor -- the expressions of WaveSolver::setup, so the bits a wave would compute.  The
+// Context builds one per grid length, on the stream of the first scan launch that wants it (ibs_api.hip).
+template <typename T, int M>
+__global__ void __launch_bounds__(kWave) k_trial_table(int N, T* __restrict__ tab) {
+  const int lane = threadIdx.x;
+  if (lane >= kWave) return;
+  T p, c, two_cd;
+  trial_start<T>(WaveSolver<T, M>::rows_start(lane, N - 2), N, p, c, two_cd);
+  tab[2 * lane] = p; tab[2 * lane + 1] = c;
+  if (lane == 0) tab[2 * kWave] = two_cd;
 }
 
 
@@ -2080,9 +2104,19 @@ static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
   hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
                      a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
                      a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
-                     a.t0_stride, a.ih2, a.ih, nparts_1d);
+                     a.t0_stride, a.ih2, a.ih, nparts_1d, scan_resident_built(IBS_M) ? a.trial_tab : nullptr);
   note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan<%s, %d>", type_name<T>(), IBS_M);
   return hipGetLastError();
+}
+// fills tab [kTrialTableLen] for grid length N (the resident form's rows per lane only)
+template <typename T>
+static hipError_t launch_trial_table(int N, T* tab, hipStream_t st) {
+  if constexpr (scan_resident_built(IBS_M)) {
+    hipLaunchKernelGGL((k_trial_table<T, IBS_M>), dim3(1), dim3(kWave), 0, st, N, tab);
+    return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;
+  }
 }
 template <typename T>
 static hipError_t launch_scan_chain(const ScanArgs<T>& a, hipStream_t st) {
@@ -2179,6 +2213,7 @@ struct IBS_CAT(Registrar, IBS_M) {
     t.gcf_fix_f32w[IBS_M] = &launch_gcf_fix<float>;
 #endif
     t.scan_f64[IBS_M] = &launch_scan<double>;
+    if constexpr (scan_resident_built(IBS_M)) t.trial_table_f64[IBS_M] = &launch_trial_table<double>;
     t.scan_chain_f64[IBS_M] = &launch_scan_chain<double>;
     t.theta0_polish_f64[IBS_M] = &launch_theta0_polish<double>;
     t.sturm_f64[IBS_M] = &launch_sturm<double>;

@@ -38,6 +38,9 @@ struct ScanArgs {
   // k_gamma_scan, 3 <= M <= 8: 1 = the resident form (set-up rows carried in registers, 186 VGPRs at M = 8: launches of at most two waves
   // per SIMD), 0 = the lean form k_gamma_scan_lean (126 VGPRs at M = 8).  ih2 = 1 / (h * h), ih = 1 / h: divided once, on the host
   int resident; T ih2, ih;
+  // resident form only: the Context's trial table for (N, rows per lane) (k_trial_table, kTrialTableLen values, built on the launch's
+  // stream), or null = every wave computes the start of its trial vector itself.  Same bits either way
+  const T* trial_tab;
 };
 // gam maximised over theta0 about the peaks of every line's coarse row (k_theta0_polish; the rule: ibs_theta0_polish.hpp).  One block
 // per line, n_starts <= 4 waves.  gam (required), lam (optional warm starts) [n_lines][n_theta0]; node_in (optional) and every output
@@ -337,6 +340,7 @@ struct LaunchTable {
   hipError_t (*gcf_f32w_rows[kMaxM + 1])(const GcfArgs<float>&, hipStream_t);  // the same, row-streamed (long grids)
   hipError_t (*gcf_f32w_g[2][kMaxM + 1])(const GcfArgs<float>&, hipStream_t);  // the same, 32 / 16 lanes per system
   hipError_t (*scan_f64[kMaxM + 1])(const ScanArgs<double>&, hipStream_t);
+  hipError_t (*trial_table_f64[kMaxM + 1])(int N, double* tab, hipStream_t);         // scan_resident_built(M) only: fills ScanArgs::trial_tab
   hipError_t (*scan_chain_f64[kMaxM + 1])(const ScanArgs<double>&, hipStream_t);
   hipError_t (*theta0_polish_f64[kMaxM + 1])(const Theta0PolishArgs<double>&, hipStream_t);
   hipError_t (*sturm_f64[kMaxM + 1])(const SturmArgs<double>&, hipStream_t);

@@ -136,6 +136,19 @@ __device__ __forceinline__ void trial_sincos(double x, double& sn, double& cs) {
   cs = ((q + 1) & 2) ? -c1 : c1;
 }
 __device__ __forceinline__ void trial_sincos(float x, float& sn, float& cs) { sn = __sinf(x); cs = __cosf(x); }
+// Start of the trial vector x_j = sin(pi j / (N - 1)) of WaveSolver::setup for a lane whose chunk begins at grid point a: x_a, x_{a+1}
+// and the factor 2 cos(pi / (N - 1)) of its recurrence.  They depend on N, the rows per lane and the lane alone: set-up forms them
+// here, and k_trial_table (ibs_kernels.hip) stores these same bits once per grid length for the resident scan kernel to load.
+template <typename T>
+__device__ __forceinline__ void trial_start(int a, int N, T& ts_prev, T& ts_cur, T& two_cd) {
+  const T dl = T(3.14159265358979323846) / T(N - 1);
+  T s0, c0, sd, cd;
+  trial_sincos(T(a) * dl, s0, c0);                 // grid point a = the left neighbour of the lane's first row
+  trial_sincos(dl, sd, cd);
+  ts_prev = s0; ts_cur = xfma(s0, cd, c0 * sd); two_cd = T(2) * cd;
+}
+// the table of k_trial_table: [2 * lane] = x_a, [2 * lane + 1] = x_{a+1} of lane's chunk, [2 * kWave] = 2 cos(pi / (N - 1))
+constexpr int kTrialTableLen = 2 * 64 + 1;
 
 // integer-built exponent helpers (v_frexp_exp / v_ldexp are slow-rate FP64 instructions):
 // expo_of: e with |x| in [2^e, 2^(e+1)) for normal x, a large negative number for 0 / denormals
@@ -461,19 +474,27 @@ __device__ __forceinline__ M2<T> scan_fwd(M2<T> P, int lane) {
 // products stay under their conditions: an identity factor in the idle rows would not do (it can turn the sign of a zero, and
 // a renormalised one moves the split of the shooting value).  A form of its own, so that scan_fwd stays as every other kernel
 // compiles it today.
+// Its lane masks are never empty in a full wave, which the conditions say (IBS_FULL_WAVE): the compiler then leaves out the
+// `s_cbranch_execz` it puts in front of a masked region for the case that no lane enters it -- a branch never taken, which cost the
+// lone wave about 19 clocks per region and sweep (docs/EXPERIMENTS.md R6.28).  (The compiler's own choice weighs the region's length
+// against an even chance of an empty mask; it has no switch for one translation unit.)  Scalar control flow only: the products and
+// their order stay.
+#ifndef IBS_FULL_WAVE      // (an A/B build defines it as the plain condition)
+#define IBS_FULL_WAVE(cond) __builtin_expect(!!(cond), 1)
+#endif
 template <typename T>
 __device__ __forceinline__ M2<T> scan_fwd_rows(M2<T> P, int lane) {
   constexpr bool RN = ScanNorm<T>::v;
   const int l16 = lane & 15, row = lane >> 4;
-  { const M2<T> F = dpp_fetch<T, 0x111, 0xF>(P); if (l16 >= 1) mul_inplace<T, false>(P, F); }   // row_shr:1
-  { const M2<T> F = dpp_fetch<T, 0x112, 0xF>(P); if (l16 >= 2) mul_inplace<T, RN>(P, F); }      // row_shr:2
-  { const M2<T> F = dpp_fetch<T, 0x114, 0xF>(P); if (l16 >= 4) mul_inplace<T, false>(P, F); }   // row_shr:4
-  { const M2<T> F = dpp_fetch<T, 0x118, 0xF>(P); if (l16 >= 8) mul_inplace<T, RN>(P, F); }      // row_shr:8
-  { const M2<T> F = dpp_fetch_rows<T, 0x142, 0xA>(P); if (row & 1) mul_inplace<T, false>(P, F); }   // row_bcast:15 -> rows 1,3
+  { const M2<T> F = dpp_fetch<T, 0x111, 0xF>(P); if (IBS_FULL_WAVE(l16 >= 1)) mul_inplace<T, false>(P, F); }   // row_shr:1
+  { const M2<T> F = dpp_fetch<T, 0x112, 0xF>(P); if (IBS_FULL_WAVE(l16 >= 2)) mul_inplace<T, RN>(P, F); }      // row_shr:2
+  { const M2<T> F = dpp_fetch<T, 0x114, 0xF>(P); if (IBS_FULL_WAVE(l16 >= 4)) mul_inplace<T, false>(P, F); }   // row_shr:4
+  { const M2<T> F = dpp_fetch<T, 0x118, 0xF>(P); if (IBS_FULL_WAVE(l16 >= 8)) mul_inplace<T, RN>(P, F); }      // row_shr:8
+  { const M2<T> F = dpp_fetch_rows<T, 0x142, 0xA>(P); if (IBS_FULL_WAVE(row & 1)) mul_inplace<T, false>(P, F); }   // row_bcast:15 -> rows 1,3
   {                                                                                             // row_bcast:31 -> rows 2,3
     const T Fa = dppu_t<0x143, 0xC>(P.a), Fc = dppu_t<0x143, 0xC>(P.c);
     const int Fe = dppu_i<0x143, 0xC>(P.e);
-    if (row >= 2) {
+    if (IBS_FULL_WAVE(row >= 2)) {
       const T na = xfma(P.a, Fa, P.b * Fc);
       P.c = xfma(P.c, Fa, P.d * Fc);
       P.a = na;
@@ -673,6 +694,10 @@ struct ResidentRows<T, M, true> {
   T a1[M], d[M], c[M], f[M], zu[M], s[M];
   T ih2, ih;
   unsigned own;      // the sign changes of a forward sweep this lane counts (sweep_count_mask): set-up forms it once
+  // the lane's entries of the per-grid trial table (trial_start's three values, loaded at kernel entry); has_tab = false (wave-uniform:
+  // the caller has no table): set-up computes them
+  T tab_prev, tab_cur, tab_two_cd;
+  bool has_tab;
 };
 
 template <typename T, int M, bool RES = false>
@@ -761,11 +786,12 @@ struct WaveSolver {
     const T e_first = e_lo;
     T ts_prev = T(0), ts_cur = T(0), two_cd = T(0), tA = T(0), tB = T(0), tC = T(0);
     if constexpr (TRIAL) {
-      const T dl = T(3.14159265358979323846) / T(N - 1);
-      T s0, c0, sd, cd;
-      trial_sincos(T(a) * dl, s0, c0);                 // grid point a = the left neighbour of this lane's first row
-      trial_sincos(dl, sd, cd);
-      ts_prev = s0; ts_cur = xfma(s0, cd, c0 * sd); two_cd = T(2) * cd;
+      if constexpr (RES) {
+        if (rr.has_tab) { ts_prev = rr.tab_prev; ts_cur = rr.tab_cur; two_cd = rr.tab_two_cd; }
+        else trial_start<T>(a, N, ts_prev, ts_cur, two_cd);
+      } else {
+        trial_start<T>(a, N, ts_prev, ts_cur, two_cd);
+      }
     }
 #pragma unroll
     for (int i = 0; i < M; ++i) {

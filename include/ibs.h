@@ -152,7 +152,9 @@ int ibs_comm_destroy(ibs_ctx* ctx);
  * staged in LDS, 1, or read from global memory by the sums, 0: two blocks per CU instead of one at N = 969; -1 = by batch size),
  * "scan_resident" (the one-wave-per-system theta0 scan at 3 to 8 rows per lane, N = 131 .. 514: 1 = k_gamma_scan, which carries the rows
  * of its set-up in registers up to the growth-rate stage, wherever it is built; 0 = k_gamma_scan_lean, which rebuilds them, everywhere;
- * -1 = the default: the former while the launch holds at most two waves per SIMD, the latter above; same results bit for bit);
+ * -1 = the default: the former while the launch holds at most two waves per SIMD, the latter above; same results bit for bit),
+ * "scan_trial_table" (k_gamma_scan: 1 = the start of every lane's trial vector is loaded from a table the context builds on the device once
+ * per grid length, the default; 0 = every wave computes it; same results bit for bit);
  * value 0 = automatic (refine_tangent, gcf_direct, scan_resident: -1); value NaN = back to what ibs_create() read from the environment
  * (IBS_FORCE_P, IBS_SCAN_CHAIN, IBS_CHAIN_W1, IBS_CHAIN_W2, IBS_GEO_LPP are read once, there); name "all" with NaN
  * resets every option.  Results never depend on these switches beyond rounding; only the kernel variant does. */
