@@ -161,18 +161,7 @@ struct DeviceGuard {
   DeviceGuard dev_guard_((ctx_)->device);                                                                   \
   if (dev_guard_.err != hipSuccess) return fail(IBS_ERR_HIP, "hipSetDevice(%d) -> %s", (ctx_)->device, hipGetErrorString(dev_guard_.err))
 
-size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-// Device buffers carved out of one workspace, sized by the very sequence of take() calls that carves them: a first pass without a
-// buffer only counts (Carve{nullptr}), the second carves.
-struct Carve {
-  char* base; size_t off = 0;
-  template <typename T> T* take(size_t n) {
-    off = pad256(off);
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
+using ibs::pad256; using ibs::Carve;      // (ibs_plan.hpp)
 
 int ensure_long_ws(ibs_ctx* c, size_t bytes) {
   if (bytes <= c->long_ws_bytes) return 0;
@@ -380,6 +369,55 @@ int staged(ibs_ctx* ctx, int32_t mem, Decl&& decl, Launch&& launch) {
   }
   HIPCHK(hs.flush_out());
   return nbad;
+}
+
+// What the geometry-fed entry points take for a batch of lines: the seven arrays [n_lines][ld], dPdrho [n_lines] and theta0 [n_theta0]
+// shared by all lines -- or, per_line, n_theta0 = 1 and theta0 [n_lines] (the points forms).  Built once from the extern "C" argument
+// list; the entry point checks it, declares it to its Stage and takes the views of its chunks from the staged copy.
+struct GeoLines {
+  const double* a[7] = {};         // bmag gradpar cvdrift cvdrift0 gds2 gds21 gds22
+  int64_t ld = 0;
+  const double *dPdrho = nullptr, *theta0 = nullptr;
+  bool per_line = false;
+  bool present() const { for (const double* p : a) if (!p) return false; return true; }
+  GeoLines declare(Stage& s, size_t n_lines, size_t n_theta0) const {
+    GeoLines d = *this;
+    for (int k = 0; k < 7; ++k) d.a[k] = s.in(a[k], n_lines * (size_t)ld);
+    d.dPdrho = s.in(dPdrho, n_lines); d.theta0 = s.in(theta0, per_line ? n_lines : n_theta0);
+    return d;
+  }
+  GeoLines at(long l0) const {     // the lines from l0 on
+    GeoLines v = *this;
+    for (int k = 0; k < 7; ++k) v.a[k] = a[k] + l0 * ld;
+    v.dPdrho = dPdrho + l0; v.theta0 = theta0 + (per_line ? l0 : 0);
+    return v;
+  }
+  // into launch arguments (ibs_launch.hpp): the geo7[7] form, and the named members of ScanArgs / Theta0PolishArgs
+  template <class A> void into(A& x) const { for (int k = 0; k < 7; ++k) x.geo7[k] = a[k]; x.dPdrho = dPdrho; x.theta0 = theta0; }
+  template <class A> void into_named(A& x) const {
+    x.bmag = a[0]; x.gradpar = a[1]; x.cvdrift = a[2]; x.cvdrift0 = a[3]; x.gds2 = a[4]; x.gds21 = a[5]; x.gds22 = a[6];
+    x.dPdrho = dPdrho; x.theta0 = theta0;
+  }
+};
+
+// The lines of a geometry-fed scan, chunk after chunk of whole lines (ibs::plan_line_chunks under kLineChunkBudget and option
+// "nearest_chunk_systems").  carve(Carve&, L) declares ctx->long_ws of a chunk of L lines -- it runs against no buffer to size the
+// chunk and LAST against ctx->long_ws, so what it sets by side effect is then real --, body(l0, Lc) launches the Lc lines from l0 on and
+// returns an IBS code; the first that is not 0 ends the loop.
+template <class CarveFn, class Body>
+int for_line_chunks(ibs_ctx* ctx, const char* what, long n_lines, int n_theta0, int N, CarveFn&& carve, Body&& body) {
+  auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
+  const ibs::LineChunks ch = ibs::plan_line_chunks(n_lines, n_theta0, ctx->opt.nearest_chunk_systems, ibs::kLineChunkBudget, bytes_of);
+  if (ensure_long_ws(ctx, ch.bytes) != 0) {
+    (void)hipGetLastError();
+    return fail(IBS_ERR_HIP, "%s: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
+                "which could not be allocated", what, ch.lines, n_theta0, N, ch.bytes);
+  }
+  Carve cv{static_cast<char*>(ctx->long_ws)};
+  carve(cv, ch.lines);
+  for (long l0 = 0; l0 < n_lines; l0 += ch.lines)
+    if (int r = body(l0, n_lines - l0 < ch.lines ? n_lines - l0 : ch.lines)) return r;
+  return 0;
 }
 
 // Nearest-sigma report (option "sigma0"): the reference takes the eigenpair NEAREST sigma0 (eigs(..., sigma=sigma0), utils.py:1597;
@@ -1053,21 +1091,20 @@ int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
                           const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
                           const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
                           double* scale, double* mu, double* dscale_dtheta0, double* dscale_ddPdrho, int32_t* info, int32_t mem) {
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
-  if (!bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho || !theta0 || !scale)
+  if (!geo.present() || !dPdrho || !theta0 || !scale)
     return fail(IBS_ERR_ARG, "null argument (the geometry arrays, dPdrho, theta0 and scale are required)");
   if (n_lines < 0 || n_theta0 < 0 || ld < N)
     return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
   if (int r = check_grid(N, h, true)) return r;
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
+  const size_t n_sys = (size_t)n_lines * n_theta0;
   ibs::MarginalScanArgs a{};
   a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
-    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_theta0);
+    geo.declare(s, n_lines, n_theta0).into(a);
     a.scale = s.out(scale, n_sys); a.mu = s.out(mu, n_sys); a.dth0 = s.out(dscale_dtheta0, n_sys); a.ddP = s.out(dscale_ddPdrho, n_sys);
     a.info = s.status(info, n_sys);
   };
@@ -1137,13 +1174,11 @@ int ibs_marginal_obj_w_grad_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, 
 
 // Scans that solve the assembled rows: the (g, c, f) rows of a chunk of whole lines are written out by k_assemble_gcf_long (the
 // arithmetic of the scan kernels' staging: ball_scan.py:267-268 + utils.py:1560-1562) and handed to solve(first system, systems, G, C, F,
-// work, work_doubles, waves) -- a one-wave-per-system kernel with ws_per_wave doubles of workspace per wave; chunks are bounded by
-// kNearestScanBytes of workspace (rows + the solver's per-wave workspace), or by option "nearest_chunk_systems".
-static constexpr size_t kNearestScanBytes = size_t(1) << 30;
+// work, work_doubles, waves) -- a one-wave-per-system kernel with ws_per_wave doubles of workspace per wave.  The chunks (rows + the
+// solver's per-wave workspace) are those of for_line_chunks.
 using ScanChunkSolve = std::function<int(long, long, double*, double*, double*, double*, size_t, long)>;
-static int scan_rows_chunked(ibs_ctx* ctx, const char* what, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
-                             const double* const geo7[7], int64_t ld, const double* dPdrho, const double* theta0, size_t ws_per_wave,
-                             const ScanChunkSolve& solve) {
+static int scan_rows_chunked(ibs_ctx* ctx, const char* what, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const GeoLines& geo,
+                             size_t ws_per_wave, const ScanChunkSolve& solve) {
   int nw = 0;
   double *work, *G, *C, *F;
   auto carve = [&](Carve& cv, long L) {          // ctx->long_ws of a chunk of L lines
@@ -1152,73 +1187,49 @@ static int scan_rows_chunked(ibs_ctx* ctx, const char* what, int32_t n_lines, in
     work = cv.take<double>((size_t)nw * ws_per_wave);
     G = cv.take<double>((size_t)S * N); C = cv.take<double>((size_t)S * N); F = cv.take<double>((size_t)S * N);
   };
-  auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
-  long L = n_lines;
-  if (ctx->opt.nearest_chunk_systems > 0) L = ctx->opt.nearest_chunk_systems / n_theta0;
-  else while (L > 1 && bytes_of(L) > kNearestScanBytes) L = (L + 1) / 2;
-  if (L < 1) L = 1;
-  if (L > n_lines) L = n_lines;
-  const size_t bytes = bytes_of(L);
-  if (ensure_long_ws(ctx, bytes) != 0) {
-    (void)hipGetLastError();
-    return fail(IBS_ERR_HIP, "%s: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
-                "which could not be allocated", what, L, n_theta0, N, bytes);
-  }
-  Carve cv{static_cast<char*>(ctx->long_ws)};
-  carve(cv, L);
-  for (long l0 = 0; l0 < n_lines; l0 += L) {
-    const int Lc = (int)(n_lines - l0 < L ? n_lines - l0 : L);
+  return for_line_chunks(ctx, what, n_lines, n_theta0, N, carve, [&](long l0, long Lc) -> int {
     ibs::ScanArgs<double> sa{};
-    sa.n_lines = Lc; sa.n_theta0 = n_theta0; sa.N = N; sa.h = h; sa.ld = ld; sa.t0_stride = 0;
-    sa.bmag = geo7[0] + l0 * ld; sa.gradpar = geo7[1] + l0 * ld; sa.cvdrift = geo7[2] + l0 * ld; sa.cvdrift0 = geo7[3] + l0 * ld;
-    sa.gds2 = geo7[4] + l0 * ld; sa.gds21 = geo7[5] + l0 * ld; sa.gds22 = geo7[6] + l0 * ld;
-    sa.dPdrho = dPdrho + l0; sa.theta0 = theta0;
+    sa.n_lines = (int)Lc; sa.n_theta0 = n_theta0; sa.N = N; sa.h = h; sa.ld = geo.ld; sa.t0_stride = 0;
+    geo.at(l0).into_named(sa);
     HIPCHK(ibs::launch_assemble_long(sa, G, C, F, nullptr, nullptr, nullptr, ctx->stream));
-    if (int r = solve(l0 * n_theta0, (long)Lc * n_theta0, G, C, F, work, (size_t)nw * ws_per_wave, (long)nw)) return r;
-  }
-  return 0;
-}
-
-// coarse scan with the nearest eigenpair: the chunks are solved by k_solve_gcf_nearest
-static int scan_nearest_device(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const geo7[7],
-                               int64_t ld, const double* dPdrho, const double* theta0, const double* sigma, double* gam,
-                               double* lam, int32_t* idx, int32_t* info) {
-  return scan_rows_chunked(ctx, "gamma_scan_nearest", n_lines, n_theta0, N, h, geo7, ld, dPdrho, theta0, ibs::nearest_ws_doubles(N),
-                           [&](long s0, long S, double* G, double* C, double* F, double* work, size_t work_doubles, long nw) -> int {
-    ibs::NearestArgs a{};
-    a.n_sys = S; a.N = N; a.h = h; a.g = G; a.c = C; a.f = F; a.gh = nullptr; a.ld = N; a.sigma = sigma + s0;
-    a.lam = lam ? lam + s0 : nullptr; a.idx = idx ? idx + s0 : nullptr; a.gam = gam ? gam + s0 : nullptr; a.X = nullptr; a.dX = nullptr;
-    a.info = info ? info + s0 : nullptr;
-    a.work = work; a.work_doubles = work_doubles; a.n_waves = nw;
-    HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
-    return 0;
+    return solve(l0 * n_theta0, Lc * n_theta0, G, C, F, work, (size_t)nw * ws_per_wave, (long)nw);
   });
 }
 
+// coarse scan with the nearest eigenpair: the chunks of scan_rows_chunked solved by k_solve_gcf_nearest
 int ibs_gamma_scan_nearest_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
                                const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
                                const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                                const double* dPdrho, const double* theta0, const double* sigma, double* gam, double* lam,
                                int32_t* idx, int32_t* info, int32_t mem) {
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
-  if (n_lines < 0 || n_theta0 < 0 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho ||
-      !theta0 || !sigma || ld < N)
+  if (n_lines < 0 || n_theta0 < 0 || !geo.present() || !dPdrho || !theta0 || !sigma || ld < N)
     return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
   if (int r = check_grid(N, h, true)) return r;
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
-  const double *geo7[7], *dP, *t0, *sig;
+  const size_t n_sys = (size_t)n_lines * n_theta0;
+  GeoLines dgeo;
+  const double* dsig;
   double *dgam, *dlam;
   int *didx, *dinfo;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) geo7[k] = s.in(src[k], in_elems);
-    dP = s.in(dPdrho, n_lines); t0 = s.in(theta0, n_theta0); sig = s.in(sigma, n_sys);
+    dgeo = geo.declare(s, n_lines, n_theta0); dsig = s.in(sigma, n_sys);
     dgam = s.out(gam, n_sys); dlam = s.out(lam, n_sys); didx = s.out(idx, n_sys); dinfo = s.status(info, n_sys);
   };
-  return staged(ctx, mem, decl,
-                [&] { return scan_nearest_device(ctx, n_lines, n_theta0, N, h, geo7, ld, dP, t0, sig, dgam, dlam, didx, dinfo); });
+  return staged(ctx, mem, decl, [&] {
+    return scan_rows_chunked(ctx, "gamma_scan_nearest", n_lines, n_theta0, N, h, dgeo, ibs::nearest_ws_doubles(N),
+                             [&](long s0, long S, double* G, double* C, double* F, double* work, size_t work_doubles, long nw) -> int {
+      ibs::NearestArgs a{};
+      a.n_sys = S; a.N = N; a.h = h; a.g = G; a.c = C; a.f = F; a.gh = nullptr; a.ld = N; a.sigma = dsig + s0;
+      a.lam = dlam ? dlam + s0 : nullptr; a.idx = didx ? didx + s0 : nullptr; a.gam = dgam ? dgam + s0 : nullptr;
+      a.info = dinfo ? dinfo + s0 : nullptr;
+      a.work = work; a.work_doubles = work_doubles; a.n_waves = nw;
+      HIPCHK(ibs::launch_gcf_nearest(a, ctx->stream));
+      return 0;
+    });
+  });
 }
 
 // the n_modes largest eigenvalues and growth rates of every (line, theta0): the chunks of scan_rows_chunked solved by k_solve_gcf_modes
@@ -1227,27 +1238,25 @@ int ibs_gamma_scan_modes_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, in
                              const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                              const double* dPdrho, const double* theta0, int32_t n_modes, double* gam, double* lam,
                              int32_t* info, int32_t mem) {
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
-  if (n_lines < 0 || n_theta0 < 0 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho ||
-      !theta0 || ld < N)
+  if (n_lines < 0 || n_theta0 < 0 || !geo.present() || !dPdrho || !theta0 || ld < N)
     return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
   if (int r = check_n_modes(n_modes)) return r;
   if (!gam && !lam && !info) return fail(IBS_ERR_ARG, "no output requested (gam, lam and info are all null)");
   if (int r = check_grid(N, h, true)) return r;
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  const size_t n_out = (size_t)n_lines * n_theta0 * n_modes, in_elems = (size_t)n_lines * ld;
-  const double *geo7[7], *dP, *t0;
+  const size_t n_out = (size_t)n_lines * n_theta0 * n_modes;
+  GeoLines dgeo;
   double *dgam, *dlam;
   int* dinfo;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) geo7[k] = s.in(src[k], in_elems);
-    dP = s.in(dPdrho, n_lines); t0 = s.in(theta0, n_theta0);
+    dgeo = geo.declare(s, n_lines, n_theta0);
     dgam = s.out(gam, n_out); dlam = s.out(lam, n_out); dinfo = s.status(info, n_out);
   };
   return staged(ctx, mem, decl, [&] {
-    return scan_rows_chunked(ctx, "gamma_scan_modes", n_lines, n_theta0, N, h, geo7, ld, dP, t0, ibs::modes_ws_doubles(N),
+    return scan_rows_chunked(ctx, "gamma_scan_modes", n_lines, n_theta0, N, h, dgeo, ibs::modes_ws_doubles(N),
                              [&](long s0, long S, double* G, double* C, double* F, double* work, size_t work_doubles, long nw) -> int {
       const long o = s0 * n_modes;
       ibs::ModesArgs a{};
@@ -1261,7 +1270,7 @@ int ibs_gamma_scan_modes_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, in
 }
 
 // ---- vector-Jacobian product of a whole (line, theta0) table of growth rates (ibs_scan_vjp.hip; nothing upstream corresponds): whole
-// lines chunk after chunk under the budget of scan_rows_chunked (kNearestScanBytes, or option "nearest_chunk_systems"); a chunk's
+// lines chunk after chunk (for_line_chunks); a chunk's
 // workspace in ctx->long_ws = the persistent grid's per-wave workspace (ibs::exact_points_ws), three cotangent rows and a verdict per system
 int ibs_gamma_scan_vjp_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
                            const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
@@ -1269,8 +1278,9 @@ int ibs_gamma_scan_vjp_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
                            const double* dPdrho, const double* theta0, const double* sigma, const double* gam_bar,
                            double* geo_bar, double* dPdrho_bar, double* theta0_bar, double* gam, double* lam, int32_t* info,
                            int32_t mem) {
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
-  if (!bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho || !theta0 || !gam_bar)
+  if (!geo.present() || !dPdrho || !theta0 || !gam_bar)
     return fail(IBS_ERR_ARG, "null argument (the geometry arrays, dPdrho, theta0 and gam_bar are required)");
   if (!geo_bar && !dPdrho_bar && !theta0_bar) return fail(IBS_ERR_ARG, "geo_bar, dPdrho_bar and theta0_bar are all null");
   if (n_lines < 0 || n_theta0 < 0 || ld < N)
@@ -1278,15 +1288,14 @@ int ibs_gamma_scan_vjp_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
   if (int r = check_grid(N, h, true)) return r;
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
   const size_t n_sys = (size_t)n_lines * n_theta0, plane = (size_t)n_lines * ld;
   const bool need_rows = geo_bar || dPdrho_bar;
   ibs::ScanVjpArgs a{};                                    // the whole call; each chunk launches a copy with its lines
   a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld; a.ld_bar = (long)ld;
+  GeoLines dgeo;
   double* d_geo_bar = nullptr;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], plane);
-    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_theta0); a.sigma = s.in(sigma, n_sys); a.gam_bar = s.in(gam_bar, n_sys);
+    dgeo = geo.declare(s, n_lines, n_theta0); a.sigma = s.in(sigma, n_sys); a.gam_bar = s.in(gam_bar, n_sys);
     d_geo_bar = s.out(geo_bar, 7 * plane); a.dPdrho_bar = s.out(dPdrho_bar, n_lines); a.theta0_bar = s.out(theta0_bar, n_sys);
     a.gam = s.out(gam, n_sys); a.lam = s.out(lam, n_sys);
     a.info = s.status(info, n_sys);
@@ -1305,37 +1314,21 @@ int ibs_gamma_scan_vjp_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
       rows = need_rows ? cv.take<double>((size_t)S * 3 * N) : nullptr;
       flag = cv.take<int>((size_t)S);
     };
-    auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
-    long L = n_lines;
-    if (ctx->opt.nearest_chunk_systems > 0) L = ctx->opt.nearest_chunk_systems / n_theta0;
-    else while (L > 1 && bytes_of(L) > kNearestScanBytes) L = (L + 1) / 2;
-    if (L < 1) L = 1;
-    if (L > n_lines) L = n_lines;
-    const size_t bytes = bytes_of(L);
-    if (ensure_long_ws(ctx, bytes) != 0) {
-      (void)hipGetLastError();
-      return fail(IBS_ERR_HIP, "gamma_scan_vjp: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
-                  "which could not be allocated", L, n_theta0, N, bytes);
-    }
-    Carve cv{static_cast<char*>(ctx->long_ws)};
-    carve(cv, L);
-    for (long l0 = 0; l0 < n_lines; l0 += L) {
+    return for_line_chunks(ctx, "gamma_scan_vjp", n_lines, n_theta0, N, carve, [&](long l0, long Lc) -> int {
       const long s0 = l0 * n_theta0;
       ibs::ScanVjpArgs c = a;
-      c.n_lines = (int)(n_lines - l0 < L ? n_lines - l0 : L);
-      for (int k = 0; k < 7; ++k) {
-        c.geo7[k] = a.geo7[k] + l0 * ld;
-        c.geo_bar[k] = d_geo_bar ? d_geo_bar + k * plane + l0 * ld : nullptr;
-      }
-      c.dPdrho = a.dPdrho + l0; c.gam_bar = a.gam_bar + s0;
+      c.n_lines = (int)Lc;
+      dgeo.at(l0).into(c);
+      for (int k = 0; k < 7; ++k) c.geo_bar[k] = d_geo_bar ? d_geo_bar + k * plane + l0 * ld : nullptr;
+      c.gam_bar = a.gam_bar + s0;
       c.sigma = a.sigma ? a.sigma + s0 : nullptr;
       c.dPdrho_bar = a.dPdrho_bar ? a.dPdrho_bar + l0 : nullptr; c.theta0_bar = a.theta0_bar ? a.theta0_bar + s0 : nullptr;
       c.gam = a.gam ? a.gam + s0 : nullptr; c.lam = a.lam ? a.lam + s0 : nullptr; c.info = a.info ? a.info + s0 : nullptr;
       c.rows = rows; c.flag = flag;
       c.work = work; c.work_doubles = (size_t)nw * per_wave; c.n_waves = nw;
       HIPCHK(ibs::launch_scan_vjp(c, ctx->stream));
-    }
-    return 0;
+      return 0;
+    });
   });
 }
 
@@ -1369,20 +1362,18 @@ int ibs_gamma_points_nearest_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double 
                                  const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
                                  const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, const double* sigma,
                                  double* gam, double* lam, int32_t* idx, double* X, double* dX, int32_t* info, int32_t mem) {
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0, true};
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
-  if (n_pts < 0 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho || !theta0 || !sigma ||
-      !gam || ld < N)
+  if (n_pts < 0 || !geo.present() || !dPdrho || !theta0 || !sigma || !gam || ld < N)
     return fail(IBS_ERR_ARG, "bad arguments (n_pts=%d ld=%lld N=%d)", n_pts, (long long)ld, N);
   if (int r = check_grid(N, h, true)) return r;
   if (n_pts == 0) return 0;
   ON_DEVICE(ctx);
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  const size_t n = (size_t)n_pts, in_elems = n * (size_t)ld, out_elems = n * (size_t)N;
+  const size_t n = (size_t)n_pts, out_elems = n * (size_t)N;
   ibs::NearestPointsArgs a{};
   a.n_pts = n_pts; a.N = N; a.h = h; a.ld = (long)ld;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
-    a.dPdrho = s.in(dPdrho, n); a.theta0 = s.in(theta0, n); a.sigma = s.in(sigma, n);
+    geo.declare(s, n, 1).into(a); a.sigma = s.in(sigma, n);
     a.gam = s.out(gam, n); a.lam = s.out(lam, n); a.idx = s.out(idx, n); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
     a.info = s.status(info, n);
   };
@@ -1507,19 +1498,17 @@ static int trial_table_for(ibs_ctx* ctx, int N, int M, const double** out) {
   return 0;
 }
 
-static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
-                           const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
-                           const double* gds2, const double* gds21, const double* gds22, int64_t ld,
-                           const double* dPdrho, const double* theta0, double* gam, double* lam, double* X,
-                           double* dX, double* dth0, int32_t* info, int32_t mem, const double* lam_guess,
-                           double guess_width, int32_t n_surf = 0, double* pack = nullptr, bool t0_per_line = false) {
-  // t0_per_line: n_theta0 = 1 and theta0[n_lines] holds one value per line (ibs_gamma_points_f64); one wave per system
+static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const GeoLines& geo, double* gam,
+                           double* lam, double* X, double* dX, double* dth0, int32_t* info, int32_t mem, const double* lam_guess,
+                           double guess_width, int32_t n_surf = 0, double* pack = nullptr) {
+  // geo.per_line: n_theta0 = 1 and theta0[n_lines] holds one value per line (ibs_gamma_points_f64); one wave per system
+  const bool t0_per_line = geo.per_line;
+  const int64_t ld = geo.ld;
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
   if (lam_guess && !(guess_width > 0)) return fail(IBS_ERR_ARG, "guess_width must be > 0");
   if (pack && (mem != IBS_MEM_DEVICE || n_surf <= 0 || n_lines % n_surf != 0 || !gam))
     return fail(IBS_ERR_ARG, "fused argmax: device pointers, gam output and n_lines %% n_surf == 0 required (n_lines=%d n_surf=%d)", n_lines, n_surf);
-  if (n_lines < 0 || n_theta0 < 0 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 ||
-      !dPdrho || !theta0 || ld < N)
+  if (n_lines < 0 || n_theta0 < 0 || !geo.present() || !geo.dPdrho || !geo.theta0 || ld < N)
     return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
   if (int r = check_grid(N, h, true)) return r;
   if (n_lines == 0 || n_theta0 == 0) return 0;
@@ -1545,14 +1534,11 @@ static int gamma_scan_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
   if (plan.chain) { a.chain_w1 = ctx->opt.chain_w1; a.chain_w2 = ctx->opt.chain_w2; }
   // (the divisions of the kernel's set-up and growth-rate stage, done once here: correctly rounded on both sides)
   a.ih2 = 1.0 / (h * h); a.ih = 1.0 / h;
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
-  const size_t n_t0_vals = t0_per_line ? (size_t)n_lines : (size_t)n_theta0;
+  const size_t n_sys = (size_t)n_lines * n_theta0, out_elems = n_sys * N;
   a.guess_width = guess_width;
   // (host pointers: gam, lam and info are always carved)
   auto decl = [&](Stage& s) {
-    a.bmag = s.in(bmag, in_elems); a.gradpar = s.in(gradpar, in_elems); a.cvdrift = s.in(cvdrift, in_elems);
-    a.cvdrift0 = s.in(cvdrift0, in_elems); a.gds2 = s.in(gds2, in_elems); a.gds21 = s.in(gds21, in_elems); a.gds22 = s.in(gds22, in_elems);
-    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_t0_vals); a.lam_guess = s.in(lam_guess, n_sys);
+    geo.declare(s, n_lines, n_theta0).into_named(a); a.lam_guess = s.in(lam_guess, n_sys);
     a.gam = s.out(gam, n_sys, true); a.lam = s.out(lam, n_sys, true); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
     a.dth0 = s.out(dth0, n_sys); a.info = s.status(info, n_sys);
   };
@@ -1594,8 +1580,8 @@ int ibs_gamma_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t 
                        const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                        const double* dPdrho, const double* theta0, double* gam, double* lam, double* X,
                        double* dX, double* dth0, int32_t* info, int32_t mem) {
-  return gamma_scan_impl(ctx, n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho,
-                         theta0, gam, lam, X, dX, dth0, info, mem, nullptr, 0.0);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  return gamma_scan_impl(ctx, n_lines, n_theta0, N, h, geo, gam, lam, X, dX, dth0, info, mem, nullptr, 0.0);
 }
 
 int ibs_gamma_scan_warm_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
@@ -1604,8 +1590,8 @@ int ibs_gamma_scan_warm_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int
                             const double* dPdrho, const double* theta0, const double* lam_guess, double guess_width,
                             double* gam, double* lam, double* X, double* dX, double* dth0, int32_t* info, int32_t mem) {
   if (!lam_guess) return fail(IBS_ERR_ARG, "lam_guess is null");
-  return gamma_scan_impl(ctx, n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho,
-                         theta0, gam, lam, X, dX, dth0, info, mem, lam_guess, guess_width);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  return gamma_scan_impl(ctx, n_lines, n_theta0, N, h, geo, gam, lam, X, dX, dth0, info, mem, lam_guess, guess_width);
 }
 
 int ibs_gamma_scan_argmax_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h,
@@ -1614,16 +1600,16 @@ int ibs_gamma_scan_argmax_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, i
                               const double* dPdrho, const double* theta0, int32_t n_surf, double* gam, double* lam,
                               double* pack, int32_t* info) {
   if (!pack) return fail(IBS_ERR_ARG, "pack is null");
-  return gamma_scan_impl(ctx, n_lines, n_theta0, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho,
-                         theta0, gam, lam, nullptr, nullptr, nullptr, info, IBS_MEM_DEVICE, nullptr, 0.0, n_surf, pack);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  return gamma_scan_impl(ctx, n_lines, n_theta0, N, h, geo, gam, lam, nullptr, nullptr, nullptr, info, IBS_MEM_DEVICE, nullptr, 0.0, n_surf, pack);
 }
 
 int ibs_gamma_points_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
                          const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
                          const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, double* gam,
                          double* lam, double* X, double* dX, double* dgam_dtheta0, int32_t* info, int32_t mem) {
-  return gamma_scan_impl(ctx, n_pts, 1, N, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, ld, dPdrho, theta0, gam,
-                         lam, X, dX, dgam_dtheta0, info, mem, nullptr, 0.0, 0, nullptr, true);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0, true};
+  return gamma_scan_impl(ctx, n_pts, 1, N, h, geo, gam, lam, X, dX, dgam_dtheta0, info, mem, nullptr, 0.0);
 }
 
 // ---- lines on a non-uniform theta grid (ibs_regrid.hip; utils.py:1565-1576): regrid onto the uniform grid of the window, then the raw
@@ -1667,12 +1653,10 @@ int ibs_regrid_rows_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, const double* th
 
 // the arguments the three geometry-fed theta entry points share, checked before the context is touched
 static int check_theta_geo(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld, double lo,
-                           double hi, const double* const src[7], int64_t ld, const double* dPdrho, const double* theta0, double* h) {
+                           double hi, const GeoLines& geo, double* h) {
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
-  bool geo_ok = true;
-  for (int k = 0; k < 7; ++k) geo_ok = geo_ok && src[k];
-  if (n_lines < 0 || n_theta0 < 0 || !geo_ok || !dPdrho || !theta0 || ld < N)
-    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  if (n_lines < 0 || n_theta0 < 0 || !geo.present() || !geo.dPdrho || !geo.theta0 || geo.ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)geo.ld, N);
   return check_theta_args(N, theta, theta_ld, lo, hi, h);
 }
 
@@ -1681,9 +1665,9 @@ int ibs_assemble_gcf_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
                                const double* cvdrift0, const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                                const double* dPdrho, const double* theta0, int32_t theta0_per_line, double* g_u, double* gh,
                                double* c_u, double* f_u, double* h_out, int32_t* info, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0, theta0_per_line != 0};
   double h = 0.0;
-  if (int r = check_theta_geo(ctx, n_lines, n_theta0, N, theta, theta_ld, theta_lo, theta_hi, src, ld, dPdrho, theta0, &h)) return r;
+  if (int r = check_theta_geo(ctx, n_lines, n_theta0, N, theta, theta_ld, theta_lo, theta_hi, geo, &h)) return r;
   if (!g_u || !gh || !c_u || !f_u) return fail(IBS_ERR_ARG, "g_u, gh, c_u and f_u are required");
   if (theta0_per_line && n_theta0 != 1) return fail(IBS_ERR_ARG, "theta0_per_line needs n_theta0 = 1 (one theta0 per line), not %d", n_theta0);
   if (h_out) *h_out = h;
@@ -1692,11 +1676,10 @@ int ibs_assemble_gcf_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
   ibs::RegridArgs a{};
   a.n_lines = n_lines; a.per_line = n_theta0; a.N = N; a.theta_ld = theta_ld; a.lo = theta_lo; a.hi = theta_hi; a.ld = ld;
   a.t0_per_line = theta0_per_line ? 1 : 0; a.ld_out = N; a.n_cu = ctx->chip.n_cu;
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
+  const size_t n_sys = (size_t)n_lines * n_theta0, out_elems = n_sys * N;
   auto decl = [&](Stage& s) {
     a.theta = s.in(theta, theta_ld ? (size_t)n_lines * theta_ld : (size_t)N);
-    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
-    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, theta0_per_line ? (size_t)n_lines : (size_t)n_theta0);
+    geo.declare(s, n_lines, n_theta0).into(a);
     a.g_u = s.out(g_u, out_elems); a.gh = s.out(gh, out_elems); a.c_u = s.out(c_u, out_elems); a.f_u = s.out(f_u, out_elems);
     a.info = s.status(info, n_sys);
   };
@@ -1704,29 +1687,27 @@ int ibs_assemble_gcf_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
 }
 
 // Geometry-fed scan on a non-uniform grid, on the pattern of scan_rows_chunked / launch_scan_long: the four regridded rows of a chunk of
-// whole lines are written to ctx->long_ws by k_assemble_regrid (the same budget kNearestScanBytes, the same option
-// "nearest_chunk_systems") and solved by the raw solver WITH gh, in the form plan_gcf picks for a caller-supplied half grid -- the
-// long-grid kernel beyond 2050 points, its workspace carved out of the same allocation.  A line that is not a grid reaches the solver
+// whole lines (for_line_chunks) are written to ctx->long_ws by k_assemble_regrid and solved by the raw solver WITH gh, in the form
+// plan_gcf picks for a caller-supplied half grid -- the long-grid kernel beyond 2050 points, its workspace carved out of the same allocation.  A line that is not a grid reaches the solver
 // as NaN rows and comes back with status bit 1; k_regrid_poison then makes its floating-point outputs NaN.  Every system is a function of its own line: chunking changes no bit.
 static int scan_theta_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, const double* theta, int64_t theta_ld, double lo,
-                           double hi, const double* const src[7], int64_t ld, const double* dPdrho, const double* theta0,
-                           bool t0_per_line, double* gam, double* lam, double* X, double* dX, int32_t* info, int32_t mem) {
+                           double hi, const GeoLines& geo, double* gam, double* lam, double* X, double* dX, int32_t* info, int32_t mem) {
   double h = 0.0;
-  if (int r = check_theta_geo(ctx, n_lines, n_theta0, N, theta, theta_ld, lo, hi, src, ld, dPdrho, theta0, &h)) return r;
+  if (int r = check_theta_geo(ctx, n_lines, n_theta0, N, theta, theta_ld, lo, hi, geo, &h)) return r;
   if (n_lines == 0 || n_theta0 == 0) return 0;
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * N;
+  const size_t n_sys = (size_t)n_lines * n_theta0, out_elems = n_sys * N;
   const ibs::GcfPlan plan = ibs::plan_gcf(ctx->chip, ctx->opt, ctx->built, 8, (long)n_sys, N, true, mem == IBS_MEM_HOST || gam, X || dX);
   if (plan.err == ibs::PlanError::NotBuilt) return fail(IBS_ERR_UNSUPPORTED, "no kernel built for rows-per-lane M=%d (N=%d)", plan.M, N);
   ON_DEVICE(ctx);
   if (plan.err == ibs::PlanError::NoLds) return fail(IBS_ERR_UNSUPPORTED, "N=%d needs %zu B of LDS per wave", N, plan.per_wave);
   const bool lng = plan.form == ibs::GcfForm::Long;
-  const double *dth, *geo7[7], *dP, *t0;
+  const double* dth;
+  GeoLines dgeo;
   double *dgam, *dlam, *dXo, *ddX;
   int* dinfo;
   auto decl = [&](Stage& s) {
     dth = s.in(theta, theta_ld ? (size_t)n_lines * theta_ld : (size_t)N);
-    for (int k = 0; k < 7; ++k) geo7[k] = s.in(src[k], in_elems);
-    dP = s.in(dPdrho, n_lines); t0 = s.in(theta0, t0_per_line ? (size_t)n_lines : (size_t)n_theta0);
+    dgeo = geo.declare(s, n_lines, n_theta0);
     dgam = s.out(gam, n_sys, true); dlam = s.out(lam, n_sys, true); dXo = s.out(X, out_elems); ddX = s.out(dX, out_elems);
     dinfo = s.status(info, n_sys);
   };
@@ -1739,27 +1720,13 @@ static int scan_theta_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
       G = cv.take<double>(S * N); GH = cv.take<double>(S * N); C = cv.take<double>(S * N); F = cv.take<double>(S * N);
       flag = cv.take<int>(S);
     };
-    auto bytes_of = [&](long L) { Carve sz{nullptr}; carve(sz, L); return sz.off; };
-    long L = n_lines;
-    if (ctx->opt.nearest_chunk_systems > 0) L = ctx->opt.nearest_chunk_systems / n_theta0;
-    else while (L > 1 && bytes_of(L) > kNearestScanBytes) L = (L + 1) / 2;
-    if (L < 1) L = 1;
-    if (L > n_lines) L = n_lines;
-    const size_t bytes = bytes_of(L);
-    if (ensure_long_ws(ctx, bytes) != 0) {
-      (void)hipGetLastError();
-      return fail(IBS_ERR_HIP, "%s: a chunk of %ld line(s) x %d theta0 at N=%d needs %zu bytes of device workspace, "
-                  "which could not be allocated", t0_per_line ? "gamma_points_theta" : "gamma_scan_theta", L, n_theta0, N, bytes);
-    }
-    Carve cv{static_cast<char*>(ctx->long_ws)};
-    carve(cv, L);
-    for (long l0 = 0; l0 < n_lines; l0 += L) {
-      const long Lc = n_lines - l0 < L ? n_lines - l0 : L, s0 = l0 * n_theta0, S = Lc * n_theta0;
+    const int rc = for_line_chunks(ctx, geo.per_line ? "gamma_points_theta" : "gamma_scan_theta", n_lines, n_theta0, N, carve,
+                                   [&](long l0, long Lc) -> int {
+      const long s0 = l0 * n_theta0, S = Lc * n_theta0;
       ibs::RegridArgs ra{};
       ra.n_lines = Lc; ra.per_line = n_theta0; ra.N = N; ra.theta = dth + (theta_ld ? l0 * theta_ld : 0); ra.theta_ld = theta_ld;
-      ra.lo = lo; ra.hi = hi; ra.ld = ld; ra.t0_per_line = t0_per_line ? 1 : 0; ra.n_cu = ctx->chip.n_cu;
-      for (int k = 0; k < 7; ++k) ra.geo7[k] = geo7[k] + l0 * ld;
-      ra.dPdrho = dP + l0; ra.theta0 = t0 + (t0_per_line ? l0 : 0);
+      ra.lo = lo; ra.hi = hi; ra.ld = geo.ld; ra.t0_per_line = geo.per_line ? 1 : 0; ra.n_cu = ctx->chip.n_cu;
+      dgeo.at(l0).into(ra);
       ra.g_u = G; ra.gh = GH; ra.c_u = C; ra.f_u = F; ra.ld_out = N; ra.info = flag;
       HIPCHK(ibs::launch_assemble_regrid(ra, ctx->stream));
       ibs::GcfArgs<double> ga{};
@@ -1769,7 +1736,9 @@ static int scan_theta_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int3
       ga.X = dXo ? dXo + (size_t)s0 * N : nullptr; ga.dX = ddX ? ddX + (size_t)s0 * N : nullptr;
       if (int r = launch_planned_gcf<double>(ctx, plan, ga, work)) return r;
       HIPCHK(ibs::launch_regrid_poison(S, N, flag, ga.lam, ga.gam, ga.X, ga.dX, ctx->stream));
-    }
+      return 0;
+    });
+    if (rc) return rc;
     flag_sigma<double>(ctx, (long)n_sys, dlam, dinfo);
     return 0;
   });
@@ -1780,17 +1749,16 @@ int ibs_gamma_scan_theta_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, in
                              const double* cvdrift0, const double* gds2, const double* gds21, const double* gds22, int64_t ld,
                              const double* dPdrho, const double* theta0, double* gam, double* lam, double* X, double* dX,
                              int32_t* info, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  return scan_theta_impl(ctx, n_lines, n_theta0, N, theta, theta_ld, theta_lo, theta_hi, src, ld, dPdrho, theta0, false, gam, lam, X, dX,
-                         info, mem);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  return scan_theta_impl(ctx, n_lines, n_theta0, N, theta, theta_ld, theta_lo, theta_hi, geo, gam, lam, X, dX, info, mem);
 }
 
 int ibs_gamma_points_theta_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, const double* theta, int64_t theta_ld, double theta_lo,
                                double theta_hi, const double* bmag, const double* gradpar, const double* cvdrift, const double* cvdrift0,
                                const double* gds2, const double* gds21, const double* gds22, int64_t ld, const double* dPdrho,
                                const double* theta0, double* gam, double* lam, double* X, double* dX, int32_t* info, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  return scan_theta_impl(ctx, n_pts, 1, N, theta, theta_ld, theta_lo, theta_hi, src, ld, dPdrho, theta0, true, gam, lam, X, dX, info, mem);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0, true};
+  return scan_theta_impl(ctx, n_pts, 1, N, theta, theta_ld, theta_lo, theta_hi, geo, gam, lam, X, dX, info, mem);
 }
 
 int ibs_scan_starts_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_alpha, int32_t n_theta0, const double* alpha,
@@ -2145,13 +2113,12 @@ int ibs_sturm_count_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const 
 
 // ---- geometry-fed Sturm count and the count-pair certificate of geometry-fed growth rates (ibs_certify.hip).  The argument checks
 // come before any device use.
-static int geo_cert_check(const ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, int64_t ld, const double* const src[7],
-                          const double* dPdrho, const double* theta0, bool even_ok) {
+static int geo_cert_check(const ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const GeoLines& geo, bool even_ok) {
   if (!ctx) return fail(IBS_ERR_ARG, "null context");
-  for (int k = 0; k < 7; ++k) if (!src[k]) return fail(IBS_ERR_ARG, "null argument (the seven geometry arrays are required)");
-  if (!dPdrho || !theta0) return fail(IBS_ERR_ARG, "null argument (dPdrho and theta0 are required)");
-  if (n_lines < 0 || n_theta0 < 0 || ld < N)
-    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)ld, N);
+  if (!geo.present()) return fail(IBS_ERR_ARG, "null argument (the seven geometry arrays are required)");
+  if (!geo.dPdrho || !geo.theta0) return fail(IBS_ERR_ARG, "null argument (dPdrho and theta0 are required)");
+  if (n_lines < 0 || n_theta0 < 0 || geo.ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d)", n_lines, n_theta0, (long long)geo.ld, N);
   if ((int64_t)n_lines * n_theta0 > (int64_t)std::numeric_limits<int32_t>::max())
     return fail(IBS_ERR_ARG, "n_lines * n_theta0 = %lld exceeds 2^31 - 1", (long long)((int64_t)n_lines * n_theta0));
   if (!even_ok) return check_grid(N, h, true);
@@ -2164,17 +2131,16 @@ int ibs_geo_sturm_count_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int
                             const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
                             const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
                             const double* shift, int32_t* count, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, ld, src, dPdrho, theta0, true)) return r;   // (no Simpson stage: even N is fine)
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, geo, true)) return r;   // (no Simpson stage: even N is fine)
   if (!shift || !count) return fail(IBS_ERR_ARG, "null argument (shift and count are required)");
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
+  const size_t n_sys = (size_t)n_lines * n_theta0;
   ibs::CertifyArgs a{};
   a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
-    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, n_theta0); a.shift = s.in(shift, n_sys);
+    geo.declare(s, n_lines, n_theta0).into(a); a.shift = s.in(shift, n_sys);
     a.count = s.out(count, n_sys);
   };
   return staged(ctx, mem, decl, [&]() -> int {
@@ -2183,21 +2149,19 @@ int ibs_geo_sturm_count_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int
   });
 }
 
-// per_line: n_theta0 = 1 and theta0[n_lines] holds one value per line (the points form)
-static int geo_certify_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const src[7], int64_t ld,
-                            const double* dPdrho, const double* theta0, const double* lam, double tol_factor, int32_t* cert,
-                            int32_t mem, bool per_line) {
-  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, ld, src, dPdrho, theta0, false)) return r;
+// geo.per_line: n_theta0 = 1 and theta0[n_lines] holds one value per line (the points form)
+static int geo_certify_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const GeoLines& geo, const double* lam,
+                            double tol_factor, int32_t* cert, int32_t mem) {
+  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, geo, false)) return r;
   if (!lam || !cert) return fail(IBS_ERR_ARG, "null argument (lam and cert are required)");
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld;
+  const size_t n_sys = (size_t)n_lines * n_theta0;
   ibs::CertifyArgs a{};
-  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld; a.t0_stride = per_line ? 1 : 0;
+  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)geo.ld; a.t0_stride = geo.per_line ? 1 : 0;
   a.tol_factor = tol_factor > 0 ? tol_factor : 4.0;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) a.geo7[k] = s.in(src[k], in_elems);
-    a.dPdrho = s.in(dPdrho, n_lines); a.theta0 = s.in(theta0, per_line ? (size_t)n_lines : (size_t)n_theta0); a.lam = s.in(lam, n_sys);
+    geo.declare(s, n_lines, n_theta0).into(a); a.lam = s.in(lam, n_sys);
     a.cert = s.out(cert, n_sys);
   };
   const int rc = staged(ctx, mem, decl, [&]() -> int {
@@ -2214,37 +2178,35 @@ int ibs_gamma_scan_certify_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
                                const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
                                const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
                                const double* lam, double tol_factor, int32_t* cert, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  return geo_certify_impl(ctx, n_lines, n_theta0, N, h, src, ld, dPdrho, theta0, lam, tol_factor, cert, mem, false);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  return geo_certify_impl(ctx, n_lines, n_theta0, N, h, geo, lam, tol_factor, cert, mem);
 }
 
 int ibs_gamma_points_certify_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
                                  const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
                                  const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, const double* lam,
                                  double tol_factor, int32_t* cert, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  return geo_certify_impl(ctx, n_pts, 1, N, h, src, ld, dPdrho, theta0, lam, tol_factor, cert, mem, true);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0, true};
+  return geo_certify_impl(ctx, n_pts, 1, N, h, geo, lam, tol_factor, cert, mem);
 }
 
 // Device pointers: list, solve and second certificate are queued back to back; nothing is read back in between (the list and its
 // counter stay on the device: ibs_certify.hip).  Host pointers: the in-out arrays go up with the inputs and come back as outputs.
-static int geo_reclose_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* const src[7], int64_t ld,
-                            const double* dPdrho, const double* theta0, double tol_factor, int32_t* cert, double* lam, double* gam,
-                            double* X, double* dX, int32_t mem, bool per_line) {
-  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, ld, src, dPdrho, theta0, false)) return r;
+static int geo_reclose_impl(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const GeoLines& geo, double tol_factor,
+                            int32_t* cert, double* lam, double* gam, double* X, double* dX, int32_t mem) {
+  if (int r = geo_cert_check(ctx, n_lines, n_theta0, N, h, geo, false)) return r;
   if (!cert || !lam || !gam) return fail(IBS_ERR_ARG, "null argument (cert, lam and gam are required)");
   if (n_lines == 0 || n_theta0 == 0) return 0;
   ON_DEVICE(ctx);
-  const size_t n_sys = (size_t)n_lines * n_theta0, in_elems = (size_t)n_lines * ld, out_elems = n_sys * (size_t)N;
+  const size_t n_sys = (size_t)n_lines * n_theta0, out_elems = n_sys * (size_t)N;
   ibs::RecloseArgs a{};
   ibs::CertifyArgs& c = a.c;
-  c.n_lines = n_lines; c.n_theta0 = n_theta0; c.N = N; c.h = h; c.ld = (long)ld; c.t0_stride = per_line ? 1 : 0;
+  c.n_lines = n_lines; c.n_theta0 = n_theta0; c.N = N; c.h = h; c.ld = (long)geo.ld; c.t0_stride = geo.per_line ? 1 : 0;
   c.tol_factor = tol_factor > 0 ? tol_factor : 4.0;
   const int *cert_up = nullptr;
   const double *lam_up = nullptr, *gam_up = nullptr, *X_up = nullptr, *dX_up = nullptr;
   auto decl = [&](Stage& s) {
-    for (int k = 0; k < 7; ++k) c.geo7[k] = s.in(src[k], in_elems);
-    c.dPdrho = s.in(dPdrho, n_lines); c.theta0 = s.in(theta0, per_line ? (size_t)n_lines : (size_t)n_theta0);
+    geo.declare(s, n_lines, n_theta0).into(c);
     if (s.host) {
       cert_up = s.in((const int*)cert, n_sys); lam_up = s.in((const double*)lam, n_sys); gam_up = s.in((const double*)gam, n_sys);
       X_up = s.in((const double*)X, out_elems); dX_up = s.in((const double*)dX, out_elems);
@@ -2283,16 +2245,16 @@ int ibs_gamma_scan_reclose_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, 
                                const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
                                const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
                                double tol_factor, int32_t* cert, double* lam, double* gam, double* X, double* dX, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  return geo_reclose_impl(ctx, n_lines, n_theta0, N, h, src, ld, dPdrho, theta0, tol_factor, cert, lam, gam, X, dX, mem, false);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  return geo_reclose_impl(ctx, n_lines, n_theta0, N, h, geo, tol_factor, cert, lam, gam, X, dX, mem);
 }
 
 int ibs_gamma_points_reclose_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* bmag, const double* gradpar,
                                  const double* cvdrift, const double* cvdrift0, const double* gds2, const double* gds21,
                                  const double* gds22, int64_t ld, const double* dPdrho, const double* theta0, double tol_factor,
                                  int32_t* cert, double* lam, double* gam, double* X, double* dX, int32_t mem) {
-  const double* src[7] = {bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22};
-  return geo_reclose_impl(ctx, n_pts, 1, N, h, src, ld, dPdrho, theta0, tol_factor, cert, lam, gam, X, dX, mem, true);
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0, true};
+  return geo_reclose_impl(ctx, n_pts, 1, N, h, geo, tol_factor, cert, lam, gam, X, dX, mem);
 }
 
 int ibs_surface_argmax_f64(ibs_ctx* ctx, int32_t n_surf, int32_t n_per, const double* gam, int32_t* idx,
@@ -2358,12 +2320,12 @@ int ibs_theta0_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
                           const double* gam, const double* lam, const int32_t* node_in, int32_t n_starts, double xtol,
                           int32_t max_eval, double* theta0_star, double* gam_star, double* lam_star, int32_t* node,
                           int32_t* n_eval, int32_t* info, int32_t* n_found, int32_t mem) {
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
   if (n_starts < 1 || n_starts > ibs::t0p::kMaxSlots || !(xtol > 0) || !std::isfinite(xtol) || max_eval < 1 ||
       max_eval > ibs::t0p::kMaxEval)
     return fail(IBS_ERR_ARG, "n_starts in [1, %d], xtol > 0 and finite, max_eval in [1, %d] required (n_starts=%d xtol=%g max_eval=%d)",
                 ibs::t0p::kMaxSlots, ibs::t0p::kMaxEval, n_starts, xtol, max_eval);
-  if (n_lines < 0 || n_theta0 < 1 || N < 1 || !bmag || !gradpar || !cvdrift || !cvdrift0 || !gds2 || !gds21 || !gds22 || !dPdrho ||
-      !theta0 || !gam || !theta0_star || !gam_star || ld < N)
+  if (n_lines < 0 || n_theta0 < 1 || N < 1 || !geo.present() || !dPdrho || !theta0 || !gam || !theta0_star || !gam_star || ld < N)
     return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d; the arrays, theta0, gam, theta0_star and gam_star are required)",
                 n_lines, n_theta0, (long long)ld, N);
   if (int r = check_grid(N, h)) return r;
@@ -2379,11 +2341,9 @@ int ibs_theta0_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
   ibs::Theta0PolishArgs<double> a{};
   a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = ld;
   a.n_starts = n_starts; a.xtol = xtol; a.max_eval = max_eval; a.w1 = ctx->opt.chain_w1; a.w2 = ctx->opt.chain_w2;
-  const size_t in_elems = (size_t)n_lines * ld, n_sys = (size_t)n_lines * n_theta0, n_slots = (size_t)n_lines * n_starts;
+  const size_t n_sys = (size_t)n_lines * n_theta0, n_slots = (size_t)n_lines * n_starts;
   auto decl = [&](Stage& s) {
-    a.bmag = s.in(bmag, in_elems); a.gradpar = s.in(gradpar, in_elems); a.cvdrift = s.in(cvdrift, in_elems);
-    a.cvdrift0 = s.in(cvdrift0, in_elems); a.gds2 = s.in(gds2, in_elems); a.gds21 = s.in(gds21, in_elems); a.gds22 = s.in(gds22, in_elems);
-    a.dPdrho = s.in(dPdrho, (size_t)n_lines); a.theta0 = s.in(theta0, (size_t)n_theta0); a.gam = s.in(gam, n_sys); a.lam = s.in(lam, n_sys);
+    geo.declare(s, n_lines, n_theta0).into_named(a); a.gam = s.in(gam, n_sys); a.lam = s.in(lam, n_sys);
     a.node_in = s.in(node_in, n_slots);
     a.theta0_star = s.out(theta0_star, n_slots); a.gam_star = s.out(gam_star, n_slots); a.lam_star = s.out(lam_star, n_slots);
     a.node = s.out(node, n_slots); a.n_eval = s.out(n_eval, n_slots); a.n_found = s.out(n_found, (size_t)n_lines);

@@ -380,4 +380,36 @@ inline int plan_grad_wpb(const Chip& chip, int n_pts, int N) {
   return spread_wpb((long)((size_t)chip.lds_per_block / per_wave), kGcfMaxWaves, n_pts, chip.n_cu);
 }
 
+// ---------------------------------------------------------------- whole-line chunks under one workspace budget
+inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
+// Device buffers carved out of one workspace, sized by the very sequence of take() calls that carves them: a first pass without a
+// buffer only counts (Carve{nullptr}), the second carves.
+struct Carve {
+  char* base; size_t off = 0;
+  template <typename T> T* take(size_t n) {
+    off = pad256(off);
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += n * sizeof(T);
+    return p;
+  }
+};
+
+// The geometry-fed scans that keep per-system rows in a workspace (nearest, modes, the scan VJP, the non-uniform-grid scans) work
+// through their lines in chunks of whole lines: a chunk's workspace (rows + the solver's per-wave workspace) stays within this many
+// bytes, or the chunk holds option "nearest_chunk_systems" systems.
+constexpr size_t kLineChunkBudget = size_t(1) << 30;
+struct LineChunks { long lines; size_t bytes; };      // lines per chunk (the last chunk may be shorter), bytes_of(lines)
+// bytes_of(L) = the workspace of a chunk of L lines.  chunk_systems > 0 (the option): that many systems, rounded down to whole lines.
+// Otherwise n_lines is halved, rounding up, while it is over the budget: NOT the largest count that fits (7 lines of which 3 would fit
+// go 4, 2).  Launch shapes follow from this sequence.  One line over the budget stays one line: the caller tries the allocation.
+template <class BytesOf>
+LineChunks plan_line_chunks(long n_lines, int n_theta0, long chunk_systems, size_t budget, BytesOf&& bytes_of) {
+  long L = n_lines;
+  if (chunk_systems > 0) L = chunk_systems / n_theta0;
+  else while (L > 1 && bytes_of(L) > budget) L = (L + 1) / 2;
+  if (L < 1) L = 1;
+  if (L > n_lines) L = n_lines;
+  return LineChunks{L, bytes_of(L)};
+}
+
 }  // namespace ibs

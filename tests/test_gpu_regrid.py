@@ -239,6 +239,15 @@ def test_results_do_not_depend_on_batch_order_or_chunks(ctx, tables, N):
         ctx.set_option("nearest_chunk_systems", None)
         for key in keys:
             assert same_bits(r[key], full[key]), ("chunk", chunk, key)
+    # the points form in chunks of 2, 2 and 1 points: a chunk starts at its own theta0 (neighbouring points differ in theta0)
+    pick = np.arange(5) % len(THETA0)
+    pts = ctx.gamma_points_theta(th, *geo7, dP, THETA0[pick], want_X=True, want_info=True)
+    ctx.set_option("nearest_chunk_systems", 2)
+    r = ctx.gamma_points_theta(th, *geo7, dP, THETA0[pick], want_X=True, want_info=True)
+    ctx.set_option("nearest_chunk_systems", None)
+    for key in keys:
+        assert same_bits(r[key], pts[key]), ("points in chunks", key)
+        assert same_bits(pts[key], full[key][np.arange(5), pick]), ("mixed points", key)
 
 
 # ---- 5. invalid grids ----------------------------------------------------------------------------------------------------

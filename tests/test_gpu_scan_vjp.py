@@ -224,7 +224,7 @@ def raw_host_call(ctx, d, ld):
 
 @pytest.mark.parametrize("nearest", [False, True])
 def test_results_are_bitwise_repeatable_and_independent_of_the_call(ctx, nearest):
-    """4. the same call twice; the lines in reversed order; 1-line chunks (nearest_chunk_systems) against the default; host pointers
+    """4. the same call twice; the lines in reversed order; 1-line chunks, and chunks of 2 and 1 lines (nearest_chunk_systems), against the default; host pointers
     with a row pitch of N + 6 (padding back as 0) against device pointers: identical bits"""
     import torch
     dev = torch.device("cuda:0")
@@ -242,10 +242,13 @@ def test_results_are_bitwise_repeatable_and_independent_of_the_call(ctx, nearest
     try:
         c = run(ctx, d)
         assert ctx.last_launch() == ("ibs::k_scan_vjp_reduce", 4)          # (one line: one block of four waves)
+        ctx.set_option("nearest_chunk_systems", 2 * len(T5))               # (a chunk of two lines, then a short last one)
+        c2 = run(ctx, d)
     finally:
         ctx.set_option("nearest_chunk_systems", None)
     for k in KEYS:
         assert same_bits(c[k], a[k]), k
+        assert same_bits(c2[k], a[k]), ("chunks of 2 and 1 lines", k)
     up = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     t = ctx.gamma_scan_vjp(d["h"], *[up(x) for x in d["geo7"]], up(d["dP"]), up(d["t0"]), up(d["gbar"]), sigma=up(d["sigma"]),
                            want_info=True)
