@@ -102,6 +102,8 @@ SYMBOLS = {
     "ibs_theta0_polish_step": (C.c_int, [_P, _D, _I32, _P]),
     "ibs_theta0_polish_result": (C.c_int, [_P, _P, _P, _P, _P]),
     "ibs_row_peaks_f64": (C.c_int, [_I32, _I32, _I32, _P, _P, _P]),
+    "ibs_marginal_theta0_polish_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _I32, _D, _I32,
+                                                 _P, _P, _P, _P, _P, _P, _P, _I32]),
 }
 
 

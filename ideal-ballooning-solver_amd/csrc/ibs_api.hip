@@ -1115,6 +1115,45 @@ int ibs_marginal_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32
   });
 }
 
+// mu = 1 / s* maximised over theta0 on every line (k_marginal_theta0_polish; the rule: ibs_theta0_polish.hpp).  The argument checks are
+// those of ibs_theta0_polish_f64, before the context; the grid and the workspace those of ibs_marginal_scan_f64
+int ibs_marginal_theta0_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                                   const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                                   const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                                   const double* mu, const int32_t* node_in, int32_t n_starts, double xtol, int32_t max_eval,
+                                   double* theta0_star, double* mu_star, double* scale_star, int32_t* node, int32_t* n_eval,
+                                   int32_t* info, int32_t* n_found, int32_t mem) {
+  const GeoLines geo{{bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22}, ld, dPdrho, theta0};
+  if (n_starts < 1 || n_starts > ibs::t0p::kMaxSlots || !(xtol > 0) || !std::isfinite(xtol) || max_eval < 1 ||
+      max_eval > ibs::t0p::kMaxEval)
+    return fail(IBS_ERR_ARG, "n_starts in [1, %d], xtol > 0 and finite, max_eval in [1, %d] required (n_starts=%d xtol=%g max_eval=%d)",
+                ibs::t0p::kMaxSlots, ibs::t0p::kMaxEval, n_starts, xtol, max_eval);
+  if (n_lines < 0 || n_theta0 < 1 || N < 1 || !geo.present() || !dPdrho || !theta0 || !mu || !theta0_star || !mu_star || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_theta0=%d ld=%lld N=%d; the arrays, theta0, mu, theta0_star and mu_star are required)",
+                n_lines, n_theta0, (long long)ld, N);
+  if (int r = check_grid(N, h, true)) return r;
+  const bool host = mem == IBS_MEM_HOST;
+  if (host && !ibs::t0p::grid_ok(theta0, n_theta0)) return fail(IBS_ERR_ARG, "theta0 must be finite and strictly increasing");
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_lines == 0) return 0;
+  ON_DEVICE(ctx);
+  ibs::MarginalPolishArgs a{};
+  a.n_lines = n_lines; a.n_theta0 = n_theta0; a.N = N; a.h = h; a.ld = (long)ld;
+  a.n_starts = n_starts; a.xtol = xtol; a.max_eval = max_eval;
+  const size_t n_sys = (size_t)n_lines * n_theta0, n_slots = (size_t)n_lines * n_starts;
+  auto decl = [&](Stage& s) {
+    geo.declare(s, n_lines, n_theta0).into(a); a.mu = s.in(mu, n_sys); a.node_in = s.in(node_in, n_slots);
+    a.theta0_star = s.out(theta0_star, n_slots); a.mu_star = s.out(mu_star, n_slots); a.scale_star = s.out(scale_star, n_slots);
+    a.node = s.out(node, n_slots); a.n_eval = s.out(n_eval, n_slots); a.n_found = s.out(n_found, (size_t)n_lines);
+    a.info = s.status(info, n_slots);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, (long)n_slots, ibs::marginal_ws(N, true).total)) return r;
+    HIPCHK(ibs::launch_marginal_theta0_polish(a, ctx->stream));
+    return 0;
+  });
+}
+
 // the objective of the margin's refinement in (alpha, theta0): val = -mu = -1 / s* and its gradient at geometry-fed points (k_marginal_points)
 int ibs_marginal_obj_w_grad_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, double h, const double* geo, int64_t ld,
                                 const double* theta0, double del_alpha, double* val, double* jac, double* scale, double* dscale,

@@ -203,6 +203,19 @@ struct MarginalScanArgs {
   double* work; size_t work_doubles; long n_waves;
 };
 hipError_t launch_marginal_scan(const MarginalScanArgs& a, hipStream_t st);
+// mu = 1 / s* maximised over theta0 about the peaks of every line's coarse row (ibs_marginal_polish.hip; the rule: ibs_theta0_polish.hpp):
+// one wave per (line, slot) on the persistent grid of min(n_lines * n_starts, n_waves) waves, workspace marginal_ws(N, true).  mu
+// (required) [n_lines][n_theta0]; node_in (optional) and every output but n_found [n_lines] are [n_lines][n_starts]; theta0_star and
+// mu_star are required
+struct MarginalPolishArgs {
+  int n_lines, n_theta0, N; double h;
+  const double* geo7[7]; long ld;                                   // as MarginalScanArgs
+  const double *dPdrho, *theta0, *mu; const int* node_in;
+  int n_starts; double xtol; int max_eval;
+  double *theta0_star, *mu_star, *scale_star; int *node, *n_eval, *info, *n_found;
+  double* work; size_t work_doubles; long n_waves;
+};
+hipError_t launch_marginal_theta0_polish(const MarginalPolishArgs& a, hipStream_t st);
 // geometry-fed points with the gradient of s* in (alpha, theta0) (ibs_marginal_points.hip): one wave per point, workspace marginal_ws(N, true)
 struct MarginalPointsArgs {
   int n_pts, N; double h; long ld;

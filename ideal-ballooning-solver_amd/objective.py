@@ -334,18 +334,27 @@ class AdjointStep:
         return dict(scale=host["scale"], alpha=pts[:, 0].copy(), theta0=pts[:, 1].copy(), dscale_dalpha=host["dscale_dalpha"],
                     dscale_dtheta0=host["dscale_dtheta0"], wout_bar=wout_bar)
 
-    def marginal(self, wouts, steps=None, refine=True, jac="reference"):
+    def marginal(self, wouts, steps=None, refine=True, jac="reference", n_starts=1, theta0_polish=False):
         """the marginal-stability scale s* of every surface of every equilibrium of the step (BallooningScan.marginal: the smallest
         critical scale of dPdrho over (alpha, theta0), refined from the coarse minimum unless refine=False), on the SurfaceTables
         frame, the sharding of equilibria over ranks and the ONE all-gather of run().  wouts as in run().
         Returns dict(scale, alpha, theta0: (n_eq, n_surf)), identical on every rank; with steps (n_eq,), entry 0 unused, also dscale
         (n_dof, n_surf) = (scale[1:] - scale[0]) / steps[1:, None]: the forward differences of sims_runner_NCSX.py:258-261 applied
         to the margin.  scale = inf (no scale makes the surface unstable) is a result, not a failure.  jac: the gradient the
-        refinement runs on, as in BallooningScan.marginal ("reference", the default, or "exact_tangent")."""
+        refinement runs on, as in BallooningScan.marginal ("reference", the default, or "exact_tangent").  n_starts, theta0_polish:
+        passed to BallooningScan.marginal (multi-start refinement from the K best peaks of mu; start at the crest of the best line's
+        theta0 envelope); a bad combination raises ValueError before anything runs; the defaults make the calls made before."""
         import torch
         from .geometry import SurfaceTables
-        from .scan import check_marginal_jac, gather_rows_tensor
+        from .scan import check_marginal_jac, check_n_starts, gather_rows_tensor
         check_marginal_jac(jac)
+        if theta0_polish and check_n_starts(n_starts) != 1:
+            raise ValueError("theta0_polish=True takes n_starts=1")
+        more = {}                          # (nothing at all with the defaults: the call is then exactly what it was)
+        if check_n_starts(n_starts) != 1:
+            more["n_starts"] = int(n_starts)
+        if theta0_polish:
+            more["theta0_polish"] = True
         n_eq, ns = len(wouts), len(self.svals)
         own = shard_dofs(n_eq, self.rank, self.world)
         err = None
@@ -362,7 +371,7 @@ class AdjointStep:
                 r0, r1 = fr.fill(0, mine, self.n_threads)
                 if pinned:
                     self.ctx.upload_tables_rows(fr, self.device, r0, r1)
-                m = scan.marginal(refine=refine, jac=jac)
+                m = scan.marginal(refine=refine, jac=jac, **more)
                 local = np.stack([m["scale"], m["alpha"], m["theta0"]], axis=1).reshape(len(own), 3 * ns)
                 rows = torch.from_numpy(np.ascontiguousarray(local, dtype=np.float64)).to(self.device)
             else:

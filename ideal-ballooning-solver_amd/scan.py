@@ -357,7 +357,7 @@ class BallooningScan:
         self.n_starts = check_n_starts(n_starts)
         self.last_candidates = self.last_peaks = None
         self.theta0_polish = bool(theta0_polish)
-        self.last_envelope = None
+        self.last_envelope = self.last_marginal_envelope = None
         if self.theta0_polish:
             if tables is None or device is None:
                 raise ValueError("theta0_polish=True runs on the resident path: tables= and device= are required")
@@ -549,7 +549,69 @@ class BallooningScan:
                     cluster=((status & CLUSTER_BIT) != 0).reshape(shape))
 
     # -- marginal stability on the coarse grid of the surfaces this rank owns, one launch
-    def marginal(self, refine=False, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, jac="reference"):
+    def _marginal_coarse(self):
+        """the coarse table of marginal(): dict(tab (n_own, nalpha, ntheta0) numpy, and -- for the calls that follow on the same lines
+        -- geo7, dP, t0 and the scan's mu in the memory kind of the path: device tensors or numpy)"""
+        na, nt = len(self.alpha_scan), len(self.theta0_scan)
+        if not self.own:
+            return dict(tab=np.zeros((0, na, nt)))
+        if self.tables is not None and self.device is not None:
+            import torch
+            surf = np.repeat(self._own_surf(), na)
+            r = self.ctx.fieldline_geometry(self.tables, surf, np.tile(self.alpha_scan, len(self.own)), self.theta,
+                                            device=self.device)
+            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
+            geo7 = [r["geo"][k] for k in range(7)]
+            out = self.ctx.marginal_scan(self.h, *geo7, r["dPdrho"], t0, want_info=True)
+            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())          # (bit 8, an infinite margin, is informational)
+            if nbad:
+                raise IbsError("%d of %d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)"
+                               % (nbad, out["info"].numel()))
+            return dict(tab=out["scale"].cpu().numpy().reshape(len(self.own), na, nt), geo7=geo7, dP=r["dPdrho"], t0=t0, mu=out["mu"])
+        geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
+        dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
+        geo7 = [np.ascontiguousarray(geo[:, k]) for k in range(7)]
+        out = self.ctx.marginal_scan(self.h, *geo7, dP, self.theta0_scan)
+        if out.get("nbad", 0):
+            raise IbsError("%d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)" % out["nbad"])
+        return dict(tab=np.asarray(out["scale"]).reshape(len(self.own), na, nt), geo7=geo7, dP=dP, t0=self.theta0_scan, mu=out["mu"])
+
+    def _marginal_envelope(self, co, K, xtol, max_eval):
+        """marginal_envelope() on the coarse scan co (_marginal_coarse): the one polish call and its per-surface best slot"""
+        na, n = len(self.alpha_scan), len(self.own)
+        if not n:
+            z = np.zeros((0, na, K))
+            return dict(theta0=z, mu=z.copy(), scale=z.copy(), node=z.astype(np.int32), n_eval=z.astype(np.int32),
+                        n_found=np.zeros((0, na), np.int32), surface=np.zeros((0, 3)))
+        out = self.ctx.marginal_theta0_polish(self.h, *co["geo7"], co["dP"], co["t0"], co["mu"], n_starts=K, xtol=xtol,
+                                              max_eval=max_eval, want_info=True)
+        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        nbad = int((((host(out["info"]) >> 16) & 3) != 0).sum())
+        if nbad:
+            raise IbsError("%d solves of the margin's envelope were flagged (status bits 0-1: iteration cap or invalid data)" % nbad)
+        res = {k: host(out[k]).reshape(n, na, K) for k in ("theta0", "mu", "scale", "node", "n_eval")}
+        res["n_found"] = host(out["n_found"]).reshape(n, na)
+        flat = np.where(np.isnan(res["mu"]), -np.inf, res["mu"]).reshape(n, na * K)
+        best = np.argmax(flat, axis=1)                                           # (first maximum)
+        rows = np.arange(n)
+        res["surface"] = np.stack([res["theta0"].reshape(n, -1)[rows, best], self.alpha_scan[best // K],
+                                   res["scale"].reshape(n, -1)[rows, best]], axis=1)
+        return res
+
+    # -- every line's margin maximised over theta0 between the nodes of the coarse grid, two launches
+    def marginal_envelope(self, n_starts=1, xtol=1e-5, max_eval=32):
+        """mu_env(alpha) = max over theta0 of mu(alpha, theta0) = 1 / s* of every line of the coarse grid, i.e. the line's smallest
+        critical scale: the coarse Context.marginal_scan, then Context.marginal_theta0_polish about the n_starts <= 4 best peaks of
+        every line's row of mu (Brent between the nodes on the lines the scan read: no geometry launch beyond the coarse scan's), on
+        the resident path or with the fieldlines callback.  Returns numpy dict(theta0, mu, scale, node, n_eval (n_own, nalpha,
+        n_starts), n_found (n_own, nalpha), surface (n_own, 3) = (theta0*, alpha, s*) of the best slot of every surface, first
+        maximum of mu in (alpha, slot) order).  mu is never below the coarse row, so surface[:, 2] is never above the coarse minimum
+        of s*.  Flagged solves (status bits 0-1) raise; scale = inf is a result."""
+        if isinstance(n_starts, bool) or not isinstance(n_starts, (int, np.integer)) or not 1 <= n_starts <= MAX_ROW_STARTS:
+            raise ValueError("n_starts must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, n_starts))
+        return self._marginal_envelope(self._marginal_coarse(), int(n_starts), xtol, max_eval)
+
+    def marginal(self, refine=False, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, jac="reference", n_starts=1, theta0_polish=False):
         """per owned surface, the smallest critical scale s* of dPdrho over the coarse (alpha, theta0) grid and where it sits
         (Context.marginal_scan): dict(scale (n_own,), alpha, theta0, index (n_own, 2) = (i_alpha, i_theta0) of the first minimum,
         table (n_own, nalpha, ntheta0)).  s* < 1: some line of the surface is unstable now; s* scales dPdrho at FIXED geometry
@@ -569,38 +631,44 @@ class BallooningScan:
         geometry launch (in the same pinned form), one alpha-tangent launch (ibs_fieldline_geometry_dalpha_f64) and one point launch
         (ibs_marginal_obj_w_grad_tangent_f64); the dict has the same keys and dscale is then exact in both variables, so the refined
         point is a stationary point of the s* returned (marginal_sensitivity()).  Either mode leaves its (alpha, theta0) per owned
-        surface on the object for marginal_sensitivity()."""
+        surface on the object for marginal_sensitivity().
+        n_starts=K > 1 (refine=True; K <= 16, else ValueError): every surface is refined from the K best peaks of its table of mu =
+        1 / s* (pick_starts' rule: Context.scan_peaks on the resident path, the numpy rule with the callback; slot 0 is the first
+        maximum of mu) -- a basin whose crest lies between nodes can rank below the first minimum in the table and still hold the
+        surface's margin.  The distinct slots of all surfaces run through the same lockstep loop and ONE final launch; slots from
+        n_found on copy slot 0 and are not evaluated; a table whose maximum mu is 0 stays at scale = inf with no evaluation.  The
+        winner is the smallest refined scale, slot 0 on ties: scale, alpha, theta0, start, dscale, dPdrho are the winner's, and the
+        dict gains candidates (n_own, K, 3) = (scale, alpha, theta0) of every slot and n_found (n_own,); evals and task are then
+        (n_own, K).  With refine=False the starts are not used.  n_starts=1 (the default) makes exactly the calls it made before
+        the option existed.
+        theta0_polish=True (n_starts=1, else ValueError): every line's mu is first maximised over theta0 between the nodes
+        (marginal_envelope's polish call on the lines of the coarse scan, one slot per line) and every surface starts at the crest
+        of its best line -- marginal_envelope's `surface` -- in place of the best node; refine=False reports that point.  The
+        envelope is left in .last_marginal_envelope.  theta0_polish=False (the default) makes exactly the calls it made before."""
         tangent = check_marginal_jac(jac) == "exact_tangent"
+        K = check_n_starts(n_starts)
+        if theta0_polish and K != 1:
+            raise ValueError("theta0_polish=True takes n_starts=1")
         if tangent and (self.tables is None or self.device is None):
             raise IbsError("marginal(jac='exact_tangent') needs tables= and device=: a host geometry callable has no alpha-tangent")
         na, nt = len(self.alpha_scan), len(self.theta0_scan)
-        if not self.own:
-            tab = np.zeros((0, na, nt))
-        elif self.tables is not None and self.device is not None:
-            import torch
-            surf = np.repeat(self._own_surf(), na)
-            r = self.ctx.fieldline_geometry(self.tables, surf, np.tile(self.alpha_scan, len(self.own)), self.theta,
-                                            device=self.device)
-            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
-            out = self.ctx.marginal_scan(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, want_info=True)
-            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())          # (bit 8, an infinite margin, is informational)
-            if nbad:
-                raise IbsError("%d of %d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)"
-                               % (nbad, out["info"].numel()))
-            tab = out["scale"].cpu().numpy().reshape(len(self.own), na, nt)
-        else:
-            geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
-            dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
-            out = self.ctx.marginal_scan(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan)
-            if out.get("nbad", 0):
-                raise IbsError("%d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)" % out["nbad"])
-            tab = np.asarray(out["scale"]).reshape(len(self.own), na, nt)
+        co = self._marginal_coarse()
+        tab = co["tab"]
         flat = tab.reshape(len(tab), -1)
         k = np.argmin(flat, axis=1) if len(tab) else np.zeros(0, dtype=np.int64)
         ia, it = k // nt, k % nt
         res = dict(scale=flat[np.arange(len(tab)), k], alpha=self.alpha_scan[ia], theta0=self.theta0_scan[it],
                    index=np.stack([ia, it], axis=1), table=tab)
-        if refine:
+        if theta0_polish:
+            env = self.last_marginal_envelope = self._marginal_envelope(co, 1, 1e-5, 32)
+            crest = dict(res, scale=env["surface"][:, 2].copy(), alpha=env["surface"][:, 1].copy(), theta0=env["surface"][:, 0].copy())
+            if refine:
+                res = dict(self._marginal_refine(crest, maxiter, ftol, gtol, tangent), coarse_scale=res["scale"])
+            else:
+                res = crest
+        elif refine and K > 1:
+            res = self._marginal_refine_multi(res, co, K, maxiter, ftol, gtol, tangent)
+        elif refine:
             res = self._marginal_refine(res, maxiter, ftol, gtol, tangent)
         self._last_marginal_points = np.stack([res["alpha"], res["theta0"]], axis=1).astype(np.float64).reshape(len(tab), 2)
         return res
@@ -658,25 +726,35 @@ class BallooningScan:
 
     def _marginal_refine(self, res, maxiter, ftol, gtol, tangent=False):
         """the lockstep loop of refine_batched on the margin's objective, from the first minimum of every coarse table"""
+        n = len(self.own)
+        start = np.stack([res["alpha"], res["theta0"]], axis=1).astype(np.float64).reshape(n, 2)
+        # (an all-inf table: mu = 0 with a zero gradient all around the start)
+        r = self._marginal_refine_points(np.arange(n), start, np.isfinite(res["scale"]), maxiter, ftol, gtol, tangent)
+        return dict(res, coarse_scale=res["scale"], start=start, alpha=r["x"][:, 0].copy(), theta0=r["x"][:, 1].copy(), evals=r["evals"],
+                    task=r["task"], rounds=r["rounds"], scale=r["scale"], dscale=r["dscale"], dPdrho=r["dPdrho"])
+
+    def _marginal_refine_points(self, own_idx, start, active, maxiter, ftol, gtol, tangent):
+        """the loop itself on n points: point q belongs to owned surface own_idx[q] (repeats allowed) and starts at start[q]; points
+        that are not `active` are not moved.  Every round is one `points` call on the points still running, and one more on all n
+        fills dict(x (n, 2), evals, task (n,), rounds, scale, dscale, dPdrho)."""
         points = self._marginal_points_tangent if tangent else self._marginal_points
         import ctypes as C
         from . import _lib
         lib = _lib.lib()
         lo = np.array([0.0, 0.0]); hi = np.array([np.pi, 0.5 * np.pi])
-        n = len(self.own)
+        n = len(own_idx)
         p = lambda a: C.c_void_p(a.ctypes.data)
-        start = np.stack([res["alpha"], res["theta0"]], axis=1).astype(np.float64).reshape(n, 2)
         x = np.clip(start, lo, hi)
         states = [C.create_string_buffer(lib.ibs_lbfgsb2_state_bytes()) for _ in range(n)]
         for k in range(n):
             lib.ibs_lbfgsb2_init(states[k], p(x[k]), p(lo), p(hi), float(ftol), float(gtol), int(maxiter), 20)
-        active = np.isfinite(res["scale"])                  # (an all-inf table: mu = 0 with a zero gradient all around the start)
+        active = np.array(active, dtype=bool)
         evals = np.zeros(n, dtype=np.int32)
         task = np.full(n, 10, dtype=np.int32)
         rounds = 0
         while active.any():
             idx = np.nonzero(active)[0]
-            r = points(idx, x[idx])
+            r = points(own_idx[idx], x[idx])
             rounds += 1
             evals[idx] += 1
             for q, k in enumerate(idx):
@@ -688,14 +766,47 @@ class BallooningScan:
                 fk = C.c_double(0.0); cnt = np.zeros(5, dtype=np.int32)
                 lib.ibs_lbfgsb2_result(states[k], p(x[k]), C.byref(fk), p(cnt))
                 task[k] = cnt[2]
-        out = dict(res, coarse_scale=res["scale"], start=start, alpha=x[:, 0].copy(), theta0=x[:, 1].copy(), evals=evals, task=task,
-                   rounds=rounds)
+        out = dict(x=x, evals=evals, task=task, rounds=rounds)
         if n:
-            fin = points(np.arange(n), x)
+            fin = points(own_idx, x)
             out.update(scale=fin["scale"], dscale=fin["dscale"], dPdrho=fin["dPdrho"])
         else:
             out.update(scale=np.zeros(0), dscale=np.zeros((0, 2)), dPdrho=np.zeros(0))
         return out
+
+    def _marginal_refine_multi(self, res, co, K, maxiter, ftol, gtol, tangent):
+        """marginal(refine=True, n_starts=K > 1): the starts from the K best peaks of every surface's table of mu, all distinct slots of
+        all surfaces through _marginal_refine_points at once, the winner per surface"""
+        n, na, nt = len(self.own), len(self.alpha_scan), len(self.theta0_scan)
+        start, n_found = np.zeros((n, K, 2)), np.zeros(n, dtype=np.int32)
+        if n and self.tables is not None and self.device is not None:
+            import torch
+            pk = self.ctx.scan_peaks(torch.from_numpy(self.alpha_scan).to(self.device), co["t0"], co["mu"].reshape(n, na, nt), K,
+                                     want_found=True)
+            start, n_found = pk["start"].cpu().numpy(), pk["n_found"].cpu().numpy()
+        else:
+            mu = np.asarray(co["mu"]).reshape(n, na, nt) if n else np.zeros((0, na, nt))
+            for q in range(n):
+                ps = pick_starts(mu[q], self.alpha_scan, self.theta0_scan, K)
+                start[q], n_found[q] = ps["start"], ps["n_found"]
+        run = np.maximum(n_found, 1)                                   # (a table whose maximum mu is 0: one point, not evaluated)
+        own_idx = np.repeat(np.arange(n), run)
+        slot = np.concatenate([np.arange(m) for m in run]) if n else np.zeros(0, dtype=np.int64)
+        x0 = start[own_idx, slot].reshape(len(own_idx), 2)
+        r = self._marginal_refine_points(own_idx, x0, n_found[own_idx] > 0, maxiter, ftol, gtol, tangent)
+        cand, evals, task = np.zeros((n, K, 3)), np.zeros((n, K), dtype=np.int32), np.full((n, K), 10, dtype=np.int32)
+        point = np.zeros((n, K), dtype=np.int64)                       # the point behind every slot: padded slots copy slot 0
+        first = np.concatenate([[0], np.cumsum(run)[:-1]]) if n else np.zeros(0, dtype=np.int64)
+        for q in range(n):
+            point[q] = first[q]
+            point[q, :run[q]] = first[q] + np.arange(run[q])
+        if n:
+            cand = np.stack([r["scale"][point], r["x"][point, 0], r["x"][point, 1]], axis=2)
+            evals, task = r["evals"][point], r["task"][point]
+        win = point[np.arange(n), np.argmin(cand[:, :, 0], axis=1)] if n else np.zeros(0, dtype=np.int64)      # (slot 0 on ties)
+        return dict(res, coarse_scale=res["scale"], start=x0[win], alpha=r["x"][win, 0].copy(),
+                    theta0=r["x"][win, 1].copy(), evals=evals, task=task, rounds=r["rounds"], scale=r["scale"][win], dscale=r["dscale"][win],
+                    dPdrho=r["dPdrho"][win], candidates=cand, n_found=n_found)
 
     # -- jac="exact": val and the exact gradient at a batch of points (numpy or device tensors in, numpy out); sigma None = lam_max's pair
     # (geo_da: the alpha-tangent planes of jac="exact_tangent", geo then being the (8, n, N) planes of the points' own lines)

@@ -418,6 +418,34 @@ class Context:
                      ar.out("info", shape, _I32, want_info))
         return ar.result(rc)
 
+    def marginal_theta0_polish(self, h, bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22, dPdrho, theta0, mu, n_starts=1, xtol=1e-5,
+                               max_eval=32, node=None, want_scale=True, want_info=False, want_found=True):
+        """mu = 1 / s* of every line maximised over theta0 between the nodes of its coarse row (ibs_marginal_theta0_polish_f64; the
+        rule: scan.row_peaks and scan.polish_theta0): about the n_starts <= 4 best peaks of mu[line], or about the nodes the caller
+        names.  Arrays as in marginal_scan, any odd N in [66, 65537]; theta0 (n_theta0,): finite and strictly increasing; mu (n_lines,
+        n_theta0): marginal_scan's mu on these lines; node int32 (n_lines, n_starts), optional: the nodes to polish about (-1 = skip
+        the slot) instead of the row's own peaks.
+        Returns dict(theta0, mu (n_lines, n_starts)[, scale = s* at theta0: bitwise marginal_scan's there], node, n_eval int32
+        (n_lines, n_starts)[, info int32: multisection passes | status << 16][, n_found int32 (n_lines,)], nbad): mu is never below
+        the coarse row; status bit 8 = the returned point has scale = inf (mu = 0), bit 10 = the node itself was returned, bit 11 =
+        max_eval reached, bit 12 = one-sided bracket.  Slots from n_found on repeat slot 0; a row without a finite entry gives NaN."""
+        K = int(n_starts)
+        if K != n_starts or not 1 <= K <= MAX_ROW_STARTS:
+            raise IbsError("n_starts must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, n_starts))
+        geo = (bmag, gradpar, cvdrift, cvdrift0, gds2, gds21, gds22)
+        shape = (int(geo[0].shape[0]), int(theta0.shape[0]))
+        if tuple(mu.shape) != shape:
+            raise IbsError("marginal_theta0_polish: mu must be %s, not %s" % (shape, tuple(mu.shape)))
+        slots = (shape[0], K)
+        if node is not None and tuple(node.shape) != slots:
+            raise IbsError("marginal_theta0_polish: node must be %s, not %s" % (slots, tuple(node.shape)))
+        ar = _Args(self)
+        head, _, N = ar.geo(h, geo, dPdrho, theta0)
+        rc = ar.call("ibs_marginal_theta0_polish_f64", *head, ar.inp(mu), ar.inp(node, _I32), K, float(xtol), int(max_eval),
+                     ar.out("theta0", slots), ar.out("mu", slots), ar.out("scale", slots, want=want_scale), ar.out("node", slots, _I32),
+                     ar.out("n_eval", slots, _I32), ar.out("info", slots, _I32, want_info), ar.out("n_found", (shape[0],), _I32, want_found))
+        return ar.result(rc)
+
     @staticmethod
     def _three_lines(geo):
         n_pts, three, eight, N = geo.shape

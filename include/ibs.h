@@ -52,7 +52,7 @@
  *            SOME vector of the cluster's invariant subspace (it satisfies the pencil to the residual bound of ibs_solve_gcf_vjp_f64
  *            and is otherwise unspecified) and gam is that vector's quotient.  Informational: not counted by return values > 0.
  *            The derivative of one member of a cluster does not exist: do not hand such a pair to ibs_solve_gcf_vjp_f64.
- *     bits 10-12, ibs_theta0_polish_f64 only, per start slot, all informational (not counted by return values > 0): bit 10 = the
+ *     bits 10-12, ibs_theta0_polish_f64 and ibs_marginal_theta0_polish_f64 only, per start slot, all informational (not counted by return values > 0): bit 10 = the
  *            coarse node itself was returned (no evaluated point beat it strictly); bit 11 = the search stopped at max_eval;
  *            bit 12 = one-sided bracket (the row ends at the node, or the neighbour on that side is NaN).
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
@@ -798,6 +798,36 @@ int ibs_theta0_polish_init(void* state, int32_t n_theta0, const double* theta0, 
 int ibs_theta0_polish_step(void* state, double gam, int32_t eval_status, double* x_next);
 int ibs_theta0_polish_result(const void* state, double* theta0_star, double* gam_star, int32_t* n_eval, int32_t* status);
 int ibs_row_peaks_f64(int32_t n_rows, int32_t n_theta0, int32_t K, const double* gam, int32_t* node, int32_t* n_found);
+
+/* The margin of every line maximised over theta0 BETWEEN the nodes of ibs_marginal_scan_f64's table: mu_env = max over theta0 of
+ * mu(line, theta0) = 1 / s*, i.e. the smallest critical scale of the line, about the n_starts best peaks of the line's coarse row of
+ * mu.  The twin of ibs_theta0_polish_f64 on the margin; nothing upstream corresponds.  The rule is that call's, point for point (row
+ * peaks, bracket, Brent's bounded search seeded with the three node values, incumbent, slots from n_found on repeat slot 0, NaN rows,
+ * node_in), with mu in place of gam: s* = +inf is the VALUE mu = 0, an evaluation with status bit 0 or 1 counts as -inf and its bits
+ * are OR-ed into the slot's word.  The ibs_theta0_polish_init / _step / _result state machine drives the same search on the host.
+ *   The seven arrays [n_lines][ld], dPdrho [n_lines], theta0 [n_theta0] (finite and strictly increasing): as ibs_marginal_scan_f64;
+ *   mu [n_lines][n_theta0]: the coarse table, that call's mu (required);  node_in [n_lines][n_starts], optional, as in
+ *   ibs_theta0_polish_f64;
+ *   theta0_star, mu_star [n_lines][n_starts] (required);  scale_star = s* at theta0_star, node, n_eval, info (int32)
+ *   [n_lines][n_starts] and n_found [n_lines] optional.
+ *   Every evaluation is a cold solve: scale_star is bit for bit ibs_marginal_scan_f64's scale of that line at theta0_star (where the
+ *   node itself is returned, one more solve at the node supplies it; it enters neither n_eval nor info), and mu_star = 1 / scale_star.
+ *   info: bits 0..15 = multisection passes of all evaluations of the slot, saturated; bits 16.. = the status: bits 0-1, 10, 11, 12 as
+ *   in ibs_theta0_polish_f64, bit 8 iff the returned point has s* = +inf (mu_star = 0; informational).
+ * FP64, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED).  n_starts outside [1, 4], xtol <= 0 or not finite,
+ * max_eval outside [1, 64], a dimension < 1, ld < N or a required pointer NULL: IBS_ERR_ARG; all of these run before the context is
+ * touched; n_lines = 0: nothing happens.  A theta0 grid that is not finite and strictly increasing: IBS_ERR_ARG on host pointers; on
+ * device pointers every slot gets status bit 1 and NaN.  Host or device pointers (mem); host pointers: returns the number of slots with
+ * status bit 0 or 1.  One wavefront per (line, slot) on the persistent grid and workspace of ibs_marginal_scan_f64
+ * (k_marginal_theta0_polish, csrc/ibs_marginal_polish.hip), at most max_eval <= 64 evaluations per slot whatever the data; no
+ * floating-point atomics: results are bitwise repeatable and independent of n_lines, of the order of the lines and, for slot 0, of
+ * n_starts.  The frozen-geometry caveat of ibs_marginal_scan_f64 applies. */
+int ibs_marginal_theta0_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_theta0, int32_t N, double h, const double* bmag,
+                                   const double* gradpar, const double* cvdrift, const double* cvdrift0, const double* gds2,
+                                   const double* gds21, const double* gds22, int64_t ld, const double* dPdrho, const double* theta0,
+                                   const double* mu, const int32_t* node_in, int32_t n_starts, double xtol, int32_t max_eval,
+                                   double* theta0_star, double* mu_star, double* scale_star, int32_t* node, int32_t* n_eval,
+                                   int32_t* info, int32_t* n_found, int32_t mem);
 
 #ifdef __cplusplus
 }
