@@ -43,6 +43,7 @@ SYMBOLS = {
     "ibs_solve_gcf_f32": (C.c_int, [_P, _I64, _I32, C.c_float, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I32]),
     "ibs_solve_gcf_nearest_f64": (C.c_int, [_P, _I64, _I32, _D, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_solve_gcf_modes_f64": (C.c_int, [_P, _I64, _I32, _D, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _I32]),
+    "ibs_solve_gcf_modes_basis_f64": (C.c_int, [_P, _I64, _I32, _D, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_gamma_scan_modes_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _P, _P, _I32]),
     "ibs_solve_gcf_vjp_f64": (C.c_int, [_P, _I64, _I32, _D, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "ibs_marginal_gcf_f64": (C.c_int, [_P, _I64, _I32, _D, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I32]),

@@ -20,7 +20,7 @@ import warnings
 
 import torch
 
-from .solver import CLUSTER_BIT, IbsError, VjpStatusWarning, default_context, vjp_status_message
+from .solver import BASIS_BIT, CLUSTER_BIT, OPEN_CLUSTER_BIT, IbsError, VjpStatusWarning, default_context, vjp_status_message
 
 _MODES = ("max", "nearest")
 
@@ -66,16 +66,34 @@ def solve_gcf(h, g, c, f, eigenpair="max", sigma=None, ctx=None):
 
 class _SolveGcfModes(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, h, g, c, f, n_modes, ictx):
-        r = ictx.solve_gcf_modes(h, g, c, f, n_modes, want_X=True, want_info=True)
-        fctx.save_for_backward(g, c, f, r["lam"], r["X"], ((r["info"] >> 16) & CLUSTER_BIT).ne(0))
+    def forward(fctx, h, g, c, f, n_modes, ictx, mean):
+        r = ictx.solve_gcf_modes(h, g, c, f, n_modes, want_X=True, want_info=True, basis=mean)
+        st = r["info"] >> 16
+        cluster, lam = (st & CLUSTER_BIT).ne(0), r["lam"]
+        pool = []
+        if mean:
+            # a COMPLETE cluster: every member has its basis vector and none lies below the last mode (cluster_first names the group)
+            cf = r["cluster_first"].long()
+            over = lambda v: torch.zeros_like(lam).scatter_add_(1, cf, v.to(lam.dtype)).gather(1, cf)      # summed over the group
+            size = over(torch.ones_like(lam))
+            pooled = cluster & over(cluster & ((st & BASIS_BIT).eq(0) | (st & OPEN_CLUSTER_BIT).ne(0))).eq(0)
+            lam = torch.where(pooled, over(r["lam"]) / size, r["lam"])
+            pool = [cf, size, pooled]
+        fctx.save_for_backward(g, c, f, r["lam"], r["X"], cluster, *pool)
         fctx.h, fctx.ictx = h, ictx
-        return r["gam"], r["lam"]
+        return r["gam"], lam
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(fctx, gam_bar, lam_bar):
-        g, c, f, lam, X, cluster = fctx.saved_tensors
+        g, c, f, lam, X, cluster, *pool = fctx.saved_tensors
+        if pool:
+            # lam of every member of a complete cluster is the cluster's mean: its members' cotangents, pooled and divided by m, go
+            # to each member's own lam-only VJP -- the sum is the derivative of the mean, which exists.  gam of a member has none.
+            cf, size, pooled = pool
+            share = torch.zeros_like(lam_bar).scatter_add_(1, cf, torch.where(pooled, lam_bar, torch.zeros_like(lam_bar))).gather(1, cf) / size
+            lam_bar = torch.where(pooled, share, lam_bar)
+            cluster = cluster & ~(pooled & gam_bar.eq(0))
         active = gam_bar.ne(0) | lam_bar.ne(0)                    # (n_sys, n_modes): the pairs the cotangent reaches
         rows = [torch.zeros_like(g), torch.zeros_like(c), torch.zeros_like(f)]
         flags = [(active & cluster).any(1).sum()]
@@ -99,16 +117,23 @@ class _SolveGcfModes(torch.autograd.Function):
                          "no derivative of its own, NaN rows)" % n_cluster)
         if parts:
             warnings.warn("; ".join(parts), VjpStatusWarning, stacklevel=2)
-        return None, rows[0], rows[1], rows[2], None, None
+        return None, rows[0], rows[1], rows[2], None, None, None
 
 
-def solve_gcf_modes(h, g, c, f, n_modes, ctx=None):
+def solve_gcf_modes(h, g, c, f, n_modes, ctx=None, cluster="refuse"):
     """(gam, lam), each (n_sys, n_modes), of the n_modes largest eigenpairs of the raw systems g, c, f (n_sys, N), mode 0 = lam_max's
     (Context.solve_gcf_modes).  Differentiable in g, c and f: the backward is one Context.solve_gcf_vjp per mode the cotangent
     reaches, on that mode's (lam, X) and cotangent columns, summed.  A clustered mode (status bit 9: a neighbouring eigenvalue within
     4 N eps ||A||) has no derivative of its own: with a non-zero cotangent the system's rows are NaN and a VjpStatusWarning is issued;
-    with a zero cotangent it contributes nothing."""
-    return _SolveGcfModes.apply(float(h), g, c, f, int(n_modes), ctx or default_context(g.device.index or 0))
+    with a zero cotangent it contributes nothing.
+    cluster="mean": the forward builds the Ritz basis of every cluster (Context.solve_gcf_modes(basis=True)) and every member of a
+    complete cluster -- all its members found, none below the last mode asked for -- returns the cluster's MEAN lam, whose derivative
+    exists: (1 / m) sum_i x_i^T (dS - lam_i dF) x_i / x_i^T F x_i over the basis, i.e. the members' lam-only VJPs with their
+    cotangents pooled and divided by m.  A cotangent on gam of a clustered mode, or on any member of an open or incomplete
+    cluster, is refused as above."""
+    if cluster not in ("refuse", "mean"):
+        raise ValueError("cluster must be 'refuse' or 'mean', not %r" % (cluster,))
+    return _SolveGcfModes.apply(float(h), g, c, f, int(n_modes), ctx or default_context(g.device.index or 0), cluster == "mean")
 
 
 class _MarginalScale(torch.autograd.Function):

@@ -1030,6 +1030,34 @@ int ibs_solve_gcf_modes_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, co
   });
 }
 
+// ---- spectrum mode with an F-orthonormal Ritz basis of every cluster of modes (ibs_modes_basis.hip)
+// the same persistent grid, basis_ws_doubles(N) of ctx->long_ws per wave; the members' vectors are built in the caller's X rows
+int ibs_solve_gcf_modes_basis_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh, const double* c,
+                                  const double* f, int64_t ld, int32_t n_modes, double* lam, double* gam, double* X, double* dX,
+                                  int32_t* cluster_first, int32_t* info, int32_t mem) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (n_sys < 0 || !g || !c || !f || ld < N)
+    return fail(IBS_ERR_ARG, "bad arguments (n_sys=%lld ld=%lld N=%d)", (long long)n_sys, (long long)ld, N);
+  if (int r = check_n_modes(n_modes)) return r;
+  if (!X) return fail(IBS_ERR_ARG, "X is null (the basis of a cluster is built in the caller's X rows)");
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_sys == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t in_elems = (size_t)n_sys * ld, n_out = (size_t)n_sys * n_modes, out_elems = n_out * N;
+  ibs::ModesBasisArgs a{};
+  a.n_sys = n_sys; a.N = N; a.h = h; a.ld = ld; a.n_modes = n_modes;
+  auto decl = [&](Stage& s) {
+    a.g = s.in(g, in_elems); a.c = s.in(c, in_elems); a.f = s.in(f, in_elems); a.gh = s.in(gh, in_elems);
+    a.lam = s.out(lam, n_out); a.gam = s.out(gam, n_out); a.X = s.out(X, out_elems); a.dX = s.out(dX, out_elems);
+    a.cluster_first = s.out(cluster_first, n_out); a.info = s.status(info, n_out);
+  };
+  return staged(ctx, mem, decl, [&]() -> int {
+    if (int r = with_wave_ws(ctx, a, a.n_sys, ibs::basis_ws_doubles(N))) return r;
+    HIPCHK(ibs::launch_gcf_modes_basis(a, ctx->stream));
+    return 0;
+  });
+}
+
 // ---- exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip)
 // the persistent grid of long_waves() with its workspace in ctx->long_ws (vjp_ws_doubles(N) per wave)
 int ibs_solve_gcf_vjp_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* c, const double* f,

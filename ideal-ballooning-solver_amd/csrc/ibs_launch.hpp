@@ -101,6 +101,20 @@ struct ModesArgs {
   double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
 };
 hipError_t launch_gcf_modes(const ModesArgs& a, hipStream_t st);
+// the same with an F-orthonormal Ritz basis of every cluster of modes (ibs_modes_basis.hip; the construction: ibs_modes_basis.hpp).
+// X is required: the members' vectors are built in the caller's rows.  cluster_first [n_sys][n_modes], optional.  Per-wave
+// workspace, in this order: the five rows of the elimination (the first three serve the unclustered modes' eigenvector stage),
+// kMaxModes closed eigenvalues, kMaxModes growth rates of a cluster's members, then status words, cluster_first and the open flag
+// (2 kMaxModes + 1 ints, in 2 kMaxModes doubles of room)
+constexpr size_t basis_rows_doubles(int N) { return 5 * (size_t)N; }
+constexpr size_t basis_ws_doubles(int N) { return basis_rows_doubles(N) + 4 * (size_t)kMaxModes; }
+struct ModesBasisArgs {
+  long n_sys; int N; double h;
+  const double *g, *c, *f, *gh; long ld; int n_modes;            // gh: null = mean of neighbouring g
+  double *lam, *gam, *X, *dX; int* cluster_first; int* info;      // X required, the others optional
+  double* work; size_t work_doubles; long n_waves;                // the launch refuses a workspace below min(n_sys, n_waves) waves
+};
+hipError_t launch_gcf_modes_basis(const ModesBasisArgs& a, hipStream_t st);
 // exact vector-Jacobian product of gam and lam in the (g, c, f) rows (ibs_vjp.hip), FP64, any N in [66, kMaxLongN]: one wave per
 // system, persistent grid of min(n_sys, n_waves) waves, each with vjp_ws_doubles(N) doubles of workspace at work + wave * vjp_ws_doubles(N)
 constexpr size_t vjp_ws_doubles(int N) { return 3 * (size_t)N; }

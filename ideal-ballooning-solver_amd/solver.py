@@ -31,6 +31,8 @@ EXACT_VJP_SHIFT = 16 + 6
 # spectrum mode (ibs_*_modes_f64): modes per system at most, and the informational status bit of a clustered mode (info >> 16)
 MAX_MODES = 16
 CLUSTER_BIT = 1 << 9
+# ibs_solve_gcf_modes_basis_f64: the mode's vector is a member of its cluster's Ritz basis; the cluster continues below the last mode
+BASIS_BIT, OPEN_CLUSTER_BIT = 1 << 13, 1 << 14
 # multi-start refinement (ibs_scan_peaks_f64): starts per surface at most
 MAX_STARTS = 16
 MAX_ROW_STARTS = 4      # ibs_theta0_polish_f64: start slots per line
@@ -360,12 +362,16 @@ class Context:
             raise IbsError("n_modes must be an integer in [1, %d], not %r" % (MAX_MODES, n_modes))
         return int(n_modes)
 
-    def solve_gcf_modes(self, h, g, c, f, n_modes, gh=None, want_X=False, want_info=False):
+    def solve_gcf_modes(self, h, g, c, f, n_modes, gh=None, want_X=False, want_info=False, basis=False):
         """the n_modes LARGEST eigenpairs of every system (ibs_solve_gcf_modes_f64), 1 <= n_modes <= 16: g, c, f (and gh, optional
         half-grid g as in solve_gcf): (n_sys, N).  Returns dict(lam, gam[, X, dX][, info], nbad): lam, gam, info (n_sys, n_modes),
         mode 0 = lam_max and the eigenvalues descending; X, dX (n_sys, n_modes, N), the entry of largest magnitude +1.  info
         status bit 9 (CLUSTER_BIT, per mode, informational): a neighbouring eigenvalue lies within 4 N eps ||A|| -- lam holds, the
-        vector is some vector of the cluster's invariant subspace and gam its quotient."""
+        vector is some vector of the cluster's invariant subspace and gam its quotient.
+        basis=True (ibs_solve_gcf_modes_basis_f64): the members of every cluster get an F-orthonormal Ritz basis of the cluster
+        (status bits BASIS_BIT, OPEN_CLUSTER_BIT; include/ibs.h); X and dX are always returned, and cluster_first (n_sys, n_modes)
+        int32, the first mode of every mode's cluster (its own index where it is in none).  Everything else as with basis=False, bit
+        for bit."""
         K = self._n_modes(n_modes)
         if len(g.shape) != 2:
             raise IbsError("solve_gcf_modes: g must be (n_sys, N), not %s" % (tuple(g.shape),))
@@ -374,6 +380,11 @@ class Context:
             if a is not None and tuple(a.shape) != (n_sys, N):
                 raise IbsError("solve_gcf_modes: %s must be (%d, %d) like g, not %s" % (name, n_sys, N, tuple(a.shape)))
         ar = _Args(self)
+        if basis:
+            rc = ar.call("ibs_solve_gcf_modes_basis_f64", n_sys, N, float(h), ar.inp(g), ar.inp(gh), ar.inp(c), ar.inp(f), N, K,
+                         ar.out("lam", (n_sys, K)), ar.out("gam", (n_sys, K)), ar.out("X", (n_sys, K, N)), ar.out("dX", (n_sys, K, N)),
+                         ar.out("cluster_first", (n_sys, K), _I32), ar.out("info", (n_sys, K), _I32, want_info))
+            return ar.result(rc)
         rc = ar.call("ibs_solve_gcf_modes_f64", n_sys, N, float(h), ar.inp(g), ar.inp(gh), ar.inp(c), ar.inp(f), N, K,
                      ar.out("lam", (n_sys, K)), ar.out("gam", (n_sys, K)), ar.out("X", (n_sys, K, N), want=want_X),
                      ar.out("dX", (n_sys, K, N), want=want_X), ar.out("info", (n_sys, K), _I32, want_info))

@@ -52,9 +52,13 @@
  *            SOME vector of the cluster's invariant subspace (it satisfies the pencil to the residual bound of ibs_solve_gcf_vjp_f64
  *            and is otherwise unspecified) and gam is that vector's quotient.  Informational: not counted by return values > 0.
  *            The derivative of one member of a cluster does not exist: do not hand such a pair to ibs_solve_gcf_vjp_f64.
+ *            ibs_solve_gcf_modes_basis_f64 gives the members of a cluster an F-orthonormal Ritz basis of it instead (bits 13, 14).
  *     bits 10-12, ibs_theta0_polish_f64 and ibs_marginal_theta0_polish_f64 only, per start slot, all informational (not counted by return values > 0): bit 10 = the
  *            coarse node itself was returned (no evaluated point beat it strictly); bit 11 = the search stopped at max_eval;
  *            bit 12 = one-sided bracket (the row ends at the node, or the neighbour on that side is NaN).
+ *     bits 13-14, ibs_solve_gcf_modes_basis_f64 only, per mode, both informational (not counted by return values > 0): bit 13 "basis" =
+ *            the mode's vector is a member of its cluster's F-orthonormal Ritz basis; bit 14 "open cluster" = the cluster continues
+ *            below the last mode asked for, so the basis spans a part of the cluster's invariant subspace.
  *   - idx (nearest-sigma entry points): the number of eigenvalues strictly above the returned one (0 = lam_max); -1 where the status
  *     reports invalid data.  Those entry points return the eigenpair the reference's eigs(A, 1, sigma=sigma0) returns (utils.py:1597)
  *     for every sigma, lam_max's among them; they never set bit 4.
@@ -207,6 +211,26 @@ int ibs_solve_gcf_nearest_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, 
 int ibs_solve_gcf_modes_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
                             const double* c, const double* f, int64_t ld, int32_t n_modes, double* lam, double* gam,
                             double* X, double* dX, int32_t* info, int32_t mem);
+/* The same with an F-orthonormal basis of every CLUSTER of modes (conventions above: bits 9, 13 and 14).  Arguments as
+ * ibs_solve_gcf_modes_f64, except: X is required (else IBS_ERR_ARG: the members' vectors are built in the caller's rows) and
+ * cluster_first [n_sys][n_modes] (int32, optional) receives the index of the first mode of every mode's cluster, the mode's own index
+ * where it is in none.  A cluster: consecutive modes whose closed eigenvalues lie less than tau = 4 N eps ||A|| apart, the last mode
+ * alone included where the first eigenvalue NOT asked for lies within tau of it.  Of the same input, lam of every mode, the pass
+ * count, status bits 0, 1 and 9 and every output of every mode outside the clusters are ibs_solve_gcf_modes_f64's, bit for bit.  The
+ * m <= 16 returned members of a cluster get m vectors of the cluster's invariant subspace (inverse iteration at each member's lam
+ * with Gram-Schmidt against the members before it, csrc/ibs_modes_basis.hpp) that are
+ *   - F-orthogonal: |<x^_i, x^_j>_F| <= 64 N eps, <x, y>_F = sum f_r x_r y_r over the interior rows, x^ = x / sqrt(<x, x>_F);
+ *   - Ritz vectors: |x^_i^T S x^_j| <= 64 N eps ||A|| for i != j, the Ritz values descending with the mode index (an m x m
+ *     Rayleigh-Ritz step: the choice is canonical wherever the splitting inside the cluster is resolvable);
+ *   - each an eigenvector of its lam to the residual bound of ibs_solve_gcf_vjp_f64; a cluster at most tau / 8 wide: within
+ *     max(1e-8, 64 eps ||A|| / gap_out) of the subspace, gap_out = the distance to the nearest eigenvalue outside the cluster;
+ *   - scaled so that the entry of largest magnitude is +1; dX and gam are the FD4 / Simpson derivative and quotient of that vector.
+ * Their modes carry status bit 13, those of an open cluster bit 14 too.  A member whose vector could not be completed gets bit 0
+ * (counted), its lam kept, gam and its X / dX rows NaN; the members found still meet the above.  Results are bitwise repeatable and
+ * independent of n_sys and of the system's place in the batch.  A batch without clusters costs what ibs_solve_gcf_modes_f64 costs. */
+int ibs_solve_gcf_modes_basis_f64(ibs_ctx* ctx, int64_t n_sys, int32_t N, double h, const double* g, const double* gh,
+                                  const double* c, const double* f, int64_t ld, int32_t n_modes, double* lam, double* gam,
+                                  double* X, double* dX, int32_t* cluster_first, int32_t* info, int32_t mem);
 /* Exact vector-Jacobian product of gam (the FD4 / Simpson quotient of utils.py:1601-1621) and of lam with respect to the rows
  * (g, c, f) of raw systems on a uniform grid, the half-grid g the mean of neighbouring g (the systems of ibs_solve_gcf_f64).  Nothing
  * upstream corresponds: its only derivatives are the Hellmann-Feynman formulas of obj_w_grad (utils.py:1666-1725), which put gam in
