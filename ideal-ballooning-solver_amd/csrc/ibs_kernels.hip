@@ -414,7 +414,8 @@ struct SrcDirectH {      // ... with a caller-supplied half-grid g (ibs_solve_gc
 // After WaveSolver::solve<true>: a solve whose closing bracket failed the consistency checks is closed again by division-form
 // multisection on the original rows `rows` (reclose_division: a few eps ||A||, independent of N).  flags (GcfArgs::flags,
 // ibs_set_option "reclose"): bit 0 = re-close, bit 1 = only mark (diagnostics); a suspect system carries the informational status
-// bit 3 either way.  Returns true when lam was replaced: the caller then repeats the eigenvector stage at it (redo_vector_at).
+// bit 3 either way.  Returns true when lam was replaced: the caller then re-stages what its eigenvector stage overwrote, sets a second
+// WaveSolver up, runs sweep(lam) / twisted(lam) and repeats its growth-rate stage (finish / finish_chunk) at it.
 template <typename T, int M, class Rows>
 __device__ __forceinline__ bool reclose_suspect(const WaveSolver<T, M>& ws, SolveInfo& inf, const Rows& rows, int N, T h, int flags,
                                                 T& lam) {
@@ -1964,31 +1965,22 @@ __global__ void __launch_bounds__(256) k_sturm_count(long n_sys, int N, T h, con
   if (valid && lane == 0) count_out[sys] = cnt;
 }
 
-// ---------------------------------------------------------------- launchers
-template <typename T>
-static hipError_t launch_gcf(const GcfArgs<T>& a, hipStream_t st) {
+// ---------------------------------------------------------------- launchers (launch_kernel: ibs_launch.hpp)
+// T = the solver's type, TI = the element type in memory: k_solve_gcf<T, M>, or, FP32 rows widened as they are staged, k_solve_gcf_wide<M>
+template <typename T, typename TI = T>
+static hipError_t launch_gcf(const GcfArgs<TI>& a, hipStream_t st) {
   const int wpb = a.wpb;
   const size_t lds = (size_t)wpb * 3 * lds_pitch(a.N) * sizeof(T);
   const long nblk = (a.n_sys + wpb - 1) / wpb;
-  auto kern = k_solve_gcf<T, IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
-                     a.lam, a.gam, a.X, a.dX, a.info, a.gh, a.flags);
-  note_launch(nblk, wpb * 64, "ibs::k_solve_gcf<%s, %d>", type_name<T>(), IBS_M);
-  return hipGetLastError();
-}
-static hipError_t launch_gcf_wide(const GcfArgs<float>& a, hipStream_t st) {
-  const int wpb = a.wpb;
-  const size_t lds = (size_t)wpb * 3 * lds_pitch(a.N) * sizeof(double);
-  const long nblk = (a.n_sys + wpb - 1) / wpb;
-  auto kern = k_solve_gcf_wide<IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
-                     a.lam, a.gam, a.X, a.dX, a.info, a.flags);
-  note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_wide<%d>", IBS_M);
-  return hipGetLastError();
+  if constexpr (std::is_same_v<T, TI>) {
+    return launch_kernel(k_solve_gcf<T, IBS_M>, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, [&] { note_launch(nblk, wpb * 64, "ibs::k_solve_gcf<%s, %d>", type_name<T>(), IBS_M); },
+                         a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
+                         a.lam, a.gam, a.X, a.dX, a.info, a.gh, a.flags);
+  } else {
+    return launch_kernel(k_solve_gcf_wide<IBS_M>, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, [&] { note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_wide<%d>", IBS_M); },
+                         a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
+                         a.lam, a.gam, a.X, a.dX, a.info, a.flags);
+  }
 }
 template <typename TI>
 static hipError_t launch_gcf_direct(const GcfArgs<TI>& a, hipStream_t st) {
@@ -2000,14 +1992,9 @@ static hipError_t launch_gcf_direct(const GcfArgs<TI>& a, hipStream_t st) {
     void (*kern)(long, int, double, const TI*, const TI*, const TI*, long, TI*, TI*, TI*, TI*, int*, int, int*, long*, double*);
     if constexpr (w2) kern = k_solve_gcf_direct_w2<double, IBS_M, TI>;      // (only the form that runs is instantiated)
     else kern = k_solve_gcf_direct<double, IBS_M, TI>;
-    if (lds) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, (double)a.h, a.g, a.c, a.f, a.ld,
-                       a.lam, a.gam, a.X, a.dX, a.info, a.flags, a.fix_count, a.fix_sys, a.fix_center);
-    note_launch(nblk, wpb * 64, w2 ? "ibs::k_solve_gcf_direct_w2<double, %d, %s>" : "ibs::k_solve_gcf_direct<double, %d, %s>", IBS_M, type_name<TI>());
-    return hipGetLastError();
+    return launch_kernel(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, [&] { note_launch(nblk, wpb * 64, w2 ? "ibs::k_solve_gcf_direct_w2<double, %d, %s>" : "ibs::k_solve_gcf_direct<double, %d, %s>", IBS_M, type_name<TI>()); },
+                         a.n_sys, a.N, (double)a.h, a.g, a.c, a.f, a.ld,
+                         a.lam, a.gam, a.X, a.dX, a.info, a.flags, a.fix_count, a.fix_sys, a.fix_center);
   } else {
     return hipErrorInvalidValue;
   }
@@ -2017,12 +2004,8 @@ template <typename TI>
 static hipError_t launch_gcf_fix(const GcfArgs<TI>& a, hipStream_t st) {
   const size_t lds = ((size_t)3 * (a.N - 2) + lds_pitch(a.N)) * sizeof(double);
   long nblk = a.n_sys < 128 ? a.n_sys : 128;          // (a few dozen suspects per million systems; an empty pass of 1,024 blocks cost 25 us)
-  auto kern = k_fix_gcf<IBS_M, TI>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64), lds, st, a.fix_count, a.fix_sys, a.fix_center, a.N, (double)a.h, a.g, a.c, a.f,
-                     a.ld, a.lam, a.gam, a.X, a.dX, a.info);
-  return hipGetLastError();
+  return launch_kernel(k_fix_gcf<IBS_M, TI>, dim3((unsigned)nblk), dim3(64), lds, st, [] {}, a.fix_count, a.fix_sys, a.fix_center, a.N, (double)a.h,
+                       a.g, a.c, a.f, a.ld, a.lam, a.gam, a.X, a.dX, a.info);
 }
 #ifdef IBS_WITH_F32
 // the occupancy cap pays where the allocator would otherwise take AGPRs (one wave per SIMD): checked per M in the resource table
@@ -2035,48 +2018,34 @@ static hipError_t launch_gcf_f32lam_direct(const GcfArgs<float>& a, hipStream_t 
     void (*kern)(long, int, float, const float*, const float*, const float*, long, float*, int*);
     if constexpr (w2) kern = k_solve_gcf_f32lam_direct_w2<IBS_M>;
     else kern = k_solve_gcf_f32lam_direct<IBS_M>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), 0, st, a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld, a.lam, a.info);
-    note_launch(nblk, wpb * 64, w2 ? "ibs::k_solve_gcf_f32lam_direct_w2<%d>" : "ibs::k_solve_gcf_f32lam_direct<%d>", IBS_M);
-    return hipGetLastError();
+    return launch_kernel(kern, dim3((unsigned)nblk), dim3(wpb * 64), 0, st, [&] { note_launch(nblk, wpb * 64, w2 ? "ibs::k_solve_gcf_f32lam_direct_w2<%d>" : "ibs::k_solve_gcf_f32lam_direct<%d>", IBS_M); },
+                         a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld, a.lam, a.info);
   } else {
     return hipErrorInvalidValue;
   }
 }
 #endif
-template <typename T>
-static hipError_t launch_gcf_rows(const GcfArgs<T>& a, hipStream_t st) {
+// T, TI as launch_gcf: k_solve_gcf_rows<T, M, TI>
+template <typename T, typename TI = T>
+static hipError_t launch_gcf_rows(const GcfArgs<TI>& a, hipStream_t st) {
   if constexpr (IBS_M >= 3) {
     const int wpb = a.wpb;
     const size_t lds = (size_t)wpb * lds_pitch(a.N) * sizeof(T);
     const long nblk = (a.n_sys + wpb - 1) / wpb;
-    auto kern = k_solve_gcf_rows<T, IBS_M>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
-                       a.lam, a.gam, a.X, a.dX, a.info, a.flags);
-    note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_rows<%s, %d, %s>", type_name<T>(), IBS_M, type_name<T>());
-    return hipGetLastError();
+    const auto note = [&] {
+      if constexpr (std::is_same_v<T, TI>) note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_rows<%s, %d, %s>", type_name<T>(), IBS_M, type_name<T>());
+      else note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_rows<double, %d, float>", IBS_M);
+    };
+    return launch_kernel(k_solve_gcf_rows<T, IBS_M, TI>, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, note, a.n_sys, a.N, (T)a.h, a.g, a.c, a.f,
+                         a.ld, a.lam, a.gam, a.X, a.dX, a.info, a.flags);
   } else {
     return hipErrorInvalidValue;
   }
 }
 #ifdef IBS_WITH_F32
-static hipError_t launch_gcf_rows_wide(const GcfArgs<float>& a, hipStream_t st) {
-  if constexpr (IBS_M >= 3) {
-    const int wpb = a.wpb;
-    const size_t lds = (size_t)wpb * lds_pitch(a.N) * sizeof(double);
-    const long nblk = (a.n_sys + wpb - 1) / wpb;
-    auto kern = k_solve_gcf_rows<double, IBS_M, float>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, (double)a.h, a.g, a.c, a.f, a.ld,
-                       a.lam, a.gam, a.X, a.dX, a.info, a.flags);
-    note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_rows<double, %d, float>", IBS_M);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
+// (dead device code below IBS_ROWS_MIN_M: the FP32-rows form was built for every M >= 3 before, where no table entry takes it, and is
+//  instantiated here only so that the library's kernels stay the same set; dropping it is a change of its own)
+template hipError_t launch_gcf_rows<double, float>(const GcfArgs<float>&, hipStream_t);
 #endif
 template <typename T>
 static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
@@ -2087,33 +2056,24 @@ static hipError_t launch_scan(const ScanArgs<T>& a, hipStream_t st) {
   const int nparts_1d = sg.flat ? (a.n_theta0 + wpb - 1) / wpb : 0;
   if constexpr (scan_resident_built(IBS_M)) {
     if (!a.resident) {
-      auto lean = k_gamma_scan_lean<T, IBS_M>;
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lean), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(lean, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
-                         a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
-                         a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
-                         a.t0_stride, nparts_1d);
-      note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan_lean<%s, %d>", type_name<T>(), IBS_M);
-      return hipGetLastError();
+      return launch_kernel(k_gamma_scan_lean<T, IBS_M>, grid, dim3(wpb * 64), lds, st, [&] { note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan_lean<%s, %d>", type_name<T>(), IBS_M); },
+                           a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
+                           a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
+                           a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
+                           a.t0_stride, nparts_1d);
     }
   }
-  auto kern = k_gamma_scan<T, IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
-                     a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
-                     a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
-                     a.t0_stride, a.ih2, a.ih, nparts_1d, scan_resident_built(IBS_M) ? a.trial_tab : nullptr);
-  note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan<%s, %d>", type_name<T>(), IBS_M);
-  return hipGetLastError();
+  return launch_kernel(k_gamma_scan<T, IBS_M>, grid, dim3(wpb * 64), lds, st, [&] { note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan<%s, %d>", type_name<T>(), IBS_M); },
+                       a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
+                       a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
+                       a.dX, a.dth0, a.info, a.lam_guess, a.guess_width, a.lines_per_surf, a.surf_counter, a.pack, a.pack_mode,
+                       a.t0_stride, a.ih2, a.ih, nparts_1d, scan_resident_built(IBS_M) ? a.trial_tab : nullptr);
 }
 // fills tab [kTrialTableLen] for grid length N (the resident form's rows per lane only)
 template <typename T>
 static hipError_t launch_trial_table(int N, T* tab, hipStream_t st) {
   if constexpr (scan_resident_built(IBS_M)) {
-    hipLaunchKernelGGL((k_trial_table<T, IBS_M>), dim3(1), dim3(kWave), 0, st, N, tab);
-    return hipGetLastError();
+    return launch_kernel(k_trial_table<T, IBS_M>, dim3(1), dim3(kWave), 0, st, [] {}, N, tab);
   } else {
     return hipErrorInvalidValue;
   }
@@ -2122,67 +2082,46 @@ template <typename T>
 static hipError_t launch_scan_chain(const ScanArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb, chain = a.chain;
   const size_t lds = (size_t)scan_lds_rows(wpb, 1, scan_chain_need_x(IBS_M, a.X || a.dX)) * lds_pitch(a.N) * sizeof(T);
-  auto kern = k_gamma_scan_chain<T, IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
   const int waves_per_line = (a.n_theta0 + chain - 1) / chain;
   const ScanGrid sg = scan_grid(a.n_lines, (waves_per_line + wpb - 1) / wpb);
   const dim3 grid(sg.x, sg.y, sg.z);
   const int nparts_1d = sg.flat ? (waves_per_line + wpb - 1) / wpb : 0;
-  hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
-                     a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
-                     a.dX, a.dth0, a.info, chain, a.chain_w1, a.chain_w2, nparts_1d);
-  note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan_chain<%s, %d>", type_name<T>(), IBS_M);
-  return hipGetLastError();
+  return launch_kernel(k_gamma_scan_chain<T, IBS_M>, grid, dim3(wpb * 64), lds, st, [&] { note_launch(sg.blocks(), wpb * 64, "ibs::k_gamma_scan_chain<%s, %d>", type_name<T>(), IBS_M); },
+                       a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
+                       a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
+                       a.dX, a.dth0, a.info, chain, a.chain_w1, a.chain_w2, nparts_1d);
 }
 template <typename T>
 static hipError_t launch_theta0_polish(const Theta0PolishArgs<T>& a, hipStream_t st) {
   const size_t lds = (size_t)theta0_polish_lds_rows(IBS_M, a.n_starts) * lds_pitch(a.N) * sizeof(T);
-  auto kern = k_theta0_polish<T, IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.n_lines), dim3(a.n_starts * 64), lds, st, a);
-  note_launch(a.n_lines, a.n_starts * 64, "ibs::k_theta0_polish<%s, %d>", type_name<T>(), IBS_M);
-  return hipGetLastError();
+  return launch_kernel(k_theta0_polish<T, IBS_M>, dim3((unsigned)a.n_lines), dim3(a.n_starts * 64), lds, st, [&] { note_launch(a.n_lines, a.n_starts * 64, "ibs::k_theta0_polish<%s, %d>", type_name<T>(), IBS_M); },
+                       a);
 }
 template <typename T>
 static hipError_t launch_sturm(const SturmArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb;
   const size_t lds = (size_t)wpb * a.N * sizeof(T);
   const long nblk = (a.n_sys + wpb - 1) / wpb;
-  auto kern = k_sturm_count<T, IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
-                     a.shift, a.count);
-  note_launch(nblk, wpb * 64, "ibs::k_sturm_count<%s, %d>", type_name<T>(), IBS_M);
-  return hipGetLastError();
+  return launch_kernel(k_sturm_count<T, IBS_M>, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, [&] { note_launch(nblk, wpb * 64, "ibs::k_sturm_count<%s, %d>", type_name<T>(), IBS_M); },
+                       a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
+                       a.shift, a.count);
 }
 
 template <typename T>
 static hipError_t launch_grad(const GradArgs<T>& a, hipStream_t st) {
   const int wpb = a.wpb;
   const size_t lds = (size_t)wpb * 8 * lds_pitch(a.N) * sizeof(T);
-  auto kern = k_obj_w_grad<T, IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((a.n_pts + wpb - 1) / wpb), dim3(wpb * 64), lds, st, a.n_pts, a.N, a.h, a.geo,
-                     a.arr_stride ? a.arr_stride : a.ld, a.line_stride ? a.line_stride : 8 * a.ld, a.theta0, a.del_alpha, a.val, a.jac, a.gam, a.dalpha, a.dth0, a.info);
-  note_launch((a.n_pts + wpb - 1) / wpb, wpb * 64, "ibs::k_obj_w_grad<%s, %d>", type_name<T>(), IBS_M);
-  return hipGetLastError();
+  return launch_kernel(k_obj_w_grad<T, IBS_M>, dim3((a.n_pts + wpb - 1) / wpb), dim3(wpb * 64), lds, st, [&] { note_launch((a.n_pts + wpb - 1) / wpb, wpb * 64, "ibs::k_obj_w_grad<%s, %d>", type_name<T>(), IBS_M); },
+                       a.n_pts, a.N, a.h, a.geo,
+                       a.arr_stride ? a.arr_stride : a.ld, a.line_stride ? a.line_stride : 8 * a.ld, a.theta0, a.del_alpha, a.val, a.jac, a.gam, a.dalpha, a.dth0, a.info);
 }
 
 template <typename T>
 static hipError_t launch_refine_eval(const RefineEvalArgs<T>& a, hipStream_t st) {
   const size_t lds = (size_t)(a.lds_tangent ? 12 : 8) * lds_pitch(a.N) * sizeof(T) + 32 * sizeof(T) + sizeof(RefineState) + sizeof(lbfgsb2::Work);
-  auto kern = k_refine_eval<T, IBS_M>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(a.n_c_max), dim3(256), lds, st, a);
-  note_launch(a.n_c_max, 256, "ibs::k_refine_eval<%s, %d>", type_name<T>(), IBS_M);
-  return hipGetLastError();
+  return launch_kernel(k_refine_eval<T, IBS_M>, dim3(a.n_c_max), dim3(256), lds, st, [&] { note_launch(a.n_c_max, 256, "ibs::k_refine_eval<%s, %d>", type_name<T>(), IBS_M); },
+                       a);
 }
-
 #define IBS_CAT2(a, b) a##b
 #define IBS_CAT(a, b) IBS_CAT2(a, b)
 struct IBS_CAT(Registrar, IBS_M) {
@@ -2195,7 +2134,7 @@ struct IBS_CAT(Registrar, IBS_M) {
     // more waves and is faster (N_zeta = 1024, M = 16: 198 VGPRs, two waves per SIMD, 3.7e7 against 3.0e7 solves/s)
     t.gcf_rows_f64[IBS_M] = &launch_gcf_rows<double>;
 #ifdef IBS_WITH_F32
-    t.gcf_f32w_rows[IBS_M] = &launch_gcf_rows_wide;
+    t.gcf_f32w_rows[IBS_M] = &launch_gcf_rows<double, float>;
 #endif
 #endif
 #if IBS_M >= IBS_DIRECT_MIN_M
@@ -2221,7 +2160,7 @@ struct IBS_CAT(Registrar, IBS_M) {
     t.refine_f64[IBS_M] = &launch_refine_eval<double>;
 #ifdef IBS_WITH_F32
     t.gcf_f32[IBS_M] = &launch_gcf<float>;
-    t.gcf_f32_wide[IBS_M] = &launch_gcf_wide;
+    t.gcf_f32_wide[IBS_M] = &launch_gcf<double, float>;
 #endif
   }
 };

@@ -336,13 +336,9 @@ static hipError_t launch_gcf_g(const GcfArgs<T>& a, hipStream_t st) {
   const size_t lds = (size_t)wpb * G * lds_pitch(a.N) * sizeof(T);
   const long nwaves = (a.n_sys + G - 1) / G;
   const long nblk = (nwaves + wpb - 1) / wpb;
-  auto kern = k_solve_gcf_g<T, IBS_M, IBS_P>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
-                     a.lam, a.gam, a.X, a.dX, a.info, a.flags, a.fix_count, a.fix_sys, a.fix_center);
-  note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_g<%s, %d, %d, %s>", type_name<T>(), IBS_M, IBS_P, type_name<T>());
-  return hipGetLastError();
+  return launch_kernel(k_solve_gcf_g<T, IBS_M, IBS_P>, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, [&] { note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_g<%s, %d, %d, %s>", type_name<T>(), IBS_M, IBS_P, type_name<T>()); },
+                       a.n_sys, a.N, a.h, a.g, a.c, a.f, a.ld,
+                       a.lam, a.gam, a.X, a.dX, a.info, a.flags, a.fix_count, a.fix_sys, a.fix_center);
 }
 #ifdef IBS_WITH_F32
 // FP32 in HBM, FP64 in the solver (the sub-wave sibling of k_solve_gcf_wide)
@@ -352,13 +348,9 @@ static hipError_t launch_gcf_g_wide(const GcfArgs<float>& a, hipStream_t st) {
   const size_t lds = (size_t)wpb * G * lds_pitch(a.N) * sizeof(double);
   const long nwaves = (a.n_sys + G - 1) / G;
   const long nblk = (nwaves + wpb - 1) / wpb;
-  auto kern = k_solve_gcf_g<double, IBS_M, IBS_P, float>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, a.n_sys, a.N, (double)a.h, a.g, a.c, a.f, a.ld,
-                     a.lam, a.gam, a.X, a.dX, a.info, a.flags, a.fix_count, a.fix_sys, a.fix_center);
-  note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_g<double, %d, %d, float>", IBS_M, IBS_P);
-  return hipGetLastError();
+  return launch_kernel(k_solve_gcf_g<double, IBS_M, IBS_P, float>, dim3((unsigned)nblk), dim3(wpb * 64), lds, st, [&] { note_launch(nblk, wpb * 64, "ibs::k_solve_gcf_g<double, %d, %d, float>", IBS_M, IBS_P); },
+                       a.n_sys, a.N, (double)a.h,
+                       a.g, a.c, a.f, a.ld, a.lam, a.gam, a.X, a.dX, a.info, a.flags, a.fix_count, a.fix_sys, a.fix_center);
 }
 #endif
 template <typename T>
@@ -366,16 +358,12 @@ static hipError_t launch_scan_g(const ScanArgs<T>& a, hipStream_t st) {
   constexpr int G = 64 / IBS_P;
   const int wpb = a.wpb;
   const size_t lds = (size_t)scan_lds_rows(wpb, G) * lds_pitch(a.N) * sizeof(T);
-  auto kern = k_gamma_scan_g<T, IBS_M, IBS_P>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
   const int per_blk = wpb * G;
   dim3 grid((unsigned)(((a.n_theta0 + per_blk - 1) / per_blk) * a.n_lines));
-  hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
-                     a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
-                     a.dX, a.dth0, a.info);
-  note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan_g<%s, %d, %d>", type_name<T>(), IBS_M, IBS_P);
-  return hipGetLastError();
+  return launch_kernel(k_gamma_scan_g<T, IBS_M, IBS_P>, grid, dim3(wpb * 64), lds, st, [&] { note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan_g<%s, %d, %d>", type_name<T>(), IBS_M, IBS_P); },
+                       a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
+                       a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
+                       a.dX, a.dth0, a.info);
 }
 
 template <typename T>
@@ -383,16 +371,12 @@ static hipError_t launch_scan_g_chain(const ScanArgs<T>& a, hipStream_t st) {
   constexpr int G = 64 / IBS_P;
   const int wpb = a.wpb, chain = a.chain < 1 ? 1 : a.chain;
   const size_t lds = (size_t)scan_lds_rows(wpb, G, a.X || a.dX) * lds_pitch(a.N) * sizeof(T);
-  auto kern = k_gamma_scan_g_chain<T, IBS_M, IBS_P>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
   const int per_blk = wpb * G * chain;
   dim3 grid((unsigned)(((a.n_theta0 + per_blk - 1) / per_blk) * a.n_lines));
-  hipLaunchKernelGGL(kern, grid, dim3(wpb * 64), lds, st, a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
-                     a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
-                     a.dX, a.dth0, a.info, chain, a.chain_w1, a.chain_w2, a.lam_guess, a.guess_width);
-  note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan_g_chain<%s, %d, %d>", type_name<T>(), IBS_M, IBS_P);
-  return hipGetLastError();
+  return launch_kernel(k_gamma_scan_g_chain<T, IBS_M, IBS_P>, grid, dim3(wpb * 64), lds, st, [&] { note_launch(grid.x, wpb * 64, "ibs::k_gamma_scan_g_chain<%s, %d, %d>", type_name<T>(), IBS_M, IBS_P); },
+                       a.n_lines, a.n_theta0, a.N, a.h, a.bmag, a.gradpar,
+                       a.cvdrift, a.cvdrift0, a.gds2, a.gds21, a.gds22, a.ld, a.dPdrho, a.theta0, a.gam, a.lam, a.X,
+                       a.dX, a.dth0, a.info, chain, a.chain_w1, a.chain_w2, a.lam_guess, a.guess_width);
 }
 
 #define IBS_CAT3_(a, b, c) a##b##_##c

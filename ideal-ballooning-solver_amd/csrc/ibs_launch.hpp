@@ -388,4 +388,17 @@ LaunchNote& last_launch();      // thread-local (ibs_api.hip)
 void note_launch(long blocks, int threads, const char* fmt, ...);
 template <typename T> constexpr const char* type_name() { return sizeof(T) == 8 ? "double" : "float"; }
 
+// One launch of the per-M launchers: the dynamic-LDS limit of `kern` raised to `lds` where any is asked for, the launch, `note()` (the
+// site's note_launch: only a launch that was issued is noted), the launch's error.
+template <class Note, class... KA, class... A>
+inline hipError_t launch_kernel(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Note&& note, const A&... args) {
+  if (lds) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  note();
+  return hipGetLastError();
+}
+
 }  // namespace ibs
