@@ -22,6 +22,7 @@
 #include "ibs_regrid.hpp"
 #include "ibs_scan_peaks.hpp"
 #include "ibs_theta0_polish.hpp"
+#include "ibs_local_eq.hpp"
 #include <chrono>
 #include <thread>
 
@@ -1236,6 +1237,59 @@ int ibs_marginal_obj_w_grad_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, 
     if (int r = with_wave_ws(ctx, a, a.n_pts, ibs::marginal_ws(N, true).total)) return r;
     HIPCHK(ibs::launch_marginal_tangent_points(a, ctx->stream));
     return 0;
+  });
+}
+
+// ---- local-equilibrium scan: shear and pressure variations of every line (ibs_local_eq.hip; the rule: ibs_local_eq.hpp).  Whole lines
+// chunk after chunk (for_line_chunks, a line's n_var variations standing where the theta0 values of a scan stand); a chunk's workspace
+// in ctx->long_ws = the per-wave workspace (ibs::local_eq_ws) of its persistent grid: long_waves() waves, and never more than
+// kLineChunkBudget admits, so that one line with many variations on a long grid stays within the budget as well
+int ibs_local_eq_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_var, int32_t N, double theta_lo, double h, const double* geo,
+                          int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps, int64_t ps_ld,
+                          const double* var, double shift, double* gam, double* lam, int32_t* count, int32_t* info, int flags) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!geo || !dPdrho || !centre || !sigma || !var)
+    return fail(IBS_ERR_ARG, "null argument (geo, dPdrho, centre, sigma and var are required)");
+  if (!gam && !lam && !count) return fail(IBS_ERR_ARG, "no output requested (gam, lam and count are all null)");
+  if (n_lines < 0 || n_var < 1 || ld < N || (ps && ps_ld < N))
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_var=%d ld=%lld ps_ld=%lld N=%d)", n_lines, n_var, (long long)ld, (long long)ps_ld, N);
+  if (flags != IBS_MEM_DEVICE && flags != IBS_MEM_HOST) return fail(IBS_ERR_ARG, "flags must be IBS_MEM_DEVICE or IBS_MEM_HOST, not %d", flags);
+  if (!std::isfinite(theta_lo) || (count && !std::isfinite(shift)))
+    return fail(IBS_ERR_ARG, "theta_lo and the shift of a requested count must be finite (theta_lo=%g shift=%g)", theta_lo, shift);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_lines == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n_sys = (size_t)n_lines * n_var, plane = (size_t)n_lines * (size_t)ld;
+  ibs::LocalEqArgs a{};                                    // the whole call; each chunk launches a copy with its lines
+  a.n_var = n_var; a.N = N; a.theta_lo = theta_lo; a.h = h; a.ld = (long)ld; a.plane = plane; a.ps_ld = (long)ps_ld; a.shift = shift;
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, 8 * plane); a.dPdrho = s.in(dPdrho, n_lines); a.centre = s.in(centre, n_lines); a.sigma = s.in(sigma, n_lines);
+    a.ps = s.in(ps, (size_t)n_lines * (size_t)ps_ld); a.var = s.in(var, 3 * (size_t)n_var);
+    a.gam = s.out(gam, n_sys); a.lam = s.out(lam, n_sys); a.count = s.out(count, n_sys);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, flags, decl, [&]() -> int {
+    const size_t per_wave = ibs::local_eq_ws(N).total;
+    const long wave_cap = (long)(ibs::kLineChunkBudget / (per_wave * sizeof(double)));      // (>= 340: a wave's workspace is at most 3 MB)
+    long nw = 0;
+    double* work = nullptr;
+    auto carve = [&](Carve& cv, long L) {                  // ctx->long_ws of a chunk of L lines
+      nw = long_waves(ctx, L * n_var);
+      if (nw > wave_cap) nw = wave_cap;
+      work = cv.take<double>((size_t)nw * per_wave);
+    };
+    return for_line_chunks(ctx, "local_eq_scan", n_lines, n_var, N, carve, [&](long l0, long Lc) -> int {
+      const long s0 = l0 * n_var;
+      ibs::LocalEqArgs c = a;
+      c.n_lines = (int)Lc;
+      c.geo = a.geo + l0 * ld; c.dPdrho = a.dPdrho + l0; c.centre = a.centre + l0; c.sigma = a.sigma + l0;
+      c.ps = a.ps ? a.ps + l0 * ps_ld : nullptr;
+      c.gam = a.gam ? a.gam + s0 : nullptr; c.lam = a.lam ? a.lam + s0 : nullptr; c.count = a.count ? a.count + s0 : nullptr;
+      c.info = a.info ? a.info + s0 : nullptr;
+      c.work = work; c.work_doubles = (size_t)nw * per_wave; c.n_waves = nw;
+      HIPCHK(ibs::launch_local_eq_scan(c, ctx->stream));
+      return 0;
+    });
   });
 }
 

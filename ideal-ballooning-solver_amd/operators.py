@@ -191,6 +191,26 @@ def dPdrho_of(cvdrift, gbdrift, bmag):
     return -1.0 * 0.5 * np.mean((cvdrift - gbdrift) * bmag ** 2)
 
 
+def local_eq_fold(theta, line8, dPdrho, centre, sigma, theta0, eps, p, ps=None):
+    """The rule of the local-equilibrium scan (csrc/ibs_local_eq.hpp, Context.local_eq_scan) in numpy: the line line8 = (bmag, gradpar,
+    cvdrift, cvdrift0, gds2, gds21, gds22, gbdrift) on the grid theta under a relative change eps of its surface's global shear and a
+    factor p on its pressure gradient, folded at theta0 (the ballooning angle of the varied equilibrium):
+        x     = theta0 (1 + eps) + sigma eps (theta - centre) + (p - 1) ps
+        cv'   = gbdrift + p (cvdrift - gbdrift) + x cvdrift0
+        gd'   = gds2 + 2 x gds21 + x^2 gds22
+        dP'   = p dPdrho
+    centre: the centre of the line's secular term (alpha for lines of Context.fieldline_geometry); sigma = sign(-phiedge) = +-1; ps:
+    the change of the integrated local shear per unit of (p - 1), in units of the fold variable (None: 0, frozen local shear; the
+    s-alpha model's row is -alpha0 (sin theta - sin theta0) / shat0).  eps = 0, p = 1, ps = None is the theta0 fold of
+    ball_scan.py:267-268.  Returns (dP', cv', gd'), ready for gamma_ball_full(dP', theta, bmag, gradpar, cv', gd')."""
+    theta = np.asarray(theta, dtype=np.float64)
+    cv, cv0, gds2, gds21, gds22, gb = (np.asarray(line8[k], dtype=np.float64) for k in (2, 3, 4, 5, 6, 7))
+    x = theta0 * (1.0 + eps) + sigma * eps * (theta - centre)
+    if ps is not None:
+        x = x + (p - 1.0) * np.asarray(ps, dtype=np.float64)
+    return p * dPdrho, gb + p * (cv - gb) + x * cv0, gds2 + 2 * x * gds21 + x * x * gds22
+
+
 def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004, eigenpair="max", jac="reference"):
     """Factory for a drop-in `obj_w_grad(x0, vs, rho_val, theta, vguess00, sigma00=0.42)` (utils.py:1632).
 

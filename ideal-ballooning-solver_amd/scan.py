@@ -474,6 +474,45 @@ class BallooningScan:
         cnt = self.ctx.geo_sturm_count(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan, shift)
         return np.asarray(cnt).reshape(len(self.own), na, nt)
 
+    # -- the s-alpha picture of the owned surfaces: shear and pressure variations of every line of the alpha grid, two launches
+    def local_eq(self, eps, p, theta0=None, shift=0.0, count_only=False):
+        """gam, lam_max and the number of eigenvalues above `shift` of every line of the alpha grid of every owned surface under the
+        relative changes eps (n_eps,) of the surface's global shear and the factors p (n_p,) on its pressure gradient, folded at
+        theta0 (n_theta0,; default: the coarse theta0 grid), by the rule of operators.local_eq_fold with centre = alpha, sigma =
+        sign(-phiedge) of the tables and no ps row -- the geometry re-evaluated with d_iota_d_s (1 + eps) and d_pressure_d_s p, at
+        frozen local shear on the pressure axis.  Resident path only (tables= and device=, else ValueError): ONE geometry launch and
+        ONE Context.local_eq_scan call.  Returns numpy dict(gam, lam, count (n_own, nalpha, n_theta0, n_eps, n_p), gam_max, unstable
+        (n_own, n_eps, n_p) = the envelope over (alpha, theta0): the largest gam and "some line has an eigenvalue above shift";
+        theta0, eps, p).  count_only=True: count and unstable alone, no eigenvalue is computed.  Flagged solves raise IbsError."""
+        if self.tables is None or self.device is None:
+            raise ValueError("local_eq() runs on the resident path: tables= and device= are required")
+        eps = np.atleast_1d(np.asarray(eps, dtype=np.float64))
+        p = np.atleast_1d(np.asarray(p, dtype=np.float64))
+        t0 = self.theta0_scan if theta0 is None else np.atleast_1d(np.asarray(theta0, dtype=np.float64))
+        na, n = len(self.alpha_scan), len(self.own)
+        shape = (n, na, len(t0), len(eps), len(p))
+        var = np.stack([a.ravel() for a in np.meshgrid(t0, eps, p, indexing="ij")], axis=1)
+        keys = ("count",) if count_only else ("gam", "lam", "count")
+        res = dict(theta0=t0, eps=eps, p=p)
+        if n:
+            surf = np.repeat(self._own_surf(), na)
+            alpha = np.tile(self.alpha_scan, n)
+            r = self.ctx.fieldline_geometry(self.tables, surf, alpha, self.theta, device=self.device)
+            sigma = np.sign(-np.asarray(self.tables.scal)[surf, 4])
+            out = self.ctx.local_eq_scan(self.theta[0], self.h, r["geo"], r["dPdrho"], alpha, sigma, var, shift=shift,
+                                         count_only=count_only, want_info=True)
+            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())
+            if nbad:
+                raise IbsError("%d of %d local-equilibrium solves were flagged (status bits 0-1: iteration cap or invalid data)"
+                               % (nbad, out["info"].numel()))
+            res.update({k: out[k].cpu().numpy().reshape(shape) for k in keys})
+        else:
+            res.update({k: np.zeros(shape, dtype=np.int32 if k == "count" else np.float64) for k in keys})
+        res["unstable"] = (res["count"] > 0).any(axis=(1, 2))
+        if not count_only:
+            res["gam_max"] = res["gam"].max(axis=(1, 2))
+        return res
+
     # -- every line's growth rate maximised over theta0 between the nodes of the coarse grid, two launches
     def envelope(self, n_starts=1, xtol=1e-5, max_eval=32):
         """gam_env(alpha) = max over theta0 of gam(alpha, theta0) of every line of the coarse grid: the coarse scan, then

@@ -457,6 +457,32 @@ class Context:
                      ar.out("n_eval", slots, _I32), ar.out("info", slots, _I32, want_info), ar.out("n_found", (shape[0],), _I32, want_found))
         return ar.result(rc)
 
+    # ---- local-equilibrium scan -------------------------------------------------------------
+    def local_eq_scan(self, theta_lo, h, geo, dPdrho, centre, sigma, var, ps=None, shift=0.0, count_only=False, want_info=False):
+        """gam, lam_max and the number of eigenvalues above `shift` of every line under the variations var of its surface's shear and
+        pressure gradient (ibs_local_eq_scan_f64; the rule: operators.local_eq_fold).  geo (8, n_lines, N): fieldline_geometry's
+        output on the uniform grid theta_lo + j h; dPdrho, centre (= alpha of such lines), sigma (= sign(-phiedge), +-1) (n_lines,);
+        var (n_var, 3) = (theta0, eps, p); ps (n_lines, N), optional.  The memory kind is geo's; the small arrays may be numpy either
+        way.  count_only=True: the count alone, no eigenvalue is computed (the stable / unstable diagram).
+        Returns dict([gam, lam, ]count int32[, info int32], nbad) shaped (n_lines, n_var).  A line with non-finite data, a sigma
+        that is not +-1 or a non-finite triple gives status 2, NaN gam and lam and count -1 on those systems alone."""
+        eight, n_lines, N = geo.shape
+        if eight != 8:
+            raise IbsError("geo must be (8, n_lines, N)")
+        n_var = int(var.shape[0])
+        if tuple(var.shape) != (n_var, 3):
+            raise IbsError("var must be (n_var, 3) = (theta0, eps, p)")
+        if ps is not None and tuple(ps.shape) != (n_lines, N):
+            raise IbsError("ps must be (n_lines, N) = %s, not %s" % ((n_lines, N), tuple(ps.shape)))
+        ar = _Args(self)
+        shape = (n_lines, n_var)
+        pgeo = ar.inp(geo)
+        rc = ar.call("ibs_local_eq_scan_f64", n_lines, n_var, N, float(theta_lo), float(h), pgeo, N, ar.inp(dPdrho, upload=True),
+                     ar.inp(centre, upload=True), ar.inp(sigma, upload=True), ar.inp(ps, upload=True), N, ar.inp(var, upload=True),
+                     float(shift), ar.out("gam", shape, want=not count_only), ar.out("lam", shape, want=not count_only),
+                     ar.out("count", shape, _I32), ar.out("info", shape, _I32, want_info))
+        return ar.result(rc)
+
     @staticmethod
     def _three_lines(geo):
         n_pts, three, eight, N = geo.shape

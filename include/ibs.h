@@ -414,6 +414,41 @@ int ibs_marginal_obj_w_grad_tangent_f64(ibs_ctx* ctx, int32_t n_pts, int32_t N, 
                                         int64_t ld, const double* theta0, double* val, double* jac, double* scale, double* dscale,
                                         double* dPdrho, double* geo_bar, int32_t* info, int32_t mem);
 
+/* Local-equilibrium scan: the s-alpha picture of a real field line -- gam, lam_max and the number of eigenvalues above `shift` of every
+ * line under variations of its surface's global shear and pressure gradient about the equilibrium, from the line's eight arrays alone
+ * (no geometry launch per shear value).  Nothing upstream corresponds for a real line: bishop_ball_s-alpha.py does the analytic
+ * shifted-circle model only.  THE RULE (csrc/ibs_local_eq.hpp; numpy: ibs_amd.operators.local_eq_fold), per line and variation v =
+ * (theta0, eps, p), eps = the relative change of the shear, p = the factor on the pressure gradient, theta_j = theta_lo + j h:
+ *     x_j   = theta0 (1 + eps) + sigma eps (theta_j - centre) + (p - 1) ps_j
+ *     cv'_j = gbdrift_j + p (cvdrift_j - gbdrift_j) + x_j cvdrift0_j
+ *     gd'_j = gds2_j + 2 x_j gds21_j + x_j^2 gds22_j
+ *     dP'   = p dPdrho
+ *     g = |gradpar| gd' / bmag,  c = -dP' cv' / (|gradpar| bmag),  f = gd' / bmag^2 / (|gradpar| bmag)          (utils.py:1560-1562)
+ * then the operator of every other entry point: half-grid g = mean of neighbours, lam_max of (T, F), gam by the FD4 + Simpson quotient
+ * (utils.py:1574-1621).  eps = 0, p = 1, ps = NULL: the fold of ibs_gamma_scan_f64.  ps = NULL, centre = alpha: the geometry
+ * re-evaluated with d_iota_d_s (1 + eps) and d_pressure_d_s p (scal columns 2, 3 of ibs_fieldline_geometry_f64) and folded at theta0,
+ * the ballooning angle of the varied equilibrium -- a frozen-local-shear variation on the pressure axis (the caveat of
+ * ibs_marginal_scan_f64).  ps: the change of the integrated local shear per unit of (p - 1), in units of the fold variable, from a
+ * local-equilibrium code; the s-alpha model's row is -alpha0 (sin theta - sin theta0) / shat0.  eps is relative to the surface's own
+ * shear: on a surface with shat -> 0 the shear axis degenerates (gds21, gds22, cvdrift0 vanish).
+ *   geo [8][n_lines][ld]: bmag gradpar cvdrift cvdrift0 gds2 gds21 gds22 gbdrift, as ibs_fieldline_geometry_f64 writes them;
+ *   dPdrho, centre (= alpha for lines of ibs_fieldline_geometry_f64), sigma (= sign(-phiedge), +1 or -1) [n_lines];
+ *   ps [n_lines][ps_ld >= N] or NULL (= 0); var [n_var][3] = (theta0, eps, p); shift: a HOST scalar, finite if count is given;
+ *   gam, lam, count, info [n_lines][n_var]; gam, lam and count may each be NULL, not all three (IBS_ERR_ARG).  count alone: no
+ *   eigenvalue is computed -- the stable / unstable diagram at one pass over the rows per system;
+ *   info: bits 0-15 = multisection passes, status bits 0 (iteration cap), 1 (a line with non-finite data or g, f <= 0, sigma not +-1,
+ *   a non-finite triple: NaN gam and lam, count -1, of those systems only);
+ *   flags: IBS_MEM_DEVICE or IBS_MEM_HOST, the `mem` of the other entry points (anything else: IBS_ERR_ARG).
+ * FP64, uniform grids, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED); a NULL required argument, ld < N, ps_ld < N,
+ * n_var < 1: IBS_ERR_ARG; all of these run before the context is touched.  One wavefront per (line, variation) forms the rows and
+ * solves them in division form in one kernel (k_local_eq_scan, csrc/ibs_local_eq.hip).  No atomics: a system's outputs depend on its
+ * line and its triple alone, bit for bit -- not on the batch, the order of the lines or the chunks of whole lines the call is worked
+ * through in when its workspace would exceed the budget (option "nearest_chunk_systems" sets the chunk). */
+int ibs_local_eq_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_var, int32_t N, double theta_lo, double h, const double* geo,
+                          int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps,
+                          int64_t ps_ld, const double* var, double shift, double* gam, double* lam, int32_t* count, int32_t* info,
+                          int flags);
+
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
  * and utils.py:1556-1624; with dgam_dtheta0 also utils.py:1666-1680 (Hellmann-Feynman d/dtheta0).
