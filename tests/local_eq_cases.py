@@ -19,6 +19,33 @@ def salpha_base_line(th, theta0, shat0=1.0, alpha0=0.5):
     return line, -1.0, -alpha0 * (np.sin(th) - np.sin(theta0)) / shat0
 
 
+def persistent_waves():
+    """the persistent grid of the long path on device 0: long_waves() of csrc/ibs_api.hip, 8 waves per CU"""
+    import torch
+    return 8 * torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def assert_wave_reuse(ctx, kernel, n_sys, at_most=None):
+    """the launch before this call was `kernel` on fewer blocks than systems (a wave served more than one); returns the blocks"""
+    name, blocks = ctx.last_launch()
+    print("%s: %d blocks for %d systems" % (name, blocks, n_sys))
+    assert kernel in name and 0 < blocks < n_sys and (at_most is None or blocks <= at_most), (name, blocks, n_sys, at_most)
+    return blocks
+
+
+def wave_reuse_batch(waves, factor=1.3):
+    """three s-alpha lines at N = 67 (theta0 = 0, 0.1, -0.3, with their ps rows) x the product of 9 theta0, 10 eps and at least 10 p:
+    2,700 systems, the p axis lengthened until the batch holds `factor` x `waves` systems.  dict(th, lines, dP, centre, sigma, ps, var)"""
+    import itertools
+    th = bo.theta_grid(67)
+    t0s = (0.0, 0.1, -0.3)
+    base = [salpha_base_line(th, t0) for t0 in t0s]
+    n_p = max(10, -(-int(np.ceil(factor * waves)) // (3 * 90)))
+    var = np.array(list(itertools.product(np.linspace(-0.4, 0.4, 9), np.linspace(-0.9, 1.0, 10), np.linspace(0.0, 3.0, n_p))))
+    return dict(th=th, lines=np.stack([b[0] for b in base]), dP=np.array([b[1] for b in base]), centre=np.array(t0s),
+                sigma=np.ones(3), ps=np.stack([b[2] for b in base]), var=var)
+
+
 def to_geo(lines):
     """(n_lines, 8, N) -> the (8, n_lines, N) layout of Context.fieldline_geometry"""
     return np.ascontiguousarray(np.transpose(np.asarray(lines, dtype=np.float64), (1, 0, 2)))

@@ -73,6 +73,14 @@ def assert_tight(groups, tau):
         assert gr["width"] <= tau / 8 and gr["gap_out"] >= 2 * tau, (gr, tau)
 
 
+def tight_clusters(th, g, c, f, K):
+    """[(first, last)] of the reference clusters of two or more modes that touch modes 0 .. K-1 and are at most tau / 8 wide and at
+    least 2 tau from the rest of the spectrum"""
+    ref, groups = reference_clusters(th, g, c, f, K)
+    return [(gr["first"], gr["last"]) for gr in groups
+            if gr["last"] > gr["first"] and gr["width"] <= ref["tau"] / 8 and gr["gap_out"] >= 2 * ref["tau"]]
+
+
 def subspace_of(th, g, c, f, first, last):
     """F-orthonormal reference basis (n, last - first + 1) of modes first .. last of the whole spectrum"""
     from scipy.linalg import eigh_tridiagonal

@@ -3,7 +3,11 @@ the rule in numpy (ibs_amd.operators.local_eq_fold) + the CPU oracles (tests/loc
 
 Tolerances, the project's own: |gam - gam_oracle| <= 1e-8; |lam - lam_oracle| <= 4 N eps ||A||; counts exact, every count compared at a
 fixed shift on a system with |lam_max - shift| > 16 N^2 eps ||A|| (asserted on the oracle side).  The counts at lam_oracle +- 8 N eps ||A||
-are the count-pair certificate of the eigenvalue: 0 above, at least 1 below -- what the lam tolerance itself implies."""
+are the count-pair certificate of the eigenvalue: 0 above, at least 1 below -- what the lam tolerance itself implies.
+
+Tests 9-12 run the kernel where a wave serves more than one system (the persistent grid of 8 waves per CU: the batch is sized from the
+device's CU count, and Context.last_launch must report fewer blocks than systems), on padded rows through the raw entry point, on the
+branches of the rule and under the wave cap of the workspace budget."""
 import itertools
 import os
 
@@ -250,3 +254,152 @@ def test_scan_driver_local_eq_on_ncsx_tables(ctx):
     assert "gam" not in rc and np.array_equal(rc["count"], r["count"]) and np.array_equal(rc["unstable"], r["unstable"])
     with pytest.raises(ValueError):
         ibs_amd.BallooningScan(ctx, None, th, svals, nalpha=4, ntheta0=3, tables=tabs).local_eq(eps, p)
+
+
+# ---- the persistent grid: more systems than waves, faults on a reused wave, padded rows, the rule's branches, the wave cap
+@pytest.fixture(scope="module")
+def reuse(ctx):
+    """9. the batch of tests/local_eq_cases.wave_reuse_batch (2,700 systems at N = 67 on a grid of 8 waves per CU) and its clean run,
+    shared by the three tests below"""
+    b = lc.wave_reuse_batch(lc.persistent_waves())
+    args = (b["th"][0], b["th"][1] - b["th"][0], lc.to_geo(b["lines"]), b["dP"], b["centre"], b["sigma"], b["var"])
+    r = ctx.local_eq_scan(*args, ps=b["ps"], shift=0.0, want_info=True)
+    lc.assert_wave_reuse(ctx, "k_local_eq_scan", r["gam"].size)
+    assert r["gam"].size >= 1.3 * lc.persistent_waves()
+    return b, args, r
+
+
+def test_more_systems_than_waves_against_the_oracle(ctx, reuse):
+    """9a. every system of the batch against the oracle: gam, lam, the count at shift 0.  Measured on the CPU side: every oracle value
+    finite, min |lam| / margin 2.6e5, 42 % of the systems unstable"""
+    b, args, r = reuse
+    g, c, f = lc.rows_of(b["th"], b["lines"], b["dP"], b["centre"], b["sigma"], b["var"], ps=b["ps"])
+    ref = lc.oracle_of(b["th"], g, c, f)
+    assert np.isfinite(ref["gam"]).all() and np.isfinite(ref["lam"]).all()
+    count0 = lc.counts_of(b["th"], g, c, f, 0.0)
+    print("wave reuse N=67: %d systems, %.0f %% unstable" % (count0.size, 100.0 * (count0 > 0).mean()))
+    assert 0.2 < (count0 > 0).mean() < 0.8                   # (both branches of the growth-rate stage are well populated)
+    check_against_oracle(r, ref, "wave reuse N=67, %d systems" % count0.size, count0)
+
+
+def test_faults_between_clean_systems_on_one_wave(ctx, reuse):
+    """9b. eps = NaN in every 7th triple, sigma = 0.5 on line 1, one NaN in gds21 of line 2: status 2, NaN gam and lam, count -1 on exactly
+    those systems, every other system bitwise the clean run's.  With the lines in this order a wave's second system is one of line 2, so
+    a fault follows a clean system on every reused wave; the same batch with the lines reversed puts the clean line last, where clean
+    systems follow the faults.  count_only on the clean batch: the clean run's counts, no pass counted"""
+    b, args, clean = reuse
+    lo, h, geo, dP, centre, sigma, var = args
+    n_var = len(var)
+    bad_lines, bad_sigma, bad_var = b["lines"].copy(), sigma.copy(), var.copy()
+    bad_var[::7, 1] = np.nan
+    bad_sigma[1] = 0.5
+    bad_lines[2, 5, 40] = np.nan
+    hit = np.zeros((3, n_var), dtype=bool)
+    hit[1] = hit[2] = hit[:, ::7] = True
+    for order in ([0, 1, 2], [2, 1, 0]):
+        r = ctx.local_eq_scan(lo, h, lc.to_geo(bad_lines[order]), dP[order], centre[order], bad_sigma[order], bad_var, ps=b["ps"][order],
+                              shift=0.0, want_info=True)
+        lc.assert_wave_reuse(ctx, "k_local_eq_scan", hit.size)
+        r = {k: (v[np.argsort(order)] if k != "nbad" else v) for k, v in r.items()}
+        assert r["nbad"] == hit.sum(), (order, r["nbad"], hit.sum())
+        assert (status(r)[hit] == 2).all() and (status(r)[~hit] == 0).all()
+        assert np.isnan(r["gam"][hit]).all() and np.isnan(r["lam"][hit]).all() and (r["count"][hit] == -1).all()
+        for k in KEYS:
+            assert np.array_equal(r[k][~hit], clean[k][~hit]), (order, k)
+    rc = ctx.local_eq_scan(*args, ps=b["ps"], shift=0.0, count_only=True, want_info=True)
+    lc.assert_wave_reuse(ctx, "k_local_eq_scan", hit.size)
+    assert set(rc) == {"count", "info", "nbad"} and rc["nbad"] == 0
+    assert np.array_equal(rc["count"], clean["count"]) and not rc["info"].any()
+
+
+def raw_local_eq(ctx, n_lines, n_var, N, lo, h, geo, ld, dP, centre, sigma, ps, ps_ld, var, shift, device, want_gam=True):
+    """ibs_local_eq_scan_f64 itself on the caller's leading dimensions, host pointers or device pointers -> (return value, outputs)"""
+    import ctypes
+    import torch
+    shape = (n_lines, n_var)
+    ins = [np.ascontiguousarray(a, dtype=np.float64) for a in (geo, dP, centre, sigma, ps, var)]
+    out = dict(gam=np.zeros(shape), lam=np.zeros(shape), count=np.zeros(shape, np.int32), info=np.zeros(shape, np.int32))
+    if device:
+        ctx._stream_from_torch(torch.device("cuda:0"))
+        ins = [torch.from_numpy(a).to("cuda:0") for a in ins]
+        out = {k: torch.from_numpy(v).to("cuda:0") for k, v in out.items()}
+        p = lambda a: ctypes.c_void_p(a.data_ptr())
+    else:
+        p = lambda a: ctypes.c_void_p(a.ctypes.data)
+    rc = ctx._lib.ibs_local_eq_scan_f64(ctx._h, n_lines, n_var, N, float(lo), float(h), p(ins[0]), ld, p(ins[1]), p(ins[2]), p(ins[3]),
+                                        p(ins[4]), ps_ld, p(ins[5]), float(shift), p(out["gam"]) if want_gam else None, p(out["lam"]),
+                                        p(out["count"]), p(out["info"]), 0 if device else 1)
+    if device:
+        torch.cuda.synchronize()
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+    return rc, out
+
+
+def test_padded_rows_through_the_raw_entry(ctx, g3):
+    """10. ld = N + 5 and ps_ld = N + 3 with NaN in every padding element, 3 NCSX lines x 6 triples at N = 513: the four outputs are
+    Context.local_eq_scan's bits on the packed arrays, from host pointers and from device pointers; gam = NULL changes neither lam nor info"""
+    th, lines, dP, alpha, sigma, ps, var = ncsx_batch(g3, 3)
+    N, lo, h, geo = 513, th[0], th[1] - th[0], lc.to_geo(lines)
+    packed = ctx.local_eq_scan(lo, h, geo, dP, alpha, sigma, var, ps=ps, shift=0.0, want_info=True)
+    assert packed["nbad"] == 0 and np.isfinite(packed["gam"]).all()
+    geo_p, ps_p = np.full((8, 3, N + 5), np.nan), np.full((3, N + 3), np.nan)
+    geo_p[:, :, :N], ps_p[:, :N] = geo, ps
+    for device in (False, True):
+        rc, r = raw_local_eq(ctx, 3, len(var), N, lo, h, geo_p, N + 5, dP, alpha, sigma, ps_p, N + 3, var, 0.0, device)
+        assert "k_local_eq_scan" in ctx.last_launch()[0]
+        assert rc == 0 and not (r["info"] >> 16).any(), (device, rc)
+        for k in KEYS:
+            assert np.array_equal(r[k], packed[k]), (device, k)
+        rc, r = raw_local_eq(ctx, 3, len(var), N, lo, h, geo_p, N + 5, dP, alpha, sigma, ps_p, N + 3, var, 0.0, device, want_gam=False)
+        assert rc == 0 and not r["gam"].any()                # (not written)
+        for k in ("lam", "count", "info"):
+            assert np.array_equal(r[k], packed[k]), (device, k)
+
+
+def test_the_rule_takes_the_magnitude_of_gradpar(ctx, g3):
+    """11a. the lines of test 10 with gradpar negated on lines 0 and 2: the same bits"""
+    th, lines, dP, alpha, sigma, ps, var = ncsx_batch(g3, 3)
+    lo, h = th[0], th[1] - th[0]
+    r = ctx.local_eq_scan(lo, h, lc.to_geo(lines), dP, alpha, sigma, var, ps=ps, shift=0.0, want_info=True)
+    flipped = lines.copy()
+    flipped[[0, 2], 1] *= -1.0
+    assert (flipped[0, 1] < 0).all() and (flipped[1, 1] > 0).all()
+    rf = ctx.local_eq_scan(lo, h, lc.to_geo(flipped), dP, alpha, sigma, var, ps=ps, shift=0.0, want_info=True)
+    assert r["nbad"] == rf["nbad"] == 0
+    for k in KEYS:
+        assert np.array_equal(rf[k], r[k]), k
+
+
+def test_off_centre_theta_window(ctx):
+    """11b. theta_lo = -3 pi + 0.37, N = 771, h = 6 pi / 770: one s-alpha line built on that grid with centre 0.25 x the five triples of
+    EDGE_VAR against the oracle on theta_lo + j h, counts at shift 0"""
+    N, lo, h = 771, -3 * np.pi + 0.37, 6 * np.pi / 770
+    th = lo + h * np.arange(N)
+    assert abs(th[0] + th[-1]) > 0.7                         # (not symmetric about 0)
+    line, dP, ps = lc.salpha_base_line(th, 0.25)
+    args = ([line], np.array([dP]), np.array([0.25]), np.ones(1), EDGE_VAR)
+    g, c, f = lc.rows_of(th, *args, ps=ps[None])
+    r = ctx.local_eq_scan(lo, h, lc.to_geo(args[0]), *args[1:], ps=ps[None], shift=0.0, want_info=True)
+    check_against_oracle(r, lc.oracle_of(th, g, c, f), "s-alpha off-centre window N=771", lc.counts_of(th, g, c, f, 0.0))
+
+
+def test_wave_cap_on_the_longest_grid(ctx):
+    """12. N = 65,537, one s-alpha line x 400 triples (theta0 = 0.1, eps x p on 20 x 20), count_only: the workspace budget of a chunk
+    caps the grid at 2^30 / (6 N 8 bytes) = 341 waves, below the 400 systems; the counts are those of two calls with 200 triples each,
+    bit for bit.  (No count is compared with the oracle at this length: test 5.)"""
+    import time
+    N = 65537
+    th = bo.theta_grid(N)
+    line, dP, ps = lc.salpha_base_line(th, 0.1)
+    var = np.array([(0.1, e, p) for e in np.linspace(-0.9, 1.0, 20) for p in np.linspace(0.0, 3.0, 20)])
+    args = (th[0], th[1] - th[0], lc.to_geo([line]), np.array([dP]), np.array([0.1]), np.ones(1))
+    kw = dict(ps=ps[None], shift=0.0, count_only=True, want_info=True)
+    ctx.synchronize()
+    t = time.perf_counter()
+    r = ctx.local_eq_scan(*args, var, **kw)
+    dt = time.perf_counter() - t
+    blocks = lc.assert_wave_reuse(ctx, "k_local_eq_scan", 400, at_most=2 ** 30 // (6 * N * 8))
+    print("wave cap N=65537: 400 systems on %d blocks, %.3f s (host pointers, the call)" % (blocks, dt))
+    assert r["nbad"] == 0 and not r["info"].any() and (r["count"] >= 0).all()
+    halves = [ctx.local_eq_scan(*args, var[k:k + 200], **kw) for k in (0, 200)]
+    assert np.array_equal(np.concatenate([q["count"] for q in halves], axis=1), r["count"])

@@ -2,7 +2,7 @@
 order against ibs_amd.row_peaks on the device's own table of mu, s* against the CPU oracle at the device's own theta0* (4 u, u from
 marginal_oracle.solve: tests/test_gpu_marginal.py's bound), theta0* against the oracle-driven host state machine (8 xtol), scale_star
 bitwise against ibs_marginal_scan_f64 at theta0*, the incumbent rule on the edge cases, the bitwise invariances of one call, the status
-words; and the drivers (BallooningScan.marginal_envelope, marginal(n_starts=K | theta0_polish=True), AdjointStep.marginal) on the NCSX
+words, a batch of more slots than the persistent grid has waves; and the drivers (BallooningScan.marginal_envelope, marginal(n_starts=K | theta0_polish=True), AdjointStep.marginal) on the NCSX
 tables of tests/golden/G8_*."""
 import os
 
@@ -196,6 +196,49 @@ def test_status_words(ctx):
     assert "(-1)" in str(e.value)
     rb = polish(ctx, N, nt, t0=bad)
     assert np.isnan(rb["theta0"]).all() and np.isnan(rb["mu"]).all() and np.isnan(rb["scale"]).all() and ((rb["info"] >> 16) == 2).all()
+
+
+def test_more_slots_than_waves(ctx):
+    """N = 67, the six case lines with their coarse rows on 15 nodes, K = 3, tiled until the slots number 1.3 times the persistent grid (8
+    waves per CU): every wave rebuilds G and C in its workspace for every evaluation of every slot it serves.  Every 5th line has a NaN in
+    gds21 and keeps its case's finite row -- each evaluation fails (status bit 1), the node comes back with the row's entry (the
+    incumbent rule of csrc/ibs_theta0_polish.hpp); every 11th line has a row without a finite entry -- node -1, nothing is evaluated, as
+    test_status_words pins it.  Every line's outputs: the bits of the same line in the batch of the 18 (case, kind) pairs"""
+    import time
+    from tests.local_eq_cases import assert_wave_reuse, persistent_waves
+    N, nt, K = 67, 15, 3
+    h, geo7, dP, t0, mu, _ = coarse(ctx, N, nt)
+    n_case = len(tc.CASES)
+
+    def run(case, kind):
+        geo = [a[case].copy() for a in geo7]
+        geo[5][kind == 1, 30] = np.nan
+        m = mu[case].copy()
+        m[kind == 2] = np.nan
+        t = time.perf_counter()
+        r = down(ctx.marginal_theta0_polish(h, *[up(a) for a in geo], up(dP[case]), up(t0), up(m), n_starts=K, xtol=XTOL, want_info=True))
+        return r, time.perf_counter() - t
+
+    case18, kind18 = np.tile(np.arange(n_case), 3), np.repeat(np.arange(3), n_case)
+    ref, _ = run(case18, kind18)
+    assert same(polish(ctx, N, nt, K=K), ref, rows_b=slice(0, n_case)), "the clean lines of the reference batch differ from the call alone"
+    st = ref["info"] >> 16
+    nan_line, no_row = kind18 == 1, kind18 == 2
+    slot_node = np.clip(ref["node"], 0, None)
+    assert (ref["node"][nan_line] >= 0).all() and (st[nan_line] & 2).all() and (st[nan_line] & BIT_NODE).all() and (ref["n_eval"][nan_line] > 0).all()
+    assert np.array_equal(bits(ref["theta0"][nan_line]), bits(t0[slot_node[nan_line]]))
+    assert np.array_equal(bits(ref["mu"][nan_line]), bits(np.take_along_axis(mu[case18], slot_node, axis=1)[nan_line]))
+    assert (ref["node"][no_row] == -1).all() and not ref["n_found"][no_row].any() and not ref["n_eval"][no_row].any() and not ref["info"][no_row].any()
+    assert all(np.isnan(ref[k][no_row]).all() for k in KEYS)
+    assert not (st[kind18 == 0] & 3).any()
+    n_lines = -(-int(np.ceil(1.3 * persistent_waves())) // K)
+    i = np.arange(n_lines)
+    case, kind = i % n_case, np.where(i % 11 == 0, 2, np.where(i % 5 == 0, 1, 0))
+    r, dt = run(case, kind)
+    blocks = assert_wave_reuse(ctx, "k_marginal_theta0_polish", n_lines * K)
+    print("polish wave reuse N=67: %d lines x %d slots on %d blocks, %.3f s (uploads, the call, downloads); mean n_eval %.2f, max %d"
+          % (n_lines, K, blocks, dt, r["n_eval"].mean(), r["n_eval"].max()))
+    assert same(r, ref, rows_b=kind * n_case + case), "a line's outputs depend on the systems its waves served before"
 
 
 # ---- the drivers on the NCSX tables (the shapes of tests/test_gpu_marginal_refine.py's driver test)

@@ -1,7 +1,8 @@
 """GPU: the spectrum mode with an F-orthonormal Ritz basis of every cluster (ibs_solve_gcf_modes_basis_f64,
 Context.solve_gcf_modes(basis=True), autograd.solve_gcf_modes(cluster="mean")) against the contract of tests/modes_basis_oracle.py:
 (a) residual, (b) F-orthogonality, (c) the Ritz property, (d) the distance from the reference subspace of tight clusters, (e) gam;
-(f) identity with ibs_solve_gcf_modes_f64 outside the clusters; (g) bitwise repeatability and independence of the batch.
+(f) identity with ibs_solve_gcf_modes_f64 outside the clusters; (g) bitwise repeatability and independence of the batch -- of a batch
+of four times the persistent grid as well, where every wave serves four systems from one slice of workspace.
 
 Every test recomputes the reference clusters with scipy and asserts its own precondition -- the clusters it is about are at most
 tau / 8 wide and at least 2 tau from the rest of the spectrum -- before it looks at the GPU's output.  Groups the oracle finds
@@ -75,20 +76,32 @@ def assert_named_clusters(line, K, named):
         assert gr and gr[0]["last"] == last and gr[0]["width"] <= ref["tau"] / 8 and gr[0]["gap_out"] >= 2 * ref["tau"], (first, last, groups)
 
 
-@pytest.mark.parametrize("N", [513, 771, 2049, 4097])
+SHORT = (67, 131, 195)      # n = N - 2 = 65, 129, 193 interior rows: one row beyond one, two and three blocks of 64 of the recurrences
+
+
+@pytest.mark.parametrize("N", [67, 131, 195, 513, 771, 2049, 4097])
 def test_contract_on_a_mixed_batch(ctx, N):
-    """K = 2, 4, 8 on host pointers, K = 4 on device pointers as well (the same bits): (a)-(e) on every system of the mixed batch"""
+    """K = 2, 4, 8 on host pointers, K = 4 on device pointers as well (the same bits): (a)-(e) on every system of the mixed batch; K = 1 and
+    16 as well at N = 131.  On the short grids the wells are resolved by a few points each and their spectra differ from grid to grid:
+    the clusters a line is tested on are the reference's own at that length -- the tight, isolated ones, of which the double well and
+    the two triple wells have at least one; the rest (the quad well's second pair at N = 131, its first four modes and the triple
+    well's second triplet at N = 195) are ambiguous partitions to check_system"""
     import torch
     lines = mixed(N)
-    named = [[(0, 1)], [], [(0, 2), (3, 5)], [(0, 3)], [], [(1, 2)]]
+    Ks = (1, 2, 4, 8, 16) if N == 131 else (2, 4, 8)
+    if N in SHORT:
+        named = [mb.tight_clusters(*line, max(Ks)) for line in lines]
+        assert all(named[i] for i in (0, 2, 5)) and not named[1] and not named[4], named
+    else:
+        named = [[(0, 1)], [], [(0, 2), (3, 5)], [(0, 3)], [], [(1, 2)]]
     for line, nm in zip(lines, named):
-        assert_named_clusters(line, 8, nm)
+        assert_named_clusters(line, max(Ks), nm)
     for line in (lines[1], lines[4]):
-        ref, groups = mb.reference_clusters(*line, 8)
+        ref, groups = mb.reference_clusters(*line, max(Ks))
         assert all(g["first"] == g["last"] and g["gap_out"] >= 2 * ref["tau"] for g in groups)      # the s-alpha lines have no cluster
     g, c, f = stack(lines)
     h = spacing(lines[0])
-    for K in (2, 4, 8):
+    for K in Ks:
         r = ctx.solve_gcf_modes(h, g, c, f, K, want_info=True, basis=True)
         assert r["nbad"] == 0 and r["X"].shape == (len(lines), K, N) and r["cluster_first"].dtype == np.int32
         for i, line in enumerate(lines):
@@ -200,6 +213,76 @@ def test_c_entry(ctx):
     ref = ctx.solve_gcf_modes(h, g, c, f, K, want_info=True, basis=True)
     for k in KEYS:
         assert np.array_equal(ref[k], clean[k]), k
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.int64) if a.dtype == np.float64 else a
+
+
+def test_more_systems_than_waves(ctx):
+    """N = 67, K = 4: the six lines of the mixed batch and an invalid system (g < 0 at one inner point) drawn in a fixed pseudo-random order
+    to four times the persistent grid (8 waves per CU), so that every wave serves four systems and the lam, gam, status and cluster rows
+    and the open flag it keeps in its workspace pass from a clustered system to an invalid one, from an invalid one to a clustered one
+    and from a clustered one to one without a cluster (asserted on the launch's own grid).  Every system: the bits of its kind in the
+    batch of seven"""
+    from tests.local_eq_cases import assert_wave_reuse, persistent_waves
+    N, K, INVALID = 67, 4, 6
+    lines = mixed(N)
+    assert all(mb.tight_clusters(*lines[i], K) for i in (0, 2, 3, 5)) and not mb.tight_clusters(*lines[1], K)
+    g, c, f = (np.concatenate([a, a[2:3]]) for a in stack(lines))
+    g[INVALID, 33] = -1.0
+    h = spacing(lines[0])
+    seven = ctx.solve_gcf_modes(h, g, c, f, K, want_info=True, basis=True)
+    st7 = seven["info"] >> 16
+    assert seven["nbad"] == K and (st7[INVALID] == 2).all() and not (st7[:INVALID] & 3).any()
+    assert all(np.isnan(seven[k][INVALID]).all() for k in ("lam", "gam", "X", "dX"))
+    clustered = [i for i in range(INVALID) if (st7[i] & BASIS).any()]
+    plain = [i for i in range(INVALID) if not (st7[i] & (CL | BASIS | OPEN)).any()]
+    assert set(clustered) >= {0, 2, 3, 5} and set(plain) >= {1}, (clustered, plain)
+    n_sys = 4 * persistent_waves()
+    kind = np.random.default_rng(67).integers(0, 7, n_sys)
+    r = ctx.solve_gcf_modes(h, g[kind], c[kind], f[kind], K, want_info=True, basis=True)
+    blocks = assert_wave_reuse(ctx, "k_solve_gcf_modes_basis", n_sys)
+    steps = set(zip(kind[:-blocks].tolist(), kind[blocks:].tolist()))      # (system, the next system of the same wave)
+    assert any((a, INVALID) in steps for a in clustered) and any((INVALID, b) in steps for b in clustered)
+    assert any((a, b) in steps for a in clustered for b in plain)
+    assert r["nbad"] == K * (kind == INVALID).sum() and ((r["info"][kind == INVALID] >> 16) == 2).all()
+    for k in KEYS:
+        assert np.array_equal(bits(r[k]), bits(seven[k][kind])), k
+
+
+def test_c_entry_padded_rows_and_no_dX(ctx):
+    """the raw entry point with ld = N + 7 for g, c, f and a caller's half-grid g, NaN in every padding element, N = 131, K = 4: with dX
+    and with dX = NULL (the derivative of a cluster's members then goes through a work row) every output is the packed call's, bit for bit"""
+    lib = ctx._lib
+    N, K, ld = 131, 4, 131 + 7
+    lines = [mb.triple_well(N), mo.salpha_line(N, -4.0), mo.double_well(N)]
+    assert mb.tight_clusters(*lines[0], K) and mb.tight_clusters(*lines[2], K)
+    g, c, f = stack(lines)
+    h = spacing(lines[0])
+    gh = np.zeros_like(g)
+    gh[:, :-1] = np.sqrt(g[:, :-1] * g[:, 1:])
+    packed = ctx.solve_gcf_modes(h, g, c, f, K, gh=gh, want_info=True, basis=True)
+    assert packed["nbad"] == 0 and ((packed["info"][[0, 2]] >> 16) & BASIS).any(axis=1).all()
+
+    def pad(a):
+        out = np.full((3, ld), np.nan)
+        out[:, :N] = a
+        return out
+
+    rows = [pad(a) for a in (g, gh, c, f)]
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)
+    for with_dx in (True, False):
+        out = dict(lam=np.zeros((3, K)), gam=np.zeros((3, K)), X=np.zeros((3, K, N)), dX=np.zeros((3, K, N)),
+                   cluster_first=np.zeros((3, K), np.int32), info=np.zeros((3, K), np.int32))
+        rc = lib.ibs_solve_gcf_modes_basis_f64(ctx._h, 3, N, h, *[p(a) for a in rows], ld, K, p(out["lam"]), p(out["gam"]), p(out["X"]),
+                                               p(out["dX"]) if with_dx else None, p(out["cluster_first"]), p(out["info"]), 1)
+        assert rc == 0 and "k_solve_gcf_modes_basis<true>" in ctx.last_launch()[0], (with_dx, rc, ctx.last_launch())
+        for k in KEYS:
+            if k != "dX" or with_dx:
+                assert np.array_equal(bits(out[k]), bits(packed[k])), (with_dx, k)
+        assert with_dx or not out["dX"].any()               # (not written)
 
 
 def test_autograd_cluster_mean(ctx):
