@@ -23,6 +23,7 @@
 #include "ibs_scan_peaks.hpp"
 #include "ibs_theta0_polish.hpp"
 #include "ibs_local_eq.hpp"
+#include "ibs_local_eq_boundary.hpp"
 #include <chrono>
 #include <thread>
 
@@ -1288,6 +1289,55 @@ int ibs_local_eq_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_var, int32_t 
       c.info = a.info ? a.info + s0 : nullptr;
       c.work = work; c.work_doubles = (size_t)nw * per_wave; c.n_waves = nw;
       HIPCHK(ibs::launch_local_eq_scan(c, ctx->stream));
+      return 0;
+    });
+  });
+}
+
+// ---- local-equilibrium boundaries: the crossings of the stability boundary along rays in (eps, p) of every line
+// (ibs_local_eq_boundary.hip; the rule for a ray: ibs_local_eq_boundary.hpp).  Whole lines chunk after chunk exactly as the scan above, a
+// line's n_ray rays standing where its variations stand; the kernel forms its rows in LDS, so a chunk carves nothing from ctx->long_ws
+int ibs_local_eq_boundary_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int32_t N, double theta_lo, double h, const double* geo,
+                              int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps,
+                              int64_t ps_ld, const double* rays, double shift, int32_t max_cross, double xtol, double* t_stable,
+                              double* t_unstable, int32_t* n_cross, int32_t* lo_unstable, int32_t* node_count, int32_t* info, int flags) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!geo || !dPdrho || !centre || !sigma || !rays || !t_stable || !t_unstable || !n_cross)
+    return fail(IBS_ERR_ARG, "null argument (geo, dPdrho, centre, sigma, rays, t_stable, t_unstable and n_cross are required)");
+  if (n_lines < 0 || n_ray < 1 || ld < N || (ps && ps_ld < N))
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_ray=%d ld=%lld ps_ld=%lld N=%d)", n_lines, n_ray, (long long)ld, (long long)ps_ld, N);
+  if (max_cross < 1 || max_cross > ibs::kMaxCross || !(xtol >= 0.0 && xtol < 1.0))
+    return fail(IBS_ERR_ARG, "max_cross must lie in [1, %d] and xtol in [0, 1) (max_cross=%d xtol=%g)", ibs::kMaxCross, max_cross, xtol);
+  if (flags != IBS_MEM_DEVICE && flags != IBS_MEM_HOST) return fail(IBS_ERR_ARG, "flags must be IBS_MEM_DEVICE or IBS_MEM_HOST, not %d", flags);
+  if (!std::isfinite(theta_lo) || !std::isfinite(shift))
+    return fail(IBS_ERR_ARG, "theta_lo and shift must be finite (theta_lo=%g shift=%g)", theta_lo, shift);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_lines == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n_sys = (size_t)n_lines * n_ray, plane = (size_t)n_lines * (size_t)ld;
+  ibs::LocalEqBoundaryArgs a{};                            // the whole call; each chunk launches a copy with its lines
+  a.n_ray = n_ray; a.N = N; a.theta_lo = theta_lo; a.h = h; a.ld = (long)ld; a.plane = plane; a.ps_ld = (long)ps_ld; a.shift = shift;
+  a.max_cross = max_cross; a.xtol = xtol;
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, 8 * plane); a.dPdrho = s.in(dPdrho, n_lines); a.centre = s.in(centre, n_lines); a.sigma = s.in(sigma, n_lines);
+    a.ps = s.in(ps, (size_t)n_lines * (size_t)ps_ld); a.rays = s.in(rays, 7 * (size_t)n_ray);
+    a.t_stable = s.out(t_stable, n_sys * max_cross); a.t_unstable = s.out(t_unstable, n_sys * max_cross); a.n_cross = s.out(n_cross, n_sys);
+    a.lo_unstable = s.out(lo_unstable, n_sys); a.node_count = s.out(node_count, n_sys * 64);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, flags, decl, [&]() -> int {
+    auto carve = [&](Carve&, long) {};                     // (no per-wave workspace)
+    return for_line_chunks(ctx, "local_eq_boundary", n_lines, n_ray, N, carve, [&](long l0, long Lc) -> int {
+      const long s0 = l0 * n_ray;
+      ibs::LocalEqBoundaryArgs c = a;
+      c.n_lines = (int)Lc;
+      c.geo = a.geo + l0 * ld; c.dPdrho = a.dPdrho + l0; c.centre = a.centre + l0; c.sigma = a.sigma + l0;
+      c.ps = a.ps ? a.ps + l0 * ps_ld : nullptr;
+      c.t_stable = a.t_stable + s0 * max_cross; c.t_unstable = a.t_unstable + s0 * max_cross; c.n_cross = a.n_cross + s0;
+      c.lo_unstable = a.lo_unstable ? a.lo_unstable + s0 : nullptr; c.node_count = a.node_count ? a.node_count + s0 * 64 : nullptr;
+      c.info = a.info ? a.info + s0 : nullptr;
+      c.n_waves = long_waves(ctx, Lc * n_ray);
+      HIPCHK(ibs::launch_local_eq_boundary(c, ctx->stream));
       return 0;
     });
   });

@@ -211,6 +211,27 @@ def local_eq_fold(theta, line8, dPdrho, centre, sigma, theta0, eps, p, ps=None):
     return p * dPdrho, gb + p * (cv - gb) + x * cv0, gds2 + 2 * x * gds21 + x * x * gds22
 
 
+def local_eq_ray_triples(rays, t):
+    """The rule for a ray of the local-equilibrium boundaries (csrc/ibs_local_eq_boundary.hpp, Context.local_eq_boundary) in numpy:
+    rays (..., 7) = (theta0, eps0, p0, d_eps, d_p, t_lo, t_hi) and parameters t, broadcast against the rays' leading shape, give the
+    triples (..., 3) = (theta0, eps0 + t d_eps, p0 + t d_p) that local_eq_fold takes.  theta0 does not vary along a ray.  The
+    pressure axis at fixed shear is d_eps = 0, d_p = 1, the shear axis d_eps = 1, d_p = 0."""
+    rays = np.asarray(rays, dtype=np.float64)
+    t = np.asarray(t, dtype=np.float64)
+    th0, eps, p = np.broadcast_arrays(rays[..., 0], rays[..., 1] + t * rays[..., 3], rays[..., 2] + t * rays[..., 4])
+    return np.stack([th0, eps, p], axis=-1)
+
+
+def local_eq_ray_nodes(rays):
+    """the 64 pass-0 nodes (..., 64) of rays (..., 7): t_lo + k (t_hi - t_lo) / 63, node 63 being t_hi itself (the kernel forms node k
+    with one fused multiply-add: the two may differ in the last bit)"""
+    rays = np.asarray(rays, dtype=np.float64)
+    lo, hi = rays[..., 5:6], rays[..., 6:7]
+    t = lo + np.arange(64.0) * ((hi - lo) / 63.0)
+    t[..., 63] = hi[..., 0]
+    return t
+
+
 def make_obj_w_grad(fieldlines, ctx=None, del_alpha=0.004, eigenpair="max", jac="reference"):
     """Factory for a drop-in `obj_w_grad(x0, vs, rho_val, theta, vguess00, sigma00=0.42)` (utils.py:1632).
 

@@ -278,6 +278,17 @@ SIGMA_COARSE = 1.0
 SIGMA_FINAL = 0.42
 
 
+def first_unstable(t_stable, t_unstable, lo_unstable, t_lo):
+    """The envelope of BallooningScan.local_eq_boundary over (alpha, theta0): from t_stable, t_unstable (n, nalpha, n_theta0, n_fixed,
+    max_cross) and lo_unstable (n, nalpha, n_theta0, n_fixed) the smallest t = (t_stable + t_unstable) / 2 of a crossing from stable
+    to unstable (t_stable < t_unstable) of any line of the surface, +inf where there is none, t_lo where a line is unstable at t_lo.
+    Returns (n, n_fixed)."""
+    t_stable, t_unstable = np.asarray(t_stable), np.asarray(t_unstable)
+    up = t_stable < t_unstable                              # (NaN beyond n_cross: False)
+    first = np.where(up, 0.5 * (t_stable + t_unstable), np.inf).min(axis=(1, 2, 4), initial=np.inf)
+    return np.where((np.asarray(lo_unstable) > 0).any(axis=(1, 2)), float(t_lo), first)
+
+
 def check_eigenpair(eigenpair):
     if eigenpair not in EIGENPAIRS:
         raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
@@ -511,6 +522,54 @@ class BallooningScan:
         res["unstable"] = (res["count"] > 0).any(axis=(1, 2))
         if not count_only:
             res["gam_max"] = res["gam"].max(axis=(1, 2))
+        return res
+
+    # -- the boundaries of that picture: marginal pressure factor (or shear change) of every line of the alpha grid, two launches
+    def local_eq_boundary(self, fixed, t_range, theta0=None, axis="p", shift=0.0, max_cross=4, xtol=1e-12):
+        """Where every line of the alpha grid of every owned surface crosses the stability boundary ("an eigenvalue above `shift`")
+        along one axis of the (eps, p) plane of local_eq(), closed on the device (Context.local_eq_boundary).
+            axis="p":   fixed = the relative shear changes eps (n_fixed,), t_range = (p_lo, p_hi): a ray runs along the pressure factor
+                        p at each eps -- the marginal pressure gradient at each shear
+            axis="eps": fixed = the pressure factors p (n_fixed,), t_range = (eps_lo, eps_hi): a ray runs along eps at each p
+        with the rule of local_eq (centre = alpha, sigma = sign(-phiedge), no ps row), folded at theta0 (n_theta0,; default: the coarse
+        theta0 grid); the ray parameter t IS the running coordinate.  Resident path only (tables= and device=, else ValueError): ONE
+        geometry launch and ONE boundary call.  Returns numpy dict(t_stable, t_unstable, t (n_own, nalpha, n_theta0, n_fixed,
+        max_cross), NaN beyond n_cross; n_cross, lo_unstable, info (n_own, nalpha, n_theta0, n_fixed); first_unstable (n_own,
+        n_fixed) = the envelope over (alpha, theta0): the smallest t at which any line of the surface crosses from stable to unstable,
+        +inf where none does, t_lo where some line is unstable at t_lo already -- the surface's first-stability limit; theta0, fixed,
+        t_range, axis).  A crossing is a change of verdict between two of 64 equidistant nodes of t_range: a tangency and two
+        crossings between one pair of nodes are missed.  Flagged systems (status bits 0-1) raise IbsError."""
+        if self.tables is None or self.device is None:
+            raise ValueError("local_eq_boundary() runs on the resident path: tables= and device= are required")
+        if axis not in ("p", "eps"):
+            raise ValueError("axis must be 'p' or 'eps', not %r" % (axis,))
+        fixed = np.atleast_1d(np.asarray(fixed, dtype=np.float64))
+        t_lo, t_hi = (float(v) for v in t_range)
+        t0 = self.theta0_scan if theta0 is None else np.atleast_1d(np.asarray(theta0, dtype=np.float64))
+        na, n = len(self.alpha_scan), len(self.own)
+        shape = (n, na, len(t0), len(fixed))
+        tt, ff = (a.ravel() for a in np.meshgrid(t0, fixed, indexing="ij"))
+        zero, one = np.zeros_like(ff), np.ones_like(ff)
+        cols = (tt, ff, zero, zero, one) if axis == "p" else (tt, zero, ff, one, zero)
+        rays = np.stack([*cols, np.full_like(ff, t_lo), np.full_like(ff, t_hi)], axis=1)
+        res = dict(theta0=t0, fixed=fixed, t_range=(t_lo, t_hi), axis=axis)
+        if n:
+            surf = np.repeat(self._own_surf(), na)
+            alpha = np.tile(self.alpha_scan, n)
+            r = self.ctx.fieldline_geometry(self.tables, surf, alpha, self.theta, device=self.device)
+            sigma = np.sign(-np.asarray(self.tables.scal)[surf, 4])
+            out = self.ctx.local_eq_boundary(self.theta[0], self.h, r["geo"], r["dPdrho"], alpha, sigma, rays, shift=shift,
+                                             max_cross=max_cross, xtol=xtol, want_info=True)
+            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())
+            if nbad:
+                raise IbsError("%d of %d local-equilibrium boundary systems were flagged (status bits 0-1: pass cap or invalid data)"
+                               % (nbad, out["info"].numel()))
+            res.update({k: out[k].cpu().numpy().reshape(shape + (max_cross,)) for k in ("t_stable", "t_unstable", "t")})
+            res.update({k: out[k].cpu().numpy().reshape(shape) for k in ("n_cross", "lo_unstable", "info")})
+        else:
+            res.update({k: np.full(shape + (max_cross,), np.nan) for k in ("t_stable", "t_unstable", "t")})
+            res.update({k: np.zeros(shape, dtype=np.int32) for k in ("n_cross", "lo_unstable", "info")})
+        res["first_unstable"] = first_unstable(res["t_stable"], res["t_unstable"], res["lo_unstable"], t_lo)
         return res
 
     # -- every line's growth rate maximised over theta0 between the nodes of the coarse grid, two launches

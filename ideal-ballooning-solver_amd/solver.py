@@ -483,6 +483,42 @@ class Context:
                      ar.out("count", shape, _I32), ar.out("info", shape, _I32, want_info))
         return ar.result(rc)
 
+    # ---- local-equilibrium boundaries --------------------------------------------------------
+    def local_eq_boundary(self, theta_lo, h, geo, dPdrho, centre, sigma, rays, ps=None, shift=0.0, max_cross=4, xtol=1e-12,
+                          want_nodes=False, want_info=False):
+        """The parameters t at which every line crosses the stability boundary ("an eigenvalue above `shift`") along the rays
+        (n_ray, 7) = (theta0, eps0, p0, d_eps, d_p, t_lo, t_hi) in the (eps, p) plane of the local-equilibrium rule
+        (ibs_local_eq_boundary_f64; triples of a ray: operators.local_eq_ray_triples), closed on the device to xtol (t_hi - t_lo).
+        The other arguments are local_eq_scan's.  A crossing is a change of verdict between two of the 64 nodes
+        operators.local_eq_ray_nodes(rays); the first max_cross (1 .. 4) in increasing t are closed and returned.
+        Returns dict(t_stable, t_unstable, t = their mean (n_lines, n_ray, max_cross), NaN beyond n_cross; n_cross, lo_unstable = the
+        verdict at t_lo, int32 (n_lines, n_ray)[; node_count int32 (n_lines, n_ray, 64) = the counts at the nodes][; info], nbad).
+        info: bits 0-15 passes over the rows; status (info >> 16) bit 0 pass cap, 1 invalid system (NaN, n_cross -1: non-finite line
+        data, g or f <= 0 on the ray, sigma not +-1, a non-finite ray or t_lo >= t_hi), 2 more than max_cross crossings, 3 the
+        bracket's ends became neighbours in FP64 before xtol was met.  A tangency and two crossings between one pair of nodes are
+        missed: narrow the range or split the ray."""
+        eight, n_lines, N = geo.shape
+        if eight != 8:
+            raise IbsError("geo must be (8, n_lines, N)")
+        n_ray = int(rays.shape[0])
+        if tuple(rays.shape) != (n_ray, 7):
+            raise IbsError("rays must be (n_ray, 7) = (theta0, eps0, p0, d_eps, d_p, t_lo, t_hi)")
+        if ps is not None and tuple(ps.shape) != (n_lines, N):
+            raise IbsError("ps must be (n_lines, N) = %s, not %s" % ((n_lines, N), tuple(ps.shape)))
+        max_cross = int(max_cross)
+        ar = _Args(self)
+        shape = (n_lines, n_ray)
+        pgeo = ar.inp(geo)
+        cross = shape + (max(max_cross, 0),)
+        rc = ar.call("ibs_local_eq_boundary_f64", n_lines, n_ray, N, float(theta_lo), float(h), pgeo, N, ar.inp(dPdrho, upload=True),
+                     ar.inp(centre, upload=True), ar.inp(sigma, upload=True), ar.inp(ps, upload=True), N, ar.inp(rays, upload=True),
+                     float(shift), max_cross, float(xtol), ar.out("t_stable", cross), ar.out("t_unstable", cross),
+                     ar.out("n_cross", shape, _I32), ar.out("lo_unstable", shape, _I32),
+                     ar.out("node_count", shape + (64,), _I32, want_nodes), ar.out("info", shape, _I32, want_info))
+        res = ar.result(rc)
+        res["t"] = 0.5 * (res["t_stable"] + res["t_unstable"])
+        return res
+
     @staticmethod
     def _three_lines(geo):
         n_pts, three, eight, N = geo.shape

@@ -449,6 +449,40 @@ int ibs_local_eq_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_var, int32_t 
                           int64_t ps_ld, const double* var, double shift, double* gam, double* lam, int32_t* count, int32_t* info,
                           int flags);
 
+/* Local-equilibrium boundaries: the CURVE of the s-alpha picture where ibs_local_eq_scan_f64 gives the raster -- the parameters at which
+ * every line crosses the stability boundary along straight rays in the (eps, p) plane of the rule above, closed to rounding on the
+ * device.  A ray is seven doubles (theta0, eps0, p0, d_eps, d_p, t_lo, t_hi), t_lo < t_hi; the triple at parameter t is (theta0,
+ * eps0 + t d_eps, p0 + t d_p), the rows at t are those of the rule at that triple and the operator is the one every entry point solves.
+ * The pressure axis at fixed shear: d_eps = 0, d_p = 1; the shear axis: d_eps = 1, d_p = 0; oblique rays are allowed; theta0 does not vary
+ * along a ray (the fold variable stays linear in t; numpy: ibs_amd.operators.local_eq_ray_triples).  The verdict at t is "the pencil has
+ * an eigenvalue above `shift`" (count > 0).
+ *   inputs up to ps_ld: as ibs_local_eq_scan_f64; rays [n_ray][7]; shift: a HOST scalar, finite; max_cross in [1, 4]; xtol in [0, 1);
+ *   t_stable, t_unstable [n_lines][n_ray][max_cross]: the two ends of each closed bracket, by verdict, in increasing t; NaN beyond n_cross;
+ *   n_cross [n_lines][n_ray]: crossings returned (all three required);
+ *   lo_unstable [n_lines][n_ray] or NULL: the verdict at t_lo;
+ *   node_count [n_lines][n_ray][64] or NULL: the counts above shift at the nodes t_lo + k (t_hi - t_lo) / 63 of pass 0 -- the diagram row
+ *   at node resolution, for free;
+ *   info [n_lines][n_ray] or NULL: bits 0-15 = passes over the rows; status bits 0 (a crossing was not closed in 12 passes), 1 (invalid:
+ *   non-finite data in the line, g or f <= 0 at any evaluated t, sigma not +-1, a non-finite ray, t_lo >= t_hi -- NaN parameters, n_cross,
+ *   lo_unstable and node counts -1, of that system alone), 2 (more than max_cross crossings: the first max_cross are returned), 3 (the
+ *   bracket's ends became FP64 neighbours before xtol was met; always with xtol = 0);
+ *   flags: IBS_MEM_DEVICE or IBS_MEM_HOST.
+ * Pass 0 puts the 64 lanes of a wavefront at the 64 nodes; a crossing is an adjacent node pair with different verdicts.  Each kept
+ * crossing is closed in turn: 64 points strictly inside the bracket, the new bracket = the first adjacent pair (ends included) whose
+ * verdicts differ, until its width is <= xtol (t_hi - t_lo): six passes for 1e-12.  LIMITS: a tangency (double root) and two crossings
+ * between one pair of nodes are missed -- narrow the range or split the ray; within rounding of the marginal point the verdict may
+ * flicker, and the first flip is returned; theta0 is fixed per ray; ps is consumed, not computed; no derivatives of t*.
+ * FP64, uniform grids, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED); a NULL required argument, ld < N, ps_ld < N,
+ * n_ray < 1, max_cross outside [1, 4], xtol outside [0, 1), a non-finite shift: IBS_ERR_ARG; all of these run before the context is
+ * touched.  One wavefront per (line, ray) (k_local_eq_boundary, csrc/ibs_local_eq_boundary.hip; the staged form:
+ * csrc/ibs_local_eq_boundary.hpp), no atomics, no workspace: a system's outputs depend on its line and its ray alone, bit for bit --
+ * not on the batch, the order of the lines or the chunks of whole lines (option "nearest_chunk_systems"). */
+int ibs_local_eq_boundary_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int32_t N, double theta_lo, double h, const double* geo,
+                              int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps,
+                              int64_t ps_ld, const double* rays, double shift, int32_t max_cross, double xtol, double* t_stable,
+                              double* t_unstable, int32_t* n_cross, int32_t* lo_unstable, int32_t* node_count, int32_t* info,
+                              int flags);
+
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
  * and utils.py:1556-1624; with dgam_dtheta0 also utils.py:1666-1680 (Hellmann-Feynman d/dtheta0).
