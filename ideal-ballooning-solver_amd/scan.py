@@ -320,6 +320,64 @@ def check_marginal_jac(jac):
     return jac
 
 
+def _host(a):
+    """a device tensor or a host array as numpy"""
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _flagged(info, any_bit=False):
+    """which solves of the info words (sweeps | status << 16; numpy or a device tensor, no synchronisation) failed: status bits 0-1
+    (iteration cap, invalid data) for every call whose higher bits are informational (a tie, a cluster, an infinite margin, the
+    polish's bits 10-12); any_bit: the lam_max scan and its points have no informational bit, so any status bit fails them."""
+    status = info >> 16
+    return (status if any_bit else status & 3) != 0
+
+
+def _check_flags(message, info, any_bit=False):
+    """raise IbsError(message % (flagged[, total])) if a solve of the info words failed (one synchronisation for a device tensor)"""
+    nbad = int(_host(_flagged(info, any_bit).sum()))
+    if nbad:
+        raise IbsError(message % (nbad, int(np.prod(info.shape)))[:message.count("%d")])
+
+
+BOX_LO, BOX_HI = np.array([0.0, 0.0]), np.array([np.pi, 0.5 * np.pi])      # ball_scan.py:311
+
+
+def _lockstep(evaluate, x0, active, maxiter, ftol, gtol):
+    """The host-driven L-BFGS-B of ball_scan.py:307-314 for n points at once: one optimizer state per point (csrc/ibs_lbfgsb2.hpp
+    through the C ABI ibs_lbfgsb2_*), advanced in lockstep.  Every round calls evaluate(idx, x[idx]) -> numpy (val (m,), jac (m, 2))
+    ONCE, idx being exactly the still-running points in increasing order, then steps each of them; a point's trajectory does not
+    depend on the points beside it.  x0 (n, 2) is clipped to the box; points that are not `active` are neither moved nor evaluated.
+    Returns dict(x (n, 2), f (n,): the objective at the last accepted iterate, NaN where nothing was evaluated, evals int32 (n,),
+    task int32 (n,): the task codes of lbfgsb.TASKS, 10 where nothing was evaluated, rounds = the largest evals)."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.lib()
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    x = np.clip(np.asarray(x0, dtype=np.float64).reshape(-1, 2), BOX_LO, BOX_HI)
+    n = len(x)
+    states = [C.create_string_buffer(lib.ibs_lbfgsb2_state_bytes()) for _ in range(n)]
+    for k in range(n):
+        lib.ibs_lbfgsb2_init(states[k], p(x[k]), p(BOX_LO), p(BOX_HI), float(ftol), float(gtol), int(maxiter), 20)
+    active = np.array(active, dtype=bool)
+    f, evals, task = np.full(n, np.nan), np.zeros(n, dtype=np.int32), np.full(n, 10, dtype=np.int32)
+    rounds = 0
+    while active.any():
+        idx = np.nonzero(active)[0]
+        val, jac = evaluate(idx, x[idx])
+        rounds += 1
+        evals[idx] += 1
+        for q, k in enumerate(idx):
+            gk = np.ascontiguousarray(jac[q], dtype=np.float64)
+            if not lib.ibs_lbfgsb2_step(states[k], float(val[q]), p(gk), p(x[k])):
+                active[k] = False
+    for k in np.nonzero(evals)[0]:
+        fk = C.c_double(0.0); cnt = np.zeros(5, dtype=np.int32)
+        lib.ibs_lbfgsb2_result(states[k], p(x[k]), C.byref(fk), p(cnt))
+        f[k], task[k] = fk.value, cnt[2]
+    return dict(x=x, f=f, evals=evals, task=task, rounds=rounds)
+
+
 class BallooningScan:
     """Coarse (alpha, theta0) scan -> argmax -> L-BFGS-B refinement -> final solve, per surface.
     eigenpair="max" (the default): every stage returns lam_max's eigenpair (the physical growth rate).  eigenpair="nearest":
@@ -339,20 +397,21 @@ class BallooningScan:
     (surface_argmax_pack), and the final solves are certified and re-closed the same way.  The solves inside the refinement's objective
     are NOT certified: they only steer the optimizer, and the final solve at its end point is what is reported.  The counts of the
     last run are in .last_certificate = dict(checked, reclosed, failed); failed > 0 raises IbsError.  certify=False (the default)
-    takes exactly the code path it took before the option existed.
+    adds no call and no keyword to any call.
     n_starts=K > 1: every surface is refined from the K best peaks of its coarse table (pick_starts / ibs_scan_peaks_f64: local
     maxima over the eight neighbours, ranked by value; slot 0 is the first maximum, upstream's one start) and the best refined
     candidate is reported, slot 0 winning ties -- a narrow basin whose crest lies between nodes can rank below the first maximum in
     the table and still hold the surface's maximum.  All n K points run through the refinement and the final solve in one batch; a
     surface with fewer than K peaks repeats slot 0 in the remaining slots (duplicated work, never preferred by the first-maximum
     rule).  .last_candidates (n_own, K, 3) = (theta0, alpha, gam) of every slot and .last_peaks = dict(index, value (n_own, K),
-    n_found (n_own,)) describe the last run (device tensors on the device path, not synchronised).  n_starts=1 (the default) takes
-    exactly the code path and the calls it took before the option existed.
+    n_found (n_own,)) describe the last run (device tensors on the device path, not synchronised).  n_starts changes two steps of
+    device_rows() only: how the starts are picked and how the rows are selected from the candidates.
     theta0_polish=True (tables= and device= only, n_starts=1, eigenpair="max"; else ValueError): after the coarse scan every line's
     growth rate is maximised over theta0 between the nodes (Context.theta0_polish, one call with one slot per line, on the lines
     the scan staged: no geometry launch), and every surface's refinement starts from its best polished (alpha_i, theta0*) in place of
     the best node; refine=False rows report that point and its value.  .last_envelope holds that call's outputs (device tensors).
-    theta0_polish=False (the default) makes exactly the calls it made before the option existed."""
+    Every mode runs the one sequence of device_rows(); tools/bitwise_vs_parent.py --parent-scan compares a rewrite of this file with
+    the one it replaces, Context call by Context call and bit by bit."""
 
     def __init__(self, ctx, fieldlines, theta, rho_arr, nalpha=24, ntheta0=15, del_alpha=0.004,
                  rank=0, world=1, dist=None, gather_device=None, tables=None, device=None, surf_index=None, eigenpair="max",
@@ -422,48 +481,60 @@ class BallooningScan:
         r = self.ctx.fieldline_geometry(self.tables, [js] * len(alphas), alphas, self.theta)
         return np.ascontiguousarray(np.transpose(r["geo"], (1, 0, 2)))
 
+    @property
+    def _on_device(self):
+        """the resident path: geometry by the HIP kernel from `tables`, consumed on `device`"""
+        return self.tables is not None and self.device is not None
+
+    def _coarse_lines(self, want_t0=True):
+        """The lines of the coarse alpha grid of the owned surfaces (at least one), surface-major, in the memory kind of the path --
+        device tensors on the resident path (ONE geometry launch), numpy from the fieldlines callback: dict(geo: the 8 planes
+        ((8, n_lines, N) resident, (n_lines, 8, N) callback), geo7: the seven planes a solve takes, dP (ball_scan.py:262 with the
+        callback), t0: the coarse theta0 grid, and the host maps surf (resident only: the table index) and alpha of every line).
+        want_t0=False: no t0 and no upload of it (the local-equilibrium calls fold at their own theta0).  device_rows() does not
+        come here: its lines are chunk ranges of the cached device maps of _resident_inputs(), between two marks of its phase timer."""
+        na, n = len(self.alpha_scan), len(self.own)
+        alpha = np.tile(self.alpha_scan, n)
+        if not self._on_device:
+            geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
+            dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
+            return dict(geo=geo, geo7=[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP=dP, t0=self.theta0_scan, alpha=alpha)
+        surf = np.repeat(self._own_surf(), na)
+        r = self.ctx.fieldline_geometry(self.tables, surf, alpha, self.theta, device=self.device)
+        lines = dict(geo=r["geo"], geo7=[r["geo"][k] for k in range(7)], dP=r["dPdrho"], surf=surf, alpha=alpha)
+        if want_t0:
+            import torch
+            lines["t0"] = torch.from_numpy(self.theta0_scan).to(self.device)
+        return lines
+
+    def _line_sigma(self, surf):
+        """sigma = sign(-phiedge) of the surface of every line (surf: table indices), the sign the local-equilibrium fold takes"""
+        return np.sign(-np.asarray(self.tables.scal)[surf, 4])
+
     # -- A5: coarse scan of the surfaces this rank owns, one launch
     def coarse(self):
-        if self.tables is not None and self.device is not None and self.own:
-            import torch
-            na = len(self.alpha_scan)
-            surf = np.repeat(self._own_surf(), na)
-            r = self.ctx.fieldline_geometry(self.tables, surf, np.tile(self.alpha_scan, len(self.own)), self.theta,
-                                            device=self.device)
-            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
-            geo7 = [r["geo"][k] for k in range(7)]
-            if self.nearest:
-                out = self.ctx.gamma_scan_nearest(self.h, *geo7, r["dPdrho"], t0, SIGMA_COARSE, want_info=True)
-                nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())      # (bit 5, a tie, is informational)
-            else:
-                out = self.ctx.gamma_scan(self.h, *geo7, r["dPdrho"], t0, want_info=True, **self._certify_kw())
-                # device-pointer calls are asynchronous and return no count of flagged systems: read the info words
-                nbad = int(((out["info"] >> 16) != 0).sum().item())
-            if nbad:
-                raise IbsError("%d of %d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)"
-                               % (nbad, out["info"].numel()))
-            if self.certify:
-                self._coarse_cert = out["cert"]
-            return out["gam"].cpu().numpy().reshape(len(self.own), na, len(self.theta0_scan))
-        geos = [np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own]
-        if not geos:
+        na, nt = len(self.alpha_scan), len(self.theta0_scan)
+        if not self.own:
             self._coarse_cert = np.zeros(0, dtype=np.int32)
-            return np.zeros((0, len(self.alpha_scan), len(self.theta0_scan)))
-        geo = np.concatenate(geos, axis=0)                                 # (n_own*nalpha, 8, N)
-        dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
-        geo7 = [np.ascontiguousarray(geo[:, k]) for k in range(7)]
+            return np.zeros((0, na, nt))
+        ln = self._coarse_lines()
+        # device-pointer calls are asynchronous and return no count of flagged systems: there the info words are read
+        kw = dict(want_info=True) if self._on_device else {}
         if self.nearest:
-            r = self.ctx.gamma_scan_nearest(self.h, *geo7, dP, self.theta0_scan, SIGMA_COARSE)
+            out = self.ctx.gamma_scan_nearest(self.h, *ln["geo7"], ln["dP"], ln["t0"], SIGMA_COARSE, **kw)
         else:
-            r = self.ctx.gamma_scan(self.h, *geo7, dP, self.theta0_scan, **self._certify_kw())
-        if r.get("nbad", 0):
-            raise IbsError("%d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)" % r["nbad"])
+            out = self.ctx.gamma_scan(self.h, *ln["geo7"], ln["dP"], ln["t0"], **kw, **self._certify_kw())
+        if self._on_device:
+            _check_flags("%d of %d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)", out["info"],
+                         any_bit=not self.nearest)
+        elif out.get("nbad", 0):
+            raise IbsError("%d coarse-scan solves were flagged (status word != 0: invalid data or iteration cap)" % out["nbad"])
         if self.certify:
-            self._coarse_cert = r["cert"]
-        return np.asarray(r["gam"]).reshape(len(self.own), len(self.alpha_scan), len(self.theta0_scan))
+            self._coarse_cert = out["cert"]
+        return _host(out["gam"]).reshape(len(self.own), na, nt)
 
     def _certify_kw(self):
-        """keyword of the solver calls: nothing at all without certify (the calls are then exactly what they were)"""
+        """keyword of the solver calls: nothing at all without certify"""
         return dict(certify=True) if self.certify else {}
 
     # -- unstable modes on the coarse grid of the surfaces this rank owns, one launch
@@ -473,17 +544,9 @@ class BallooningScan:
         na, nt = len(self.alpha_scan), len(self.theta0_scan)
         if not self.own:
             return np.zeros((0, na, nt), dtype=np.int32)
-        if self.tables is not None and self.device is not None:
-            import torch
-            r = self.ctx.fieldline_geometry(self.tables, np.repeat(self._own_surf(), na), np.tile(self.alpha_scan, len(self.own)),
-                                            self.theta, device=self.device)
-            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
-            cnt = self.ctx.geo_sturm_count(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, shift)
-            return cnt.cpu().numpy().reshape(len(self.own), na, nt)
-        geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
-        dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
-        cnt = self.ctx.geo_sturm_count(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan, shift)
-        return np.asarray(cnt).reshape(len(self.own), na, nt)
+        ln = self._coarse_lines()
+        cnt = self.ctx.geo_sturm_count(self.h, *ln["geo7"], ln["dP"], ln["t0"], shift)
+        return _host(cnt).reshape(len(self.own), na, nt)
 
     # -- the s-alpha picture of the owned surfaces: shear and pressure variations of every line of the alpha grid, two launches
     def local_eq(self, eps, p, theta0=None, shift=0.0, count_only=False):
@@ -495,7 +558,7 @@ class BallooningScan:
         ONE Context.local_eq_scan call.  Returns numpy dict(gam, lam, count (n_own, nalpha, n_theta0, n_eps, n_p), gam_max, unstable
         (n_own, n_eps, n_p) = the envelope over (alpha, theta0): the largest gam and "some line has an eigenvalue above shift";
         theta0, eps, p).  count_only=True: count and unstable alone, no eigenvalue is computed.  Flagged solves raise IbsError."""
-        if self.tables is None or self.device is None:
+        if not self._on_device:
             raise ValueError("local_eq() runs on the resident path: tables= and device= are required")
         eps = np.atleast_1d(np.asarray(eps, dtype=np.float64))
         p = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -506,16 +569,10 @@ class BallooningScan:
         keys = ("count",) if count_only else ("gam", "lam", "count")
         res = dict(theta0=t0, eps=eps, p=p)
         if n:
-            surf = np.repeat(self._own_surf(), na)
-            alpha = np.tile(self.alpha_scan, n)
-            r = self.ctx.fieldline_geometry(self.tables, surf, alpha, self.theta, device=self.device)
-            sigma = np.sign(-np.asarray(self.tables.scal)[surf, 4])
-            out = self.ctx.local_eq_scan(self.theta[0], self.h, r["geo"], r["dPdrho"], alpha, sigma, var, shift=shift,
+            ln = self._coarse_lines(want_t0=False)
+            out = self.ctx.local_eq_scan(self.theta[0], self.h, ln["geo"], ln["dP"], ln["alpha"], self._line_sigma(ln["surf"]), var, shift=shift,
                                          count_only=count_only, want_info=True)
-            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())
-            if nbad:
-                raise IbsError("%d of %d local-equilibrium solves were flagged (status bits 0-1: iteration cap or invalid data)"
-                               % (nbad, out["info"].numel()))
+            _check_flags("%d of %d local-equilibrium solves were flagged (status bits 0-1: iteration cap or invalid data)", out["info"])
             res.update({k: out[k].cpu().numpy().reshape(shape) for k in keys})
         else:
             res.update({k: np.zeros(shape, dtype=np.int32 if k == "count" else np.float64) for k in keys})
@@ -539,7 +596,7 @@ class BallooningScan:
         +inf where none does, t_lo where some line is unstable at t_lo already -- the surface's first-stability limit; theta0, fixed,
         t_range, axis).  A crossing is a change of verdict between two of 64 equidistant nodes of t_range: a tangency and two
         crossings between one pair of nodes are missed.  Flagged systems (status bits 0-1) raise IbsError."""
-        if self.tables is None or self.device is None:
+        if not self._on_device:
             raise ValueError("local_eq_boundary() runs on the resident path: tables= and device= are required")
         if axis not in ("p", "eps"):
             raise ValueError("axis must be 'p' or 'eps', not %r" % (axis,))
@@ -554,16 +611,11 @@ class BallooningScan:
         rays = np.stack([*cols, np.full_like(ff, t_lo), np.full_like(ff, t_hi)], axis=1)
         res = dict(theta0=t0, fixed=fixed, t_range=(t_lo, t_hi), axis=axis)
         if n:
-            surf = np.repeat(self._own_surf(), na)
-            alpha = np.tile(self.alpha_scan, n)
-            r = self.ctx.fieldline_geometry(self.tables, surf, alpha, self.theta, device=self.device)
-            sigma = np.sign(-np.asarray(self.tables.scal)[surf, 4])
-            out = self.ctx.local_eq_boundary(self.theta[0], self.h, r["geo"], r["dPdrho"], alpha, sigma, rays, shift=shift,
+            ln = self._coarse_lines(want_t0=False)
+            out = self.ctx.local_eq_boundary(self.theta[0], self.h, ln["geo"], ln["dP"], ln["alpha"], self._line_sigma(ln["surf"]), rays, shift=shift,
                                              max_cross=max_cross, xtol=xtol, want_info=True)
-            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())
-            if nbad:
-                raise IbsError("%d of %d local-equilibrium boundary systems were flagged (status bits 0-1: pass cap or invalid data)"
-                               % (nbad, out["info"].numel()))
+            _check_flags("%d of %d local-equilibrium boundary systems were flagged (status bits 0-1: pass cap or invalid data)",
+                         out["info"])
             res.update({k: out[k].cpu().numpy().reshape(shape + (max_cross,)) for k in ("t_stable", "t_unstable", "t")})
             res.update({k: out[k].cpu().numpy().reshape(shape) for k in ("n_cross", "lo_unstable", "info")})
         else:
@@ -584,35 +636,35 @@ class BallooningScan:
             raise ValueError("envelope() maximises lam_max's growth rate: eigenpair='nearest' is not supported")
         if isinstance(n_starts, bool) or not isinstance(n_starts, (int, np.integer)) or not 1 <= n_starts <= MAX_ROW_STARTS:
             raise ValueError("n_starts must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, n_starts))
-        na, K = len(self.alpha_scan), int(n_starts)
+        K = int(n_starts)
         if not self.own:
-            z = np.zeros((0, na, K))
-            return dict(theta0=z, gam=z.copy(), node=z.astype(np.int32), n_eval=z.astype(np.int32), n_found=np.zeros((0, na), np.int32),
-                        surface=np.zeros((0, 3)))
-        if self.tables is not None and self.device is not None:
-            import torch
-            r = self.ctx.fieldline_geometry(self.tables, np.repeat(self._own_surf(), na), np.tile(self.alpha_scan, len(self.own)),
-                                            self.theta, device=self.device)
-            geo7, dP, t0 = [r["geo"][k] for k in range(7)], r["dPdrho"], torch.from_numpy(self.theta0_scan).to(self.device)
-        else:
-            geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
-            dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
-            geo7, t0 = [np.ascontiguousarray(geo[:, k]) for k in range(7)], self.theta0_scan
-        sc = self.ctx.gamma_scan(self.h, *geo7, dP, t0, want_info=True)
-        out = self.ctx.theta0_polish(self.h, *geo7, dP, t0, sc["gam"], n_starts=K, xtol=xtol, max_eval=max_eval, lam=sc["lam"],
-                                     want_info=True)
-        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
-        nbad = int(((host(sc["info"]) >> 16) != 0).sum()) + int((((host(out["info"]) >> 16) & 3) != 0).sum())
+            return self._envelope_rows(None, K, ("theta0", "gam"), "gam", "gam")
+        ln = self._coarse_lines()
+        sc = self.ctx.gamma_scan(self.h, *ln["geo7"], ln["dP"], ln["t0"], want_info=True)
+        out = self.ctx.theta0_polish(self.h, *ln["geo7"], ln["dP"], ln["t0"], sc["gam"], n_starts=K, xtol=xtol, max_eval=max_eval,
+                                     lam=sc["lam"], want_info=True)
+        nbad = int(_flagged(_host(sc["info"]), any_bit=True).sum()) + int(_flagged(_host(out["info"])).sum())
         if nbad:
             raise IbsError("%d solves of the envelope were flagged (status bits 0-1: iteration cap or invalid data)" % nbad)
-        n = len(self.own)
-        res = {k: host(out[k]).reshape(n, na, K) for k in ("theta0", "gam", "node", "n_eval")}
-        res["n_found"] = host(out["n_found"]).reshape(n, na)
-        flat = np.where(np.isnan(res["gam"]), -np.inf, res["gam"]).reshape(n, na * K)
+        return self._envelope_rows(out, K, ("theta0", "gam"), "gam", "gam")
+
+    def _envelope_rows(self, out, K, keys, rank, value):
+        """the result of a theta0 polish call `out` with K slots per line of the coarse grid (None: no owned surface) as numpy:
+        out's float arrays `keys`, node and n_eval as (n_own, nalpha, K), n_found (n_own, nalpha), and surface (n_own, 3) = (theta0*,
+        alpha, out[value]) of the slot with the largest out[rank] of every surface (NaN ranks last), first maximum in (alpha, slot)
+        order"""
+        n, na = len(self.own), len(self.alpha_scan)
+        if out is None:
+            z = np.zeros((0, na, K))
+            return dict({k: z.copy() for k in keys}, node=z.astype(np.int32), n_eval=z.astype(np.int32),
+                        n_found=np.zeros((0, na), np.int32), surface=np.zeros((0, 3)))
+        res = {k: _host(out[k]).reshape(n, na, K) for k in keys + ("node", "n_eval")}
+        res["n_found"] = _host(out["n_found"]).reshape(n, na)
+        flat = np.where(np.isnan(res[rank]), -np.inf, res[rank]).reshape(n, na * K)
         best = np.argmax(flat, axis=1)                                           # (first maximum)
         rows = np.arange(n)
         res["surface"] = np.stack([res["theta0"].reshape(n, -1)[rows, best], self.alpha_scan[best // K],
-                                   res["gam"].reshape(n, -1)[rows, best]], axis=1)
+                                   res[value].reshape(n, -1)[rows, best]], axis=1)
         return res
 
     # -- the top of the spectrum on the coarse grid of the surfaces this rank owns, one launch
@@ -625,26 +677,13 @@ class BallooningScan:
         if not self.own:
             z = np.zeros((0, na, nt, int(n_modes)))
             return dict(lam=z, gam=z.copy(), cluster=z.astype(bool))
-        if self.tables is not None and self.device is not None:
-            import torch
-            r = self.ctx.fieldline_geometry(self.tables, np.repeat(self._own_surf(), na), np.tile(self.alpha_scan, len(self.own)),
-                                            self.theta, device=self.device)
-            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
-            out = self.ctx.gamma_scan_modes(self.h, *[r["geo"][k] for k in range(7)], r["dPdrho"], t0, n_modes, want_info=True)
-            out = {k: out[k].cpu().numpy() for k in ("lam", "gam", "info")}
-        else:
-            geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
-            dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
-            out = self.ctx.gamma_scan_modes(self.h, *[np.ascontiguousarray(geo[:, k]) for k in range(7)], dP, self.theta0_scan, n_modes,
-                                            want_info=True)
-        status = np.asarray(out["info"]) >> 16
-        nbad = int(((status & 3) != 0).sum())
-        if nbad:
-            raise IbsError("%d of %d modes of the coarse grid were flagged (status bits 0-1: iteration cap or invalid data)"
-                           % (nbad, status.size))
+        ln = self._coarse_lines()
+        out = self.ctx.gamma_scan_modes(self.h, *ln["geo7"], ln["dP"], ln["t0"], n_modes, want_info=True)
+        out = {k: _host(out[k]) for k in ("lam", "gam", "info")}
+        _check_flags("%d of %d modes of the coarse grid were flagged (status bits 0-1: iteration cap or invalid data)", out["info"])
         shape = (len(self.own), na, nt, -1)
-        return dict(lam=np.asarray(out["lam"]).reshape(shape), gam=np.asarray(out["gam"]).reshape(shape),
-                    cluster=((status & CLUSTER_BIT) != 0).reshape(shape))
+        return dict(lam=out["lam"].reshape(shape), gam=out["gam"].reshape(shape),
+                    cluster=(((out["info"] >> 16) & CLUSTER_BIT) != 0).reshape(shape))
 
     # -- marginal stability on the coarse grid of the surfaces this rank owns, one launch
     def _marginal_coarse(self):
@@ -653,48 +692,26 @@ class BallooningScan:
         na, nt = len(self.alpha_scan), len(self.theta0_scan)
         if not self.own:
             return dict(tab=np.zeros((0, na, nt)))
-        if self.tables is not None and self.device is not None:
-            import torch
-            surf = np.repeat(self._own_surf(), na)
-            r = self.ctx.fieldline_geometry(self.tables, surf, np.tile(self.alpha_scan, len(self.own)), self.theta,
-                                            device=self.device)
-            t0 = torch.from_numpy(self.theta0_scan).to(self.device)
-            geo7 = [r["geo"][k] for k in range(7)]
-            out = self.ctx.marginal_scan(self.h, *geo7, r["dPdrho"], t0, want_info=True)
-            nbad = int((((out["info"] >> 16) & 3) != 0).sum().item())          # (bit 8, an infinite margin, is informational)
-            if nbad:
-                raise IbsError("%d of %d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)"
-                               % (nbad, out["info"].numel()))
-            return dict(tab=out["scale"].cpu().numpy().reshape(len(self.own), na, nt), geo7=geo7, dP=r["dPdrho"], t0=t0, mu=out["mu"])
-        geo = np.concatenate([np.asarray(self.fieldlines(self.rho_arr[k], self.alpha_scan)) for k in self.own], axis=0)
-        dP = -0.5 * np.mean((geo[:, 2] - geo[:, 7]) * geo[:, 0] ** 2, axis=1)   # ball_scan.py:262
-        geo7 = [np.ascontiguousarray(geo[:, k]) for k in range(7)]
-        out = self.ctx.marginal_scan(self.h, *geo7, dP, self.theta0_scan)
-        if out.get("nbad", 0):
-            raise IbsError("%d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)" % out["nbad"])
-        return dict(tab=np.asarray(out["scale"]).reshape(len(self.own), na, nt), geo7=geo7, dP=dP, t0=self.theta0_scan, mu=out["mu"])
+        ln = self._coarse_lines()
+        if self._on_device:
+            out = self.ctx.marginal_scan(self.h, *ln["geo7"], ln["dP"], ln["t0"], want_info=True)
+            _check_flags("%d of %d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)", out["info"])
+        else:
+            out = self.ctx.marginal_scan(self.h, *ln["geo7"], ln["dP"], ln["t0"])
+            if out.get("nbad", 0):
+                raise IbsError("%d marginal-stability solves were flagged (status bits 0-1: iteration cap or invalid data)" % out["nbad"])
+        return dict(tab=_host(out["scale"]).reshape(len(self.own), na, nt), geo7=ln["geo7"], dP=ln["dP"], t0=ln["t0"], mu=out["mu"])
 
     def _marginal_envelope(self, co, K, xtol, max_eval):
         """marginal_envelope() on the coarse scan co (_marginal_coarse): the one polish call and its per-surface best slot"""
-        na, n = len(self.alpha_scan), len(self.own)
-        if not n:
-            z = np.zeros((0, na, K))
-            return dict(theta0=z, mu=z.copy(), scale=z.copy(), node=z.astype(np.int32), n_eval=z.astype(np.int32),
-                        n_found=np.zeros((0, na), np.int32), surface=np.zeros((0, 3)))
+        keys = ("theta0", "mu", "scale")
+        if not self.own:
+            return self._envelope_rows(None, K, keys, "mu", "scale")
         out = self.ctx.marginal_theta0_polish(self.h, *co["geo7"], co["dP"], co["t0"], co["mu"], n_starts=K, xtol=xtol,
                                               max_eval=max_eval, want_info=True)
-        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
-        nbad = int((((host(out["info"]) >> 16) & 3) != 0).sum())
-        if nbad:
-            raise IbsError("%d solves of the margin's envelope were flagged (status bits 0-1: iteration cap or invalid data)" % nbad)
-        res = {k: host(out[k]).reshape(n, na, K) for k in ("theta0", "mu", "scale", "node", "n_eval")}
-        res["n_found"] = host(out["n_found"]).reshape(n, na)
-        flat = np.where(np.isnan(res["mu"]), -np.inf, res["mu"]).reshape(n, na * K)
-        best = np.argmax(flat, axis=1)                                           # (first maximum)
-        rows = np.arange(n)
-        res["surface"] = np.stack([res["theta0"].reshape(n, -1)[rows, best], self.alpha_scan[best // K],
-                                   res["scale"].reshape(n, -1)[rows, best]], axis=1)
-        return res
+        _check_flags("%d solves of the margin's envelope were flagged (status bits 0-1: iteration cap or invalid data)",
+                     _host(out["info"]))
+        return self._envelope_rows(out, K, keys, "mu", "scale")
 
     # -- every line's margin maximised over theta0 between the nodes of the coarse grid, two launches
     def marginal_envelope(self, n_starts=1, xtol=1e-5, max_eval=32):
@@ -724,7 +741,7 @@ class BallooningScan:
         refined beside it (the rounds' geometry runs in one form of the geometry kernel: MARGINAL_GEO_LPP).  A surface whose coarse table is all +inf stays at its
         start point with scale = inf and no evaluation (its gradient is 0).
         jac="reference" (the default): the rounds take d s* / d alpha from the del_alpha difference of the rows, three lines per point
-        (ibs_marginal_obj_w_grad_f64), exactly as before the option existed.  jac="exact_tangent" (tables= and device= required, else
+        (ibs_marginal_obj_w_grad_f64).  jac="exact_tangent" (tables= and device= required, else
         IbsError; any other value is refused): d s* / d alpha is the derivative, from ONE line per point -- every round is one forward
         geometry launch (in the same pinned form), one alpha-tangent launch (ibs_fieldline_geometry_dalpha_f64) and one point launch
         (ibs_marginal_obj_w_grad_tangent_f64); the dict has the same keys and dscale is then exact in both variables, so the refined
@@ -737,17 +754,18 @@ class BallooningScan:
         n_found on copy slot 0 and are not evaluated; a table whose maximum mu is 0 stays at scale = inf with no evaluation.  The
         winner is the smallest refined scale, slot 0 on ties: scale, alpha, theta0, start, dscale, dPdrho are the winner's, and the
         dict gains candidates (n_own, K, 3) = (scale, alpha, theta0) of every slot and n_found (n_own,); evals and task are then
-        (n_own, K).  With refine=False the starts are not used.  n_starts=1 (the default) makes exactly the calls it made before
-        the option existed.
+        (n_own, K).  With refine=False the starts are not used.
         theta0_polish=True (n_starts=1, else ValueError): every line's mu is first maximised over theta0 between the nodes
         (marginal_envelope's polish call on the lines of the coarse scan, one slot per line) and every surface starts at the crest
         of its best line -- marginal_envelope's `surface` -- in place of the best node; refine=False reports that point.  The
-        envelope is left in .last_marginal_envelope.  theta0_polish=False (the default) makes exactly the calls it made before."""
+        envelope is left in .last_marginal_envelope.
+        The calls every combination of these options makes are held to those of the file's previous version by
+        tools/bitwise_vs_parent.py --parent-scan."""
         tangent = check_marginal_jac(jac) == "exact_tangent"
         K = check_n_starts(n_starts)
         if theta0_polish and K != 1:
             raise ValueError("theta0_polish=True takes n_starts=1")
-        if tangent and (self.tables is None or self.device is None):
+        if tangent and not self._on_device:
             raise IbsError("marginal(jac='exact_tangent') needs tables= and device=: a host geometry callable has no alpha-tangent")
         na, nt = len(self.alpha_scan), len(self.theta0_scan)
         co = self._marginal_coarse()
@@ -773,54 +791,58 @@ class BallooningScan:
 
     # -- the margin's objective at X[q] = (alpha, theta0) of owned surface own_idx[q], all at once: one geometry step (the three
     # lines of every point: the geometry kernel on `device`, staged through the host without one, or the host callable) and one
-    # ibs_marginal_obj_w_grad_f64 launch; numpy out
-    def _marginal_points(self, own_idx, X):
-        n, N, d = len(own_idx), len(self.theta), self.del_alpha
-        al = np.stack([X[:, 0] - 0.5 * d, X[:, 0], X[:, 0] + 0.5 * d], axis=1)
+    # ibs_marginal_obj_w_grad_f64 launch; numpy out.  tangent (jac="exact_tangent"): from ONE line per point -- the points' own
+    # lines, their alpha-tangent, then one ibs_marginal_obj_w_grad_tangent_f64 launch
+    def _marginal_points(self, own_idx, X, tangent=False):
+        # the geometry kernel picks its form from the size of the batch, and the forms differ in the last bits of the rows: left to
+        # that, a surface's trajectory (and its refined point, to 1e-10) would depend on how many others run beside it.  One form
+        # for every round (pinned) makes the refinement of a surface the same in any batch, bit for bit
         if self.tables is not None:
-            surf = np.repeat(self._own_surf()[own_idx], 3)
-            # the geometry kernel picks its form from the size of the batch, and the forms differ in the last bits of the rows: left
-            # to that, a surface's trajectory (and its refined point, to 1e-10) would depend on how many others run beside it.  One
-            # form for every round makes the refinement of a surface the same in any batch, bit for bit
-            with self.ctx.option_default("geo_lpp", MARGINAL_GEO_LPP):
-                r = self.ctx.fieldline_geometry(self.tables, surf, al.reshape(-1), self.theta, device=self.device)
-            if self.device is not None:
-                import torch
-                geo = r["geo"].view(8, n, 3, N).permute(1, 2, 0, 3).contiguous()
-                t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
-            else:
-                geo = np.ascontiguousarray(r["geo"].reshape(8, n, 3, N).transpose(1, 2, 0, 3))
-                t0 = np.ascontiguousarray(X[:, 1])
+            geo, geo_da, t0 = self._point_lines(self._own_surf()[own_idx], X, tangent, pinned=True)
         else:
-            geo = np.stack([np.asarray(self.fieldlines(self.rho_arr[self.own[k]], al[q])) for q, k in enumerate(own_idx)])
+            d = self.del_alpha
+            geo = np.stack([np.asarray(self.fieldlines(self.rho_arr[self.own[k]], np.array([a - 0.5 * d, a, a + 0.5 * d])))
+                            for a, k in zip(X[:, 0], own_idx)])
             t0 = np.ascontiguousarray(X[:, 1])
-        out = self.ctx.marginal_obj_w_grad(self.h, geo, t0, d, want_grad=True, want_info=True)
-        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
-        out = {key: host(v) for key, v in out.items() if key != "nbad"}
-        bad = (((out["info"] >> 16) & 3) != 0) | ~np.isfinite(out["val"]) | ~np.isfinite(out["jac"]).all(axis=1)
+        if tangent:
+            out = self.ctx.marginal_obj_w_grad_tangent(self.h, geo, geo_da, t0, want_grad=True, want_info=True)
+        else:
+            out = self.ctx.marginal_obj_w_grad(self.h, geo, t0, self.del_alpha, want_grad=True, want_info=True)
+        out = {key: _host(v) for key, v in out.items() if key != "nbad"}
+        bad = _flagged(out["info"]) | ~np.isfinite(out["val"]) | ~np.isfinite(out["jac"]).all(axis=1)
         if bad.any():
             raise IbsError("%d of %d marginal-stability solves of the refinement were flagged (status bits 0-1: iteration cap or "
-                           "invalid data) or gave a non-finite objective" % (int(bad.sum()), n))
+                           "invalid data) or gave a non-finite objective" % (int(bad.sum()), len(own_idx)))
         return out
 
-    # -- the same from ONE line per point (jac="exact_tangent"): the geometry of the points' own lines in the pinned form, their
-    # alpha-tangent, then one ibs_marginal_obj_w_grad_tangent_f64 launch; numpy out
-    def _marginal_points_tangent(self, own_idx, X):
-        import torch
-        n = len(own_idx)
-        surf = np.ascontiguousarray(self._own_surf()[own_idx])
-        al = np.ascontiguousarray(X[:, 0])
-        with self.ctx.option_default("geo_lpp", MARGINAL_GEO_LPP):
-            r = self.ctx.fieldline_geometry(self.tables, surf, al, self.theta, device=self.device)
-        ra = self.ctx.fieldline_geometry_dalpha(self.tables, surf, al, self.theta, device=self.device)
-        t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
-        out = self.ctx.marginal_obj_w_grad_tangent(self.h, r["geo"], ra["geo_da"], t0, want_grad=True, want_info=True)
-        out = {key: v.cpu().numpy() for key, v in out.items() if key != "nbad"}
-        bad = (((out["info"] >> 16) & 3) != 0) | ~np.isfinite(out["val"]) | ~np.isfinite(out["jac"]).all(axis=1)
-        if bad.any():
-            raise IbsError("%d of %d marginal-stability solves of the refinement were flagged (status bits 0-1: iteration cap or "
-                           "invalid data) or gave a non-finite objective" % (int(bad.sum()), n))
-        return out
+    def _point_lines(self, surf, X, tangent, pinned=False):
+        """the lines of a batch of points X[q] = (alpha, theta0) on the surfaces of table index surf[q], by the geometry kernel: ->
+        (geo, geo_da, t0) on `device` (numpy where the scan has tables but no device).  tangent False: the three lines at alpha -
+        del_alpha / 2, alpha, alpha + del_alpha / 2 of every point, geo (n, 3, 8, N), geo_da None.  tangent True: the point's own
+        line, geo (8, n, N), and its alpha-tangent planes geo_da.  pinned: the forward launch runs in the geometry kernel's form
+        MARGINAL_GEO_LPP whatever the size of the batch."""
+        import contextlib
+        n, N, d = len(surf), len(self.theta), self.del_alpha
+        form = self.ctx.option_default("geo_lpp", MARGINAL_GEO_LPP) if pinned else contextlib.nullcontext()
+        geo_da = None
+        if tangent:
+            surf, al = np.ascontiguousarray(surf), np.ascontiguousarray(X[:, 0])
+            with form:
+                geo = self.ctx.fieldline_geometry(self.tables, surf, al, self.theta, device=self.device)["geo"]
+            geo_da = self.ctx.fieldline_geometry_dalpha(self.tables, surf, al, self.theta, device=self.device)["geo_da"]
+        else:
+            al = np.stack([X[:, 0] - 0.5 * d, X[:, 0], X[:, 0] + 0.5 * d], axis=1).reshape(-1)
+            with form:
+                geo = self.ctx.fieldline_geometry(self.tables, np.repeat(surf, 3), al, self.theta, device=self.device)["geo"]
+            if self.device is not None:
+                geo = geo.view(8, n, 3, N).permute(1, 2, 0, 3).contiguous()
+            else:
+                geo = np.ascontiguousarray(geo.reshape(8, n, 3, N).transpose(1, 2, 0, 3))
+        t0 = np.ascontiguousarray(X[:, 1])
+        if self.device is not None:
+            import torch
+            t0 = torch.from_numpy(t0).to(self.device)
+        return geo, geo_da, t0
 
     def _marginal_refine(self, res, maxiter, ftol, gtol, tangent=False):
         """the lockstep loop of refine_batched on the margin's objective, from the first minimum of every coarse table"""
@@ -835,38 +857,13 @@ class BallooningScan:
         """the loop itself on n points: point q belongs to owned surface own_idx[q] (repeats allowed) and starts at start[q]; points
         that are not `active` are not moved.  Every round is one `points` call on the points still running, and one more on all n
         fills dict(x (n, 2), evals, task (n,), rounds, scale, dscale, dPdrho)."""
-        points = self._marginal_points_tangent if tangent else self._marginal_points
-        import ctypes as C
-        from . import _lib
-        lib = _lib.lib()
-        lo = np.array([0.0, 0.0]); hi = np.array([np.pi, 0.5 * np.pi])
-        n = len(own_idx)
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        x = np.clip(start, lo, hi)
-        states = [C.create_string_buffer(lib.ibs_lbfgsb2_state_bytes()) for _ in range(n)]
-        for k in range(n):
-            lib.ibs_lbfgsb2_init(states[k], p(x[k]), p(lo), p(hi), float(ftol), float(gtol), int(maxiter), 20)
-        active = np.array(active, dtype=bool)
-        evals = np.zeros(n, dtype=np.int32)
-        task = np.full(n, 10, dtype=np.int32)
-        rounds = 0
-        while active.any():
-            idx = np.nonzero(active)[0]
-            r = points(own_idx[idx], x[idx])
-            rounds += 1
-            evals[idx] += 1
-            for q, k in enumerate(idx):
-                gk = np.ascontiguousarray(r["jac"][q], dtype=np.float64)
-                if not lib.ibs_lbfgsb2_step(states[k], float(r["val"][q]), p(gk), p(x[k])):
-                    active[k] = False
-        for k in range(n):
-            if evals[k]:
-                fk = C.c_double(0.0); cnt = np.zeros(5, dtype=np.int32)
-                lib.ibs_lbfgsb2_result(states[k], p(x[k]), C.byref(fk), p(cnt))
-                task[k] = cnt[2]
-        out = dict(x=x, evals=evals, task=task, rounds=rounds)
-        if n:
-            fin = points(own_idx, x)
+        def evaluate(idx, X):
+            r = self._marginal_points(own_idx[idx], X, tangent)
+            return r["val"], r["jac"]
+        r = _lockstep(evaluate, start, active, maxiter, ftol, gtol)
+        out = dict(x=r["x"], evals=r["evals"], task=r["task"], rounds=r["rounds"])
+        if len(own_idx):
+            fin = self._marginal_points(own_idx, r["x"], tangent)
             out.update(scale=fin["scale"], dscale=fin["dscale"], dPdrho=fin["dPdrho"])
         else:
             out.update(scale=np.zeros(0), dscale=np.zeros((0, 2)), dPdrho=np.zeros(0))
@@ -877,7 +874,7 @@ class BallooningScan:
         all surfaces through _marginal_refine_points at once, the winner per surface"""
         n, na, nt = len(self.own), len(self.alpha_scan), len(self.theta0_scan)
         start, n_found = np.zeros((n, K, 2)), np.zeros(n, dtype=np.int32)
-        if n and self.tables is not None and self.device is not None:
+        if n and self._on_device:
             import torch
             pk = self.ctx.scan_peaks(torch.from_numpy(self.alpha_scan).to(self.device), co["t0"], co["mu"].reshape(n, na, nt), K,
                                      want_found=True)
@@ -914,9 +911,8 @@ class BallooningScan:
             val, jac, r = self.ctx.obj_w_grad_exact_tangent(self.h, geo, geo_da, t0, sigma=sigma, want_info=True)
         else:
             val, jac, r = self.ctx.obj_w_grad_exact(self.h, geo, t0, self.del_alpha, sigma=sigma, want_info=True)
-        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
-        val, jac = host(val), host(jac)
-        vst = (host(r["info"]) >> EXACT_VJP_SHIFT) & 3
+        val, jac = _host(val), _host(jac)
+        vst = (_host(r["info"]) >> EXACT_VJP_SHIFT) & 3
         if np.any(vst):
             raise IbsError(vjp_status_message(int(np.sum(vst & 1)), int(np.sum(vst >> 1))))
         bad = ~(np.isfinite(val) & np.isfinite(jac).all(axis=1))
@@ -969,77 +965,39 @@ class BallooningScan:
         sigma[k], ibs_obj_w_grad_nearest_f64; jac="exact": ibs_obj_w_grad_exact_f64, for either eigenpair; jac="exact_tangent": the
         geometry of the n lines themselves by the row kernels, their alpha-tangent, then ibs_obj_w_grad_exact_tangent_f64).
         Returns (val (n,), jac (n, 2))."""
-        n = len(surf_idx)
-        d = self.del_alpha
-        if self.tangent:
-            import torch
-            al = np.ascontiguousarray(X[:, 0])
-            r = self.ctx.fieldline_geometry(self.tables, surf_idx, al, self.theta, device=self.device)
-            ra = self.ctx.fieldline_geometry_dalpha(self.tables, surf_idx, al, self.theta, device=self.device)
-            t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
-            sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device) if self.nearest else None
-            return self._obj_exact(r["geo"], t0, sg, geo_da=ra["geo_da"])
-        al = np.stack([X[:, 0] - 0.5 * d, X[:, 0], X[:, 0] + 0.5 * d], axis=1).reshape(-1)
-        r = self.ctx.fieldline_geometry(self.tables, np.repeat(surf_idx, 3), al, self.theta, device=self.device)
-        N = len(self.theta)
-        geo = r["geo"].view(8, n, 3, N).permute(1, 2, 0, 3).contiguous()
         import torch
-        t0 = torch.from_numpy(np.ascontiguousarray(X[:, 1])).to(self.device)
+        geo, geo_da, t0 = self._point_lines(surf_idx, X, self.tangent)
+        sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device) if self.nearest else None
         if self.exact:
-            sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device) if self.nearest else None
-            return self._obj_exact(geo, t0, sg)
+            return self._obj_exact(geo, t0, sg, geo_da=geo_da)
         if self.nearest:
-            sg = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)).to(self.device)
-            val, jac = self.ctx.obj_w_grad_nearest(self.h, geo, t0, sg, d)
+            val, jac = self.ctx.obj_w_grad_nearest(self.h, geo, t0, sg, self.del_alpha)
         else:
-            val, jac = self.ctx.obj_w_grad(self.h, geo, t0, d)
+            val, jac = self.ctx.obj_w_grad(self.h, geo, t0, self.del_alpha)
         return val.cpu().numpy(), jac.cpu().numpy()
 
     def refine_batched(self, starts, maxiter=30, ftol=5.0e-11, gtol=2.0e-8, sigma0=None, surf_idx=None):
         """the per-surface L-BFGS-B of ball_scan.py:307-314 (same bounds, tolerances and iteration cap) for every owned
-        surface at once, driven from the host: one optimizer state per surface (csrc/ibs_lbfgsb2.hpp through the C ABI
-        ibs_lbfgsb2_*), and every round ONE batched geometry + objective launch for the surfaces still running.
-        The host-driven form of refine_device(), which it is tested against.
+        surface at once, driven from the host (_lockstep): every round ONE batched geometry + objective launch for the surfaces
+        still running.  The host-driven form of refine_device(), which it is tested against.
         starts: (n, 2); sigma0 (n,): the shifts of eigenpair="nearest"; surf_idx (n,): the table index of every point's surface
         (None: point k lies on owned surface k -- with it n points need not be n surfaces: the multi-start refinement).
-        Returns (x_opt (n, 2), f_opt (n,) = -gam, rounds)."""
-        import ctypes as C
-        from . import _lib
-        lib = _lib.lib()
-        lo = np.array([0.0, 0.0]); hi = np.array([np.pi, 0.5 * np.pi])
+        Returns (x_opt (n, 2), f_opt (n,) = -gam, rounds); jac="exact*" leaves the evaluations per point in ._batched_evals."""
         surf = self._own_surf() if surf_idx is None else np.ascontiguousarray(surf_idx, dtype=np.int32)
-        n = len(surf)
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        x = np.clip(np.asarray(starts, dtype=np.float64).reshape(n, 2), lo, hi)
-        states = [C.create_string_buffer(lib.ibs_lbfgsb2_state_bytes()) for _ in range(n)]
-        for k in range(n):
-            lib.ibs_lbfgsb2_init(states[k], p(x[k]), p(lo), p(hi), float(ftol), float(gtol), int(maxiter), 20)
-        active = np.ones(n, dtype=bool)
-        rounds = 0
-        if self.exact:
-            self._batched_evals = np.zeros(n, dtype=np.int32)   # evaluations per surface of this call (diagnostic)
-        while active.any():
-            idx = np.nonzero(active)[0]
+
+        def evaluate(idx, X):
             if not self.nearest:
-                f, g = self.batched_obj_w_grad(surf[idx], x[idx])
-            else:
-                f, g = self.batched_obj_w_grad(surf[idx], x[idx], np.asarray(sigma0)[idx])
-                if not (np.all(np.isfinite(f)) and np.all(np.isfinite(g))):
-                    raise IbsError("%d objective solves of the refinement were flagged (invalid data or iteration cap)"
-                                   % int(np.sum(~(np.isfinite(f) & np.isfinite(g).all(axis=1)))))
-            rounds += 1
-            if self.exact:
-                self._batched_evals[idx] += 1
-            for q, k in enumerate(idx):
-                gk = np.ascontiguousarray(g[q], dtype=np.float64)
-                if not lib.ibs_lbfgsb2_step(states[k], float(f[q]), p(gk), p(x[k])):
-                    active[k] = False
-        fo = np.empty(n)
-        for k in range(n):
-            fk = C.c_double(0.0)
-            lib.ibs_lbfgsb2_result(states[k], p(x[k]), C.byref(fk), None)
-            fo[k] = fk.value
-        return x, fo, rounds
+                return self.batched_obj_w_grad(surf[idx], X)
+            f, g = self.batched_obj_w_grad(surf[idx], X, np.asarray(sigma0)[idx])
+            if not (np.all(np.isfinite(f)) and np.all(np.isfinite(g))):
+                raise IbsError("%d objective solves of the refinement were flagged (invalid data or iteration cap)"
+                               % int(np.sum(~(np.isfinite(f) & np.isfinite(g).all(axis=1)))))
+            return f, g
+        r = _lockstep(evaluate, np.asarray(starts, dtype=np.float64).reshape(len(surf), 2), np.ones(len(surf), dtype=bool), maxiter,
+                      ftol, gtol)
+        if self.exact:
+            self._batched_evals = r["evals"]   # evaluations per surface of this call (diagnostic)
+        return r["x"], r["f"], r["rounds"]
 
     def refine_device(self, starts, maxiter=30, ftol=5.0e-11, gtol=2.0e-8):
         """the same maximisation with the L-BFGS-B state machines on the device as well (ibs_refine_f64): no host
@@ -1086,10 +1044,17 @@ class BallooningScan:
 
     def device_rows(self, refine=True, phases=None, chunks=None, fill=None):
         """(theta0*, alpha*, gam) of the owned surfaces as an (n_own, 3) DEVICE tensor + a device scalar counting what went
-        wrong (flagged solves, non-finite maxima): geometry -> coarse scan with the fused per-surface first maximum
-        (ibs_gamma_scan_argmax_f64) -> start points on the device (ibs_scan_starts_f64) -> L-BFGS-B per surface on the device
-        (ibs_refine_f64 on device pointers) -> final geometry + solve, one line per point (ibs_gamma_points_f64).  Nothing
-        returns to the host in between.
+        wrong (flagged solves, non-finite maxima).  The one sequence of every mode: per chunk geometry -> coarse stage
+        (_coarse_stage: the scan, certified and re-closed with certify=True) -> pick (_pick_starts: n_starts points per surface),
+        then refinement of all n_own n_starts points (ibs_refine_f64 on device pointers; the host-driven refine_batched for
+        eigenpair="nearest", jac="exact*" and N > 2050, which ibs_refine_f64 does not cover) -> final geometry + solve, one line per
+        point -> select (n_starts > 1: every surface's best candidate, slot 0 on ties, by ibs_surface_argmax_pack_f64 and a device
+        gather; .last_candidates, .last_peaks) -> bookkeeping.  Nothing returns to the host in between beyond what the host-driven
+        refinement does; bad counts the flagged solves of ALL candidates and a non-finite coarse maximum once per surface.
+        refine=False: the coarse pick itself (slot 0).  The stages by mode:
+        eigenpair="max": coarse scan with the fused per-surface first maximum (ibs_gamma_scan_argmax_f64) -> start points on the
+        device (ibs_scan_starts_f64) -> L-BFGS-B per surface on the device -> final solve (ibs_gamma_points_f64); any status bit
+        fails a solve.
         eigenpair="nearest": the coarse scan with the eigenpair nearest 1.0 (ibs_gamma_scan_nearest_f64) -> per-surface first
         maximum (ibs_surface_argmax_pack_f64) -> start points and each surface's shift 1.3 |max| + 0.05 (ibs_scan_starts_f64) ->
         the host-driven L-BFGS-B (refine_batched: one geometry + ibs_obj_w_grad_nearest_f64 launch per round) -> final geometry +
@@ -1107,10 +1072,8 @@ class BallooningScan:
         n = len(self.own)
         if n == 0:
             return torch.empty((0, 3), dtype=torch.float64, device=dev), torch.zeros((), dtype=torch.float64, device=dev)
-        if self.n_starts > 1:
-            return self._device_rows_multi(refine, phases, chunks, fill)
         res = self._resident_inputs()
-        na = len(self.alpha_scan)
+        na, K = len(self.alpha_scan), self.n_starts
         ev = {}
 
         def mark(name):
@@ -1118,138 +1081,10 @@ class BallooningScan:
                 e = torch.cuda.Event(enable_timing=True); e.record(); ev.setdefault(name, []).append(e)
         res["n_bad"].zero_()
         chunks = chunks or [(0, n)]
-        start = torch.empty((n, 2), dtype=torch.float64, device=dev)
-        gmax = torch.empty((n,), dtype=torch.float64, device=dev)
-        sig0 = torch.empty((n,), dtype=torch.float64, device=dev) if self.nearest else None
         bad = res["n_bad"][0] * 0
-        ccount = torch.zeros(3, dtype=torch.float64, device=dev) if self.certify else None
+        self._cert_dev = torch.zeros(3, dtype=torch.float64, device=dev) if self.certify else None
         t_fill = 0.0
-        envs = []
-        for c0, c1 in chunks:
-            if fill is not None:
-                t0 = time.perf_counter(); fill(c0, c1); t_fill += time.perf_counter() - t0
-            mark("g0")
-            geo = ctx.fieldline_geometry(self.tables, res["surf"][c0 * na:c1 * na], res["al"][c0 * na:c1 * na], res["th"], device=dev)
-            mark("g1")
-            if self.nearest:
-                sc = ctx.gamma_scan_nearest(self.h, *[geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], SIGMA_COARSE,
-                                            want_info=True)
-                sc["pack"] = ctx.surface_argmax_pack(sc["gam"].view(c1 - c0, -1))
-                st, sg = ctx.scan_starts(res["alpha"], res["t0"], sc["pack"], res["n_bad"], want_sigma0=True)
-                sig0[c0:c1] = sg
-                flagged = ((sc["info"] >> 16) & 3) != 0
-            else:
-                sc = ctx.gamma_scan_argmax(self.h, [geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], c1 - c0)
-                if self.certify:
-                    # the table's eigenvalues are certified and re-closed in place, the per-surface maximum taken again from it
-                    g7 = [geo["geo"][k] for k in range(7)]
-                    cert = ctx.certify_scan(self.h, *g7, geo["dPdrho"], res["t0"], sc["lam"])
-                    ctx.reclose_scan(self.h, *g7, geo["dPdrho"], res["t0"], cert, sc["lam"], sc["gam"])
-                    sc["pack"] = ctx.surface_argmax_pack(sc["gam"].view(c1 - c0, -1))
-                    ccount = ccount + self._cert_counts(cert)
-                st = ctx.scan_starts(res["alpha"], res["t0"], sc["pack"], res["n_bad"])
-                flagged = (sc["info"] >> 16) != 0
-            gm = sc["pack"][:, 0]
-            if self.theta0_polish:
-                # every line's crest between the nodes; the surface's start is the first maximum of gam_env over its lines
-                env = ctx.theta0_polish(self.h, *[geo["geo"][k] for k in range(7)], geo["dPdrho"], res["t0"], sc["gam"], lam=sc["lam"],
-                                        want_info=True)
-                envs.append(env)
-                ge = torch.nan_to_num(env["gam"].view(c1 - c0, na), nan=-float("inf"))
-                gm = ge.max(dim=1).values
-                col = torch.arange(na, device=dev).expand_as(ge)
-                first = torch.where(ge == gm[:, None], col, na).min(dim=1).values.clamp(max=na - 1)
-                ok = torch.isfinite(gm) & (gm != 0.0)                              # (else the start scan_starts gave: (0, 0))
-                t_star = env["theta0"].view(c1 - c0, na).gather(1, first[:, None])[:, 0]
-                st = torch.where(ok[:, None], torch.stack([res["alpha"][first], t_star], dim=1), st)
-                gm = torch.where(ok, gm, sc["pack"][:, 0])
-                flagged = torch.cat([flagged.view(-1), (((env["info"] >> 16) & 3) != 0).view(-1)])
-            mark("s1")
-            if len(chunks) == 1:
-                start, gmax = st, gm
-            else:
-                start[c0:c1] = st; gmax[c0:c1] = gm
-            bad = bad + flagged.sum()
-        if envs:
-            self.last_envelope = {k: torch.cat([e[k] for e in envs]) for k in envs[0] if k != "nbad"}
-        mark("r0")
-        if refine and self.nearest:
-            # ibs_refine_f64 has no nearest-sigma form: the host-driven state machines, one geometry + ibs_obj_w_grad_nearest_f64
-            # launch per round at each surface's shift
-            xh, fh, rounds = self.refine_batched(start.cpu().numpy(), sigma0=sig0.cpu().numpy())
-            xo = torch.from_numpy(xh).to(dev)
-            mark("r1")
-            xa, xt = xo[:, 0].contiguous(), xo[:, 1].contiguous()
-            gf = ctx.fieldline_geometry(self.tables, res["pt_surf"], xa, res["th"], device=dev)
-            fin = ctx.gamma_points_nearest(self.h, *[gf["geo"][k] for k in range(7)], gf["dPdrho"], xt, SIGMA_FINAL, want_info=True)
-            rows = torch.stack([xt, xa, fin["gam"]], dim=1)
-            bad = bad + (((fin["info"] >> 16) & 3) != 0).sum()
-            self.last_refine = dict(n_evals=self._batched_evals if self.exact else None, rounds=rounds)
-        elif refine:
-            if len(self.theta) > 2050 or self.exact:
-                # (jac="exact": ibs_refine_f64 has no exact form -- refine_batched with one ibs_obj_w_grad_exact_f64 launch per round)
-                # ibs_refine_f64 holds the register-resident evaluation kernel (N <= 2050): beyond, the same L-BFGS-B state machines
-                # run on the host (ibs_lbfgsb2_*) and every round is ONE batched geometry + ibs_obj_w_grad_f64 launch for the
-                # surfaces still running (refine_batched: the form refine_device is tested against)
-                xh, fh, rounds = self.refine_batched(start.cpu().numpy())
-                xo = torch.from_numpy(xh).to(dev); ne = self._batched_evals if self.exact else None
-            else:
-                xo, fo, ne, rounds = ctx.refine_device(self.tables, res["pt_surf"], start, res["th"], self.del_alpha)
-            mark("r1")
-            xa, xt = xo[:, 0].contiguous(), xo[:, 1].contiguous()
-            gf = ctx.fieldline_geometry(self.tables, res["pt_surf"], xa, res["th"], device=dev)
-            fin = ctx.gamma_points(self.h, *[gf["geo"][k] for k in range(7)], gf["dPdrho"], xt, want_info=True, **self._certify_kw())
-            if self.certify:
-                ccount = ccount + self._cert_counts(fin["cert"])
-            rows = torch.stack([xt, xa, fin["gam"]], dim=1)
-            bad = bad + ((fin["info"] >> 16) != 0).sum()
-            self.last_refine = dict(n_evals=ne, rounds=rounds)
-        else:
-            mark("r1")
-            rows = torch.stack([start[:, 1], start[:, 0], gmax], dim=1)
-        bad = bad + res["n_bad"][0]
-        self._last_rows = rows           # (sensitivity()'s default points)
-        self._cert_dev = ccount          # (checked, reclosed, failed) of this call, on the device: read with the rows' one copy
-        mark("f1")
-        if phases is not None:
-            torch.cuda.synchronize()
-            span = lambda a, b: sum(x.elapsed_time(y) for x, y in zip(ev[a], ev[b]))
-            phases["geometry_ms"] = span("g0", "g1"); phases["scan_argmax_ms"] = span("g1", "s1")
-            phases["refine_ms"] = span("r0", "r1"); phases["final_solve_ms"] = span("r1", "f1")
-            if fill is not None:
-                phases["host_tables_ms"] = t_fill * 1e3
-                phases["coarse_chunks"] = len(chunks)
-        return rows, bad.to(torch.float64)
-
-    def _device_rows_multi(self, refine, phases, chunks, fill):
-        """device_rows() for n_starts = K > 1: per chunk the coarse table goes through ibs_scan_peaks_f64 (K starts per surface, and
-        their shifts in nearest mode); all n K points are refined in the form the mode uses for one start (ibs_refine_f64 on device
-        pointers, or refine_batched with the point -> surface map), ONE final geometry and ONE final solve run for all of them (all
-        certified and counted with certify=True), ibs_surface_argmax_pack_f64 over [n][K] picks every surface's best candidate (slot
-        0 wins ties) and a device gather forms the rows.  bad counts the flagged solves of ALL candidates, n_bad once per surface.
-        Nothing returns to the host in between beyond what the refinement form already does.  refine=False: slot 0, the rows of
-        n_starts = 1."""
-        import time
-        import torch
-        ctx, dev, K = self.ctx, self.device, self.n_starts
-        n = len(self.own)
-        res = self._resident_inputs()
-        na, nt = len(self.alpha_scan), len(self.theta0_scan)
-        ev = {}
-
-        def mark(name):
-            if phases is not None:
-                e = torch.cuda.Event(enable_timing=True); e.record(); ev.setdefault(name, []).append(e)
-        res["n_bad"].zero_()
-        chunks = chunks or [(0, n)]
-        f64 = dict(dtype=torch.float64, device=dev)
-        start, peak = torch.empty((n, K, 2), **f64), torch.empty((n, K), **f64)
-        index = torch.empty((n, K), dtype=torch.int32, device=dev)
-        found = torch.empty((n,), dtype=torch.int32, device=dev)
-        sig0 = torch.empty((n, K), **f64) if self.nearest else None
-        bad = res["n_bad"][0] * 0
-        ccount = torch.zeros(3, **f64) if self.certify else None
-        t_fill = 0.0
+        pk = {}                            # the picks of all owned surfaces: start, peak[, sigma0][, index, n_found][, the envelope]
         for c0, c1 in chunks:
             if fill is not None:
                 t0 = time.perf_counter(); fill(c0, c1); t_fill += time.perf_counter() - t0
@@ -1257,61 +1092,64 @@ class BallooningScan:
             geo = ctx.fieldline_geometry(self.tables, res["surf"][c0 * na:c1 * na], res["al"][c0 * na:c1 * na], res["th"], device=dev)
             mark("g1")
             g7 = [geo["geo"][k] for k in range(7)]
-            if self.nearest:
-                sc = ctx.gamma_scan_nearest(self.h, *g7, geo["dPdrho"], res["t0"], SIGMA_COARSE, want_info=True)
-                flagged = ((sc["info"] >> 16) & 3) != 0
-            else:
-                # (the scan kernel of n_starts = 1, so that the table -- and slot 0 -- has that run's bits; its fused maximum is not used)
-                sc = ctx.gamma_scan_argmax(self.h, g7, geo["dPdrho"], res["t0"], c1 - c0)
-                if self.certify:
-                    cert = ctx.certify_scan(self.h, *g7, geo["dPdrho"], res["t0"], sc["lam"])
-                    ctx.reclose_scan(self.h, *g7, geo["dPdrho"], res["t0"], cert, sc["lam"], sc["gam"])
-                    ccount = ccount + self._cert_counts(cert)
-                flagged = (sc["info"] >> 16) != 0
-            pk = ctx.scan_peaks(res["alpha"], res["t0"], sc["gam"].view(c1 - c0, na, nt), K, n_bad=res["n_bad"],
-                                want_sigma0=self.nearest, want_index=True, want_found=True)
+            sc = self._coarse_stage(g7, geo["dPdrho"], c1 - c0)
+            bad = bad + _flagged(sc["info"], any_bit=not self.nearest).sum()
+            picked = self._pick_starts(sc, g7, geo["dPdrho"], c1 - c0)
             mark("s1")
-            start[c0:c1] = pk["start"]; peak[c0:c1] = pk["peak"]; index[c0:c1] = pk["index"]; found[c0:c1] = pk["n_found"]
-            if self.nearest:
-                sig0[c0:c1] = pk["sigma0"]
-            bad = bad + flagged.sum()
-        self.last_peaks = dict(index=index, value=peak, n_found=found)
+            for key, v in picked.items():
+                if len(chunks) == 1:       # (one chunk: its tensors as they are, no copy)
+                    pk[key] = v
+                else:
+                    per = len(v) // (c1 - c0)                  # rows per surface: 1, or nalpha for the envelope's
+                    if key not in pk:
+                        pk[key] = torch.empty((n * per,) + v.shape[1:], dtype=v.dtype, device=dev)
+                    pk[key][c0 * per:c1 * per] = v
+        if "env_info" in pk:               # (theta0_polish: the envelope's rows are per line)
+            bad = bad + _flagged(pk["env_info"]).sum()
+            self.last_envelope = {key[4:]: v for key, v in pk.items() if key.startswith("env_")}
+        if K > 1:
+            self.last_peaks = dict(index=pk["index"], value=pk["peak"], n_found=pk["n_found"])
+        start, peak = pk["start"], pk["peak"]
         mark("r0")
-        pts = start.view(n * K, 2)
         if refine:
+            pts, pt_surf = start.view(n * K, 2), res["pt_surf_k" if K > 1 else "pt_surf"]
             if self.nearest or self.exact or len(self.theta) > 2050:
-                # (the host-driven state machines, as for one start: ibs_refine_f64 has no nearest-sigma and no exact form, and holds
-                # the register-resident evaluation kernel, N <= 2050)
-                xh, fh, rounds = self.refine_batched(pts.cpu().numpy(), sigma0=sig0.view(-1).cpu().numpy() if self.nearest else None,
-                                                     surf_idx=np.repeat(self._own_surf(), K))
+                # ibs_refine_f64 has no nearest-sigma and no exact form, and holds the register-resident evaluation kernel (N <= 2050):
+                # there the same L-BFGS-B state machines run on the host (ibs_lbfgsb2_*) and every round is ONE batched geometry +
+                # objective launch for the points still running (refine_batched: the form refine_device is tested against)
+                xh, fh, rounds = self.refine_batched(pts.cpu().numpy(), sigma0=pk["sigma0"].view(-1).cpu().numpy() if self.nearest else None,
+                                                     surf_idx=np.repeat(self._own_surf(), K) if K > 1 else None)
                 xo = torch.from_numpy(xh).to(dev); ne = self._batched_evals if self.exact else None
             else:
-                xo, fo, ne, rounds = ctx.refine_device(self.tables, res["pt_surf_k"], pts, res["th"], self.del_alpha)
+                xo, fo, ne, rounds = ctx.refine_device(self.tables, pt_surf, pts, res["th"], self.del_alpha)
             mark("r1")
             xa, xt = xo[:, 0].contiguous(), xo[:, 1].contiguous()
-            gf = ctx.fieldline_geometry(self.tables, res["pt_surf_k"], xa, res["th"], device=dev)
+            gf = ctx.fieldline_geometry(self.tables, pt_surf, xa, res["th"], device=dev)
             g7 = [gf["geo"][k] for k in range(7)]
             if self.nearest:
                 fin = ctx.gamma_points_nearest(self.h, *g7, gf["dPdrho"], xt, SIGMA_FINAL, want_info=True)
-                bad = bad + (((fin["info"] >> 16) & 3) != 0).sum()
             else:
                 fin = ctx.gamma_points(self.h, *g7, gf["dPdrho"], xt, want_info=True, **self._certify_kw())
                 if self.certify:
-                    ccount = ccount + self._cert_counts(fin["cert"])
-                bad = bad + ((fin["info"] >> 16) != 0).sum()
-            cand = torch.stack([xt, xa, fin["gam"]], dim=1).view(n, K, 3)
-            best = ctx.surface_argmax_pack(fin["gam"].view(n, K))[:, 1]
-            best = torch.where(best < K, best, torch.zeros_like(best)).to(torch.int64)      # (no finite candidate: slot 0, and bad > 0)
-            rows = torch.gather(cand, 1, best.view(n, 1, 1).expand(n, 1, 3)).reshape(n, 3)
+                    self._cert_dev = self._cert_dev + self._cert_counts(fin["cert"])
+            bad = bad + _flagged(fin["info"], any_bit=not self.nearest).sum()
+            cand = torch.stack([xt, xa, fin["gam"]], dim=1)
             self.last_refine = dict(n_evals=ne, rounds=rounds)
         else:
             mark("r1")
-            cand = torch.stack([start[:, :, 1], start[:, :, 0], peak], dim=2)
-            rows = cand[:, 0].contiguous()
-        self.last_candidates = cand
+            cand = torch.stack([start[..., 1], start[..., 0], peak], dim=-1)
+        if K > 1:                          # select: the best refined candidate of every surface; unrefined, the first maximum
+            cand = self.last_candidates = cand.view(n, K, 3)
+            if refine:
+                best = ctx.surface_argmax_pack(fin["gam"].view(n, K))[:, 1]
+                best = torch.where(best < K, best, torch.zeros_like(best)).to(torch.int64)  # (no finite candidate: slot 0, and bad > 0)
+                rows = torch.gather(cand, 1, best.view(n, 1, 1).expand(n, 1, 3)).reshape(n, 3)
+            else:
+                rows = cand[:, 0].contiguous()
+        else:
+            rows = cand
         bad = bad + res["n_bad"][0]
-        self._last_rows = rows           # (sensitivity()'s default points)
-        self._cert_dev = ccount
+        self._last_rows = rows             # (sensitivity()'s default points)
         mark("f1")
         if phases is not None:
             torch.cuda.synchronize()
@@ -1322,6 +1160,53 @@ class BallooningScan:
                 phases["host_tables_ms"] = t_fill * 1e3
                 phases["coarse_chunks"] = len(chunks)
         return rows, bad.to(torch.float64)
+
+    def _coarse_stage(self, g7, dP, m):
+        """the coarse scan of a chunk of m surfaces on its lines' planes g7, dP: dict(gam, lam, info[, pack]) on the device.  max: the
+        scan with the fused per-surface first maximum (pack); certify=True certifies the table's eigenvalues and re-closes them in
+        place -- the pack is then stale and dropped -- and adds the counts to ._cert_dev.  nearest: the scan at SIGMA_COARSE."""
+        ctx, t0 = self.ctx, self._resident["t0"]
+        if self.nearest:
+            return ctx.gamma_scan_nearest(self.h, *g7, dP, t0, SIGMA_COARSE, want_info=True)
+        sc = ctx.gamma_scan_argmax(self.h, g7, dP, t0, m)
+        if self.certify:
+            cert = ctx.certify_scan(self.h, *g7, dP, t0, sc["lam"])
+            ctx.reclose_scan(self.h, *g7, dP, t0, cert, sc["lam"], sc["gam"])
+            self._cert_dev = self._cert_dev + self._cert_counts(cert)
+            del sc["pack"]
+        return sc
+
+    def _pick_starts(self, sc, g7, dP, m):
+        """the refinement's starts of a chunk of m surfaces from its coarse scan sc: dict(start, peak[, sigma0 in nearest mode]) on
+        the device.  n_starts = 1: start (m, 2), peak (m,) from the per-surface first maximum (the scan's fused pack, else
+        ibs_surface_argmax_pack_f64 over the table) by ibs_scan_starts_f64; theta0_polish moves every surface's start to the crest of
+        its best line (ibs_theta0_polish_f64, whose outputs ride along as env_*).  n_starts = K > 1: start (m, K, 2), peak (m, K),
+        index, n_found of the K best peaks (ibs_scan_peaks_f64 on the table: the scan kernel is that of K = 1, so that slot 0 has
+        that run's bits).  Either way a non-finite maximum is counted once per surface in the resident n_bad."""
+        ctx, res, K = self.ctx, self._resident, self.n_starts
+        na, nt = len(self.alpha_scan), len(self.theta0_scan)
+        if K > 1:
+            pk = ctx.scan_peaks(res["alpha"], res["t0"], sc["gam"].view(m, na, nt), K, n_bad=res["n_bad"], want_sigma0=self.nearest,
+                                want_index=True, want_found=True)
+            return {key: pk[key] for key in ("start", "peak", "index", "n_found") + (("sigma0",) if self.nearest else ())}
+        pack = sc["pack"] if "pack" in sc else ctx.surface_argmax_pack(sc["gam"].view(m, -1))
+        if self.nearest:
+            st, sg = ctx.scan_starts(res["alpha"], res["t0"], pack, res["n_bad"], want_sigma0=True)
+            return dict(start=st, peak=pack[:, 0], sigma0=sg)
+        st, gm = ctx.scan_starts(res["alpha"], res["t0"], pack, res["n_bad"]), pack[:, 0]
+        if not self.theta0_polish:
+            return dict(start=st, peak=gm)
+        # every line's crest between the nodes; the surface's start is the first maximum of gam_env over its lines
+        import torch
+        env = ctx.theta0_polish(self.h, *g7, dP, res["t0"], sc["gam"], lam=sc["lam"], want_info=True)
+        ge = torch.nan_to_num(env["gam"].view(m, na), nan=-float("inf"))
+        top = ge.max(dim=1).values
+        col = torch.arange(na, device=self.device).expand_as(ge)
+        first = torch.where(ge == top[:, None], col, na).min(dim=1).values.clamp(max=na - 1)
+        ok = torch.isfinite(top) & (top != 0.0)                              # (else the start scan_starts gave: (0, 0))
+        t_star = env["theta0"].view(m, na).gather(1, first[:, None])[:, 0]
+        st = torch.where(ok[:, None], torch.stack([res["alpha"][first], t_star], dim=1), st)
+        return dict({"env_" + key: v for key, v in env.items() if key != "nbad"}, start=st, peak=torch.where(ok, top, gm))
 
     def sensitivity(self, points=None, eigenpair=None):
         """exact derivatives of every owned surface's gam at ONE point (alpha, theta0) of that surface, with respect to the point and
@@ -1333,7 +1218,7 @@ class BallooningScan:
         tab_mn_bar (n_own, 6, mnmax), tab_nyq_bar (n_own, 7, mnmax_nyq), scal_bar (n_own, 6))."""
         import torch
         from . import autograd as iag
-        if self.tables is None or self.device is None:
+        if not self._on_device:
             raise IbsError("sensitivity() needs a scan built with tables= and device=")
         mode = self.eigenpair if eigenpair is None else check_eigenpair(eigenpair)
         dev, own = self.device, self._own_surf()
@@ -1370,7 +1255,7 @@ class BallooningScan:
         import torch
         from . import autograd as iag
         from .objective import smooth_max
-        if self.tables is None or self.device is None:
+        if not self._on_device:
             raise IbsError("smooth_max() needs a scan built with tables= and device=")
         dev, own = self.device, self._own_surf()
         n, na = len(own), len(self.alpha_scan)
@@ -1402,7 +1287,7 @@ class BallooningScan:
         (n_own, 7, mnmax_nyq), scal_bar (n_own, 6))."""
         import torch
         from . import autograd as iag
-        if self.tables is None or self.device is None:
+        if not self._on_device:
             raise IbsError("marginal_sensitivity() needs a scan built with tables= and device=")
         dev, own = self.device, self._own_surf()
         n = len(own)
@@ -1476,26 +1361,21 @@ class BallooningScan:
         solve (ball_scan.py:248-339), no collective"""
         if self.certify:
             self.last_certificate = dict(checked=0, reclosed=0, failed=0)
-        if self.certify and self.tables is not None and self.device is not None:
+        if self._on_device:
             import torch
             rows, bad = self.device_rows(refine)
             if not len(self.own):
                 return rows.cpu().numpy().reshape(0, 3)
-            host = torch.cat([rows.reshape(-1), bad.reshape(1), self._cert_dev]).cpu().numpy()    # the one copy (and synchronisation)
-            self.last_certificate = dict(checked=int(host[-3]), reclosed=int(host[-2]), failed=int(host[-1]))
-            host = host[:-3]
+            # the one copy (and synchronisation): the rows, the count of what went wrong and, with certify, the certificate counts
+            host = torch.cat([rows.reshape(-1), bad.reshape(1)] + ([self._cert_dev] if self.certify else [])).cpu().numpy()
+            if self.certify:
+                self.last_certificate = dict(checked=int(host[-3]), reclosed=int(host[-2]), failed=int(host[-1]))
+                host = host[:-3]
             if host[-1] != 0 or not np.all(np.isfinite(host[:-1])):
                 raise IbsError("%d solves of this rank's scan were flagged or produced non-finite growth rates (status word != 0: "
                                "invalid data or iteration cap)" % int(host[-1]))
-            self._raise_uncertified()
-            return host[:-1].reshape(len(self.own), 3)
-        if self.tables is not None and self.device is not None:
-            import torch
-            rows, bad = self.device_rows(refine)
-            host = torch.cat([rows.reshape(-1), bad.reshape(1)]).cpu().numpy()          # the one copy (and synchronisation)
-            if host[-1] != 0 or not np.all(np.isfinite(host[:-1])):
-                raise IbsError("%d solves of this rank's scan were flagged or produced non-finite growth rates (status word != 0: "
-                               "invalid data or iteration cap)" % int(host[-1]))
+            if self.certify:
+                self._raise_uncertified()
             return host[:-1].reshape(len(self.own), 3)
         tabs = self.coarse()
         rows = []

@@ -64,7 +64,7 @@ def tangent_leg():
     coarse = scan.marginal()
     x0 = np.stack([coarse["alpha"], coarse["theta0"]], axis=1)
     idx = np.arange(ns)
-    legs = dict(reference=lambda: scan._marginal_points(idx, x0), exact_tangent=lambda: scan._marginal_points_tangent(idx, x0))
+    legs = dict(reference=lambda: scan._marginal_points(idx, x0), exact_tangent=lambda: scan._marginal_points(idx, x0, tangent=True))
     full = {k: (lambda k=k: scan.marginal(refine=True, jac=k)) for k in legs}
     for fn in list(legs.values()) + list(full.values()):
         fn()
