@@ -13,6 +13,10 @@ Simpson quotient of utils.py:1601-1621), not the Hellmann-Feynman formulas of ut
     gam = iag.gamma_scan(h, *geo[:7], dP, theta0)       # theta0 (n_theta0,): the scan kernel forward, ONE ibs_gamma_scan_vjp_f64 backward
     objective.smooth_max(gam.reshape(n_surf, n_alpha, -1), 20.0).sum().backward()
 
+    lam = iag.local_eq_lam(theta[0], h, geo, dP, alpha, sigma, line_of, var)            # lam_max at (line, theta0, eps, p) points
+    t = iag.local_eq_crossing(theta[0], h, geo, dP, alpha, sigma, rays)                # first stable -> unstable crossing of every (line, ray)
+    t.nansum().backward()           # the implicit-function rule on lam_max(t*) = shift, through the geometry to the tables
+
 Float64 CUDA tensors throughout; uniform grids, odd N in [66, 65537] (the limits of the kernels).  A backward whose VJP flags a system
 (status bits 0-1 of ibs_solve_gcf_vjp_f64) issues a VjpStatusWarning.  `import ibs_amd` does not import
 this module, nor torch."""
@@ -326,3 +330,95 @@ def fieldline_geometry(tables, line_surf, line_alpha, theta, tab_mn=None, tab_ny
                                  d[6] if scal is None else scal)
     line_surf = torch.as_tensor(line_surf, device=line_alpha.device).to(torch.int32)
     return _FieldlineGeometry.apply(tables, line_surf, line_alpha, theta, tab_mn, tab_nyq, scal, ictx)
+
+
+def _raise_flagged(info, what):
+    nbad = int(((info >> 16) & 3).ne(0).sum().item())
+    if nbad:
+        raise IbsError("%d of %d %s were flagged (status bits 0-1: iteration cap or invalid data)" % (nbad, info.numel(), what))
+
+
+class _LocalEqLam(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, theta_lo, h, geo, dPdrho, centre, sigma, line_of, var, ps, ictx):
+        r = ictx.local_eq_grad(theta_lo, h, geo, dPdrho, centre, sigma, line_of, var, ps=ps, want_geo_bar=True, want_info=True)
+        _raise_flagged(r["info"], "local-equilibrium points")
+        fctx.save_for_backward(r["geo_bar"], r["dlam"], line_of.to(torch.int64))
+        fctx.n_lines = int(geo.shape[1])
+        return r["lam"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, lam_bar):
+        geo_bar, dlam, line_of = fctx.saved_tensors
+        N = geo_bar.shape[2]
+        gb = torch.zeros((8, fctx.n_lines, N), dtype=geo_bar.dtype, device=geo_bar.device).index_add_(1, line_of, geo_bar * lam_bar[None, :, None])
+        dP = torch.zeros(fctx.n_lines, dtype=geo_bar.dtype, device=geo_bar.device).index_add_(0, line_of, dlam[:, 3] * lam_bar)
+        return None, None, gb, dP, None, None, None, dlam[:, :3] * lam_bar[:, None], None, None
+
+
+def local_eq_lam(theta_lo, h, geo, dPdrho, centre, sigma, line_of, var, ps=None, ctx=None):
+    """lam_max (n_pts,) at the points (line_of[k], var[k] = (theta0, eps, p)) of the local-equilibrium rule on the lines geo (8, n_lines,
+    N), dPdrho (n_lines,) on the grid theta_lo + j h -- the planes fieldline_geometry returns -- with centre, sigma (n_lines,) and the
+    optional ps (n_lines, N) of Context.local_eq_scan (Context.local_eq_grad, ibs_local_eq_grad_f64).  Differentiable in geo, dPdrho
+    and var: the backward is the cotangent times the planes and the derivatives the forward's kernel returns (Hellmann-Feynman on the
+    discrete pencil, exact for the lam returned; lam_max must be simple), summed over the points of a line.  centre, sigma, ps and the
+    grid get no gradient.  Composes with fieldline_geometry.  Status bits 0-1 raise IbsError."""
+    ictx = ctx or default_context(geo.device.index or 0)
+    line_of = torch.as_tensor(line_of, device=geo.device).to(torch.int32)
+    var = torch.as_tensor(var, dtype=geo.dtype, device=geo.device)
+    return _LocalEqLam.apply(float(theta_lo), float(h), geo, dPdrho, centre, sigma, line_of, var, ps, ictx)
+
+
+class _LocalEqCrossing(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, theta_lo, h, geo, dPdrho, centre, sigma, rays, ps, shift, xtol, ictx):
+        b = ictx.local_eq_boundary_grad(theta_lo, h, geo, dPdrho, centre, sigma, rays, ps=ps, shift=shift, xtol=xtol, want_geo_bar=True)
+        _raise_flagged(b["info"], "local-equilibrium boundary systems")
+        if b["grad_nbad"]:
+            raise IbsError("%d local-equilibrium points at the crossings were flagged (status bits 0-1)" % b["grad_nbad"])
+        up = b["t_stable"] < b["t_unstable"]                 # (NaN beyond n_cross: False)
+        has = up.any(dim=2)
+        first = up.to(torch.int8).argmax(dim=2)
+        t = torch.where(has, b["t"].gather(2, first[..., None])[..., 0], torch.full_like(b["t"][..., 0], float("nan")))
+        l_sel, r_sel = torch.nonzero(has, as_tuple=True)
+        c_sel = first[l_sel, r_sel]
+        # the rows of dt_geo of the chosen crossings: pts lists every gathered crossing in (line, ray, crossing) order
+        where = torch.full(tuple(up.shape), -1, dtype=torch.int64)
+        pts = torch.from_numpy(b["pts"])
+        where[pts[:, 0], pts[:, 1], pts[:, 2]] = torch.arange(len(pts))
+        sel = where.to(geo.device)[l_sel, r_sel, c_sel]
+        fctx.save_for_backward(b["dt_geo"][:, sel], b["dt"][l_sel, r_sel, c_sel], t[l_sel, r_sel], l_sel, r_sel)
+        fctx.shape = (int(geo.shape[1]), int(rays.shape[0]))
+        lt = torch.where(has, b["dlam_dt"].gather(2, first[..., None])[..., 0], torch.full_like(t, float("nan")))
+        fctx.mark_non_differentiable(lt)
+        return t, lt
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, t_bar, _lt_bar):
+        dt_geo, dt, t, l_sel, r_sel = fctx.saved_tensors
+        n_lines, n_ray = fctx.shape
+        tb = t_bar[l_sel, r_sel]
+        kw = dict(dtype=dt.dtype, device=dt.device)
+        gb = torch.zeros((8, n_lines, dt_geo.shape[2]), **kw).index_add_(1, l_sel, dt_geo * tb[None, :, None])
+        dP = torch.zeros(n_lines, **kw).index_add_(0, l_sel, dt[:, 4] * tb)
+        z = torch.zeros_like(tb)
+        # t* depends on d_eps and d_p through the triple at t*: eps = eps0 + t d_eps, p = p0 + t d_p
+        cols = torch.stack([dt[:, 0] * tb, dt[:, 1] * tb, dt[:, 2] * tb, t * dt[:, 1] * tb, t * dt[:, 2] * tb, z, z], dim=1)
+        rb = torch.zeros((n_ray, 7), **kw).index_add_(0, r_sel, cols)
+        return None, None, gb, dP, None, None, rb, None, None, None, None
+
+
+def local_eq_crossing(theta_lo, h, geo, dPdrho, centre, sigma, rays, ps=None, shift=0.0, xtol=1e-12, ctx=None, want_slope=False):
+    """t* (n_lines, n_ray) of the FIRST stable -> unstable crossing of every line along every ray (n_ray, 7) = (theta0, eps0, p0, d_eps,
+    d_p, t_lo, t_hi) of Context.local_eq_boundary, NaN where a (line, ray) has none among the returned crossings.  Differentiable in
+    geo, dPdrho and the rays' (theta0, eps0, p0, d_eps, d_p): the backward is the implicit-function rule on lam_max(t*) = shift,
+    d t* / d (.) = -lam_(.) / lam_t with the derivatives of lam_max from ONE Context.local_eq_grad call at the crossings
+    (Context.local_eq_boundary_grad); the cotangent of a ray is summed over the lines, that of a line over the rays.  t_lo, t_hi, shift,
+    centre, sigma and ps get no gradient.  At a tangency lam_t -> 0 and the gradients are inf or NaN by arithmetic: want_slope=True
+    returns (t*, lam_t) so that the caller can judge.  Composes with fieldline_geometry.  Status bits 0-1 raise IbsError."""
+    ictx = ctx or default_context(geo.device.index or 0)
+    rays = torch.as_tensor(rays, dtype=geo.dtype, device=geo.device)
+    t, lt = _LocalEqCrossing.apply(float(theta_lo), float(h), geo, dPdrho, centre, sigma, rays, ps, float(shift), float(xtol), ictx)
+    return (t, lt) if want_slope else t

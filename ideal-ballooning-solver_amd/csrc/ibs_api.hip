@@ -24,6 +24,7 @@
 #include "ibs_theta0_polish.hpp"
 #include "ibs_local_eq.hpp"
 #include "ibs_local_eq_boundary.hpp"
+#include "ibs_local_eq_grad.hpp"
 #include <chrono>
 #include <thread>
 
@@ -1338,6 +1339,61 @@ int ibs_local_eq_boundary_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int3
       c.info = a.info ? a.info + s0 : nullptr;
       c.n_waves = long_waves(ctx, Lc * n_ray);
       HIPCHK(ibs::launch_local_eq_boundary(c, ctx->stream));
+      return 0;
+    });
+  });
+}
+
+// ---- local-equilibrium gradients: lam_max, gam, d lam_max / d (theta0, eps, p, dPdrho) and the cotangent planes at points (line, theta0,
+// eps, p) (ibs_local_eq_grad.hip; the formulas: ibs_local_eq_grad.hpp).  The geometry is staged once; the POINTS go chunk after chunk
+// (for_line_chunks with a point standing where a line with one theta0 stands), a chunk's workspace in ctx->long_ws = the per-wave
+// workspace (ibs::local_eq_grad_ws) of its persistent grid: long_waves() waves, and never more than kLineChunkBudget admits
+int ibs_local_eq_grad_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_pts, int32_t N, double theta_lo, double h, const double* geo,
+                          int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps, int64_t ps_ld,
+                          const int32_t* line_of, const double* var, double* lam, double* gam, double* dlam, double* geo_bar,
+                          int64_t ld_bar, int32_t* info, int flags) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!geo || !dPdrho || !centre || !sigma || !line_of || !var)
+    return fail(IBS_ERR_ARG, "null argument (geo, dPdrho, centre, sigma, line_of and var are required)");
+  if (!lam && !gam && !dlam && !geo_bar) return fail(IBS_ERR_ARG, "no output requested (lam, gam, dlam and geo_bar are all null)");
+  if (n_lines < 0 || n_pts < 0 || ld < N || (ps && ps_ld < N) || (geo_bar && ld_bar < N))
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_pts=%d ld=%lld ps_ld=%lld ld_bar=%lld N=%d)", n_lines, n_pts, (long long)ld,
+                (long long)ps_ld, (long long)ld_bar, N);
+  if (flags != IBS_MEM_DEVICE && flags != IBS_MEM_HOST) return fail(IBS_ERR_ARG, "flags must be IBS_MEM_DEVICE or IBS_MEM_HOST, not %d", flags);
+  if (!std::isfinite(theta_lo)) return fail(IBS_ERR_ARG, "theta_lo must be finite (theta_lo=%g)", theta_lo);
+  if (int r = check_grid(N, h, true)) return r;
+  if (n_pts == 0) return 0;
+  ON_DEVICE(ctx);
+  const size_t n = (size_t)n_pts, plane = (size_t)n_lines * (size_t)ld;
+  ibs::LocalEqGradArgs a{};                                // the whole call; each chunk launches a copy with its points
+  a.n_lines = n_lines; a.N = N; a.theta_lo = theta_lo; a.h = h; a.ld = (long)ld; a.plane = plane; a.ps_ld = (long)ps_ld;
+  // (host pointers: the rows of geo_bar are packed on the device and come back one by one, so the caller's entries N..ld_bar-1 stay as they were)
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, 8 * plane); a.dPdrho = s.in(dPdrho, n_lines); a.centre = s.in(centre, n_lines); a.sigma = s.in(sigma, n_lines);
+    a.ps = s.in(ps, (size_t)n_lines * (size_t)ps_ld); a.line_of = s.in(line_of, n); a.var = s.in(var, 3 * n);
+    a.lam = s.out(lam, n); a.gam = s.out(gam, n); a.dlam = s.out(dlam, 4 * n);
+    a.geo_bar = s.out_rows(geo_bar, 8 * n, N, ld_bar); a.ld_bar = (long)s.rows_ld(N, ld_bar); a.plane_bar = n * (size_t)a.ld_bar;
+    a.info = s.status(info, n);
+  };
+  return staged(ctx, flags, decl, [&]() -> int {
+    const size_t per_wave = ibs::local_eq_grad_ws(N).total;
+    const long wave_cap = (long)(ibs::kLineChunkBudget / (per_wave * sizeof(double)));      // (>= 292: a wave's workspace is at most 3.7 MB)
+    long nw = 0;
+    double* work = nullptr;
+    auto carve = [&](Carve& cv, long P) {                  // ctx->long_ws of a chunk of P points
+      nw = long_waves(ctx, P);
+      if (nw > wave_cap) nw = wave_cap;
+      work = cv.take<double>((size_t)nw * per_wave);
+    };
+    return for_line_chunks(ctx, "local_eq_grad", n_pts, 1, N, carve, [&](long p0, long Pc) -> int {
+      ibs::LocalEqGradArgs c = a;
+      c.n_pts = Pc;
+      c.line_of = a.line_of + p0; c.var = a.var + 3 * p0;
+      c.lam = a.lam ? a.lam + p0 : nullptr; c.gam = a.gam ? a.gam + p0 : nullptr; c.dlam = a.dlam ? a.dlam + 4 * p0 : nullptr;
+      c.geo_bar = a.geo_bar ? a.geo_bar + p0 * a.ld_bar : nullptr;
+      c.info = a.info ? a.info + p0 : nullptr;
+      c.work = work; c.work_doubles = (size_t)nw * per_wave; c.n_waves = nw;
+      HIPCHK(ibs::launch_local_eq_grad(c, ctx->stream));
       return 0;
     });
   });

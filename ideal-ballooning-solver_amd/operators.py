@@ -211,6 +211,67 @@ def local_eq_fold(theta, line8, dPdrho, centre, sigma, theta0, eps, p, ps=None):
     return p * dPdrho, gb + p * (cv - gb) + x * cv0, gds2 + 2 * x * gds21 + x * x * gds22
 
 
+def _local_eq_x(theta, centre, sigma, theta0, eps, p, ps):
+    """the fold variable x of local_eq_fold and its tangents (4, N) in (theta0, eps, p, dPdrho)"""
+    dth = theta - centre
+    psr = np.zeros_like(theta) if ps is None else np.asarray(ps, dtype=np.float64)
+    x = theta0 * (1.0 + eps) + sigma * eps * dth + (p - 1.0) * psr
+    return x, np.stack([np.full_like(theta, 1.0 + eps), theta0 + sigma * dth, psr, np.zeros_like(theta)])
+
+
+def local_eq_fold_tangent(theta, line8, dPdrho, centre, sigma, theta0, eps, p, ps=None):
+    """The tangents of local_eq_fold's three results in s = (theta0, eps, p, dPdrho), in that order: returns (dP'_s (4,), cv'_s (4, N),
+    gd'_s (4, N)).  With x_s = (1 + eps, theta0 + sigma (theta - centre), ps, 0):
+        dP'_s = (0, 0, dPdrho, p),   cv'_s = cvdrift0 x_s + (0, 0, cvdrift - gbdrift, 0),   gd'_s = (2 gds21 + 2 x gds22) x_s.
+    The results are polynomials of degree <= 2 in every s, so central differences of local_eq_fold reproduce these to rounding."""
+    theta = np.asarray(theta, dtype=np.float64)
+    cv, cv0, gds21, gds22, gb = (np.asarray(line8[k], dtype=np.float64) for k in (2, 3, 5, 6, 7))
+    x, xs = _local_eq_x(theta, centre, sigma, theta0, eps, p, ps)
+    dcv = cv0[None] * xs
+    dcv[2] += cv - gb
+    return np.array([0.0, 0.0, dPdrho, p]), dcv, (2 * gds21 + 2 * x * gds22)[None] * xs
+
+
+def local_eq_lam_grad(theta, line8, dPdrho, centre, sigma, triple, X, lam, ps=None):
+    """The derivatives of lam_max at the point triple = (theta0, eps, p) of a line under the local-equilibrium rule, from an eigenpair
+    (lam, X) of the point's pencil, X (N,) with zero ends (csrc/ibs_local_eq_grad.hpp, Context.local_eq_grad): with g = |gradpar| gd' /
+    bmag, c = -dP' cv' / (|gradpar| bmag), f = gd' / (bmag^3 |gradpar|), w_j = (X_j - X_{j-1})^2 + (X_{j+1} - X_j)^2 and q = sum f X^2,
+        d lam / d s = (sum c_s X^2 - 1/2 h^-2 sum g_s w - lam sum f_s X^2) / q
+    for s = theta0, eps, p, dPdrho (the tangents of local_eq_fold_tangent) and for every entry of the eight arrays (closed forms per
+    grid point).  Exact for this lam to first order in the error of X; lam must be a simple eigenvalue.
+    Returns dict(dlam (4,), geo_bar (8, N), q, dlam_scale (4,), geo_bar_scale (8, N)): a scale is the sum of the absolute values of
+    the three terms of its component, over q -- what a deviation of the component is measured against."""
+    theta = np.asarray(theta, dtype=np.float64)
+    X = np.asarray(X, dtype=np.float64)
+    theta0, eps, p = (float(v) for v in triple)
+    B, gpr = (np.asarray(line8[k], dtype=np.float64) for k in (0, 1))
+    a = np.abs(gpr)
+    dPv, cvv, gd = local_eq_fold(theta, line8, dPdrho, centre, sigma, theta0, eps, p, ps=ps)
+    ddP, dcv, dgd = local_eq_fold_tangent(theta, line8, dPdrho, centre, sigma, theta0, eps, p, ps=ps)
+    x, _ = _local_eq_x(theta, centre, sigma, theta0, eps, p, ps)
+    g, c, f = a * gd / B, -dPv * cvv / (a * B), gd / (B ** 3 * a)
+    d2 = np.diff(X) ** 2
+    w = np.concatenate([[0.0], d2]) + np.concatenate([d2, [0.0]])
+    X2 = X * X
+    k2 = 0.5 / float(theta[1] - theta[0]) ** 2
+    q = float(np.sum(f * X2))
+    terms = np.stack([np.sum(-(ddP[:, None] * cvv[None] + dPv * dcv) / (a * B) * X2, axis=1),
+                      -k2 * np.sum(a * dgd / B * w, axis=1),
+                      -lam * np.sum(dgd / (B ** 3 * a) * X2, axis=1)])                       # (3, 4)
+    gbar, cbar, fbar = -k2 * w / q, X2 / q, -lam * X2 / q
+    z = np.zeros_like(theta)
+    sgn = np.where(gpr < 0, -1.0, 1.0)
+    cvb = -dPv * cbar / (a * B)
+    gdg, gdf = gbar * a / B, fbar / (B ** 3 * a)
+    planes = np.array([[-gbar * g / B, -cbar * c / B, -3 * fbar * f / B],
+                       [sgn * gbar * g / a, -sgn * cbar * c / a, -sgn * fbar * f / a],
+                       [z, p * cvb, z], [z, x * cvb, z],
+                       [gdg, z, gdf], [2 * x * gdg, z, 2 * x * gdf], [x * x * gdg, z, x * x * gdf],
+                       [z, (1.0 - p) * cvb, z]])                                             # (8, 3, N)
+    return dict(dlam=terms.sum(axis=0) / q, geo_bar=planes.sum(axis=1), q=q, dlam_scale=np.abs(terms).sum(axis=0) / abs(q),
+                geo_bar_scale=np.abs(planes).sum(axis=1))
+
+
 def local_eq_ray_triples(rays, t):
     """The rule for a ray of the local-equilibrium boundaries (csrc/ibs_local_eq_boundary.hpp, Context.local_eq_boundary) in numpy:
     rays (..., 7) = (theta0, eps0, p0, d_eps, d_p, t_lo, t_hi) and parameters t, broadcast against the rays' leading shape, give the

@@ -624,6 +624,62 @@ class BallooningScan:
         res["first_unstable"] = first_unstable(res["t_stable"], res["t_unstable"], res["lo_unstable"], t_lo)
         return res
 
+    # -- the first-stability limit of that picture with its exact derivatives: the boundary call, then one point launch and one geometry VJP
+    def local_eq_boundary_sensitivity(self, fixed, t_range, theta0=None, axis="p", shift=0.0):
+        """first_unstable of local_eq_boundary(fixed, t_range, theta0, axis, shift) for every owned surface and fixed value, with its exact
+        derivatives with respect to the fixed value, the shift and the surface's own tables.  Resident path only (tables= and device=,
+        else ValueError).  The derivatives are taken at the (alpha, theta0) of the coarse grid that ATTAINS the minimum (the first one in
+        (alpha, theta0, crossing) order): the envelope over a DISCRETE set of lines, C1 only where the attaining line does not switch.
+        There t* solves lam_max(t*) = shift on that line and the implicit-function rule gives d t* / d (.) = -lam_(.) / lam_t, with the
+        derivatives of lam_max from one point launch (autograd.local_eq_lam, ibs_local_eq_grad_f64) on a fresh geometry launch in which
+        every (surface, fixed value) works on its own copy of the surface's tables, and one geometry-VJP launch.  The rule is
+        local_eq()'s: frozen local shear on the pressure axis, no ps row.  lam_max must be simple; a near-tangency shows as a small
+        dlam_dt.  Where some line is unstable at t_lo already, or none crosses, the derivatives are zero and mask is False.
+        Returns local_eq_boundary's dict plus numpy mask (bool), alpha, theta0_at, lam_at, dlam_dt, dfirst_dfixed, dfirst_dshift: (n_own,
+        n_fixed); and device tensors tab_mn_bar (n_own, n_fixed, 6, mnmax), tab_nyq_bar (n_own, n_fixed, 7, mnmax_nyq), scal_bar (n_own,
+        n_fixed, 6) = d first_unstable / d tables, in the layout of marginal_sensitivity per fixed value (SurfaceTables.pullback carries
+        them to the wout arrays)."""
+        import torch
+        from . import autograd as iag
+        if not self._on_device:
+            raise ValueError("local_eq_boundary_sensitivity() runs on the resident path: tables= and device= are required")
+        res = self.local_eq_boundary(fixed, t_range, theta0=theta0, axis=axis, shift=shift)
+        dev, own = self.device, self._own_surf()
+        t0, fx = res["theta0"], res["fixed"]
+        n, nf, na = len(own), len(fx), len(self.alpha_scan)
+        cand = np.where(res["t_stable"] < res["t_unstable"], res["t"], np.inf)      # (n, nalpha, n_theta0, n_fixed, max_cross)
+        flat = np.moveaxis(cand, 3, 1).reshape(n, nf, -1)
+        arg = flat.argmin(axis=2) if flat.shape[2] else np.zeros((n, nf), dtype=np.int64)
+        ia, it, _ = np.unravel_index(arg, (na, len(t0), cand.shape[4]))
+        best = flat.min(axis=2, initial=np.inf)
+        mask = np.isfinite(best) & ~(res["lo_unstable"] > 0).any(axis=(1, 2))
+        out = {k: np.zeros((n, nf)) for k in ("alpha", "theta0_at", "lam_at", "dlam_dt", "dfirst_dfixed", "dfirst_dshift")}
+        d = self.ctx._device_tables(self.tables, dev)
+        bars = [torch.zeros((n, nf) + tuple(d[k].shape[1:]), dtype=torch.float64, device=dev) for k in (4, 5, 6)]
+        q, k = np.nonzero(mask)
+        if len(q):
+            al, th0, ts = self.alpha_scan[ia[q, k]], t0[it[q, k]], best[q, k]
+            var = np.stack([th0, fx[k], ts] if axis == "p" else [th0, ts, fx[k]], axis=1)
+            idx = torch.from_numpy(own[q].astype(np.int64)).to(dev)
+            tm, tq, sc = (d[j][idx].clone().requires_grad_(True) for j in (4, 5, 6))
+            pts = torch.arange(len(q), dtype=torch.int32, device=dev)
+            geo, dP = iag.fieldline_geometry(self.tables, pts, torch.from_numpy(np.ascontiguousarray(al)).to(dev), self._resident_inputs()["th"],
+                                             tab_mn=tm, tab_nyq=tq, scal=sc, ctx=self.ctx)
+            v = torch.from_numpy(var).to(dev).requires_grad_(True)
+            lam = iag.local_eq_lam(self.theta[0], self.h, geo, dP, al, self._line_sigma(own[q]), pts, v, ctx=self.ctx)
+            lam.sum().backward()
+            lv = v.grad.cpu().numpy()
+            lam_t, lam_f = (lv[:, 2], lv[:, 1]) if axis == "p" else (lv[:, 1], lv[:, 2])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inv = 1.0 / lam_t
+            out["alpha"][q, k], out["theta0_at"][q, k], out["lam_at"][q, k], out["dlam_dt"][q, k] = al, th0, lam.detach().cpu().numpy(), lam_t
+            out["dfirst_dfixed"][q, k], out["dfirst_dshift"][q, k] = -lam_f * inv, inv
+            w = torch.from_numpy(-inv).to(dev)
+            for bar, x in zip(bars, (tm, tq, sc)):
+                bar[torch.from_numpy(q).to(dev), torch.from_numpy(k).to(dev)] = x.grad * w.reshape((-1,) + (1,) * (x.grad.dim() - 1))
+        res.update(out, mask=mask, tab_mn_bar=bars[0], tab_nyq_bar=bars[1], scal_bar=bars[2])
+        return res
+
     # -- every line's growth rate maximised over theta0 between the nodes of the coarse grid, two launches
     def envelope(self, n_starts=1, xtol=1e-5, max_eval=32):
         """gam_env(alpha) = max over theta0 of gam(alpha, theta0) of every line of the coarse grid: the coarse scan, then

@@ -519,6 +519,82 @@ class Context:
         res["t"] = 0.5 * (res["t_stable"] + res["t_unstable"])
         return res
 
+    # ---- local-equilibrium gradients --------------------------------------------------------
+    def local_eq_grad(self, theta_lo, h, geo, dPdrho, centre, sigma, line_of, var, ps=None, want_grad=True, want_geo_bar=False,
+                      want_info=False):
+        """lam_max and gam at the points (line_of[k], theta0, eps, p) of the local-equilibrium rule with the exact derivatives of lam_max
+        (ibs_local_eq_grad_f64; numpy: operators.local_eq_lam_grad).  geo, dPdrho, centre, sigma, ps: local_eq_scan's; line_of int32
+        (n_pts,): the line of each point; var (n_pts, 3) = (theta0, eps, p).  The memory kind is geo's; the small arrays may be numpy.
+        Returns dict(lam, gam (n_pts,)[, dlam (n_pts, 4) = d lam / d (theta0, eps, p, dPdrho)][, geo_bar (8, n_pts, N) = d lam / d (the
+        eight arrays of the point's line)][, info], nbad).  want_grad=False and want_geo_bar=False: no mode is kept, lam and gam are
+        local_eq_scan's bits.  A point with status bit 0 or 1 (line_of out of range included) is NaN in every output."""
+        eight, n_lines, N = geo.shape
+        if eight != 8:
+            raise IbsError("geo must be (8, n_lines, N)")
+        n_pts = int(var.shape[0])
+        if tuple(var.shape) != (n_pts, 3) or tuple(line_of.shape) != (n_pts,):
+            raise IbsError("var must be (n_pts, 3) = (theta0, eps, p) and line_of (n_pts,)")
+        if ps is not None and tuple(ps.shape) != (n_lines, N):
+            raise IbsError("ps must be (n_lines, N) = %s, not %s" % ((n_lines, N), tuple(ps.shape)))
+        ar = _Args(self)
+        pgeo = ar.inp(geo)
+        rc = ar.call("ibs_local_eq_grad_f64", n_lines, n_pts, N, float(theta_lo), float(h), pgeo, N, ar.inp(dPdrho, upload=True),
+                     ar.inp(centre, upload=True), ar.inp(sigma, upload=True), ar.inp(ps, upload=True), N, ar.inp(line_of, _I32, True),
+                     ar.inp(var, upload=True), ar.out("lam", (n_pts,)), ar.out("gam", (n_pts,)), ar.out("dlam", (n_pts, 4), want=want_grad),
+                     ar.out("geo_bar", (8, n_pts, N), want=want_geo_bar), N, ar.out("info", (n_pts,), _I32, want_info))
+        return ar.result(rc)
+
+    def local_eq_boundary_grad(self, theta_lo, h, geo, dPdrho, centre, sigma, rays, ps=None, shift=0.0, max_cross=4, xtol=1e-12,
+                               want_geo_bar=False, want_nodes=False):
+        """local_eq_boundary with the derivatives of every returned crossing t*: ONE local_eq_boundary call, the crossings gathered on
+        the host at t = the midpoint of the closed bracket, ONE local_eq_grad call at those points, and the implicit-function rule
+        on lam_max(t*) = shift with lam_t = d_eps lam_eps + d_p lam_p:
+            d t* / d (theta0, eps0, p0, shift, dPdrho) = (-lam_theta0, -lam_eps, -lam_p, 1, -lam_dP) / lam_t.
+        Returns local_eq_boundary's dict (info included) plus lam_at, dlam_dt (n_lines, n_ray, max_cross) and dt (n_lines, n_ray,
+        max_cross, 5), NaN beyond n_cross, in the memory kind of geo; grad_nbad = local_eq_grad's flagged points; with
+        want_geo_bar also pts int (n_cross_total, 3) = the (line, ray, crossing) of every gathered point and dt_geo (8, n_cross_total,
+        N) = d t* / d (the eight arrays of that line) = -geo_bar / lam_t.  dlam_dt is returned so that the caller can judge a
+        near-tangency: lam_t = 0 gives inf or NaN by arithmetic."""
+        b = self.local_eq_boundary(theta_lo, h, geo, dPdrho, centre, sigma, rays, ps=ps, shift=shift, max_cross=max_cross, xtol=xtol,
+                                   want_nodes=want_nodes, want_info=True)
+        on_dev = _is_torch(geo)
+        host = (lambda a: a.detach().cpu().numpy()) if on_dev else np.asarray
+        nc, t = host(b["n_cross"]), host(b["t"])
+        rays_h = np.asarray(host(rays) if _is_torch(rays) else rays, dtype=np.float64)
+        shape = t.shape
+        il, ir, ic = np.nonzero(np.arange(shape[2])[None, None, :] < nc[:, :, None])
+        tt = t[il, ir, ic]
+        var = np.stack([rays_h[ir, 0], rays_h[ir, 1] + tt * rays_h[ir, 3], rays_h[ir, 2] + tt * rays_h[ir, 4]], axis=1).reshape(-1, 3)
+        lam_at, dlam_dt, dt = np.full(shape, np.nan), np.full(shape, np.nan), np.full(shape + (5,), np.nan)
+        b["grad_nbad"] = 0
+        pts = np.stack([il, ir, ic], axis=1)
+        dt_geo = None
+        if len(tt):
+            g = self.local_eq_grad(theta_lo, h, geo, dPdrho, centre, sigma, il.astype(np.int32), var, ps=ps, want_geo_bar=want_geo_bar)
+            b["grad_nbad"] = g["nbad"]
+            dl = host(g["dlam"])
+            lt = rays_h[ir, 3] * dl[:, 1] + rays_h[ir, 4] * dl[:, 2]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inv = 1.0 / lt
+                lam_at[il, ir, ic], dlam_dt[il, ir, ic] = host(g["lam"]), lt
+                dt[il, ir, ic] = np.stack([-dl[:, 0] * inv, -dl[:, 1] * inv, -dl[:, 2] * inv, inv, -dl[:, 3] * inv], axis=1)
+            if want_geo_bar:
+                if on_dev:
+                    import torch
+                    dt_geo = g["geo_bar"] * torch.from_numpy(-inv).to(g["geo_bar"].device)[None, :, None]
+                else:
+                    dt_geo = g["geo_bar"] * (-inv)[None, :, None]
+        if on_dev:
+            import torch
+            lam_at, dlam_dt, dt = (torch.from_numpy(a).to(geo.device) for a in (lam_at, dlam_dt, dt))
+        b.update(lam_at=lam_at, dlam_dt=dlam_dt, dt=dt)
+        if want_geo_bar:
+            if dt_geo is None:
+                N = int(geo.shape[2])
+                dt_geo = geo.new_zeros((8, 0, N)) if on_dev else np.zeros((8, 0, N))
+            b.update(pts=pts, dt_geo=dt_geo)
+        return b
+
     @staticmethod
     def _three_lines(geo):
         n_pts, three, eight, N = geo.shape

@@ -471,7 +471,8 @@ int ibs_local_eq_scan_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_var, int32_t 
  * crossing is closed in turn: 64 points strictly inside the bracket, the new bracket = the first adjacent pair (ends included) whose
  * verdicts differ, until its width is <= xtol (t_hi - t_lo): six passes for 1e-12.  LIMITS: a tangency (double root) and two crossings
  * between one pair of nodes are missed -- narrow the range or split the ray; within rounding of the marginal point the verdict may
- * flicker, and the first flip is returned; theta0 is fixed per ray; ps is consumed, not computed; no derivatives of t*.
+ * flicker, and the first flip is returned; theta0 is fixed per ray; ps is consumed, not computed; the derivatives of t*
+ * are a second call, ibs_local_eq_grad_f64 at the returned crossings (below).
  * FP64, uniform grids, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED); a NULL required argument, ld < N, ps_ld < N,
  * n_ray < 1, max_cross outside [1, 4], xtol outside [0, 1), a non-finite shift: IBS_ERR_ARG; all of these run before the context is
  * touched.  One wavefront per (line, ray) (k_local_eq_boundary, csrc/ibs_local_eq_boundary.hip; the staged form:
@@ -482,6 +483,39 @@ int ibs_local_eq_boundary_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int3
                               int64_t ps_ld, const double* rays, double shift, int32_t max_cross, double xtol, double* t_stable,
                               double* t_unstable, int32_t* n_cross, int32_t* lo_unstable, int32_t* node_count, int32_t* info,
                               int flags);
+
+/* Local-equilibrium gradients: lam_max of the rule above at POINTS (line, theta0, eps, p) with its EXACT derivatives -- the derivatives
+ * the scan and the boundaries lack.  lam_max is a simple eigenvalue of the discrete pencil with mode X (X_0 = X_{N-1} = 0), and
+ *     lam = (sum c_j X_j^2 - 1/2 h^-2 sum g_j w_j) / q,   q = sum f_j X_j^2,   w_j = (X_j - X_{j-1})^2 + (X_{j+1} - X_j)^2
+ * so d lam / d s = (sum c_s X^2 - 1/2 h^-2 sum g_s w - lam sum f_s X^2) / q for every parameter s of the rows (Hellmann-Feynman), exact
+ * for the lam returned to first order in the error of X.  The row tangents are polynomial (csrc/ibs_local_eq_grad.hpp; numpy:
+ * ibs_amd.operators.local_eq_fold_tangent, local_eq_lam_grad).  Along a ray of ibs_local_eq_boundary_f64 every crossing is
+ * lam_max(t*) = shift; with lam_t = d_eps lam_eps + d_p lam_p the implicit-function theorem gives d t* / d theta0 = -lam_theta0 / lam_t,
+ * d t* / d eps0 = -lam_eps / lam_t, d t* / d p0 = -lam_p / lam_t, d t* / d shift = 1 / lam_t, d t* / d dPdrho = -lam_dP / lam_t and
+ * d t* / d (arrays) = -geo_bar / lam_t (the host composition: ibs_amd Context.local_eq_boundary_grad).
+ *   inputs up to ps_ld: as ibs_local_eq_scan_f64 -- ONE staged geometry serves any number of points;
+ *   line_of int32 [n_pts]: the line of each point; var [n_pts][3] = (theta0, eps, p) of each point;
+ *   lam, gam [n_pts]; dlam [n_pts][4] = d lam / d (theta0, eps, p, dPdrho);
+ *   geo_bar [8][n_pts][ld_bar >= N] or NULL: d lam / d (every entry of the line's eight arrays), plane k = array k in the order of geo;
+ *   entries N .. ld_bar-1 of a row are never written.  lam, gam, dlam and geo_bar may each be NULL, not all four (IBS_ERR_ARG).  With
+ *   dlam and geo_bar both NULL no mode is kept and lam, gam are the bits of ibs_local_eq_scan_f64 at that line and triple;
+ *   info [n_pts] or NULL: bits 0-15 = multisection passes, status bits 0 (iteration cap), 1 (a line with non-finite data or g, f <= 0,
+ *   sigma not +-1, a non-finite triple, line_of outside [0, n_lines)): NaN in every floating-point output of those points alone, entries
+ *   0 .. N-1 of their geo_bar rows included; the line of an index out of range is never read;
+ *   flags: IBS_MEM_DEVICE or IBS_MEM_HOST.  Host pointers: returns the number of points with status bit 0 or 1.
+ * LIMITS: the derivative of lam_max, not of gam; lam_max must be simple -- on a doublet of a symmetric line the derivative of one member
+ * does not exist, and nothing detects it; at a tangency of a ray lam_t -> 0 and the d t* are inf or NaN by arithmetic; ps is consumed,
+ * not differentiated.
+ * FP64, uniform grids, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED); a NULL required argument, ld < N, ps_ld < N,
+ * ld_bar < N with geo_bar, n_lines < 0, n_pts < 0: IBS_ERR_ARG; n_pts = 0 does nothing; all of these run before the context is touched.
+ * One wavefront per point (k_local_eq_grad, csrc/ibs_local_eq_grad.hip): k_local_eq_scan's stages with the mode kept, then five
+ * lane-strided sums and the wave reduction in a fixed order.  No atomics: a point's outputs depend on the point and its line alone, bit
+ * for bit -- not on the batch, the order of the points or the chunks of points the call is worked through in (option
+ * "nearest_chunk_systems" sets the chunk). */
+int ibs_local_eq_grad_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_pts, int32_t N, double theta_lo, double h, const double* geo,
+                          int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps, int64_t ps_ld,
+                          const int32_t* line_of, const double* var, double* lam, double* gam, double* dlam, double* geo_bar,
+                          int64_t ld_bar, int32_t* info, int flags);
 
 /* Field-line geometry x theta0 grid -> growth rates.
  * Replaces: the inner loops of ball_scan.py:248-275 (theta0 fold :267-268, gamma_ball_full call :269)
