@@ -53,6 +53,8 @@ SYMBOLS = {
     "ibs_local_eq_scan_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _D, _P, _I64, _P, _P, _P, _P, _I64, _P, _D, _P, _P, _P, _P, C.c_int]),
     "ibs_local_eq_boundary_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _D, _P, _I64, _P, _P, _P, _P, _I64, _P, _D, _I32, _D, _P, _P, _P, _P, _P,
                                             _P, C.c_int]),
+    "ibs_local_eq_boundary_polish_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _D, _P, _I64, _P, _P, _P, _P, _I64, _P, _I32, _P, _P, _D, _D, _I32,
+                                                   _D, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int]),
     "ibs_local_eq_grad_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _D, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P,
                                         C.c_int]),
     "ibs_gamma_scan_nearest_f64": (C.c_int, [_P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P,

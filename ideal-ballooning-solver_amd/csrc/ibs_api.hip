@@ -24,6 +24,7 @@
 #include "ibs_theta0_polish.hpp"
 #include "ibs_local_eq.hpp"
 #include "ibs_local_eq_boundary.hpp"
+#include "ibs_local_eq_boundary_polish.hpp"
 #include "ibs_local_eq_grad.hpp"
 #include <chrono>
 #include <thread>
@@ -1339,6 +1340,68 @@ int ibs_local_eq_boundary_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int3
       c.info = a.info ? a.info + s0 : nullptr;
       c.n_waves = long_waves(ctx, Lc * n_ray);
       HIPCHK(ibs::launch_local_eq_boundary(c, ctx->stream));
+      return 0;
+    });
+  });
+}
+
+// ---- local-equilibrium boundaries minimised over theta0: the first-stability parameter of every (line, ray family) between the nodes of
+// its coarse row (ibs_local_eq_boundary_polish.hip; the rule: ibs_local_eq_boundary_polish.hpp).  Whole lines chunk after chunk as above, a
+// line's n_ray * n_starts slots standing where its rays stand; nothing is carved from ctx->long_ws
+int ibs_local_eq_boundary_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int32_t N, double theta_lo, double h, const double* geo,
+                                     int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps,
+                                     int64_t ps_ld, const double* rays, int32_t n_theta0, const double* theta0, const double* t_row,
+                                     double shift, double xtol, int32_t n_starts, double xtol_theta0, int32_t max_eval,
+                                     double* theta0_out, double* t_out, double* t_stable_out, double* t_unstable_out, int32_t* node,
+                                     int32_t* n_eval, int32_t* lo_unstable, int32_t* info, int32_t* n_found, int flags) {
+  if (!ctx) return fail(IBS_ERR_ARG, "null context");
+  if (!geo || !dPdrho || !centre || !sigma || !rays || !theta0 || !t_row || !theta0_out || !t_out || !t_stable_out || !t_unstable_out)
+    return fail(IBS_ERR_ARG, "null argument (geo, dPdrho, centre, sigma, rays, theta0, t_row, theta0_out, t_out, t_stable_out and "
+                "t_unstable_out are required)");
+  if (n_lines < 0 || n_ray < 1 || ld < N || (ps && ps_ld < N) || n_theta0 < 1 || n_theta0 > ibs::kBoundaryPolishMaxTheta0)
+    return fail(IBS_ERR_ARG, "bad arguments (n_lines=%d n_ray=%d ld=%lld ps_ld=%lld N=%d; n_theta0=%d must lie in [1, %d])", n_lines, n_ray,
+                (long long)ld, (long long)ps_ld, N, n_theta0, ibs::kBoundaryPolishMaxTheta0);
+  if (n_starts < 1 || n_starts > ibs::t0p::kMaxSlots || !(xtol_theta0 > 0) || !std::isfinite(xtol_theta0) || max_eval < 1 ||
+      max_eval > ibs::t0p::kMaxEval || !(xtol >= 0.0 && xtol < 1.0))
+    return fail(IBS_ERR_ARG, "n_starts in [1, %d], xtol_theta0 > 0 and finite, max_eval in [1, %d] and xtol in [0, 1) required "
+                "(n_starts=%d xtol_theta0=%g max_eval=%d xtol=%g)", ibs::t0p::kMaxSlots, ibs::t0p::kMaxEval, n_starts, xtol_theta0,
+                max_eval, xtol);
+  if (flags != IBS_MEM_DEVICE && flags != IBS_MEM_HOST) return fail(IBS_ERR_ARG, "flags must be IBS_MEM_DEVICE or IBS_MEM_HOST, not %d", flags);
+  if (!std::isfinite(theta_lo) || !std::isfinite(shift))
+    return fail(IBS_ERR_ARG, "theta_lo and shift must be finite (theta_lo=%g shift=%g)", theta_lo, shift);
+  if (int r = check_grid(N, h, true)) return r;
+  if (flags == IBS_MEM_HOST && !ibs::t0p::grid_ok(theta0, n_theta0)) return fail(IBS_ERR_ARG, "theta0 must be finite and strictly increasing");
+  if (n_lines == 0) return 0;
+  ON_DEVICE(ctx);
+  const int per_line = n_ray * n_starts;
+  const size_t n_fam = (size_t)n_lines * n_ray, n_sys = n_fam * n_starts, plane = (size_t)n_lines * (size_t)ld;
+  ibs::LocalEqBoundaryPolishArgs a{};                      // the whole call; each chunk launches a copy with its lines
+  a.n_ray = n_ray; a.N = N; a.theta_lo = theta_lo; a.h = h; a.ld = (long)ld; a.plane = plane; a.ps_ld = (long)ps_ld; a.shift = shift;
+  a.xtol = xtol; a.n_theta0 = n_theta0; a.n_starts = n_starts; a.xtol_theta0 = xtol_theta0; a.max_eval = max_eval;
+  auto decl = [&](Stage& s) {
+    a.geo = s.in(geo, 8 * plane); a.dPdrho = s.in(dPdrho, n_lines); a.centre = s.in(centre, n_lines); a.sigma = s.in(sigma, n_lines);
+    a.ps = s.in(ps, (size_t)n_lines * (size_t)ps_ld); a.rays = s.in(rays, 7 * (size_t)n_ray); a.theta0 = s.in(theta0, n_theta0);
+    a.t_row = s.in(t_row, n_fam * n_theta0);
+    a.theta0_out = s.out(theta0_out, n_sys); a.t_out = s.out(t_out, n_sys); a.t_stable_out = s.out(t_stable_out, n_sys);
+    a.t_unstable_out = s.out(t_unstable_out, n_sys); a.node = s.out(node, n_sys); a.n_eval = s.out(n_eval, n_sys);
+    a.lo_unstable = s.out(lo_unstable, n_sys); a.n_found = s.out(n_found, n_fam);
+    a.info = s.status(info, n_sys);
+  };
+  return staged(ctx, flags, decl, [&]() -> int {
+    auto carve = [&](Carve&, long) {};                     // (no per-wave workspace)
+    return for_line_chunks(ctx, "local_eq_boundary_polish", n_lines, per_line, N, carve, [&](long l0, long Lc) -> int {
+      const long f0 = l0 * n_ray, s0 = f0 * n_starts;
+      ibs::LocalEqBoundaryPolishArgs c = a;
+      c.n_lines = (int)Lc;
+      c.geo = a.geo + l0 * ld; c.dPdrho = a.dPdrho + l0; c.centre = a.centre + l0; c.sigma = a.sigma + l0;
+      c.ps = a.ps ? a.ps + l0 * ps_ld : nullptr;
+      c.t_row = a.t_row + f0 * n_theta0;
+      c.theta0_out = a.theta0_out + s0; c.t_out = a.t_out + s0; c.t_stable_out = a.t_stable_out + s0; c.t_unstable_out = a.t_unstable_out + s0;
+      c.node = a.node ? a.node + s0 : nullptr; c.n_eval = a.n_eval ? a.n_eval + s0 : nullptr;
+      c.lo_unstable = a.lo_unstable ? a.lo_unstable + s0 : nullptr; c.n_found = a.n_found ? a.n_found + f0 : nullptr;
+      c.info = a.info ? a.info + s0 : nullptr;
+      c.n_waves = long_waves(ctx, Lc * per_line);
+      HIPCHK(ibs::launch_local_eq_boundary_polish(c, ctx->stream));
       return 0;
     });
   });

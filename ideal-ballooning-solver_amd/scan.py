@@ -289,6 +289,56 @@ def first_unstable(t_stable, t_unstable, lo_unstable, t_lo):
     return np.where((np.asarray(lo_unstable) > 0).any(axis=(1, 2)), float(t_lo), first)
 
 
+def local_eq_first_up(t_stable, t_unstable, lo_unstable, t_lo):
+    """T of every ray of a local_eq_boundary result, with no reduction -- the per-ray form of what first_unstable reduces (the rule:
+    csrc/ibs_local_eq_boundary_polish.hpp): from t_stable, t_unstable (..., max_cross) and lo_unstable (...) the first-stability
+    parameter t_lo where the ray is unstable at t_lo, else the smallest (t_stable + t_unstable) / 2 of a crossing from stable to
+    unstable (t_stable < t_unstable; of a ray that starts stable that is crossing 0), else +inf; NaN for an invalid ray
+    (lo_unstable < 0).  t_lo: a scalar, or an array that broadcasts against lo_unstable.  Returns (...)."""
+    t_stable, t_unstable, lo = np.asarray(t_stable, dtype=np.float64), np.asarray(t_unstable, dtype=np.float64), np.asarray(lo_unstable)
+    up = t_stable < t_unstable                              # (NaN beyond n_cross: False)
+    first = np.where(up, 0.5 * (t_stable + t_unstable), np.inf).min(axis=-1, initial=np.inf)
+    return np.where(lo < 0, np.nan, np.where(lo > 0, np.asarray(t_lo, dtype=np.float64), first))
+
+
+def polish_first_up(boundary, theta0, t_row, node, t_lo, xtol=1e-5, max_eval=32):
+    """T minimised over theta0 about node `node` of the coarse row t_row (T at the nodes theta0) of ONE (line, ray family): the rule of
+    csrc/ibs_local_eq_boundary_polish.hpp restated in Python, so that it asks for the same points bit for bit as every wave of
+    ibs_local_eq_boundary_polish_f64.  boundary(theta0) -> (t_stable, t_unstable, lo_unstable, status) of the family's ray at that
+    theta0 with max_cross = 1 (scalars; status = info >> 16 of Context.local_eq_boundary).  f = -T = -local_eq_first_up(...) is
+    maximised by polish_theta0 unchanged on the row -t_row; an evaluation with status bit 0 or 1 is a failed one.  The addition: a node
+    with T = t_lo is returned at once (no evaluation, bit 10).  Where the node itself is returned one more evaluation at the node, not
+    counted in n_eval, supplies the ends.  Status bit 1 gives NaN outputs and lo_unstable -1.
+    Returns dict(theta0, t, t_stable, t_unstable, lo_unstable, n_eval, status, points: the theta0 of the search in order)."""
+    theta0 = np.asarray(theta0, dtype=np.float64)
+    row = np.asarray(t_row, dtype=np.float64)
+    j, nan = int(node), float("nan")
+    xn, Tn = float(theta0[j]), float(row[j])
+    if Tn == t_lo:
+        return dict(theta0=xn, t=Tn, t_stable=nan, t_unstable=nan, lo_unstable=1, n_eval=0, status=NODE_RETURNED_BIT, points=[])
+    seen, extra = {}, [0]
+
+    def f(u):
+        ts, tu, lo, st = boundary(u)
+        seen[u] = (float(ts), float(tu), int(lo))
+        extra[0] |= int(st) & 8
+        return -float(local_eq_first_up(np.array([ts]), np.array([tu]), lo, t_lo)), int(st)
+
+    r = polish_theta0(f, theta0, -row, j, xtol=xtol, max_eval=max_eval)
+    status = r["status"] | extra[0]
+    if status & NODE_RETURNED_BIT:
+        ts, tu, lo, st = boundary(xn)
+        status |= int(st) & 11
+        x, t, ts, tu, lo = xn, Tn, float(ts), float(tu), int(lo)
+    else:
+        x, t = r["theta0"], -r["gam"]
+        ts, tu, lo = seen[x]
+    if status & 2:
+        x = t = ts = tu = nan
+        lo = -1
+    return dict(theta0=x, t=t, t_stable=ts, t_unstable=tu, lo_unstable=lo, n_eval=r["n_eval"], status=status, points=r["points"])
+
+
 def check_eigenpair(eigenpair):
     if eigenpair not in EIGENPAIRS:
         raise ValueError("eigenpair must be 'max' or 'nearest', not %r" % (eigenpair,))
@@ -598,6 +648,11 @@ class BallooningScan:
         crossings between one pair of nodes are missed.  Flagged systems (status bits 0-1) raise IbsError."""
         if not self._on_device:
             raise ValueError("local_eq_boundary() runs on the resident path: tables= and device= are required")
+        return self._local_eq_boundary(fixed, t_range, theta0, axis, shift, max_cross, xtol)[0]
+
+    def _local_eq_boundary(self, fixed, t_range, theta0, axis, shift, max_cross, xtol):
+        """local_eq_boundary() on the resident path -> (its dict, the coarse lines it ran on (None without an owned surface), the ray
+        families (n_fixed, 7) of local_eq_boundary_envelope: the rays of one theta0 with entry 0 zeroed)"""
         if axis not in ("p", "eps"):
             raise ValueError("axis must be 'p' or 'eps', not %r" % (axis,))
         fixed = np.atleast_1d(np.asarray(fixed, dtype=np.float64))
@@ -622,10 +677,56 @@ class BallooningScan:
             res.update({k: np.full(shape + (max_cross,), np.nan) for k in ("t_stable", "t_unstable", "t")})
             res.update({k: np.zeros(shape, dtype=np.int32) for k in ("n_cross", "lo_unstable", "info")})
         res["first_unstable"] = first_unstable(res["t_stable"], res["t_unstable"], res["lo_unstable"], t_lo)
+        fam = rays[:len(fixed)].copy()
+        fam[:, 0] = 0.0
+        return res, (ln if n else None), fam
+
+    # -- the boundaries minimised over theta0 between the nodes: the coarse boundary call, then one polish call on the same lines
+    def local_eq_boundary_envelope(self, fixed, t_range, theta0=None, axis="p", shift=0.0, n_starts=1, xtol=1e-12, xtol_theta0=1e-5,
+                                   max_eval=32):
+        """local_eq_boundary(fixed, t_range, theta0, axis, shift, xtol=xtol) with every line's first-stability parameter T = the first
+        crossing from stable to unstable (local_eq_first_up) then MINIMISED over theta0 between the nodes of the theta0 grid
+        (Context.local_eq_boundary_polish; the rule: polish_first_up): the envelope over theta0 that the boundary of an s-alpha picture
+        is by convention, at the coarse alpha values.  Resident path only (tables= and device=, else ValueError): ONE geometry launch,
+        ONE boundary call for the coarse rows and ONE polish call about the n_starts <= 4 best nodes of every (line, fixed value) row.
+        Returns local_eq_boundary's dict plus theta0_env, t_env (n_own, nalpha, n_fixed, n_starts), node, n_eval, lo_unstable_env int32 of
+        that shape, n_found (n_own, nalpha, n_fixed); first_unstable_env (n_own, n_fixed) = the smallest t_env over (alpha, slot) of every
+        surface, t_lo where some line is unstable at t_lo, +inf where none crosses -- never above first_unstable; at (n_own, n_fixed, 2) =
+        (alpha, theta0*) of the attaining slot, the first in (alpha, slot) order.  Wherever no slot beat its node t_env is the coarse
+        call's T.  Flagged systems (status bits 0-1) raise IbsError."""
+        if not self._on_device:
+            raise ValueError("local_eq_boundary_envelope() runs on the resident path: tables= and device= are required")
+        if isinstance(n_starts, bool) or not isinstance(n_starts, (int, np.integer)) or not 1 <= n_starts <= MAX_ROW_STARTS:
+            raise ValueError("n_starts must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, n_starts))
+        K = int(n_starts)
+        res, ln, fam = self._local_eq_boundary(fixed, t_range, theta0, axis, shift, 4, xtol)
+        t0, t_lo = res["theta0"], res["t_range"][0]
+        na, n, nf = len(self.alpha_scan), len(self.own), len(res["fixed"])
+        slots = (n, na, nf, K)
+        if n:
+            T = local_eq_first_up(res["t_stable"], res["t_unstable"], res["lo_unstable"], t_lo)      # (n, nalpha, n_theta0, n_fixed)
+            t_row = np.ascontiguousarray(np.moveaxis(T, 2, 3)).reshape(n * na, nf, len(t0))
+            out = self.ctx.local_eq_boundary_polish(self.theta[0], self.h, ln["geo"], ln["dP"], ln["alpha"], self._line_sigma(ln["surf"]), fam,
+                                                    t0, t_row, shift=shift, xtol=xtol, n_starts=K, xtol_theta0=xtol_theta0,
+                                                    max_eval=max_eval, want_info=True)
+            _check_flags("%d of %d slots of the local-equilibrium boundary envelope were flagged (status bits 0-1: pass cap or invalid data)",
+                         out["info"])
+            env = {k: _host(out[k]).reshape(slots) for k in ("theta0", "t", "node", "n_eval", "lo_unstable")}
+            n_found = _host(out["n_found"]).reshape(n, na, nf)
+        else:
+            env = dict(theta0=np.zeros(slots), t=np.zeros(slots), node=np.zeros(slots, np.int32), n_eval=np.zeros(slots, np.int32),
+                       lo_unstable=np.zeros(slots, np.int32))
+            n_found = np.zeros((n, na, nf), np.int32)
+        flat = np.moveaxis(np.where(np.isnan(env["t"]), np.inf, env["t"]), 2, 1).reshape(n, nf, na * K)
+        arg = flat.argmin(axis=2)                                               # (first minimum in (alpha, slot) order)
+        rows, cols = np.arange(n)[:, None], np.arange(nf)[None, :]
+        th_at = np.moveaxis(env["theta0"], 2, 1).reshape(n, nf, na * K)[rows, cols, arg]
+        res.update(theta0_env=env["theta0"], t_env=env["t"], node=env["node"], n_eval=env["n_eval"], lo_unstable_env=env["lo_unstable"],
+                   n_found=n_found, first_unstable_env=flat[rows, cols, arg], at=np.stack([self.alpha_scan[arg // K], th_at], axis=2))
         return res
 
     # -- the first-stability limit of that picture with its exact derivatives: the boundary call, then one point launch and one geometry VJP
-    def local_eq_boundary_sensitivity(self, fixed, t_range, theta0=None, axis="p", shift=0.0):
+    def local_eq_boundary_sensitivity(self, fixed, t_range, theta0=None, axis="p", shift=0.0, theta0_polish=False):
         """first_unstable of local_eq_boundary(fixed, t_range, theta0, axis, shift) for every owned surface and fixed value, with its exact
         derivatives with respect to the fixed value, the shift and the surface's own tables.  Resident path only (tables= and device=,
         else ValueError).  The derivatives are taken at the (alpha, theta0) of the coarse grid that ATTAINS the minimum (the first one in
@@ -635,6 +736,10 @@ class BallooningScan:
         every (surface, fixed value) works on its own copy of the surface's tables, and one geometry-VJP launch.  The rule is
         local_eq()'s: frozen local shear on the pressure axis, no ps row.  lam_max must be simple; a near-tangency shows as a small
         dlam_dt.  Where some line is unstable at t_lo already, or none crosses, the derivatives are zero and mask is False.
+        theta0_polish=True: the limit is first_unstable_env of local_eq_boundary_envelope(fixed, t_range, theta0, axis, shift) and the
+        derivatives are taken at its polished (alpha, theta0*) = `at` in place of the best node; at an interior theta0* the envelope
+        theorem holds in theta0 (d t* / d theta0 = 0 there), so the derivatives are those of the envelope over theta0 at that alpha.  The
+        dict is then local_eq_boundary_envelope's plus the keys below.
         Returns local_eq_boundary's dict plus numpy mask (bool), alpha, theta0_at, lam_at, dlam_dt, dfirst_dfixed, dfirst_dshift: (n_own,
         n_fixed); and device tensors tab_mn_bar (n_own, n_fixed, 6, mnmax), tab_nyq_bar (n_own, n_fixed, 7, mnmax_nyq), scal_bar (n_own,
         n_fixed, 6) = d first_unstable / d tables, in the layout of marginal_sensitivity per fixed value (SurfaceTables.pullback carries
@@ -643,22 +748,30 @@ class BallooningScan:
         from . import autograd as iag
         if not self._on_device:
             raise ValueError("local_eq_boundary_sensitivity() runs on the resident path: tables= and device= are required")
-        res = self.local_eq_boundary(fixed, t_range, theta0=theta0, axis=axis, shift=shift)
         dev, own = self.device, self._own_surf()
-        t0, fx = res["theta0"], res["fixed"]
-        n, nf, na = len(own), len(fx), len(self.alpha_scan)
-        cand = np.where(res["t_stable"] < res["t_unstable"], res["t"], np.inf)      # (n, nalpha, n_theta0, n_fixed, max_cross)
-        flat = np.moveaxis(cand, 3, 1).reshape(n, nf, -1)
-        arg = flat.argmin(axis=2) if flat.shape[2] else np.zeros((n, nf), dtype=np.int64)
-        ia, it, _ = np.unravel_index(arg, (na, len(t0), cand.shape[4]))
-        best = flat.min(axis=2, initial=np.inf)
-        mask = np.isfinite(best) & ~(res["lo_unstable"] > 0).any(axis=(1, 2))
+        if theta0_polish:
+            res = self.local_eq_boundary_envelope(fixed, t_range, theta0=theta0, axis=axis, shift=shift)
+            t0, fx = res["theta0"], res["fixed"]
+            n, nf, na = len(own), len(fx), len(self.alpha_scan)
+            best, al_at, th_at = res["first_unstable_env"], res["at"][:, :, 0], res["at"][:, :, 1]
+            mask = np.isfinite(best) & ~(res["lo_unstable"] > 0).any(axis=(1, 2)) & ~(res["lo_unstable_env"] > 0).any(axis=(1, 3))
+        else:
+            res = self.local_eq_boundary(fixed, t_range, theta0=theta0, axis=axis, shift=shift)
+            t0, fx = res["theta0"], res["fixed"]
+            n, nf, na = len(own), len(fx), len(self.alpha_scan)
+            cand = np.where(res["t_stable"] < res["t_unstable"], res["t"], np.inf)      # (n, nalpha, n_theta0, n_fixed, max_cross)
+            flat = np.moveaxis(cand, 3, 1).reshape(n, nf, -1)
+            arg = flat.argmin(axis=2) if flat.shape[2] else np.zeros((n, nf), dtype=np.int64)
+            ia, it, _ = np.unravel_index(arg, (na, len(t0), cand.shape[4]))
+            best = flat.min(axis=2, initial=np.inf)
+            mask = np.isfinite(best) & ~(res["lo_unstable"] > 0).any(axis=(1, 2))
+            al_at, th_at = self.alpha_scan[ia], t0[it]
         out = {k: np.zeros((n, nf)) for k in ("alpha", "theta0_at", "lam_at", "dlam_dt", "dfirst_dfixed", "dfirst_dshift")}
         d = self.ctx._device_tables(self.tables, dev)
         bars = [torch.zeros((n, nf) + tuple(d[k].shape[1:]), dtype=torch.float64, device=dev) for k in (4, 5, 6)]
         q, k = np.nonzero(mask)
         if len(q):
-            al, th0, ts = self.alpha_scan[ia[q, k]], t0[it[q, k]], best[q, k]
+            al, th0, ts = al_at[q, k], th_at[q, k], best[q, k]
             var = np.stack([th0, fx[k], ts] if axis == "p" else [th0, ts, fx[k]], axis=1)
             idx = torch.from_numpy(own[q].astype(np.int64)).to(dev)
             tm, tq, sc = (d[j][idx].clone().requires_grad_(True) for j in (4, 5, 6))

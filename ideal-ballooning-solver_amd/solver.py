@@ -519,6 +519,41 @@ class Context:
         res["t"] = 0.5 * (res["t_stable"] + res["t_unstable"])
         return res
 
+    def local_eq_boundary_polish(self, theta_lo, h, geo, dPdrho, centre, sigma, rays, theta0, t_row, ps=None, shift=0.0, xtol=1e-12,
+                                 n_starts=1, xtol_theta0=1e-5, max_eval=32, want_info=True):
+        """The first-stability parameter T of every (line, ray family) minimised over theta0 between the nodes theta0 (n_theta0,) of
+        the coarse row t_row (n_lines, n_ray, n_theta0) = T at the nodes (ibs_local_eq_boundary_polish_f64; the rule:
+        scan.local_eq_first_up and scan.polish_first_up).  A family is a ray of local_eq_boundary whose entry 0 is replaced by the
+        theta0 under evaluation; every evaluation is local_eq_boundary(max_cross=1) at that theta0, bit for bit.  t_row: +inf where a
+        node has no crossing, t_lo where it is unstable at t_lo, NaN where it is not to be used.  The other arguments are
+        local_eq_boundary's; n_starts <= 4 slots per row, xtol_theta0 absolute, max_eval <= 64.
+        Returns dict(theta0, t, t_stable, t_unstable (n_lines, n_ray, n_starts); node, n_eval, lo_unstable[, info] int32 of that shape;
+        n_found int32 (n_lines, n_ray), nbad).  t is never above the node's T.  Status (info >> 16) bits 0-1 are failures (bit 1: NaN
+        outputs), bit 3 and bits 10 (the node itself is returned), 11 (max_eval reached), 12 (one-sided bracket) informational."""
+        K = int(n_starts)
+        if K != n_starts or not 1 <= K <= MAX_ROW_STARTS:
+            raise IbsError("n_starts must be an integer in [1, %d], not %r" % (MAX_ROW_STARTS, n_starts))
+        eight, n_lines, N = geo.shape
+        if eight != 8:
+            raise IbsError("geo must be (8, n_lines, N)")
+        n_ray, n_theta0 = int(rays.shape[0]), int(theta0.shape[0])
+        if tuple(rays.shape) != (n_ray, 7):
+            raise IbsError("rays must be (n_ray, 7) = (-, eps0, p0, d_eps, d_p, t_lo, t_hi)")
+        if ps is not None and tuple(ps.shape) != (n_lines, N):
+            raise IbsError("ps must be (n_lines, N) = %s, not %s" % ((n_lines, N), tuple(ps.shape)))
+        if tuple(t_row.shape) != (n_lines, n_ray, n_theta0):
+            raise IbsError("local_eq_boundary_polish: t_row must be %s, not %s" % ((n_lines, n_ray, n_theta0), tuple(t_row.shape)))
+        ar = _Args(self)
+        slots = (n_lines, n_ray, K)
+        pgeo = ar.inp(geo)
+        rc = ar.call("ibs_local_eq_boundary_polish_f64", n_lines, n_ray, N, float(theta_lo), float(h), pgeo, N, ar.inp(dPdrho, upload=True),
+                     ar.inp(centre, upload=True), ar.inp(sigma, upload=True), ar.inp(ps, upload=True), N, ar.inp(rays, upload=True),
+                     n_theta0, ar.inp(theta0, upload=True), ar.inp(t_row, upload=True), float(shift), float(xtol), K, float(xtol_theta0),
+                     int(max_eval), ar.out("theta0", slots), ar.out("t", slots), ar.out("t_stable", slots), ar.out("t_unstable", slots),
+                     ar.out("node", slots, _I32), ar.out("n_eval", slots, _I32), ar.out("lo_unstable", slots, _I32),
+                     ar.out("info", slots, _I32, want_info), ar.out("n_found", (n_lines, n_ray), _I32))
+        return ar.result(rc)
+
     # ---- local-equilibrium gradients --------------------------------------------------------
     def local_eq_grad(self, theta_lo, h, geo, dPdrho, centre, sigma, line_of, var, ps=None, want_grad=True, want_geo_bar=False,
                       want_info=False):

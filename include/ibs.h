@@ -53,7 +53,7 @@
  *            and is otherwise unspecified) and gam is that vector's quotient.  Informational: not counted by return values > 0.
  *            The derivative of one member of a cluster does not exist: do not hand such a pair to ibs_solve_gcf_vjp_f64.
  *            ibs_solve_gcf_modes_basis_f64 gives the members of a cluster an F-orthonormal Ritz basis of it instead (bits 13, 14).
- *     bits 10-12, ibs_theta0_polish_f64 and ibs_marginal_theta0_polish_f64 only, per start slot, all informational (not counted by return values > 0): bit 10 = the
+ *     bits 10-12, ibs_theta0_polish_f64, ibs_marginal_theta0_polish_f64 and ibs_local_eq_boundary_polish_f64 only, per start slot, all informational (not counted by return values > 0): bit 10 = the
  *            coarse node itself was returned (no evaluated point beat it strictly); bit 11 = the search stopped at max_eval;
  *            bit 12 = one-sided bracket (the row ends at the node, or the neighbour on that side is NaN).
  *     bits 13-14, ibs_solve_gcf_modes_basis_f64 only, per mode, both informational (not counted by return values > 0): bit 13 "basis" =
@@ -483,6 +483,42 @@ int ibs_local_eq_boundary_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int3
                               int64_t ps_ld, const double* rays, double shift, int32_t max_cross, double xtol, double* t_stable,
                               double* t_unstable, int32_t* n_cross, int32_t* lo_unstable, int32_t* node_count, int32_t* info,
                               int flags);
+
+/* Local-equilibrium boundaries minimised over theta0: the first-stability parameter of every (line, ray family) BETWEEN the nodes of a
+ * coarse theta0 grid -- the envelope over theta0 that the boundary of an s-alpha picture is by convention.  The rule is stated once in
+ * csrc/ibs_local_eq_boundary_polish.hpp (Python: ibs_amd.scan.polish_first_up).  A family is a ray of ibs_local_eq_boundary_f64 whose entry
+ * 0 is ignored and replaced by the theta0 under evaluation.  T(theta0) is what ibs_local_eq_boundary_f64 gives for that ray with
+ * max_cross = 1, bit for bit (every evaluation is cold): t_lo where the ray is unstable at t_lo, else (t_stable[0] + t_unstable[0]) / 2,
+ * else +inf; an evaluation with status bit 0 or 1 is a failed one.  f = -T is maximised by the rule of ibs_theta0_polish_f64 unchanged
+ * (peaks of the coarse row, n_starts <= 4 slots, the bracket between the neighbouring nodes, Brent's bounded search on the absolute
+ * tolerance xtol_theta0, at most max_eval <= 64 evaluations, the incumbent rule), with one addition: a slot whose node already has
+ * T = t_lo is returned at once, no evaluation, bit 10.
+ *   inputs up to ps_ld: as ibs_local_eq_boundary_f64; rays [n_ray][7]; theta0 [n_theta0], finite and strictly increasing,
+ *   n_theta0 in [1, 2520]; t_row [n_lines][n_ray][n_theta0] = T at the nodes (+inf: no crossing; t_lo: unstable at t_lo; NaN: not to be
+ *   used), e.g. from one ibs_local_eq_boundary_f64 call; shift, xtol: as ibs_local_eq_boundary_f64;
+ *   theta0_out, t_out, t_stable_out, t_unstable_out [n_lines][n_ray][n_starts] (required): theta0*, T(theta0*) -- never above the node's
+ *   -- and the two ends of the first crossing of the evaluation at theta0* (NaN without one, and after the early return);
+ *   node, n_eval, lo_unstable, info [n_lines][n_ray][n_starts], n_found [n_lines][n_ray], each or NULL: the slot's node (-1: the row has
+ *   no usable node; NaN outputs), the evaluations of the search, the verdict at t_lo of the evaluation at theta0*, bits 0-15 = passes
+ *   over the rows of the search | status << 16, and the peaks of the row; slots from n_found on repeat slot 0.
+ *   Status bits 0 (the pass cap in some evaluation) and 1 (invalid data in some evaluation, a non-finite family, t_lo >= t_hi, sigma not
+ *   +-1, theta0 not increasing: NaN outputs, lo_unstable -1, of that slot alone) are failures; bit 3 (some bracket's ends became FP64
+ *   neighbours before xtol) and bits 10 (the node itself is returned: t_out is the row's entry, and one more evaluation at the node, not
+ *   counted in n_eval, supplies the ends), 11 (max_eval reached) and 12 (one-sided bracket) are informational.
+ *   flags: IBS_MEM_DEVICE or IBS_MEM_HOST.  Host pointers: returns the number of slots with status bit 0 or 1.
+ * LIMITS: theta0 alone is polished; a peak is a local maximum of the row's NODES; the tangency limit of the ray rule holds in every
+ * evaluation; T(theta0) is continuous only while the first crossing stays the same branch; the cost is n_eval boundary closures.
+ * FP64, uniform grids, any odd N in [66, 65537] (even N and N outside: IBS_ERR_UNSUPPORTED); a NULL required argument, ld < N, ps_ld < N,
+ * n_ray < 1, n_theta0 outside [1, 2520], n_starts outside [1, 4], max_eval outside [1, 64], xtol_theta0 <= 0 or non-finite, xtol outside
+ * [0, 1), a non-finite shift: IBS_ERR_ARG; all of these run before the context is touched.  One wavefront per (line, family, slot)
+ * (k_local_eq_boundary_polish, csrc/ibs_local_eq_boundary_polish.hip), no atomics, no workspace: a slot's outputs depend on its line, its
+ * family, its row and its slot alone, bit for bit -- not on the batch, the order of the lines or the chunks of whole lines. */
+int ibs_local_eq_boundary_polish_f64(ibs_ctx* ctx, int32_t n_lines, int32_t n_ray, int32_t N, double theta_lo, double h, const double* geo,
+                                     int64_t ld, const double* dPdrho, const double* centre, const double* sigma, const double* ps,
+                                     int64_t ps_ld, const double* rays, int32_t n_theta0, const double* theta0, const double* t_row,
+                                     double shift, double xtol, int32_t n_starts, double xtol_theta0, int32_t max_eval,
+                                     double* theta0_out, double* t_out, double* t_stable_out, double* t_unstable_out, int32_t* node,
+                                     int32_t* n_eval, int32_t* lo_unstable, int32_t* info, int32_t* n_found, int flags);
 
 /* Local-equilibrium gradients: lam_max of the rule above at POINTS (line, theta0, eps, p) with its EXACT derivatives -- the derivatives
  * the scan and the boundaries lack.  lam_max is a simple eigenvalue of the discrete pencil with mode X (X_0 = X_{N-1} = 0), and
